@@ -10,12 +10,17 @@ N child processes of this file (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127
 BEFORE it makes any GPU call, waits for them and exits with the first non-zero exit code; under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` the ranks already exist and nothing is spawned.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (the wall time of one timed step;
+exactly --steps steps are timed, after --warmup untimed ones), and
   roofline     -- dominant kernel (wino_persist_kernel: the whole trajectory, Winograd F(2x2,3x3) on exact-fp32 MFMA, in one
                   launch; conv3x3_wino_kernel<4> per layer when the persistent path is off): algorithmic FLOP per launch /
-                  average launch duration measured with HIP events over the timed region;
-  cpu_baseline -- the oracle (CPU restatement of torchdiffeq 0.2.1 on torch-CPU convs) timed on this
-                  box's host cores on a bounded sample of the same workload (rank 0, N=1 only).
+                  average launch duration measured with HIP events over the timed region.
+A plain run does nothing else.  --full adds what takes runs of its own (median_ms_per_step, the training leg, BASELINE configs[0],
+the end-to-end model context) and
+  cpu_baseline -- the oracle (CPU restatement of torchdiffeq 0.2.1 on torch-CPU convs) timed on the host cores
+                  on a bounded sample of the same workload (rank 0, N=1 only).
+--dump-outputs DIR writes what the last timed step returned (rank 0's: the trajectory, and with --train the gradients w.r.t. z0
+and every weight) as DIR/<name>.npy; inputs and weights come from fixed seeds, so two builds can be compared output for output.
 """
 import argparse
 import glob
@@ -104,11 +109,39 @@ def parse():
     p.add_argument("--launch-check", action="store_true",
                    help="N ranks over gloo, no GPU work: exercises the self-launch and rendezvous path only (CPU tests)")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also measure what takes runs of its own: median step time, training leg, configs[0], model context, CPU baseline "
+                        "(the --no-* options above switch single parts off)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 64 MiB in all)")
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def conv_flops(f_channels, batch):
     return sum(2 * batch * ci * co * 9 * 256 for ci, co in zip(f_channels[:-1], f_channels[1:]))
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(arrays, out_dir):
+    """Writes {name: tensor} as out_dir/<name>.npy, float64 tensors as float64 and all others as float32.  When they hold more than
+    DUMP_BUDGET_BYTES together, each is cut to the same share of its elements, flattened, at flat indices drawn (sorted, with
+    repeats) from a generator seeded with 0: the same elements in every run with the same arguments."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    nbytes = lambda v: v.numel() * (8 if v.dtype == torch.float64 else 4)   # noqa: E731
+    total = sum(nbytes(v) for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            idx = torch.randint(v.numel(), (max(1, v.numel() * DUMP_BUDGET_BYTES // total),), generator=torch.Generator().manual_seed(0))
+            v = v.reshape(-1)[idx.sort().values.to(v.device)]
+        v = v.to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu()
+        np.save(os.path.join(out_dir, name + ".npy"), v.numpy())
 
 
 def host_cpu_info():
@@ -397,12 +430,13 @@ def main():
             torch.cuda.synchronize()
 
     gout = torch.randn(T, a.batch, C0, 16, 16, generator=torch.Generator().manual_seed(99)).to(dev) if a.train else None
+    last_z0 = [None]   # the leaf of the latest training step: its .grad is one of the step's outputs
 
     def step():
         if not a.train:
             with torch.no_grad():
                 return solver(z0, t)
-        zz = z0.detach().requires_grad_(True)
+        zz = last_z0[0] = z0.detach().requires_grad_(True)
         f.zero_grad()   # torch 2 default (set_to_none=True), what the reference's `optimizer.zero_grad()` (train_test.py:176) does today
         if a.adjoint:
             o = ode_rl_amd.odeint_adjoint(f, zz, t, rtol=solver.odeint_rtol, atol=solver.odeint_atol, method=a.method,
@@ -434,11 +468,12 @@ def main():
         def step():
             graph.replay()
             return graph_out
-    def measure(step_fn, steps, warmup):
+    def measure(step_fn, steps, warmup, median=True, after_timed=None):
         """W untimed steps, then EXACTLY `steps` steps bracketed by barrier + synchronize on both sides; wall = MAX over ranks.
         HIP events (on the stream the kernels are launched on: torch's current stream, which hip_ops hands to the C ABI) bracket
-        the region.  The MEDIAN step time comes from a second, untimed-for-the-record pass with one event between steps: an event
-        record inside the timed region costs a few per cent (same-box A/B), so the region the record is computed from has none."""
+        the region.  after_timed(o) sees the last timed step's result before anything else runs.  With `median`, the MEDIAN step
+        time comes from a second, untimed-for-the-record pass with one event between steps (None without): an event record
+        inside the timed region costs a few per cent (same-box A/B), so the region the record is computed from has none."""
         for _ in range(warmup):
             o = step_fn()
         sync()
@@ -452,9 +487,13 @@ def main():
         sync()
         wall = time.perf_counter() - t0
         n_persist = lib.odehip_persistent_trajectory_launches() - p0
+        if after_timed is not None:
+            after_timed(o)
         wt = torch.tensor([wall], dtype=torch.float64, device=dev)
         if dist is not None:
             dist.all_reduce(wt, op=dist.ReduceOp.MAX)
+        if not median:
+            return o, float(wt.item()), ev0.elapsed_time(ev1), None, n_persist
         m = min(steps, 20)
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(m + 1)]
         evs[0].record()
@@ -467,15 +506,26 @@ def main():
 
     lib = ode_rl_amd._lib.load()
     collective = collective_identity(dist, rank, local, world, dev, rehearsal)
-    out, wall, dev_ms, median_ms, persistent = measure(step, a.steps, a.warmup)
+    outputs = {}
+
+    def keep_outputs(o):   # copies: later steps (the median pass, a graph replay) reuse the buffers and gradients
+        outputs["trajectory"] = o.detach().clone()
+        if a.train:
+            outputs["grad_z0"] = last_z0[0].grad.clone()
+            outputs.update((f"grad_{n.replace('.', '_')}", p.grad.clone()) for n, p in f.named_parameters())
+    out, wall, dev_ms, median_ms, persistent = measure(step, a.steps, a.warmup, median=a.full,
+                                                       after_timed=keep_outputs if (a.dump_outputs and rank == 0) else None)
     assert out.shape == (T, a.batch, C0, 16, 16) and bool(torch.isfinite(out).all())
+    if outputs:
+        dump_outputs(outputs, a.dump_outputs)
+        outputs.clear()
     fwd_stats = dict(ode_rl_amd.last_stats) if a.method == "dopri5" else {}
     adj = dict(ode_rl_amd.last_adjoint_stats) if (a.method == "dopri5" and a.train and a.adjoint) else None
 
     # ---- second leg of the record: the training step of the same workload (forward + backward through the solver + the ONE
     # gradient all-reduce of north_star when N > 1), so the collective sits inside a timed region of every scaling run
     train_leg = None
-    if not a.train and not a.no_train_leg and not a.graph:
+    if a.full and not a.train and not a.no_train_leg and not a.graph:
         gout2 = torch.randn(T, a.batch, C0, 16, 16, generator=torch.Generator().manual_seed(99)).to(dev)
         from ode_rl_amd.dist import allreduce_gradients
 
@@ -496,7 +546,7 @@ def main():
 
     # ---- BASELINE configs[0] (the reference's own CPU-runnable case: B=4, same grid and method) on this GPU, next to its CPU time
     config0 = None
-    if rank == 0 and world == 1 and not a.no_config0 and not a.train and a.batch != 4 and a.shape == "A" and not a.graph:
+    if a.full and rank == 0 and world == 1 and not a.no_config0 and not a.train and a.batch != 4 and a.shape == "A" and not a.graph:
         z4_cpu = torch.randn(4, C0, 16, 16, generator=torch.Generator().manual_seed(1234)) * 0.5
         z4 = z4_cpu.to(dev)
 
@@ -512,7 +562,7 @@ def main():
     # ---- context ("also report end-to-end ODEConvGRU.forward frames/s"): the WHOLE model of models/ODEConvGRU.py around the
     # path -- conv encoder, ODEConvGRUCell, DiffEqSolver, conv decoder -- forward, and one training step (MSE loss, backward, Adam)
     model_ctx = None
-    if rank == 0 and world == 1 and not a.no_model and not a.train and a.shape == "A" and not a.graph:
+    if a.full and rank == 0 and world == 1 and not a.no_model and not a.train and a.shape == "A" and not a.graph:
         try:
             model_ctx = model_context(a, dev, T)
             if a.method != "dopri5":   # ... and with the reference's DEFAULT decoder solver (configs.yaml:79 decode_diff_method 'dopri5')
@@ -598,7 +648,7 @@ def main():
         }
         if world == 1 and not a.no_cpu_baseline and config0 is not None:
             config0["cpu"] = cpu_baseline(state, z4_cpu, t_cpu, a.method, 3.0, rtol=solver.odeint_rtol, atol=solver.odeint_atol)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(state, z0_cpu, t_cpu, a.method, a.cpu_seconds, rtol=solver.odeint_rtol, atol=solver.odeint_atol)
         else:
             res["cpu_baseline"] = None

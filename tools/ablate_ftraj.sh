@@ -20,7 +20,7 @@ build)
 run)
   cd "$ROOT"
   for v in $VARIANTS; do
-    ODEHIP_LIB=$AB/$v/lib/libodecgru_hip.so python bench.py --dtype bf16 --batch ${2:-128} --frames 40 --steps 10 --no-cpu-baseline --no-config0 ${3:-} 2>/dev/null | python -c "
+    ODEHIP_LIB=$AB/$v/lib/libodecgru_hip.so python bench.py --full --dtype bf16 --batch ${2:-128} --frames 40 --steps 10 --no-cpu-baseline --no-config0 ${3:-} 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$v', round(d['median_ms_per_step'],3), 'ms;', round(d['median_ms_per_step']*1e3/156,2), 'us per f; train leg', d['train'] and round(d['train']['median_ms_per_step'],3))"
   done ;;
 esac

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/bench_round
 mkdir -p $OUT
 cd $ROOT
-run() { name=$1; shift; timeout -k 10 280 python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || echo "$name FAILED"; python3 - $OUT/$name.json $name <<'PY'
+run() { name=$1; shift; timeout -k 10 280 python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || echo "$name FAILED"; python3 - $OUT/$name.json $name <<'PY'
 import json, sys
 try:
     d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])   # (gloo prints a connection line to stdout in the rehearsal mode)
