@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define ODEHIP_ABI_VERSION 12 /* == odehip_version(); bumped whenever a struct layout or a signature below changes */
+#define ODEHIP_ABI_VERSION 13 /* == odehip_version(); bumped whenever a struct layout or a signature below changes */
 #define ODEHIP_MAX_LAYERS 8
 #define ODEHIP_MAX_STAGES 7
 
@@ -150,6 +150,8 @@ typedef struct odehip_convstack {
                                               whole stack runs as ONE bf16 launch, one workgroup per sample (fstack_bf16.hip)   */
   const float* bias[ODEHIP_MAX_LAYERS];
   int final_tanh;                        /* final_act=True appends Tanh (helpers/utils.py:179-181)  */
+  int act;                               /* hidden activation: 0 = ReLU, 1 = Tanh (create_convnet's nonlinear); a
+                                            non-ReLU activation or a Tanh head excludes w_fused (the fused kernels are ReLU-only) */
 } odehip_convstack;
 
 size_t odehip_convstack_workspace_bytes(const odehip_convstack* f, int batch);

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ODEHIP_LIB") or os.path.join(_HERE, "lib", "libodecgru_hip.so")  # env override: A/B builds
 
-ABI_VERSION = 12   # == odehip_version() of the library these ctypes structs were written against (ODEHIP_ABI_VERSION in the header)
+ABI_VERSION = 13   # == odehip_version() of the library these ctypes structs were written against (ODEHIP_ABI_VERSION in the header)
 MAX_LAYERS = 8
 MAX_STAGES = 7
 EULER, MIDPOINT, RK4, DOPRI5 = 0, 1, 2, 3
@@ -37,6 +37,9 @@ class PackJob(ctypes.Structure):   # odehip_pack_job
                 ("kind", ctypes.c_int), ("transpose_flip", ctypes.c_int)]
 
 
+ACT_RELU, ACT_TANH = 0, 1   # odehip_convstack.act
+
+
 class ConvStack(ctypes.Structure):
     _fields_ = [
         ("n_convs", ctypes.c_int), ("ks", ctypes.c_int),
@@ -47,6 +50,7 @@ class ConvStack(ctypes.Structure):
         ("w_fused", ctypes.c_void_p),
         ("bias", ctypes.c_void_p * MAX_LAYERS),
         ("final_tanh", ctypes.c_int),
+        ("act", ctypes.c_int),   # 0 = ReLU, 1 = Tanh (ACT_RELU / ACT_TANH); sits in final_tanh's tail padding
     ]
 
 

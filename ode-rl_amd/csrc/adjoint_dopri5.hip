@@ -209,8 +209,8 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
     for (int l = 0; l < NH; ++l) hidv[l] = L.hidden(ws, slot, s, l);
     int r = enqueue_f_saving(f, Y, batch, hidv, ping, pong, &cy, nullptr, nullptr, stream);
     if (r != ODEHIP_OK) return r;
-    float* gpv[ODEHIP_MAX_LAYERS];
-    for (int l = 0; l < NL; ++l) gpv[l] = L.gp(ws, slot, s, l);
+    float* gpv[ODEHIP_MAX_LAYERS + 1];
+    for (int l = 0; l < L.NG; ++l) gpv[l] = L.gp(ws, slot, s, l);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.combine = 1;
@@ -284,7 +284,7 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
       WgradPair host[8];
       memset(host, 0, sizeof(host));
       for (int i = 0; i < n_ev; ++i) {
-        host[i].g = L.gp(ws, ev[i].slot, ev[i].stage, l);
+        host[i].g = L.gp(ws, ev[i].slot, ev[i].stage, wgrad_slot(f, l));
         host[i].a = l == 0 ? ev[i].x0 : L.hidden(ws, ev[i].slot, ev[i].stage, l - 1);
         host[i].scale = ev[i].scale;
       }
@@ -528,7 +528,7 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
   std::vector<WgradPair> host(n_eval);
   for (int l = 0; l < NL; ++l) {
     for (int e = 0; e < n_eval; ++e) {
-      host[e].g = L.gp(ws, entries[e].slot, entries[e].stage, l);
+      host[e].g = L.gp(ws, entries[e].slot, entries[e].stage, wgrad_slot(f, l));
       host[e].a = l == 0 ? entries[e].x0 : L.hidden(ws, entries[e].slot, entries[e].stage, l - 1);
       host[e].scale = entries[e].scale;
       host[e].pad_[0] = host[e].pad_[1] = host[e].pad_[2] = 0.0f;

@@ -6,18 +6,18 @@
 namespace odehip {
 
 struct AdjLayout {
-  int T, B, C, NH, max_slots, n_part;
+  int T, B, C, NH, NG, max_slots, n_part;
   size_t st, hid, slot_bytes;
   size_t off_h, off_part, off_sums, off_ping, off_pong, off_y, off_go, off_a2, off_ky, off_ka, off_slots, off_tab, off_slab, off_theta, off_state, off_psync, off_wtab, total;
   int P;  // floats of the flattened parameter vector (w0, b0, w1, b1, ...)
   AdjLayout(const odehip_convstack* f, int batch, int n_times, int max_accept) {
-    T = n_times; B = batch; C = f->channels[0]; NH = f->n_convs - 1; max_slots = max_accept + 1;
+    T = n_times; B = batch; C = f->channels[0]; NH = f->n_convs - 1; NG = grad_slots(f); max_slots = max_accept + 1;
     st = al256((size_t)B * C * kPix * 4);
     int cmax = 32;
     for (int i = 0; i <= f->n_convs; ++i) cmax = f->channels[i] > cmax ? f->channels[i] : cmax;
     hid = al256((size_t)B * cmax * kPix * 4);
     n_part = B * (C / 32) * 2 * 4;
-    slot_bytes = 7 * (st + (size_t)NH * hid + (size_t)(NH + 1) * hid);
+    slot_bytes = 7 * (st + (size_t)NH * hid + (size_t)NG * hid);
     size_t o = 0;
     auto take = [&](size_t b) { size_t r = o; o += al256(b); return r; };
     off_h = take(256);
@@ -48,7 +48,7 @@ struct AdjLayout {
     return p(ws, off_slots + (size_t)slot * slot_bytes + 7 * st + ((size_t)s * NH + l) * hid);
   }
   float* gp(const void* ws, int slot, int s, int l) const {
-    return p(ws, off_slots + (size_t)slot * slot_bytes + 7 * st + 7 * (size_t)NH * hid + ((size_t)s * (NH + 1) + l) * hid);
+    return p(ws, off_slots + (size_t)slot * slot_bytes + 7 * st + 7 * (size_t)NH * hid + ((size_t)s * NG + l) * hid);
   }
   // floats per partial array: the per-layer kernels write n_part, the sixteen-workgroup walk 64 per sample (batch <= 16)
   int part_stride() const { return n_part > 1024 ? n_part : 1024; }
@@ -59,7 +59,7 @@ struct AdjLayout {
 // byte offsets inside a slot (relocatable pointers of the device-driven path are class << 56 | one of these)
 inline size_t adj_off_xin(const AdjLayout& L, int s) { return (size_t)s * L.st; }
 inline size_t adj_off_hidden(const AdjLayout& L, int s, int l) { return 7 * L.st + ((size_t)s * L.NH + l) * L.hid; }
-inline size_t adj_off_gp(const AdjLayout& L, int s, int l) { return 7 * L.st + 7 * (size_t)L.NH * L.hid + ((size_t)s * (L.NH + 1) + l) * L.hid; }
+inline size_t adj_off_gp(const AdjLayout& L, int s, int l) { return 7 * L.st + 7 * (size_t)L.NH * L.hid + ((size_t)s * L.NG + l) * L.hid; }
 
 // adjoint_device.hip: the seminorm adjoint steered by a device-side controller on the adaptive persistent walk; returns
 // ODEHIP_OK and sets *ran = 1 when it took the call, *ran = 0 when the path is not available (the caller then runs the host loop)

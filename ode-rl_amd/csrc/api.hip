@@ -37,17 +37,24 @@ struct Carver {
   }
 };
 
+// activation code of the hidden layers' epilogues (odehip_convstack.act: 0 = ReLU, 1 = Tanh)
+static inline int hidden_act(const odehip_convstack* f) { return f->act == 1 ? kActTanh : kActRelu; }
+
 int check_stack(const odehip_convstack* f) {
   ODEHIP_REQUIRE(f, "convstack: null descriptor");
   ODEHIP_REQUIRE(f->n_convs >= 1 && f->n_convs <= ODEHIP_MAX_LAYERS, "convstack: n_convs %d out of range", f->n_convs);
   ODEHIP_REQUIRE(f->ks == 3 || f->ks == 1 || f->ks == 5, "convstack: kernel size %d unsupported", f->ks);
-  ODEHIP_REQUIRE(!f->final_tanh, "convstack: final_act=True (Tanh head) is not supported by the HIP path");
+  ODEHIP_REQUIRE(f->act == 0 || f->act == 1, "convstack: activation code %d unsupported (0 = ReLU, 1 = Tanh)", f->act);
+  ODEHIP_REQUIRE(f->final_tanh == 0 || f->final_tanh == 1, "convstack: final_tanh must be 0 or 1 (got %d)", f->final_tanh);
+  // the head's reverse sweep evaluates its conv again from the activation in front of it (enqueue_dgrad_chain)
+  ODEHIP_REQUIRE(!f->final_tanh || f->n_convs >= 2, "convstack: a Tanh head needs at least two convs");
   for (int i = 0; i <= f->n_convs; ++i)
     ODEHIP_REQUIRE(f->channels[i] > 0 && f->channels[i] % 32 == 0,
                    "convstack: channels[%d] = %d must be a positive multiple of 32", i, f->channels[i]);
   for (int i = 0; i < f->n_convs; ++i)
     ODEHIP_REQUIRE(f->w_packed[i] && f->bias[i], "convstack: layer %d has null weights/bias", i);
   if (f->w_fused) {
+    ODEHIP_REQUIRE(f->act == 0 && !f->final_tanh, "convstack: the fused bf16 image supports ReLU stacks without a Tanh head only");
     ODEHIP_REQUIRE(f->ks == 3, "convstack: the fused bf16 image needs 3x3 layers");
     for (int i = 0; i <= f->n_convs; ++i)
       ODEHIP_REQUIRE(f->channels[i] == 64, "convstack: the fused bf16 image needs 64-channel layers (channels[%d] = %d)", i, f->channels[i]);
@@ -133,14 +140,15 @@ int enqueue_f_saving(const odehip_convstack* f, const float* x_q4, int batch, fl
     a.batch = batch;
     a.skip = skip;
     if (!last) {
-      a.relu = 1;
+      a.act = hidden_act(f);
       a.dst = hidden ? hidden[l] : ((l & 1) ? pong : ping);
       cur = a.dst;
     } else if (cmb) {
       a.combine = 1;
       a.cmb = *cmb;
+      a.act = f->final_tanh ? kActTanh : kActNone;
     } else {
-      a.relu = 0;
+      a.act = f->final_tanh ? kActTanh : kActNone;
       a.dst = plain_dst;
     }
     int rc = launch_conv(a, f->ks, stream);
@@ -171,18 +179,43 @@ int enqueue_dgrad_chain(const odehip_convstack* f, const odehip_convstack* fd, i
   PersistScope one_chain;  // as in enqueue_f_saving: the chain as one persistent launch
   int rcp = one_chain.begin(f, fd, NL, /*small=*/true);
   if (rcp != ODEHIP_OK) return rcp;
+  if (f->final_tanh) {
+    // Tanh head: gp[NL-1] holds the adjoint of f's output; the chain and the head conv's weight gradient need that of the head's
+    // input, gp[NL-1] * (1 - K^2) with K = tanh(conv_{NL-1}(hidden[NL-2])), written to gp[NL] (wgrad_slot).  K is not saved: the
+    // head's conv runs again here and its epilogue forms the product.  A plain launch: scopes of a reverse sweep over a head stack
+    // never record (PersistScope::begin), so nothing is reordered around it.  (The sign of negated dynamics is applied downstream
+    // of the seed, as without a head; 1 - K^2 does not see it.)
+    ODEHIP_REQUIRE(!one_chain.recording() && !g_conv_recorder, "dgrad chain: a Tanh head inside a recorded reverse sweep");
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src1 = hidden[NL - 2];
+    a.q1 = a.qin = f->channels[NL - 1] / 4;
+    a.qout = f->channels[NL] / 4;
+    a.w_packed = f->w_packed[NL - 1];
+    a.w_wino = f->w_wino[NL - 1];
+    a.w_bf16 = f->w_bf16[NL - 1];
+    a.bias = f->bias[NL - 1];
+    a.dst = gp[NL];
+    a.bwd.mask_src = gp[NL - 1];
+    a.act = kActTanhSeed;
+    a.batch = batch;
+    a.skip = last.skip;
+    int r = launch_conv(a, f->ks, stream);
+    if (r != ODEHIP_OK) return r;
+  }
   for (int l = NL - 1; l >= 0; --l) {
     ConvArgs a;
     if (l > 0) {
       memset(&a, 0, sizeof(a));
       a.combine = 2;
-      a.bwd.mask_src = hidden[l - 1];  // ReLU output that fed conv l
+      a.bwd.mask_src = hidden[l - 1];  // activation output that fed conv l
+      a.act = f->act == 1 ? kActTanh : kActNone;   // its derivative (kActNone: the ReLU mask, as before)
       a.bwd.sc_c = 1.0f;
       a.dst = gp[l - 1];
     } else {
       a = last;
     }
-    a.src1 = gp[l];  // gradient w.r.t. the output of conv l
+    a.src1 = gp[wgrad_slot(f, l)];  // gradient w.r.t. the output of conv l (before a Tanh head)
     a.src2 = nullptr;
     a.q1 = a.qin = f->channels[l + 1] / 4;
     a.qout = f->channels[l] / 4;
@@ -225,7 +258,7 @@ extern "C" int odehip_conv_q4(const odehip_conv_desc* d, void* stream) {
   a.bias = d->bias;
   a.dst = d->dst;
   a.batch = d->batch;
-  a.relu = d->relu;
+  a.act = d->relu ? kActRelu : kActNone;
   return launch_conv(a, d->ks, (hipStream_t)stream);
 }
 

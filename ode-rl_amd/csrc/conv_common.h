@@ -12,6 +12,34 @@ __device__ __forceinline__ float relu_f(float v) { return v < 0.0f ? 0.0f : v; }
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// Forward activation of an epilogue (ConvArgs::act).  kActRelu emits exactly relu_f.  kActTanh is the device library's tanhf:
+// bounded RELATIVE error (no 1 - 2 / (exp(2x) + 1), which loses the digits of small outputs), tanh(NaN) = NaN, tanh(+-inf) = +-1.
+__device__ __forceinline__ f32x4 act_fwd(f32x4 v, int act) {
+  if (act == kActRelu) {
+    v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w);
+  } else if (act == kActTanh) {
+    v.x = tanhf(v.x); v.y = tanhf(v.y); v.z = tanhf(v.z); v.w = tanhf(v.w);
+  }
+  return v;
+}
+// Backward through the activation whose OUTPUT y fed the next conv: g * (1 - y^2) for kActTanh (an explicit fma, so every kernel
+// rounds it alike; NaN in g or y propagates, as in torch's tanh_backward), else the ReLU mask g * (y > 0).
+__device__ __forceinline__ f32x4 act_bwd(f32x4 g, f32x4 y, int act) {
+  if (act == kActTanh) {
+    g.x *= __builtin_fmaf(-y.x, y.x, 1.0f); g.y *= __builtin_fmaf(-y.y, y.y, 1.0f);
+    g.z *= __builtin_fmaf(-y.z, y.z, 1.0f); g.w *= __builtin_fmaf(-y.w, y.w, 1.0f);
+  } else {
+    g.x = y.x > 0.0f ? g.x : 0.0f; g.y = y.y > 0.0f ? g.y : 0.0f;
+    g.z = y.z > 0.0f ? g.z : 0.0f; g.w = y.w > 0.0f ? g.w : 0.0f;
+  }
+  return g;
+}
+// combine-0 store of the per-layer kernels: the activation, or (kActTanhSeed) the Tanh head's backward seed
+__device__ __forceinline__ f32x4 act_store(const ConvArgs& a, size_t off, f32x4 v) {
+  if (a.act == kActTanhSeed) return act_bwd(*(const f32x4*)(a.bwd.mask_src + off), act_fwd(v, kActTanh), kActTanh);
+  return act_fwd(v, a.act);
+}
+
 #define ODEHIP_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 constexpr int kOobOffset = 0x7fff0000;  // beyond any buffer's num_records -> DMA writes zeros
@@ -106,20 +134,13 @@ template <bool ORDER1 = true>
 __device__ __forceinline__ void emit_quad(const ConvArgs& a, int b, int Q, int P, f32x4 v, float& esum, float* nchw_override = nullptr) {
   const size_t off = (((size_t)b * a.qout + Q) * kPix + P) * 4;
   if (a.combine == 0) {
-    if (a.relu) {
-      v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w);
-    }
-    *(f32x4*)(a.dst + off) = v;
+    *(f32x4*)(a.dst + off) = act_store(a, off, v);
     return;
   }
   if (a.combine == 2) {
     const BwdArgs& w = a.bwd;
     v *= w.sc_c + w.sc_h * (w.h_ptr ? *w.h_ptr : 0.0f);
-    if (w.mask_src) {
-      const f32x4 mk = *(const f32x4*)(w.mask_src + off);
-      v.x = mk.x > 0.0f ? v.x : 0.0f; v.y = mk.y > 0.0f ? v.y : 0.0f;
-      v.z = mk.z > 0.0f ? v.z : 0.0f; v.w = mk.w > 0.0f ? v.w : 0.0f;
-    }
+    if (w.mask_src) v = act_bwd(v, *(const f32x4*)(w.mask_src + off), a.act);
     *(f32x4*)(a.dst + off) = v;
     return;
   }
@@ -137,7 +158,7 @@ __device__ __forceinline__ void emit_quad(const ConvArgs& a, int b, int Q, int P
   }
   const CombineArgs& m = a.cmb;
   const float h = m.h_ptr ? *m.h_ptr : 1.0f;
-  const f32x4 kc = v * m.k_scale;
+  const f32x4 kc = act_fwd(v, a.act) * m.k_scale;   // (a Tanh head before the sign of backwards=True / reversed time)
   if (m.k_out) *(f32x4*)(m.k_out + off) = kc;
   if constexpr (ORDER1) {
     if (m.y && m.order) {
@@ -246,12 +267,9 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, const f32x16& acc, i
   if (!a.combine) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      f32x4 v = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-      if (a.relu) {
-        v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w);
-      }
+      const f32x4 v = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
       const size_t off = (((size_t)b * a.qout + ct * 8 + 2 * g + kq) * kPix + P) * 4;
-      *(f32x4*)(a.dst + off) = v;
+      *(f32x4*)(a.dst + off) = act_store(a, off, v);
     }
     return;
   }
@@ -265,11 +283,7 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, const f32x16& acc, i
         const size_t off = (((size_t)b * a.qout + ct * 8 + 2 * g + kq) * kPix + P) * 4;
         f32x4 v = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
         v *= sc;
-        if (w.mask_src) {
-          const f32x4 mk = *(const f32x4*)(w.mask_src + off);
-          v.x = mk.x > 0.0f ? v.x : 0.0f; v.y = mk.y > 0.0f ? v.y : 0.0f;
-          v.z = mk.z > 0.0f ? v.z : 0.0f; v.w = mk.w > 0.0f ? v.w : 0.0f;
-        }
+        if (w.mask_src) v = act_bwd(v, *(const f32x4*)(w.mask_src + off), a.act);
         *(f32x4*)(a.dst + off) = v;
       }
       return;
@@ -296,7 +310,7 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, const f32x16& acc, i
     const int Q = ct * 8 + 2 * g + kq;
     const size_t off = (((size_t)b * a.qout + Q) * kPix + P) * 4;
     f32x4 kc = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-    kc *= m.k_scale;
+    kc = act_fwd(kc, a.act) * m.k_scale;   // (a Tanh head before the sign)
     if (m.k_out) *(f32x4*)(m.k_out + off) = kc;
     if (m.y && m.order) {
       combine1_tail(m, b, a.qout, Q, P, off, kc, *(const f32x4*)(m.y + off), h, combine1_prev(m, off), esum, m.out2_nchw);

@@ -293,7 +293,7 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
   // very lane at least one layer ago) are fetched now, behind the wait for the first chunk -- after the last MFMA there is only
   // arithmetic and stores left.  (Read from the table at that point they cost a scalar-cache miss each, one after the other.)
   const int tile = thh * 16 + i16, oty = tile >> 3, otx = tile & 7;
-  int e_combine = 0, e_relu = 0, e_np = 0;
+  int e_combine = 0, e_act = 0, e_np = 0;
   float* e_dst = nullptr;
   float* e_kout = nullptr;
   float* e_out1 = nullptr;
@@ -313,7 +313,7 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
     typedef const __attribute__((address_space(4))) float ConstF;
     const unsigned long long* const rl = hk.reloc;   // relocatable pointers (rel()): every pointer of the reduced paths below is
                                                      // resolved here; rows that fall to the shared epilogue (kind 5) must not carry any
-    e_relu = a.relu;
+    e_act = a.act;
     e_dst = rel(rl, a.dst);
     d_kind = a.combine == 0 ? 0 : 5;
     if (a.combine == 2) {
@@ -407,7 +407,7 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
     }
   } else if (PERSIST) {
     e_combine = a.combine;
-    e_relu = a.relu;
+    e_act = a.act;
     e_dst = a.dst;
     // a table whose step size only exists on the device (dopri5: h_by_value == 0) takes the shared epilogue for its
     // stage-combine / reverse layers; ReLU-mask layers of such a table read *h_ptr here
@@ -505,19 +505,12 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
   auto emit_pre = [&](int q, int P, f32x4 v) {
     const size_t off = (((size_t)b * QOUT + Q) * kPix + P) * 4;
     if (!e_combine) {
-      if (e_relu) {
-        v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w);
-      }
-      *(f32x4*)(e_dst + off) = v;
+      *(f32x4*)(e_dst + off) = act_fwd(v, e_act);
       return;
     }
     if (e_combine == 2) {
       v *= e_ks;
-      if (e_y) {
-        const f32x4 mk = e_yv[q];
-        v.x = mk.x > 0.0f ? v.x : 0.0f; v.y = mk.y > 0.0f ? v.y : 0.0f;
-        v.z = mk.z > 0.0f ? v.z : 0.0f; v.w = mk.w > 0.0f ? v.w : 0.0f;
-      }
+      if (e_y) v = act_bwd(v, e_yv[q], e_act);
       *(f32x4*)(e_dst + off) = v;
       return;
     }
@@ -525,7 +518,7 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
       emit_quad<false>(a, b, Q, P, v, esum);
       return;
     }
-    const f32x4 kc = v * e_ks;
+    const f32x4 kc = act_fwd(v, e_act) * e_ks;   // (a Tanh head before the sign)
     if (e_kout) *(f32x4*)(e_kout + off) = kc;
     if (e_y) {
       // a stage writes EITHER the next stage input (out1) OR the step result (out2, + its NCHW frame): only the sum that is stored is
@@ -555,20 +548,13 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
   auto emit_adapt = [&](int q, int P, f32x4 v) {
     const size_t off = (((size_t)b * QOUT + Q) * kPix + P) * 4;
     if (d_kind == 0) {
-      if (e_relu) {
-        v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w);
-      }
-      *(f32x4*)(e_dst + off) = v;
+      *(f32x4*)(e_dst + off) = act_fwd(v, e_act);
     } else if (d_kind == 2) {
       v *= d_ks;
-      if (d_has_y) {
-        const f32x4 mk = d_y[q];
-        v.x = mk.x > 0.0f ? v.x : 0.0f; v.y = mk.y > 0.0f ? v.y : 0.0f;
-        v.z = mk.z > 0.0f ? v.z : 0.0f; v.w = mk.w > 0.0f ? v.w : 0.0f;
-      }
+      if (d_has_y) v = act_bwd(v, d_y[q], e_act);
       *(f32x4*)(e_dst + off) = v;
     } else if (d_kind == 1) {
-      const f32x4 kc = v * d_ks;
+      const f32x4 kc = act_fwd(v, e_act) * d_ks;   // (a Tanh head before the sign)
       if (d_o[0]) *(f32x4*)(d_o[0] + off) = kc;
       if (d_has_y) {
         if (d_o[1]) *(f32x4*)(d_o[1] + off) = fma4(fma4(kc, d_cA, d_sa[q]), d_h, d_y[q]);
@@ -1195,7 +1181,7 @@ __device__ __forceinline__ void wino_layer16(const float* __restrict__ p_src, co
   const bool adapt1 = a.combine == 1 && a.cmb.order == 1 && !(a.cmb.err_partials && (a.cmb.out2 || a.dbg));
   const bool adapt3 = a.combine == 3 && a.bwd.n_targets <= 2 && !a.bwd.h_ptr;
   const int e_combine = adapt1 ? 6 : (adapt3 ? 7 : a.combine);
-  const int e_relu = a.relu;
+  const int e_act = a.act;
   float* const e_dst = rel(rl, a.dst);
   f32x4 d_y1 = {0.f, 0.f, 0.f, 0.f}, d_sa = {0.f, 0.f, 0.f, 0.f}, d_sb = {0.f, 0.f, 0.f, 0.f};
   float d_cB = 0.0f, d_rtol = 0.0f, d_atol = 0.0f, d_t[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -1330,22 +1316,16 @@ __device__ __forceinline__ void wino_layer16(const float* __restrict__ p_src, co
     }
   }
   if (!e_combine) {
-    if (e_relu) {
-      val.x = relu_f(val.x); val.y = relu_f(val.y); val.z = relu_f(val.z); val.w = relu_f(val.w);
-    }
-    *(f32x4*)(e_dst + off) = val;
+    *(f32x4*)(e_dst + off) = act_fwd(val, e_act);
   } else if (e_combine == 2) {
     val *= e_ks;
-    if (e_y) {
-      val.x = e_yv.x > 0.0f ? val.x : 0.0f; val.y = e_yv.y > 0.0f ? val.y : 0.0f;
-      val.z = e_yv.z > 0.0f ? val.z : 0.0f; val.w = e_yv.w > 0.0f ? val.w : 0.0f;
-    }
+    if (e_y) val = act_bwd(val, e_yv, e_act);
     *(f32x4*)(e_dst + off) = val;
   } else if (e_combine == 3) {   // reverse-sweep targets: the shared epilogue, read from the table
     float esum = 0.0f;
     emit_quad<false>(a, b, Q, P, val, esum);
   } else if (e_combine == 6) {
-    const f32x4 kc = val * e_ks;
+    const f32x4 kc = act_fwd(val, e_act) * e_ks;   // (a Tanh head before the sign)
     if (e_kout) *(f32x4*)(e_kout + off) = kc;
     if (e_y) {
       if (e_out1) *(f32x4*)(e_out1 + off) = fma4(fma4(kc, e_c1c, d_sa), e_h, e_yv);
@@ -1380,7 +1360,7 @@ __device__ __forceinline__ void wino_layer16(const float* __restrict__ p_src, co
       *(f32x4*)(d_o[1] + off) = o;
     }
   } else {
-    const f32x4 kc = val * e_ks;
+    const f32x4 kc = act_fwd(val, e_act) * e_ks;   // (a Tanh head before the sign)
     if (e_kout) *(f32x4*)(e_kout + off) = kc;
     if (e_y) {
       if (e_out1) {

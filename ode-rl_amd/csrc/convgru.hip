@@ -145,7 +145,7 @@ static int conv_layer(const float* src1, const float* src2, int cin1, int cin, i
   a.bias = bias;
   a.dst = dst;
   a.batch = batch;
-  a.relu = relu;
+  a.act = relu ? kActRelu : kActNone;
   return launch_conv(a, ks, stream);
 }
 

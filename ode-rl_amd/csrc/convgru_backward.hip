@@ -254,14 +254,14 @@ int check_cell_desc(const odehip_convgru_cell* c);
 
 // Workspace of the training path; one place knows where everything lives.
 struct EncLayout {
-  int T, B, C, NH, HH, OUT2;
+  int T, B, C, NH, NG, HH, OUT2;
   size_t hs, fh, hh, ho;
   size_t off_dts, off_frames, off_ping, off_pong, off_hstate, off_hidden, off_hode, off_gates, off_z, off_rh, off_cand, off_headhid,
       off_headout;
   size_t off_gp, off_ggates, off_gcand, off_gx, off_gzpre, off_ghode, off_gxc, off_grh, off_gh, off_gheadout, off_gheadhid, off_pgg,
       off_pgc, off_tab, off_slab, total;
   EncLayout(const odehip_encoder* e, int n_frames, int batch) {
-    T = n_frames; B = batch; C = e->cell.hidden; NH = e->f_enc.n_convs - 1; HH = e->head_hidden; OUT2 = 2 * e->out_ch;
+    T = n_frames; B = batch; C = e->cell.hidden; NH = e->f_enc.n_convs - 1; NG = grad_slots(&e->f_enc); HH = e->head_hidden; OUT2 = 2 * e->out_ch;
     hs = al256((size_t)B * C * kPix * 4);
     int cmax = 32;
     for (int i = 0; i <= e->f_enc.n_convs; ++i) cmax = e->f_enc.channels[i] > cmax ? e->f_enc.channels[i] : cmax;
@@ -283,7 +283,7 @@ struct EncLayout {
     off_cand = take((size_t)T * hs);
     off_headhid = take(hh);
     off_headout = take(ho);
-    off_gp = take((size_t)T * (NH + 1) * fh);
+    off_gp = take((size_t)T * NG * fh);
     off_ggates = take((size_t)T * 2 * hs);
     off_gcand = take((size_t)T * hs);
     off_gx = take((size_t)T * hs);
@@ -304,7 +304,7 @@ struct EncLayout {
   float* frame(void* ws, int i) const { return p(ws, off_frames + (size_t)i * hs); }
   float* hstate(void* ws, int k) const { return p(ws, off_hstate + (size_t)k * hs); }
   float* hidden(void* ws, int idx, int l) const { return p(ws, off_hidden + ((size_t)idx * NH + l) * fh); }
-  float* gp(void* ws, int idx, int l) const { return p(ws, off_gp + ((size_t)idx * (NH + 1) + l) * fh); }
+  float* gp(void* ws, int idx, int l) const { return p(ws, off_gp + ((size_t)idx * NG + l) * fh); }
   float* per(void* ws, size_t off, int idx, size_t bytes) const { return p(ws, off + (size_t)idx * bytes); }
 };
 
@@ -495,9 +495,9 @@ extern "C" int odehip_odeconvgru_encode_backward(const odehip_encoder* e, const 
     if ((rc = conv_bwd(g_gates, 2 * C, C, ks, eb->w_gates_dh, 3, &w, nullptr, eb->bf16[1], eb->wino[1])) != ODEHIP_OK) return rc;
     // h_ode = h + dt f(h):  gh = seed + dt J_f(h)^T seed
     {
-      float* gpv[ODEHIP_MAX_LAYERS];
+      float* gpv[ODEHIP_MAX_LAYERS + 1];
       const float* hv[ODEHIP_MAX_LAYERS];
-      for (int l = 0; l < NL; ++l) gpv[l] = L.gp(ws, idx, l);
+      for (int l = 0; l < L.NG; ++l) gpv[l] = L.gp(ws, idx, l);
       for (int l = 0; l + 1 < NL; ++l) hv[l] = L.hidden(ws, idx, l);
       ConvArgs a;
       memset(&a, 0, sizeof(a));
@@ -528,7 +528,7 @@ extern "C" int odehip_odeconvgru_encode_backward(const odehip_encoder* e, const 
   for (int l = 0; l < NL; ++l)   // encoder dynamics (3x3), weight of frame idx = its Euler dt
     for (int idx = 0; idx < T; ++idx) {
       WgradPair& h = host[(size_t)l * T + idx];
-      h.g = L.gp(ws, idx, l);
+      h.g = L.gp(ws, idx, wgrad_slot(&e->f_enc, l));
       h.a = l == 0 ? L.hstate(ws, idx) : L.hidden(ws, idx, l - 1);
       h.scale = frame_dt(t_host, T, idx, run_backwards);
     }

@@ -224,9 +224,9 @@ static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_
 
   // ---- 2. reverse sweep ------------------------------------------------------------------------------------------------------
   auto chain = [&](int n, int s, const BwdArgs& last) -> int {  // J_f(Y)^T seed, seed = gp[n][s][NH]
-    float* gpv[ODEHIP_MAX_LAYERS];
+    float* gpv[ODEHIP_MAX_LAYERS + 1];
     const float* hv[ODEHIP_MAX_LAYERS];
-    for (int l = 0; l < NL; ++l) gpv[l] = L.gp(ws, n, s, l);
+    for (int l = 0; l < L.NG; ++l) gpv[l] = L.gp(ws, n, s, l);
     for (int l = 0; l + 1 < NL; ++l) hv[l] = L.hidden(ws, n, s, l);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
@@ -331,7 +331,7 @@ static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_
     for (int n = 0; n < N; ++n)
       for (int s = (n == 0 ? 0 : 1); s < 7; ++s, ++e) {
         WgradPair& hp = host[(size_t)l * n_eval + e];
-        hp.g = L.gp(ws, n, s, l);
+        hp.g = L.gp(ws, n, s, wgrad_slot(f, l));
         hp.a = l == 0 ? L.xin(ws, n, s) : L.hidden(ws, n, s, l - 1);
         hp.scale = 1.0f;
         hp.pad_[0] = hp.pad_[1] = hp.pad_[2] = 0.0f;

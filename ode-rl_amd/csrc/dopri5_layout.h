@@ -8,16 +8,16 @@
 namespace odehip {
 
 struct BwdLayout {
-  int T, B, C, NH, N;
+  int T, B, C, NH, NG, N;
   size_t st, hid, slot_bytes;
   size_t off_h, off_ping, off_pong, off_go, off_k, off_gY, off_gy, off_gk1, off_slots, off_tab, off_psync, off_slab, total;
   BwdLayout(const odehip_convstack* f, int batch, int n_times, int n_steps) {
-    T = n_times; B = batch; C = f->channels[0]; NH = f->n_convs - 1; N = n_steps;
+    T = n_times; B = batch; C = f->channels[0]; NH = f->n_convs - 1; NG = grad_slots(f); N = n_steps;
     st = al256((size_t)B * C * kPix * 4);
     int cmax = 32;
     for (int i = 0; i <= f->n_convs; ++i) cmax = f->channels[i] > cmax ? f->channels[i] : cmax;
     hid = al256((size_t)B * cmax * kPix * 4);
-    slot_bytes = 7 * (st + (size_t)NH * hid + (size_t)(NH + 1) * hid);
+    slot_bytes = 7 * (st + (size_t)NH * hid + (size_t)NG * hid);
     size_t o = 0;
     auto take = [&](size_t b) { size_t r = o; o += al256(b); return r; };
     off_h = take((size_t)(N > 0 ? N : 1) * 4);
@@ -40,7 +40,7 @@ struct BwdLayout {
     return p(ws, off_slots + (size_t)n * slot_bytes + 7 * st + ((size_t)s * NH + l) * hid);
   }
   float* gp(const void* ws, int n, int s, int l) const {
-    return p(ws, off_slots + (size_t)n * slot_bytes + 7 * st + 7 * (size_t)NH * hid + ((size_t)s * (NH + 1) + l) * hid);
+    return p(ws, off_slots + (size_t)n * slot_bytes + 7 * st + 7 * (size_t)NH * hid + ((size_t)s * NG + l) * hid);
   }
 };
 

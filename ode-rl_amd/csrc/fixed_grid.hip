@@ -30,12 +30,12 @@ constexpr int kEsplit = 4;
 
 // Everything lives in the caller's workspace; this is the one place that knows where.
 struct FixedLayout {
-  int T, B, C, S, NH, save;  // NH = hidden activations per evaluation of f (n_convs - 1)
+  int T, B, C, S, NH, NG, save;  // NH = hidden activations per evaluation of f (n_convs - 1); NG = gradient slots (grad_slots)
   size_t st;                 // bytes of one (B,C,16,16) tensor
   size_t hid;                // bytes of one hidden activation (B,max_hidden,16,16)
   size_t off_h, off_ping, off_pong, off_xs, off_k, off_y, off_xin, off_hid, off_gp, off_go, off_gy, off_g2, off_tab, off_slab, off_psync, total;
   FixedLayout(const odehip_convstack* f, int batch, int n_times, int method, int save_) {
-    T = n_times; B = batch; C = f->channels[0]; S = n_stages(method); NH = f->n_convs - 1; save = save_;
+    T = n_times; B = batch; C = f->channels[0]; S = n_stages(method); NH = f->n_convs - 1; NG = grad_slots(f); save = save_;
     st = al256((size_t)B * C * kPix * 4);
     int cmax = 32;
     for (int i = 0; i <= f->n_convs; ++i) cmax = f->channels[i] > cmax ? f->channels[i] : cmax;
@@ -54,7 +54,7 @@ struct FixedLayout {
       const size_t ne = (size_t)(T - 1) * S;
       off_xin = take(ne * st);             // stage inputs (slot s = 0 unused: it is y[n])
       off_hid = take(ne * NH * hid);       // ReLU outputs of every evaluation
-      off_gp = take(ne * (NH + 1) * hid);  // gradients w.r.t. every conv output (filled by the backward sweep)
+      off_gp = take(ne * NG * hid);        // gradients w.r.t. every conv output (filled by the backward sweep)
       off_go = take((size_t)T * st);       // grad_out in Q4
       off_gy = take(st);
       off_g2 = take(2 * st);
@@ -67,7 +67,7 @@ struct FixedLayout {
   float* y(void* ws, int n) const { return p(ws, off_y + (size_t)n * st); }
   float* xin(void* ws, int n, int s) const { return s == 0 ? y(ws, n) : p(ws, off_xin + ((size_t)n * S + s) * st); }
   float* hidden(void* ws, int n, int s, int l) const { return p(ws, off_hid + (((size_t)n * S + s) * NH + l) * hid); }
-  float* gp(void* ws, int n, int s, int l) const { return p(ws, off_gp + (((size_t)n * S + s) * (NH + 1) + l) * hid); }
+  float* gp(void* ws, int n, int s, int l) const { return p(ws, off_gp + (((size_t)n * S + s) * NG + l) * hid); }
   float* go(void* ws, int j) const { return p(ws, off_go + (size_t)j * st); }
 };
 
@@ -131,7 +131,7 @@ static int wgrad_all_layers(const odehip_convstack* f, const FixedLayout& L, voi
     for (int e = 0; e < n_eval; ++e) {
       const int n = e / S, s = e % S;
       WgradPair& p = host[(size_t)l * n_eval + e];
-      p.g = L.gp(ws, n, s, l);
+      p.g = L.gp(ws, n, s, wgrad_slot(f, l));
       p.a = l > 0 ? L.hidden(ws, n, s, l - 1) : (s > 0 ? L.xin(ws, n, s) : L.y(ws, adjoint ? n + 1 : n));
       p.scale = eval_scale ? eval_scale[e] : 1.0f;
       p.pad_[0] = p.pad_[1] = p.pad_[2] = 0.0f;
@@ -452,9 +452,9 @@ extern "C" int odehip_odeint_fixed_backward(const odehip_convstack* f, const ode
 
   // dgrad chain of evaluation (n, s): GP[n][s][NH] (gradient w.r.t. k) -> ... -> gx, consumed by `targets`
   auto chain = [&](int n, int s, const BwdArgs& last) -> int {
-    float* gpv[ODEHIP_MAX_LAYERS];
+    float* gpv[ODEHIP_MAX_LAYERS + 1];
     const float* hv[ODEHIP_MAX_LAYERS];
-    for (int l = 0; l < NL; ++l) gpv[l] = L.gp(ws, n, s, l);
+    for (int l = 0; l < L.NG; ++l) gpv[l] = L.gp(ws, n, s, l);
     for (int l = 0; l + 1 < NL; ++l) hv[l] = L.hidden(ws, n, s, l);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
@@ -617,9 +617,9 @@ extern "C" int odehip_odeint_adjoint_backward(const odehip_convstack* f, const o
     return enqueue_f_saving(f, x, batch, hidv, ping, pong, &c, nullptr, nullptr, stream);
   };
   auto chain = [&](int n, int s, const BwdArgs& last) -> int {  // K^a = J_f(Y_s)^T A_s, A_s = GP[n][s][NH]
-    float* gpv[ODEHIP_MAX_LAYERS];
+    float* gpv[ODEHIP_MAX_LAYERS + 1];
     const float* hv[ODEHIP_MAX_LAYERS];
-    for (int l = 0; l < NL; ++l) gpv[l] = L.gp(ws, n, s, l);
+    for (int l = 0; l < L.NG; ++l) gpv[l] = L.gp(ws, n, s, l);
     for (int l = 0; l + 1 < NL; ++l) hv[l] = L.hidden(ws, n, s, l);
     ConvArgs a;
     memset(&a, 0, sizeof(a));

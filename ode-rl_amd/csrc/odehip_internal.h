@@ -29,6 +29,14 @@ int hip_fail(hipError_t e, const char* what);
     }                                        \
   } while (0)
 
+// ---- activation codes of ConvArgs::act
+constexpr int kActNone = 0;
+constexpr int kActRelu = 1;
+constexpr int kActTanh = 2;
+// reverse sweep of a Tanh head (combine 0 only, per-layer kernels only): the head's conv is evaluated again and
+// dst = bwd.mask_src * (1 - tanh(conv)^2), in place (dst == mask_src: the adjoint of f's output becomes that of the head's input)
+constexpr int kActTanhSeed = 3;
+
 // ---- stage-combine epilogue of the LAST conv of f (Runge-Kutta bookkeeping fused in) -------
 // k_cur = conv output.  Optional outputs, all Q4 unless stated:
 //   k_out             <- k_cur
@@ -71,6 +79,7 @@ struct CombineArgs {
 
 // ---- epilogues of the input-gradient (dgrad) convolutions of the backward sweep
 //   combine == 2: dst = scale * acc * (mask_src > 0)            (ReLU backward fused; scale = sc_c + sc_h*h)
+//                 dst = scale * acc * (1 - mask_src^2)          (act == kActTanh: Tanh backward; mask_src = the Tanh output)
 //   combine == 3: gx = acc; up to 4 targets  out_t = (a_c+a_h*h)*srcA_t + (b_c+b_h*h)*srcB_t + (g_c+g_h*h)*gx
 //                 (the reverse Runge-Kutta bookkeeping: gy += gx, gk_j += c*h*gx, next interval's seed, ...)
 struct BwdTarget {
@@ -99,8 +108,9 @@ struct ConvArgs {
   int qin;     // total input quads
   int qout;    // output quads (cout / 4)
   int batch;
-  int relu;
-  int combine; // 0: plain store (+relu); 1: CombineArgs epilogue; 2/3: BwdArgs epilogues; 4: elementwise row (no conv; see above);
+  int act;     // activation code (kAct*): combine 0 / 1 apply it to the conv output (bias included) before the store / stage combine;
+               // combine 2 takes the derivative of the layer it masks from it (kActTanh: g * (1 - y^2), else the ReLU mask)
+  int combine; // 0: plain store (+act); 1: CombineArgs epilogue; 2/3: BwdArgs epilogues; 4: elementwise row (no conv; see above);
                // 5: norm row (adaptive walk only): err_partials <- per-wave sums of ((k_prev[0] - k_prev[1]) / (atol + |y| rtol))^2
   int debug;   // diagnostic ablation bits (tools/conv_microbench.py): 1 skip DMA, 2 skip MFMA, 4 skip epilogue
   int h_by_value;  // persistent tables of fixed-grid drivers: cmb.atol holds the step size itself (read instead of *h_ptr)
@@ -164,6 +174,11 @@ extern unsigned long long* g_debug_buf;
 static inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 
 int check_stack(const odehip_convstack* f);
+// Gradient slots per evaluation in the backward layouts: one per conv output (n_convs), plus, with a Tanh head, the head's masked
+// seed gp * (1 - K^2) (slot n_convs; written by enqueue_dgrad_chain).  Stacks without a head keep their layouts byte for byte.
+inline int grad_slots(const odehip_convstack* f) { return f->n_convs + (f->final_tanh ? 1 : 0); }
+// the gradient slot the weight gradient of layer l reads: its output's, or for a Tanh head's conv the masked seed
+inline int wgrad_slot(const odehip_convstack* f, int l) { return (f->final_tanh && l == f->n_convs - 1) ? f->n_convs : l; }
 // every layer 64 -> 64, 3x3: the stacks the adaptive persistent walk takes (their adaptive drivers write order-1 stage combines)
 inline bool all_64(const odehip_convstack* f) {
   if (f->ks != 3) return false;
@@ -183,8 +198,10 @@ int enqueue_f(const odehip_convstack* f, const float* x_q4, int batch, float* pi
 int enqueue_f_saving(const odehip_convstack* f, const float* x_q4, int batch, float* const* hidden, float* ping, float* pong,
                      const CombineArgs* cmb, float* plain_dst, const int* skip, hipStream_t stream);
 
-// Input-gradient chain of one evaluation of f: gp[n_convs-1] holds the gradient w.r.t. f's output; for l = n_convs-1 .. 1 the
-// gradient w.r.t. conv l's input is masked with hidden[l-1] (ReLU) and written to gp[l-1]; conv 0 ends in `last` (combine 3
+// Input-gradient chain of one evaluation of f: gp[n_convs-1] holds the gradient w.r.t. f's output; with a Tanh head it is first
+// turned into that of the head's input, written to gp[n_convs] (grad_slots(f) entries; gp[n_convs-1] is left as it was: drivers
+// read it again, e.g. as the adjoint state); for l = n_convs-1 .. 1 the
+// gradient w.r.t. conv l's input is masked with hidden[l-1] (the activation's derivative) and written to gp[l-1]; conv 0 ends in `last` (combine 3
 // with last.bwd, or combine 1 with last.cmb; its src/weights/shape fields are filled here).  One fused bf16 launch when
 // f_dgrad carries a fused image, else one launch per layer.
 int enqueue_dgrad_chain(const odehip_convstack* f, const odehip_convstack* f_dgrad, int batch, float* const* gp,

@@ -69,6 +69,7 @@ static bool persist_available() {
 //    written in order 1 (the adaptive solver's drivers)
 static int persist_layer_kind(const ConvArgs& a) {
   if (a.combine == 4 || a.combine == 5) return a.qout == 16 && !a.src2 ? 3 : 0;   // elementwise / norm rows
+  if (a.act == kActTanhSeed) return 0;   // per-layer kernels only
   if (!a.w_wino || a.w_bf16 || a.src2 || a.q1 != a.qin || a.combine < 0 || a.combine > 3) return 0;
   if (a.qin == 16 && a.qout == 16) return (a.combine == 1 && a.cmb.order == 1) ? 3 : 1;
   if ((a.qin == 32 && a.qout == 16) || (a.qin == 16 && a.qout == 32)) return 2;
@@ -255,6 +256,8 @@ PersistScope::~PersistScope() {
 int PersistScope::begin(const odehip_convstack* f, const odehip_convstack* f2, int max_layers, bool small) {
     small_ = small;
     if (small && (g_conv_recorder || max_layers > 5)) return ODEHIP_OK;  // inside an outer scope: its recorder takes the layers
+    // a reverse sweep over a Tanh head runs its seed rows (kActTanhSeed, enqueue_dgrad_chain) as plain per-layer launches: not recorded
+    if (f2 && f->final_tanh) return ODEHIP_OK;
     // ODEHIP_EVAL_WALK=1: the <= 5 layers of a single evaluation / input-gradient chain (the encoder loop's Euler step and its
     // backward) as ONE launch of the TRAJECTORY walks -- wino_persist_kernel, or the sixteen-workgroup walk up to batch 16 -- instead
     // of the round-2 single-evaluation kernel below (9.5 us per layer against 7.5 / 3.3): the table goes up through the volatile

@@ -332,9 +332,10 @@ class PackedConvStack:
     """Packed weights of a `create_convnet` Sequential, refreshed when the live Parameters change
     (the optimizer updates them in place between calls: SURVEY.md section 8b, ownership)."""
 
-    def __init__(self, convs, final_tanh=False):
+    def __init__(self, convs, final_tanh=False, act=_lib.ACT_RELU):
         self.convs = list(convs)
         self.final_tanh = bool(final_tanh)
+        self.act = int(act)   # hidden activation (_lib.ACT_RELU / ACT_TANH)
         self._cache = {}      # compute dtype -> dict(stamp, desc, keep, dgrad)
         self._bias = None
         self.desc = None
@@ -342,8 +343,17 @@ class PackedConvStack:
     def _current_stamp(self):
         return tuple((c.weight.data_ptr(), c.weight._version, c.bias.data_ptr(), c.bias._version) for c in self.convs)
 
+    @property
+    def relu_only(self):
+        """ReLU between the convs and no Tanh head: the only stacks the bf16 kernels implement."""
+        return self.act == _lib.ACT_RELU and not self.final_tanh
+
     def refresh(self, mode=None):
         mode = mode or current_compute_dtype()
+        if mode == "bf16" and not self.relu_only:   # checked per call: the compute dtype can change between calls on a cached stack
+            raise TypeError("bf16 compute (set_compute_dtype('bf16') or autocast) supports ReLU dynamics without a Tanh head only; "
+                            "this stack has " + ("Tanh hidden layers" if self.act != _lib.ACT_RELU else "a Tanh head") +
+                            ": run it in fp32")
         stamp = self._current_stamp()
         ent = self._cache.get(mode)
         if ent is not None and ent["stamp"] == stamp:
@@ -368,7 +378,7 @@ class PackedConvStack:
         bf16 = [pack_conv_weight_bf16(c.weight) if mode == "bf16" and _bf16_ok(c.in_channels, c.out_channels, ks) else None
                 for c in convs]
         bias = [c.bias.detach().contiguous() for c in convs]
-        fused = pack_fused_bf16(convs) if mode == "bf16" and _fusable(convs, ks) else None
+        fused = pack_fused_bf16(convs) if mode == "bf16" and self.relu_only and _fusable(convs, ks) else None
         d = _lib.ConvStack()
         d.w_fused = fused.data_ptr() if fused is not None else None
         d.n_convs = len(convs)
@@ -381,6 +391,7 @@ class PackedConvStack:
             d.w_bf16[i] = bf16[i].data_ptr() if bf16[i] is not None else None
             d.bias[i] = bias[i].data_ptr()
         d.final_tanh = int(self.final_tanh)
+        d.act = self.act
         self._cache[mode] = dict(stamp=stamp, desc=d, keep=(packed, wino, bf16, fused), bias=bias, dgrad=None)
         self.desc, self._bias = d, bias
         return d
@@ -398,10 +409,12 @@ class PackedConvStack:
             wino = [next(rest) if ww else None for ww in want_wino]
             bf16 = [pack_conv_weight_bf16(c.weight, transpose_flip=True)
                     if mode == "bf16" and _bf16_ok(c.out_channels, c.in_channels, d0.ks) else None for c in self.convs]
-            fused = pack_fused_bf16(self.convs, reverse_transposed=True) if mode == "bf16" and _fusable(self.convs, d0.ks) else None
+            fused = (pack_fused_bf16(self.convs, reverse_transposed=True)
+                     if mode == "bf16" and self.relu_only and _fusable(self.convs, d0.ks) else None)
             d = _lib.ConvStack()
             d.w_fused = fused.data_ptr() if fused is not None else None
             d.n_convs, d.ks = d0.n_convs, d0.ks
+            d.final_tanh, d.act = d0.final_tanh, d0.act
             for i in range(len(self.convs) + 1):
                 d.channels[i] = d0.channels[i]
             for i, p in enumerate(packed):

@@ -2,7 +2,8 @@
 consumes (/root/reference/modules/DiffEqSolver.py:37,45-46), executed by the HIP library.
 
 Supported `func`: an `ODEFunc` (or any module exposing `gradient_net`, an nn.Sequential of stride-1
-'same' Conv2d layers separated by ReLU, as built by `helpers.utils.create_convnet`).  The dynamics are
+'same' Conv2d layers separated by ReLU or by Tanh, optionally followed by one Tanh head, as built by
+`helpers.utils.create_convnet` with nonlinear='relu' / 'tanh' and final_act=False / True).  The dynamics are
 autonomous (`ODEFunc.forward` ignores t: modules/DiffEqSolver.py:77), so `t` only sets step sizes.
 
 Semantics follow torchdiffeq 0.2.1: solution[0] = y0, float64 time, 'rk4' = 3/8 rule with one step per
@@ -11,7 +12,7 @@ output interval, strictly decreasing t integrates the negated dynamics on -t.
 import torch
 import torch.nn as nn
 
-from . import hip_ops
+from . import _lib, hip_ops
 
 FIXED_GRID = ("euler", "midpoint", "rk4")
 last_stats = hip_ops.LazyStats()  # nfe / n_accept / n_reject of the most recent dopri5 call (instrumentation; fills itself after an asynchronous solve)
@@ -37,24 +38,25 @@ def conv_stack_of(func):
     if net is None and isinstance(func, nn.Sequential):
         net = func
     if not isinstance(net, nn.Sequential):
-        raise TypeError("odeint(HIP): `func` must expose `gradient_net` (nn.Sequential of Conv2d/ReLU as built by "
+        raise TypeError("odeint(HIP): `func` must expose `gradient_net` (nn.Sequential of Conv2d/ReLU/Tanh as built by "
                         "create_convnet); arbitrary Python dynamics are not supported and there is no CPU fallback")
-    convs, final_tanh = [], False
+    # create_convnet: conv, act, conv, act, ..., conv [, Tanh]  with act all ReLU or all Tanh (helpers/utils.py, nonlinear=)
     mods = list(net)
-    for i, m in enumerate(mods):
-        if isinstance(m, nn.Conv2d):
-            convs.append(m)
-        elif isinstance(m, nn.ReLU):
-            continue
-        elif isinstance(m, nn.Tanh) and i == len(mods) - 1:
-            final_tanh = True
-        else:
-            raise TypeError(f"odeint(HIP): unsupported layer {m} in gradient_net (Conv2d/ReLU only)")
-    # create_convnet alternates conv, act, conv, ... : every conv but the last is followed by ReLU
-    for i, m in enumerate(mods[:-1]):
-        if isinstance(m, nn.Conv2d) and not isinstance(mods[i + 1], nn.ReLU):
-            raise TypeError("odeint(HIP): every hidden Conv2d must be followed by ReLU")
-    stack = hip_ops.PackedConvStack(convs, final_tanh)
+    final_tanh = len(mods) > 1 and isinstance(mods[-1], nn.Tanh) and isinstance(mods[-2], nn.Conv2d)
+    body = mods[:-1] if final_tanh else mods
+    convs = [m for m in body if isinstance(m, nn.Conv2d)]
+    acts = [m for m in body if not isinstance(m, nn.Conv2d)]
+    for m in acts:
+        if type(m) not in (nn.ReLU, nn.Tanh):
+            raise TypeError(f"odeint(HIP): unsupported layer {m} in gradient_net (Conv2d separated by ReLU or Tanh, "
+                            "optionally followed by one Tanh)")
+    if len({type(m) for m in acts}) > 1:
+        raise TypeError("odeint(HIP): the hidden activations of gradient_net must be all ReLU or all Tanh")
+    if not convs or not isinstance(body[0], nn.Conv2d) or not isinstance(body[-1], nn.Conv2d) or any(
+            isinstance(m, nn.Conv2d) == isinstance(n, nn.Conv2d) for m, n in zip(body, body[1:])):
+        raise TypeError("odeint(HIP): every hidden Conv2d must be followed by exactly one activation (ReLU or Tanh)")
+    act = _lib.ACT_TANH if acts and isinstance(acts[0], nn.Tanh) else _lib.ACT_RELU
+    stack = hip_ops.PackedConvStack(convs, final_tanh, act)
     try:
         object.__setattr__(func, "_hip_stack", stack)
     except Exception:
