@@ -22,11 +22,9 @@
  *       * tables that follow the accepted steps of an adaptive solve (odehip_odeint_dopri5_backward[_saved]: its layer table and its
  *         weight-gradient tables) travel through a library-owned ring of pinned staging buffers and device slots with asynchronous
  *         copies on the caller's stream -- no stream synchronisation (hipHostMalloc / hipMalloc when a slot has to grow);
- *       * the "small" persistent launches (ODEHIP_PERSISTENT_SMALL=1 only) own a flag area in device memory;
  *       * odehip_odeint_fixed_backward with saved_format 1 (bf16 whole-trajectory path) runs its weight-gradient launches on a
  *         library-owned side stream, ordered against the caller's stream by events in both directions (the caller's stream
- *         continues only when the side stream is done with the workspace and the gradients); ODEHIP_BF16_OVERLAP=0 keeps
- *         everything on the caller's stream.
+ *         continues only when the side stream is done with the workspace and the gradients).
  *   - library state (table cache, mailbox, error word, flag areas) is process-global and serves ONE stream at a time:
  *     the library assumes one process per GPU driving it from a single stream (the Python binding passes torch's
  *     current stream); concurrent calls from several streams or threads are not supported.

@@ -291,7 +291,7 @@ def check(rc):
             raise OdeHipError(f"a persistent launch of THIS OR AN EARLIER call gave up waiting for a partner workgroup (code {code}): the word is "
                               "read without synchronising, so the kernel that set it may belong to any call enqueued since the last check.  "
                               "Results since then are invalid (whole-trajectory launches NaN-fill their outputs; single-evaluation launches "
-                              "-- ODEHIP_PERSISTENT_SMALL=1 -- do not); persistent launches are now disabled for this process")
+                              "may not); persistent launches are now disabled for this process")
         return
     msg = load().odehip_last_error().decode("utf-8", "replace")
     if rc == -1:

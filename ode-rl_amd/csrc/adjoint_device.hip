@@ -543,25 +543,15 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
     // only the input-gradient chains, whose masks come from the SAME stage's forward chain: D_e and F_{e+1} are independent, so
     // in a woven pair every row's predecessor in its own chain lies two rows back (dep_back = 1: its input is loaded and transformed
     // while the consumers still multiply the other chain's row).
-    static const bool weave = [] { const char* e = getenv("ODEHIP_ADJOINT_WEAVE"); return !(e && e[0] == '0'); }();
-    if (weave) {
-      for (int j = 0; j < NL; ++j)
-        if ((rc = emit(F[1][j], 0)) != ODEHIP_OK) return rc;
-      for (int e = 1; e <= 5; ++e)
-        for (int j = 0; j < NL; ++j) {
-          if ((rc = emit(F[e + 1][j], (e == 1 && j == 0) ? 0 : 1)) != ODEHIP_OK) return rc;   // F2's first row follows F1's last
-          if ((rc = emit(D[e][j], 1)) != ODEHIP_OK) return rc;
-        }
-      for (int j = 0; j < NL; ++j)
-        if ((rc = emit(D[6][j], 0)) != ODEHIP_OK) return rc;
-    } else {
-      for (int e = 1; e <= 6; ++e) {
-        for (int j = 0; j < NL; ++j)
-          if ((rc = emit(F[e][j], 0)) != ODEHIP_OK) return rc;
-        for (int j = 0; j < NL; ++j)
-          if ((rc = emit(D[e][j], 0)) != ODEHIP_OK) return rc;
+    for (int j = 0; j < NL; ++j)
+      if ((rc = emit(F[1][j], 0)) != ODEHIP_OK) return rc;
+    for (int e = 1; e <= 5; ++e)
+      for (int j = 0; j < NL; ++j) {
+        if ((rc = emit(F[e + 1][j], (e == 1 && j == 0) ? 0 : 1)) != ODEHIP_OK) return rc;   // F2's first row follows F1's last
+        if ((rc = emit(D[e][j], 1)) != ODEHIP_OK) return rc;
       }
-    }
+    for (int j = 0; j < NL; ++j)
+      if ((rc = emit(D[6][j], 0)) != ODEHIP_OK) return rc;
   }
   init.rows_p2[1] = n_rows - init.rows_p2[0];
 

@@ -91,18 +91,13 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
       const int Q = mb * 8 + 2 * g + kq;
       const u32x2 pk = {pk_bf16(v[4 * g], v[4 * g + 1]), pk_bf16(v[4 * g + 2], v[4 * g + 3])};
       *(u32x2*)(act + ((row0 + 2 * nb + 1) * 18 + px + 1) * kFS + Q * 8) = pk;
-#ifndef BTRAJ_ABLATE_no_gstore
       *(u32x2*)(dst + (q4h_off + (unsigned)(g * 2 * kPix * 8 + nb * 32 * 8))) = pk;
-#endif
     }
   };
   // bias gradient of one conv output: sum over this wave's 64 pixels of the UNROUNDED gradient -- DPP sums inside the rows of 16
   // lanes, then lane 15 of each row adds the row total to the row's OWN running sum in LDS (one writer per word, evaluations in
   // order: deterministic, no barrier needed); the rows are folded once, at the end of the kernel
   auto bias_rows = [&](const f32x16& v0, const f32x16& v1, int layer) {
-#ifdef BTRAJ_ABLATE_no_bias
-    return;
-#endif
     float* slot = bpart + ((layer * 8 + wave) * 4 + (lane >> 4)) * 16;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -200,11 +195,7 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
         if (has_mask) {                      // mask of the ReLU that fed conv l = saved hidden activation l-1, prefetched now
           const char* mk = wave_uniform(hs + (size_t)(l - 1) * ba.stride_h_layer);
 #pragma unroll
-#ifdef BTRAJ_ABLATE_no_mask
-          for (int i = 0; i < 8; ++i) mreg[i] = u32x2b{0x3f803f80u, 0x3f803f80u};
-#else
           for (int i = 0; i < 8; ++i) mreg[i] = gload8_untracked(mk + (q4h_off + (unsigned)((i & 3) * 2 * kPix * 8 + (i >> 2) * 32 * 8)));
-#endif
         }
 #pragma unroll
         for (int r = 0; r < 3; ++r, ++u) {
@@ -321,11 +312,7 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
         // stage 1 closes the interval: g(y_n) = gy + gx1 + grad_out[n]  (the next interval's seed is formed from it at its stage 4)
         // and the seed of interval n-1's stage 4, (h_{n-1}/8) g(y_n), as the per-launch path forms it: term by term
         f32x16 go[2];
-#ifdef BTRAJ_ABLATE_no_go
-        go[0] = G[1]; go[1] = G[0];
-#else
         load_go(n, go);
-#endif
         const float hb = n > 0 ? ba.hdev[n - 1] : 0.0f;
         const float cs = 0.f + 0.125f * hb;
 #pragma unroll

@@ -232,7 +232,7 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
       if (!hk.first) {
         // One sample per group: the partners cannot be done before this workgroup's own consumers are through their last chunk (~1 us
         // from here): sleep through most of it instead of polling -- a polling wave takes issue slots from the consumer wave of its
-        // SIMD.  Sweep on one box (ODEHIP_PERSIST_SLEEP = periods of 0.18 us; median of 3 alternations, ms): headline 0: 1.432,
+        // SIMD.  Sweep on one box (PersistArgs::sleep6 = periods of 0.18 us; median of 3 alternations, ms): headline 0: 1.432,
         // 2: 1.504, 3: 1.435, 4: 1.401, 5: 1.389, 6: 1.409, 8: 1.452; forward + backward 0: 4.75, 4: 4.57, 5: 4.55, 6: 4.54, 8: 4.60;
         // dopri5 forward 0: 0.799, 4: 0.783, 5: 0.777, 8: 0.796; 128-channel-ended stack 0: 1.640, 4: 1.627, 5: 1.638.  A barrier that
         // releases the producers exactly when the consumers' last MFMA has issued is worse than the fixed sleep (it also holds back
@@ -661,8 +661,8 @@ struct PersistArgs {
   unsigned long long* stamps;  // diagnostic: [64 layers][8] timestamps of logical workgroup 0, or null
   int sleep6;             // PersistHook::sleep6
   int sleep6_combine;     // added in front of a layer whose input comes out of a stage-combine epilogue
-  unsigned epoch;         // 0: the flag area was zeroed for this launch; else the flags persist across launches and every word is
-                          // tagged with the epoch of the launch that wrote it (flag = epoch << 10 | layers done; xcc = epoch << 4 | id)
+  unsigned epoch;         // tag of the flag words (flag = epoch << 10 | layers done; xcc = epoch << 4 | id); always 0: every launch
+                          // gets a zeroed flag area
   const int* n_layers_ptr;  // adaptive walk only: if non-null, {first row, number of rows} of this launch's walk are read from the
                             // device (a device-side controller picks the section of the table); n_layers is then the table's size
   const unsigned long long* reloc;  // adaptive walk only: relocation bases (rel()), or null
@@ -909,23 +909,6 @@ __device__ __forceinline__ void persist_walk_v(const PersistArgs& pa, const Conv
 
 __global__ __launch_bounds__(512, 1) void wino_persist_v_kernel(const PersistArgs pa) { persist_walk_v(pa, pa.table); }
 
-// A short layer sequence (one evaluation of f, one input-gradient chain) with its table IN THE KERNEL ARGUMENTS: nothing to
-// upload or cache, so it also serves callers whose buffers change with every evaluation (adaptive solvers' backward passes, the
-// encoder loop).  The flag area is library-owned and never zeroed between launches: words carry the launch's epoch.
-constexpr int kSmallLayers = 5;
-struct SmallPersistArgs {
-  PersistArgs pa;
-  ConvArgs layers[kSmallLayers];
-};
-static_assert(sizeof(SmallPersistArgs) <= 4096, "kernel arguments are limited to 4 KiB");
-
-__global__ __launch_bounds__(512, 1) void wino_persist_small_kernel(const SmallPersistArgs sa) {
-  // the argument block itself is the table (constant address space: scalar loads, no private copy)
-  typedef const __attribute__((address_space(4))) char ConstC;
-  ConstC* base = (ConstC*)__builtin_amdgcn_kernarg_segment_ptr();
-  persist_walk<false>(sa.pa, (const ConvArgs*)(const void*)(base + offsetof(SmallPersistArgs, layers)));
-}
-
 template <int NCHUNK>
 static int launch_wino_n(const ConvArgs& a, hipStream_t stream) {
   static bool attr_set = false, attr_set_dbg = false;
@@ -969,10 +952,10 @@ int launch_wino_persist(const ConvArgs* table_dev, int n_layers, int batch, unsi
   pa.table = table_dev; pa.n_layers = n_layers; pa.batch = batch; pa.done = done; pa.xcc_of = xcc_of; pa.host_err = host_err_dev;
   pa.out_nchw = out_nchw;
   pa.stamps = g_debug_buf;
-  static const int sleep6 = [] { const char* e = getenv("ODEHIP_PERSIST_SLEEP"); return e ? atoi(e) : 5; }();  // 5 x 0.18 us (sweep in wino_layer's comment)
-  pa.sleep6 = sleep6;
-  static const int sleep6c = [] { const char* e = getenv("ODEHIP_PERSIST_SLEEP_COMBINE"); return e ? atoi(e) : 4; }();  // sweep: 0: 1.382, 4: 1.367, 6: 1.370, 8: 1.383, 12: 1.404 ms
-  pa.sleep6_combine = sleep6c;
+  constexpr int kSleep6 = 5;          // 5 x 0.18 us (sweep in wino_layer's comment)
+  constexpr int kSleep6Combine = 4;   // sweep: 0: 1.382, 4: 1.367, 6: 1.370, 8: 1.383, 12: 1.404 ms
+  pa.sleep6 = kSleep6;
+  pa.sleep6_combine = kSleep6Combine;
   pa.epoch = 0;  // the caller zeroed the flag area
   pa.n_layers_ptr = n_layers_ptr;
   pa.reloc = reloc;
@@ -985,30 +968,6 @@ int launch_wino_persist(const ConvArgs* table_dev, int n_layers, int batch, unsi
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
 }
-
-int launch_wino_persist_small(const ConvArgs* items, int n_layers, int batch, unsigned* done, unsigned* xcc_of, unsigned epoch,
-                              unsigned* host_err_dev, int grid, hipStream_t stream) {
-  static bool attr_set = false;
-  ODEHIP_REQUIRE(n_layers >= 1 && n_layers <= kSmallLayers && epoch >= 1, "wino_persist_small: bad arguments");
-  if (!attr_set) {
-    ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)wino_persist_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    int per_cu = 0;
-    ODEHIP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)wino_persist_small_kernel, 512, kWinoLds));
-    ODEHIP_REQUIRE(per_cu >= 1, "wino_persist_small: the kernel does not fit a CU");
-    attr_set = true;
-  }
-  SmallPersistArgs sa;
-  memset(&sa, 0, sizeof(sa));
-  sa.pa.table = nullptr; sa.pa.n_layers = n_layers; sa.pa.batch = batch; sa.pa.done = done; sa.pa.xcc_of = xcc_of;
-  sa.pa.host_err = host_err_dev; sa.pa.out_nchw = nullptr; sa.pa.stamps = nullptr; sa.pa.sleep6 = 5; sa.pa.sleep6_combine = 4; sa.pa.epoch = epoch;
-  sa.pa.n_layers_ptr = nullptr;
-  sa.pa.reloc = nullptr;
-  for (int i = 0; i < n_layers; ++i) sa.layers[i] = items[i];
-  hipLaunchKernelGGL(wino_persist_small_kernel, dim3(grid), dim3(512), kWinoLds, stream, sa);
-  ODEHIP_CHECK_HIP(hipGetLastError());
-  return ODEHIP_OK;
-}
-
 
 // ================================================================================================================================
 // Small batches (B <= 16; the reference trains at batch 4, configs.yaml:7): SIXTEEN workgroups per sample.
@@ -1559,8 +1518,8 @@ int launch_wino_persist16(const ConvArgs* table_dev, int n_layers, int batch, un
   // Periods of 0.18 us the producers sleep in front of their first poll (a polling wave takes issue slots from the consumer wave of
   // its SIMD).  Sweep, forward trajectory B = 4, T = 10, rk4 (ms): 0: 1.07, 1: 0.90, 2: 0.66, 3: 0.605, 4: 0.596, 6: 0.619; B = 12 / 16:
   // 3: 0.88 / 0.80, 4: 0.621 / 0.620, 5: 0.608 / 0.617.
-  static const int sleep_env = [] { const char* e = getenv("ODEHIP_PERSIST16_SLEEP"); return e ? atoi(e) : -1; }();
-  pa.sleep6 = sleep_env >= 0 ? sleep_env : (batch > 8 ? 5 : 4);
+  constexpr int kSleep6Upto8 = 4, kSleep6Above8 = 5;
+  pa.sleep6 = batch > 8 ? kSleep6Above8 : kSleep6Upto8;
   {   // tests only: the FIRST launch that sees ODEHIP_FAULT_INJECT=1 loses a workgroup (read per launch: a test flips it in-process)
     static int injected = 0;
     const char* e = getenv("ODEHIP_FAULT_INJECT");

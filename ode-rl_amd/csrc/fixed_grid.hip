@@ -389,8 +389,6 @@ extern "C" int odehip_odeint_fixed_backward(const odehip_convstack* f, const ode
     const int n_steps = n_times - 1;
     const int n_eval = n_steps * S;
     ODEHIP_REQUIRE(n_eval <= kMaxWgradEvals, "odeint backward: too many evaluations (%d)", n_eval);
-    static const bool overlap_on = [] { const char* e = getenv("ODEHIP_BF16_OVERLAP"); return !(e && e[0] == '0'); }();
-    static const int seg_env = [] { const char* e = getenv("ODEHIP_BF16_SEGMENTS"); return e ? atoi(e) : 0; }();
     int cus = 256;
     {
       int dev = 0;
@@ -398,8 +396,7 @@ extern "C" int odehip_odeint_fixed_backward(const odehip_convstack* f, const ode
     }
     const int free_cus = cus - batch;                         // the sweep holds one CU per sample
     const int esplit_c = free_cus / batch < kEsplit ? free_cus / batch : kEsplit;   // concurrent weight-gradient workgroups per sample
-    int n_seg = overlap_on && esplit_c >= 1 ? n_steps / 8 : 1;   // at least eight intervals per segment; no idle CUs: no cut
-    if (seg_env > 0) n_seg = seg_env;
+    int n_seg = esplit_c >= 1 ? n_steps / 8 : 1;   // at least eight intervals per segment; no idle CUs: no cut
     n_seg = n_seg < 1 ? 1 : (n_seg > kMaxSeg ? kMaxSeg : n_seg);
     if (n_seg > n_steps) n_seg = n_steps;
     float* bias_part = L.p(ws, L.off_g2);                      // [segment][B][NL][64] fp32: fits the two state-sized scratch tensors

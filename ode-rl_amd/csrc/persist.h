@@ -18,8 +18,9 @@ class PersistScope {
   PersistScope();
   ~PersistScope();
   // rc != OK: a sticky error of an earlier launch was found.  active(): the recorder is on.
-  // small: a sequence of at most 5 layers that is launched with its table in the kernel arguments (no cache, library-owned
-  // flags); such a scope stays inactive inside an outer scope, whose recorder then simply sees the layers
+  // small: a single evaluation / input-gradient chain of at most 5 layers, recorded only for the trajectory walks' single-evaluation
+  // mode (ODEHIP_EVAL_WALK; volatile table, library-owned flags); such a scope stays inactive inside an outer scope, whose recorder
+  // then simply sees the layers
   int begin(const odehip_convstack* f, const odehip_convstack* f2, int max_layers, bool small = false);
   bool active() const { return active_; }
   // volatile_table: the recorded table differs from call to call (buffers / coefficients that follow the accepted steps of an
@@ -56,9 +57,8 @@ class PersistScope {
   std::vector<ConvArgs> items_;
   ConvRecorder rec_ = {nullptr, 0, 0};
   bool active_ = false;
-  bool small_ = false;
   bool eval_walk_small_only_ = false;   // ODEHIP_EVAL_WALK unset: only batches the sixteen-workgroup walk takes
-  bool eval_walk_ = false;   // a small scope that runs on the trajectory walks (ODEHIP_EVAL_WALK=1): library-owned flags, volatile table
+  bool eval_walk_ = false;   // a small scope that runs on the trajectory walks (ODEHIP_EVAL_WALK): library-owned flags, volatile table
   bool adaptive_ = false;
   bool volatile_ = false;
   const int* rows_dev_ = nullptr;

@@ -37,13 +37,9 @@ struct PersistState {
   } vol[kVolSlots];
   int vol_next = 0;
   int vol_last = -1;   // slot of the upload that has not been followed by its launch yet
-  // single evaluations on the trajectory walks (ODEHIP_EVAL_WALK=1): a flag area of the library, zeroed in front of every launch
+  // single evaluations on the trajectory walks (ODEHIP_EVAL_WALK): a flag area of the library, zeroed in front of every launch
   unsigned* eval_sync = nullptr;
   int eval_batch_cap = 0;
-  // small launches: flag area that is never zeroed between launches (words are tagged with the launch's epoch)
-  unsigned* small_flags = nullptr;
-  int small_batch_cap = 0;
-  unsigned small_epoch = 0;
 };
 static PersistState g_persist;
 
@@ -254,39 +250,29 @@ PersistScope::~PersistScope() {
 }
 
 int PersistScope::begin(const odehip_convstack* f, const odehip_convstack* f2, int max_layers, bool small) {
-    small_ = small;
     if (small && (g_conv_recorder || max_layers > 5)) return ODEHIP_OK;  // inside an outer scope: its recorder takes the layers
     // a reverse sweep over a Tanh head runs its seed rows (kActTanhSeed, enqueue_dgrad_chain) as plain per-layer launches: not recorded
     if (f2 && f->final_tanh) return ODEHIP_OK;
-    // ODEHIP_EVAL_WALK=1: the <= 5 layers of a single evaluation / input-gradient chain (the encoder loop's Euler step and its
-    // backward) as ONE launch of the TRAJECTORY walks -- wino_persist_kernel, or the sixteen-workgroup walk up to batch 16 -- instead
-    // of the round-2 single-evaluation kernel below (9.5 us per layer against 7.5 / 3.3): the table goes up through the volatile
-    // ring, the flags live in a library-owned area zeroed per launch.  No host-side guard launch behind it; the sixteen-workgroup walk
-    // NaN-fills its own outputs when a wait of the launch gave up (nan_fill_row16, conv_wino.hip), and the sticky word raises at the next call.
+    // The <= 5 layers of a single evaluation / input-gradient chain (the encoder loop's Euler step and its backward) as ONE launch of
+    // the TRAJECTORY walks -- wino_persist_kernel, or the sixteen-workgroup walk up to batch 16 -- instead of one launch per layer:
+    // the table goes up through the volatile ring, the flags live in a library-owned area zeroed per launch.  No host-side guard
+    // launch behind it; the sixteen-workgroup walk NaN-fills its own outputs when a wait of the launch gave up (nan_fill_row16,
+    // conv_wino.hip), and the sticky word raises at the next call.
     // Round 4: ON for batches up to 16 (the sixteen-workgroup walk: the reference's batch 4 trains 5.16 -> 4.92 ms per step with it),
     // off above (B = 64: the cell loop 2.81 -> 2.93 ms) unless ODEHIP_EVAL_WALK=1 forces it; ODEHIP_EVAL_WALK=0 switches it off.
     // The batch is only known in finish(): a scope that turns out too large replays its rows as ordinary launches there.
     static const int eval_walk_env = [] { const char* e = getenv("ODEHIP_EVAL_WALK"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
     eval_walk_small_only_ = eval_walk_env < 0;
-    if (small && eval_walk_env != 0) {
-      small_ = false;
+    if (small) {
+      if (eval_walk_env == 0) return ODEHIP_OK;   // one launch per layer
       eval_walk_ = true;
       volatile_ = true;
-      small = false;
       for (int l = 0; l <= f->n_convs; ++l)
         if (f->channels[l] != 64) return ODEHIP_OK;   // 64-channel stacks only here
     }
-    if (small) {
-      // Measured (dopri5 forward + backward, B=64): 55 us per 5-layer launch = 11 us per layer, no better than five launches --
-      // the last layer of an adaptive solver's evaluation combines up to six earlier stages through the shared epilogue
-      // (operands fetched AFTER the last MFMA, one dependent load after the other).  Off unless asked for, until that epilogue
-      // gets the prefetched-operand treatment of the fixed-grid one.
-      static const bool small_on = [] { const char* e = getenv("ODEHIP_PERSISTENT_SMALL"); return e && e[0] == '1'; }();
-      if (!small_on) return ODEHIP_OK;
-    }
     if (f->ks != 3 || f->w_fused || (f2 && f2->w_fused) || g_debug_flags) return ODEHIP_OK;
     for (int l = 0; l <= f->n_convs; ++l)
-      if (f->channels[l] != 64 && (small || f->channels[l] != 128)) return ODEHIP_OK;  // (128-channel sides: the wide walk, finish())
+      if (f->channels[l] != 64 && f->channels[l] != 128) return ODEHIP_OK;  // (128-channel sides: the wide walk, finish())
     for (int l = 0; l < f->n_convs; ++l)
       if (f->channels[l] == 128 && f->channels[l + 1] == 128) return ODEHIP_OK;
     for (int l = 0; l < f->n_convs; ++l)
@@ -341,46 +327,7 @@ int PersistScope::finish(const float* hbuf, const float* hdev, float* out_nchw, 
       wide = wide || kind == 2;
       adaptive = adaptive || kind == 3;
     }
-    if (wide && (small_ || adaptive)) all_ok = false;   // (order-1 rows of a 128-channel-ended stack: one launch per layer)
-    if (adaptive && small_) all_ok = false;
-    if (small_ && all_ok && rec_.count <= 5) {
-      PersistState& P = g_persist;
-      bool ready = true;
-      if (batch > P.small_batch_cap || P.small_epoch >= (1u << 21)) {  // (re)allocate / re-zero the flag area: rare, synchronous
-        ready = hipStreamSynchronize(stream) == hipSuccess;
-        if (ready && batch > P.small_batch_cap) {
-          if (P.small_flags) (void)hipFree(P.small_flags);
-          P.small_flags = nullptr;
-          P.small_batch_cap = 0;
-          const int cap = batch < 64 ? 64 : batch;
-          ready = hipMalloc((void**)&P.small_flags, persist_sync_bytes(cap)) == hipSuccess;
-          if (ready) P.small_batch_cap = cap;
-        }
-        ready = ready && hipMemset(P.small_flags, 0, persist_sync_bytes(P.small_batch_cap)) == hipSuccess;
-        P.small_epoch = 0;
-      }
-      if (ready) {
-        for (int i = 0; i < rec_.count; ++i) {
-          rec_.items[i].dbg = nullptr;
-          rec_.items[i].h_by_value = 0;
-        }
-        const int rcs = launch_wino_persist_small(rec_.items, rec_.count, batch, P.small_flags,
-                                                  P.small_flags + (size_t)P.small_batch_cap * kPersistDoneStride, ++P.small_epoch,
-                                                  P.host_err_dev, kPersistGrid, stream);
-        if (rcs == ODEHIP_OK) {
-          ++P.launches;
-          // Small launches carry NO NaN guard: their flag area is epoch-tagged and shared, so there is no per-launch abort word a
-          // guard kernel could read.  Their callers (one evaluation of f, an input-gradient chain, the encoder's Euler step) are
-          // enqueue-only, so a give-up in one of them is reported LATE: the sticky host word is read by the binding at the next
-          // library call after the kernel has run (or by odehip_persistent_error), which raises "an earlier call ..." -- the data
-          // that earlier call returned is invalid.  This path is off by default (ODEHIP_PERSISTENT_SMALL=1 enables it).
-          return rcs;
-        }
-        P.enabled = 0;
-        (void)hipGetLastError();
-      }
-      all_ok = false;  // fall through to the replay
-    }
+    if (wide && adaptive) all_ok = false;   // (order-1 rows of a 128-channel-ended stack: one launch per layer)
     const ConvArgs* table = nullptr;
     if (all_ok) {
       for (int i = 0; i < rec_.count; ++i) {

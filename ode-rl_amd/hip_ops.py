@@ -279,9 +279,6 @@ def pack_conv_weight_bf16_ks(w, transpose_flip=False):
     return out
 
 
-USE_FUSED = os.environ.get("ODEHIP_NO_FUSED") is None   # bf16 mode, 64-channel 3x3 stacks: whole f in one launch (fstack_bf16.hip)
-
-
 def pack_fused_bf16(convs, reverse_transposed=False):
     """Fused bf16 image of a stack of 64 -> 64 3x3 convs in execution order (the input-gradient chain runs the layers
     backwards with transposed + flipped weights)."""
@@ -297,7 +294,8 @@ def pack_fused_bf16(convs, reverse_transposed=False):
 
 
 def _fusable(convs, ks):
-    return USE_FUSED and ks == 3 and all(c.in_channels == 64 and c.out_channels == 64 for c in convs)
+    """bf16 mode, 64-channel 3x3 stacks: whole f in one launch (fstack_bf16.hip)."""
+    return ks == 3 and all(c.in_channels == 64 and c.out_channels == 64 for c in convs)
 
 
 def _bf16_cell_ok(cell_input, hidden, ks):
@@ -306,9 +304,6 @@ def _bf16_cell_ok(cell_input, hidden, ks):
 
 def _bf16_ok(cin, cout, ks):
     return ks == 3 and cin % 16 == 0 and cin <= 128 and cin // 16 in (1, 2, 4, 8) and cout % 32 == 0
-
-
-USE_WINOGRAD = os.environ.get("ODEHIP_NO_WINOGRAD") is None   # 3x3 layers with cin % 16 == 0 run the Winograd kernel (2.25x fewer MFMAs, still exact-fp32 arithmetic)
 
 
 def conv_q4(src1, w_packed, bias, cout, ks, src2=None, relu=False, w_wino=None, w_bf16=None):
@@ -370,8 +365,8 @@ class PackedConvStack:
                 raise ValueError("the HIP path supports stride-1 'same' square convs with bias only "
                                  f"(got {c}); downsize=True dynamics are not supported")
             require_device_tensor(c.weight, "conv weight")
-        wino_ok = USE_WINOGRAD and ks == 3
-        want_wino = [wino_ok and c.in_channels % 16 == 0 for c in convs]
+        # 3x3 layers with cin % 16 == 0 run the Winograd kernel (2.25x fewer MFMAs, still exact-fp32 arithmetic)
+        want_wino = [ks == 3 and c.in_channels % 16 == 0 for c in convs]
         both = pack_conv_weights_many([(c.weight, False, False) for c in convs] + [(c.weight, True, False) for c, ww in zip(convs, want_wino) if ww])
         packed, rest = both[:len(convs)], iter(both[len(convs):])
         wino = [next(rest) if ww else None for ww in want_wino]
@@ -402,7 +397,7 @@ class PackedConvStack:
         d0 = self.refresh(mode)
         ent = self._cache[mode]
         if ent["dgrad"] is None:
-            want_wino = [USE_WINOGRAD and d0.ks == 3 and c.out_channels % 16 == 0 for c in self.convs]
+            want_wino = [d0.ks == 3 and c.out_channels % 16 == 0 for c in self.convs]
             both = pack_conv_weights_many([(c.weight, False, True) for c in self.convs] +
                                           [(c.weight, True, True) for c, ww in zip(self.convs, want_wino) if ww])
             packed, rest = both[:len(self.convs)], iter(both[len(self.convs):])

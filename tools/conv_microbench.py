@@ -15,11 +15,11 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 x = hip_ops.nchw_to_q4(torch.randn(B, 64, 16, 16, device=dev))
 wt = torch.randn(64, 64, 3, 3, device=dev) / 24
 w = hip_ops.pack_conv_weight(wt)
-ww = hip_ops.pack_conv_weight_winograd(wt) if hip_ops.USE_WINOGRAD else None
+ww = hip_ops.pack_conv_weight_winograd(wt)
 bias = torch.randn(64, device=dev)
 dst = torch.empty_like(x)
 lib = _lib.load()
-d = _lib.ConvDesc(src1=x.data_ptr(), src2=None, cin1=64, cin=64, cout=64, ks=3, batch=B, w_packed=w.data_ptr(), w_wino=ww.data_ptr() if ww is not None else None,
+d = _lib.ConvDesc(src1=x.data_ptr(), src2=None, cin1=64, cin=64, cout=64, ks=3, batch=B, w_packed=w.data_ptr(), w_wino=ww.data_ptr(),
                   bias=bias.data_ptr(), dst=dst.data_ptr(), relu=1)
 stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 N = 500

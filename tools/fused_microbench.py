@@ -23,12 +23,12 @@ out = torch.empty_like(x)
 scratch = torch.empty(2 * x.numel(), device=dev)
 stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 for mode in ("bf16 fused", "bf16 per layer", "f32"):
-    if mode == "bf16 per layer":
-        hip_ops.USE_FUSED = False
-        stack._cache.clear()
     if mode == "f32":
         ode_rl_amd.set_compute_dtype("f32")
     desc = stack.refresh()
+    if mode == "bf16 per layer":   # the same bf16 stack without its whole-f image: one launch per layer
+        desc = _lib.ConvStack.from_buffer_copy(desc)
+        desc.w_fused = None
     for flags, name in (((0, "full"), (1, "no weight DMA"), (2, "no MFMA, no reads"), (64, "MFMA on constant operands"), (3, "no DMA, no MFMA"), (65, "const MFMA, no DMA"), (0, "full"))
                         if mode == "bf16 fused" else ((0, "full"),)):
         lib.odehip_set_debug_flags(flags)
