@@ -374,8 +374,8 @@ int odehip_odeint_dopri5_backward_saved(const odehip_convstack* f, const odehip_
  * (max_accept = 0: nothing is kept for a backward pass), enqueues `attempts` attempted steps (those queued behind completion
  * return at once) and comes back WITHOUT waiting: no stats, no status.  The caller enqueues its consumers of `out` behind this
  * call, so the attempts enqueued HERE are all the solve ever gets: behind the last one sits a seal kernel which, if the solve is
- * not done, fills the frames it has not reached with NaN (ABI 10; before, collect enqueued the missing attempts behind the
- * consumers, which had then read uninitialised frames).  odehip_odeint_dopri5_collect(token) waits for the device (normally long
+ * not done or has failed (max_num_steps, dt underflow, non-finite state), fills the frames it has not reached with NaN (ABI 10;
+ * before, collect enqueued the missing attempts behind the consumers, which had then read uninitialised frames).  odehip_odeint_dopri5_collect(token) waits for the device (normally long
  * done) and reports what the synchronous call reports -- including ODEHIP_ENOTCONV / ODEHIP_ENAN, i.e. an error surfaces at
  * collect time -- or ODEHIP_ETRUNC for a sealed, unfinished solve (stats_host[3] = the attempts that were enqueued; stats are
  * filled in that case too, so the caller can size its retry).  Everything start was given (workspace, out, z0) must stay

@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
       const int y = i / W, xx = i - y * W;
       const float xv = x[pl * HW + i];
       const float pre = __builtin_fmaf(xv, a, b);
-      const float gv = pre > 0.0f ? grad_at<UP>(g, pl, y, xx, H, W) : 0.0f;
+      const float gv = pre <= 0.0f ? 0.0f : grad_at<UP>(g, pl, y, xx, H, W);   // torch's threshold_backward: NaN passes
       g_pre[pl * HW + i] = gv;
       s1 += (double)gv;
       s2 += (double)gv * (double)((xv - mu) * is);

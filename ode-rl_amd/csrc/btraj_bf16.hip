@@ -40,6 +40,9 @@ __device__ __forceinline__ u32x2b gload8_untracked(const char* p) {
   asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
   return v;
 }
+// ReLU-mask test on a saved bf16 activation, given as the fp32 bits it widens to (bf16 in the high half, zeros below): torch's
+// threshold_backward passes the gradient where !(v <= 0) -- v positive, or NaN whatever its sign bit
+__device__ __forceinline__ bool bf16_relu_pass(unsigned f32_bits) { return !(__uint_as_float(f32_bits) <= 0.0f); }
 
 __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs ba) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -255,8 +258,9 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
           f32x16& acc = nb ? acc1 : acc0;
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            const u32x2b m = mreg[nb * 4 + g];   // 4 bf16: a positive value has a non-zero magnitude and a clear sign bit
-            const bool p0 = (short)(m[0] & 0xffffu) > 0, p1 = (int)m[0] > 0xffff, p2 = (short)(m[1] & 0xffffu) > 0, p3 = (int)m[1] > 0xffff;
+            const u32x2b m = mreg[nb * 4 + g];   // 4 bf16, passed where !(v <= 0) as in torch: positive or NaN, either sign bit
+            const bool p0 = bf16_relu_pass(m[0] << 16), p1 = bf16_relu_pass(m[0] & 0xffff0000u), p2 = bf16_relu_pass(m[1] << 16),
+                       p3 = bf16_relu_pass(m[1] & 0xffff0000u);
             acc[4 * g] = p0 ? acc[4 * g] : 0.f;
             acc[4 * g + 1] = p1 ? acc[4 * g + 1] : 0.f;
             acc[4 * g + 2] = p2 ? acc[4 * g + 2] : 0.f;

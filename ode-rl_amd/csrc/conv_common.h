@@ -23,14 +23,15 @@ __device__ __forceinline__ f32x4 act_fwd(f32x4 v, int act) {
   return v;
 }
 // Backward through the activation whose OUTPUT y fed the next conv: g * (1 - y^2) for kActTanh (an explicit fma, so every kernel
-// rounds it alike; NaN in g or y propagates, as in torch's tanh_backward), else the ReLU mask g * (y > 0).
+// rounds it alike; NaN in g or y propagates, as in torch's tanh_backward), else the ReLU mask of torch's threshold_backward,
+// y <= 0 ? 0 : g: the gradient passes where y is NaN (relu_f let the NaN through; a mask y > 0 would launder it into a zero).
 __device__ __forceinline__ f32x4 act_bwd(f32x4 g, f32x4 y, int act) {
   if (act == kActTanh) {
     g.x *= __builtin_fmaf(-y.x, y.x, 1.0f); g.y *= __builtin_fmaf(-y.y, y.y, 1.0f);
     g.z *= __builtin_fmaf(-y.z, y.z, 1.0f); g.w *= __builtin_fmaf(-y.w, y.w, 1.0f);
   } else {
-    g.x = y.x > 0.0f ? g.x : 0.0f; g.y = y.y > 0.0f ? g.y : 0.0f;
-    g.z = y.z > 0.0f ? g.z : 0.0f; g.w = y.w > 0.0f ? g.w : 0.0f;
+    g.x = y.x <= 0.0f ? 0.0f : g.x; g.y = y.y <= 0.0f ? 0.0f : g.y;
+    g.z = y.z <= 0.0f ? 0.0f : g.z; g.w = y.w <= 0.0f ? 0.0f : g.w;
   }
   return g;
 }

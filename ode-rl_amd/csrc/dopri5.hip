@@ -309,13 +309,15 @@ __global__ __launch_bounds__(256) void finish_kernel(FinishArgs a, long long n4,
 
 // The SEAL of an asynchronous solve (odehip_odeint_dopri5_start): enqueued behind the last attempt start() enqueues.  The caller has
 // been handed `out` and goes on enqueueing its consumers (decoder, loss, the backward pass) behind this kernel, so nothing enqueued
-// LATER can still complete the trajectory for them.  If the solve is not done here, the frames it has not reached are filled with NaN
-// -- the consumers then compute NaN instead of reading uninitialised memory -- and the mailbox says so: collect() fails with
-// ODEHIP_ETRUNC instead of carrying on behind the consumers' backs.
+// LATER can still complete the trajectory for them.  Whenever the trajectory is incomplete here, the frames the solve has not reached
+// are filled with NaN -- the consumers then compute NaN instead of reading uninitialised memory.  Two ways to get here: the solve is
+// not done (the attempts ran out: the mailbox says so and collect() fails with ODEHIP_ETRUNC instead of carrying on behind the
+// consumers' backs), or the controller FAILED it (max_num_steps, dt underflow, non-finite state: collect() reports that status).
 __global__ __launch_bounds__(256) void seal_kernel(const DopriState* st, Mailbox* mb, float* out_nchw, long long state_floats) {
-  if (st->done) return;
+  if (st->done && st->status == 0) return;   // finished: every frame is written
   const int j0 = st->j_next, nt = st->n_times;
-  if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store((int*)&mb->truncated, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (!st->done && blockIdx.x == 0 && threadIdx.x == 0)
+    __hip_atomic_store((int*)&mb->truncated, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   const long long n = (long long)(nt - j0) * state_floats;
   float* o = out_nchw + (long long)j0 * state_floats;
   const float nan = __builtin_nanf("");
@@ -831,8 +833,8 @@ static int dopri5_forward(const odehip_convstack* f, const float* z0_nchw, const
 // ---- the asynchronous pair (ABI 8; sealed since ABI 10).  start = odehip_odeint_dopri5_saving's arguments (max_accept = 0: nothing
 // is kept) + how many attempted steps to enqueue before returning; nothing is waited for and no outcome is reported.  Behind the
 // last attempt start() enqueues the SEAL: the caller's consumers of `out` are enqueued behind start(), so attempts enqueued any later
-// could not complete the trajectory for them -- a solve that is not done at the seal gets its unreached frames NaN-filled and
-// collect() reports ODEHIP_ETRUNC.  collect(token) waits for the device (normally long done) and returns what the synchronous call
+// could not complete the trajectory for them -- a solve that is not done at the seal, or that the controller failed, gets its
+// unreached frames NaN-filled; collect() reports ODEHIP_ETRUNC for the first, the controller's status for the second.  collect(token) waits for the device (normally long done) and returns what the synchronous call
 // returns (status code, stats, accepted-step log, saved flag).  Everything the start call was given (workspace, out, z0) must stay
 // untouched until collect; at most four solves may be pending.
 extern "C" int odehip_odeint_dopri5_start(const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times, int batch,

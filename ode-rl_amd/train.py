@@ -15,10 +15,12 @@ def train_batch(model, batch_dict, optimizer, async_solver=False):
     async_solver (opt-in): a dopri5 solve inside the model only enqueues its attempted steps and the backward pass collects its outcome
     (ode_rl_amd.set_async_dopri5): the host goes on enqueueing decoder, loss and backward while the device still integrates.  A solver
     error (dt underflow, non-finite state) then surfaces at loss.backward(), not inside the forward as in torchdiffeq.  A solve that
-    needs more attempted steps than were enqueued up front is SEALED on the device (its unreached frames are NaN, never stale memory)
-    and reported as AsyncSolveTruncated by the backward pass: nothing has touched the parameters at that point, so the step is
-    repeated here on the synchronous path, from the module buffers (BatchNorm statistics) of before the sealed pass (and the next
-    asynchronous solve enqueues more attempts)."""
+    needs more attempted steps than were enqueued up front, or that fails, is SEALED on the device (its unreached frames are NaN, never
+    stale memory).  Whatever the asynchronous pass raises, nothing has touched the parameters or the optimiser at that point, and the
+    module buffers (BatchNorm statistics, which may have folded in the NaN frames) are restored to their values of before the pass.
+    An AsyncSolveTruncated is then handled here: the step is repeated on the synchronous path, whatever the caller's setting (the next
+    asynchronous solve enqueues more attempts); any other error is re-raised.  The caller's asynchronous setting is restored
+    afterwards, and an error from collecting the solves still pending on the way out never replaces the error of the pass."""
     dev = next(model.parameters()).device
     inp = batch_dict["observed_data"].to(dev) + 0.5          # train_test.py:180: [-0.5, 0.5] -> [0, 1]
     out = batch_dict["data_to_predict"].to(dev) + 0.5
@@ -40,17 +42,34 @@ def train_batch(model, batch_dict, optimizer, async_solver=False):
             try:
                 pred, loss = step()
                 hip_ops.collect_pending_solves()   # a solve nobody differentiated through (none in the models here) is checked too
-            finally:
-                hip_ops.set_async_dopri5(was)
-        except _lib.AsyncSolveTruncated:
+            except BaseException:
+                _set_async_quietly(hip_ops, was)   # the pass's error wins over one from collecting what is still pending
+                raise
+            hip_ops.set_async_dopri5(was)          # (no error so far: one from collecting here is the step's own)
+        except BaseException as e:
             with torch.no_grad():
                 for b, kept in buffers:
                     b.copy_(kept)
-            pred, loss = step()
+            if not isinstance(e, _lib.AsyncSolveTruncated):
+                raise
+            hip_ops.set_async_dopri5(False)        # the repeat is synchronous: a second truncation is impossible
+            try:
+                pred, loss = step()
+            finally:
+                _set_async_quietly(hip_ops, was)
     else:
         pred, loss = step()
     optimizer.step()
     return pred.detach() * 255.0, out * 255.0, loss.detach(), {"Per Step Loss": loss.detach()}
+
+
+def _set_async_quietly(hip_ops, on):
+    """set_async_dopri5(on) while another exception is in flight: switching off collects the pending solves, and an error of theirs
+    is dropped so that it cannot replace the one being raised (the switch is set before the collection, so it holds either way)."""
+    try:
+        hip_ops.set_async_dopri5(on)
+    except Exception:
+        pass
 
 
 def checkpoint_name(ckpt_id, step):

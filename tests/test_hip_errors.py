@@ -147,3 +147,40 @@ def test_a_non_finite_state_is_not_laundered(cuda, method):
     assert bool(torch.isnan(ref[1:, 0]).any())
     assert int((torch.isnan(ref) & ~torch.isnan(out)).sum()) == 0          # nothing the reference semantics keep NaN became a number
     assert bool(torch.isfinite(out[:, 1]).all()) and torch.equal(out[:, 1], base[:, 1])
+
+
+@pytest.mark.parametrize("training", [True, False])
+def test_a_non_finite_state_is_not_laundered_by_the_flow_decoder_backward(cuda, training):
+    """The same rule for the BACKWARD pass of VidODE's flow decoder (the fused BatchNorm + ReLU + x2 upsampling of bn_relu_up.hip): one
+    NaN pixel in its input.  torch's ReLU backward passes the gradient where the activation is NaN, so wherever the module-by-module
+    decoder (ODEHIP_FLOW_FUSED=0: torch's ReLU) has a NaN gradient the fused one has too -- a mask that zeroed it would hand the
+    optimiser a finite update computed from a NaN forward pass.  The convolutions in between are library calls that may spread NaN
+    further, so this is the superset rule (tests/test_hip_relu_nan_backward.py pins the fused pass itself with equal masks)."""
+    import copy
+    import os
+    from ode_rl_amd.models.VidODE import Decoder
+    torch.manual_seed(3)
+    dec = Decoder(256, 4, 2).to(cuda).train(training)
+    x = torch.randn(2, 256, 16, 16, device=cuda)
+    x[1, 40, 7, 9] = float("nan")
+    gout = torch.randn(2, 4, 64, 64, device=cuda)
+    res = []
+    for fused in ("1", "0"):
+        d = copy.deepcopy(dec)
+        os.environ["ODEHIP_FLOW_FUSED"] = fused
+        try:
+            xi = x.clone().requires_grad_(True)
+            d(xi).backward(gout)
+        finally:
+            os.environ.pop("ODEHIP_FLOW_FUSED")
+        res.append([("x", xi.grad)] + [(n, p.grad) for n, p in d.named_parameters()])
+    n_ref_nan = 0
+    for (name, a), (_, b) in zip(*res):
+        if training and name in ("cnn_decoder.1.bias", "cnn_decoder.5.bias"):
+            # the bias of a convolution in front of a batch-statistics BatchNorm has no gradient (the mean subtracts it again): the
+            # fused path folds it away and returns exact zeros, the modules sum a NaN gradient (test_flow_decoder_fused_equals_...)
+            assert float(a.abs().max()) == 0.0
+            continue
+        n_ref_nan += int(torch.isnan(b).sum())
+        assert int((torch.isnan(b) & ~torch.isnan(a)).sum()) == 0, f"{name}: a NaN gradient of the module-by-module decoder became a number"
+    assert n_ref_nan > 0

@@ -2,6 +2,8 @@
 every path that evaluates a conv stack -- f, the fixed-grid solvers on each kernel path, the persistent walks, dopri5 (sync and
 async), discretise-then-optimise gradients, odeint_adjoint, decreasing t, the encoder -- against the reference fixture
 (tests/golden/tanh.npz) and the oracle.  Tanh has no kink, so the gradient comparisons need no margin conditions."""
+import os
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -116,7 +118,8 @@ def test_persistent_trajectory_is_bit_identical_to_per_layer_launches(cuda, name
             n0 = lib.odehip_persistent_trajectory_launches()
             out = ode_rl_amd.odeint(f, z0, t, method="rk4")
             torch.cuda.synchronize()
-        assert lib.odehip_persistent_trajectory_launches() > n0, "the persistent path did not run"
+        if os.environ.get("ODEHIP_PERSISTENT", "1") != "0":   # switched off for the process: the switch above does not re-enable it
+            assert lib.odehip_persistent_trajectory_launches() > n0, "the persistent path did not run"
         assert torch.equal(out, ref)
     finally:
         lib.odehip_set_persistent_trajectory(was)

@@ -35,7 +35,13 @@ SED[bn_running_var_biased]='s/    const double unbiased = count > 1.0 ? var \* c
 SED[relu_launders_nan]='s/__device__ __forceinline__ float relu_f(float v) { return v < 0.0f ? 0.0f : v; }/__device__ __forceinline__ float relu_f(float v) { return fmaxf(v, 0.0f); }/'   # the ReLU of every epilogue back to v_max_f32: NaN -> 0
 SED[evalwalk_no_nan_fill]='s/      nan_fill_row16(\*(const ConvArgs\*)((ConstArgs\*)table + l), b, cq, rq, pa.reloc, pa.out_nchw);/      (void)0;/'   # sixteen-workgroup walk: a launch whose wait gave up leaves its outputs as they are
 SED[dopri5_beta32]='s|{44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0}|{44.0 / 45, -56.0 / 15, 31.0 / 9, 0, 0, 0}|'
-TESTS="tests/test_hip_backward.py::test_backward_strict_on_kink_free_dynamics tests/test_hip_frame_codec.py::test_encoder_matches_reference_fixture tests/test_hip_frame_codec.py::test_decoder_matches_reference_fixture tests/test_hip_conv.py::test_winograd5_conv_matches_torch tests/test_hip_full_size.py::test_cell_and_encoder_full_channels tests/test_hip_odeint.py::test_fixed_grid_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_dopri5_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_fixed_grid_matches_golden_and_oracle tests/test_hip_odeint.py::test_full_size_against_oracle tests/test_hip_backward.py::test_dopri5_backward_matches_autograd_through_oracle tests/test_hip_backward.py::test_dopri5_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_dopri5_saving_forward_equals_reintegration tests/test_hip_reference_configs.py::test_config0_as_stated_b4 tests/test_hip_encoder_backward.py::test_convgru_cell_backward_matches_autograd_through_oracle tests/test_hip_frame_codec.py::test_backward_matches_fp64_autograd tests/test_hip_vidode.py::test_upsample2x_matches_torch tests/test_hip_vidode.py::test_bn_relu_up_matches_torch tests/test_hip_backward.py::test_async_dopri5_forward_matches_the_synchronous_one tests/test_hip_errors.py::test_a_non_finite_state_is_not_laundered tests/test_hip_errors.py::test_a_lost_partner_in_a_single_evaluation_walk_is_loud"
+# ---- NaN semantics: a failed asynchronous solve, the ReLU-backward masks
+SED[seal_skips_failed_solve]='s|  if (st->done \&\& st->status == 0) return;   // finished: every frame is written|  if (st->done) return;|'   # seal: a solve the controller failed keeps stale frames
+SED[act_bwd_launders_nan]='s/    g.x = y.x <= 0.0f ? 0.0f : g.x; g.y = y.y <= 0.0f ? 0.0f : g.y;/    g.x = y.x > 0.0f ? g.x : 0.0f; g.y = y.y > 0.0f ? g.y : 0.0f;/;s/    g.z = y.z <= 0.0f ? 0.0f : g.z; g.w = y.w <= 0.0f ? 0.0f : g.w;/    g.z = y.z > 0.0f ? g.z : 0.0f; g.w = y.w > 0.0f ? g.w : 0.0f;/'   # fp32 ReLU backward: NaN -> 0
+SED[bn_bwd_launders_nan]='s/      const float gv = pre <= 0.0f ? 0.0f : grad_at<UP>(g, pl, y, xx, H, W);/      const float gv = pre > 0.0f ? grad_at<UP>(g, pl, y, xx, H, W) : 0.0f;/'   # fused BatchNorm + ReLU backward: NaN -> 0
+SED[bf16_mask_launders_nan]='s/          v.x = m.x <= 0.f ? 0.f : v.x; v.y = m.y <= 0.f ? 0.f : v.y; v.z = m.z <= 0.f ? 0.f : v.z; v.w = m.w <= 0.f ? 0.f : v.w;/          v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;/'   # bf16 per-evaluation mask: NaN -> 0
+SED[btraj_mask_drops_negative_nan]='s/__device__ __forceinline__ bool bf16_relu_pass(unsigned f32_bits) { return !(__uint_as_float(f32_bits) <= 0.0f); }/__device__ __forceinline__ bool bf16_relu_pass(unsigned f32_bits) { return (int)f32_bits > 0; }/'   # bf16 reverse sweep: the old sign-bit test, a NaN with its sign bit set -> 0
+TESTS="tests/test_hip_backward.py::test_backward_strict_on_kink_free_dynamics tests/test_hip_frame_codec.py::test_encoder_matches_reference_fixture tests/test_hip_frame_codec.py::test_decoder_matches_reference_fixture tests/test_hip_conv.py::test_winograd5_conv_matches_torch tests/test_hip_full_size.py::test_cell_and_encoder_full_channels tests/test_hip_odeint.py::test_fixed_grid_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_dopri5_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_fixed_grid_matches_golden_and_oracle tests/test_hip_odeint.py::test_full_size_against_oracle tests/test_hip_backward.py::test_dopri5_backward_matches_autograd_through_oracle tests/test_hip_backward.py::test_dopri5_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_dopri5_saving_forward_equals_reintegration tests/test_hip_reference_configs.py::test_config0_as_stated_b4 tests/test_hip_encoder_backward.py::test_convgru_cell_backward_matches_autograd_through_oracle tests/test_hip_frame_codec.py::test_backward_matches_fp64_autograd tests/test_hip_vidode.py::test_upsample2x_matches_torch tests/test_hip_vidode.py::test_bn_relu_up_matches_torch tests/test_hip_backward.py::test_async_dopri5_forward_matches_the_synchronous_one tests/test_hip_errors.py::test_a_non_finite_state_is_not_laundered tests/test_hip_errors.py::test_a_lost_partner_in_a_single_evaluation_walk_is_loud tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[max_num_steps-no_grad] tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[overflow-saving] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[euler-3-per_layer] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[rk4-20-persistent] tests/test_hip_relu_nan_backward.py::test_bf16_backward_passes_the_gradient_of_a_nan_channel tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-True-True-x] tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-False-False-gamma]"
 case "${1:-}" in
 build)
   for m in "${!SED[@]}"; do
