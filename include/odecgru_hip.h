@@ -510,6 +510,21 @@ int odehip_mmnist_render(const double* init, const int* digit_ids, const unsigne
                          const float* lut256, int batch, int n_digits, int t_in, int t_out, float* out_in, float* out_pred,
                          void* stream);
 
+/* Evaluation metrics of predicted frames against the ground truth (frame_metrics.hip) -- what the reference's test() computes per
+ * predicted frame on the host (train_test.py:104-117: F.mse_loss(...).item(), math.log10, utils.get_normalized_ssim), in two launches
+ * on `stream` with no host synchronisation.  pred, truth: (batch, n_frames, channels, 64, 64) fp32, contiguous; channels 1 or 3 (any
+ * other frame shape: ODEHIP_EINVAL).  data_range R > 0: the value range of the frames (1 for [0, 1], 255 for [0, 255]).  Out, all written:
+ *   sse[b][t]    sum over the frame of (pred - truth)^2
+ *   ssim[b][t]   scikit-image's structural_similarity(gaussian_weights=True, use_sample_covariance=False, data_range=R) per channel
+ *                (sigma 1.5, 11 taps, mean over rows / columns 5..58), averaged over the channels
+ *   mse[t]       sum_b sse[b][t] / (batch * channels * 64 * 64)
+ *   psnr[t]      10 log10(R^2 / mse[t]); +inf where mse[t] == 0 (the reference divides by zero there and raises)
+ *   ssim_t[t]    sum_b ssim[b][t] / batch
+ * Every reduction runs in a fixed order (no atomics: two calls are bitwise equal).  A NaN in a frame makes that frame's sse / ssim
+ * and the three [t] values NaN and leaves every other frame alone.  Arguments are checked before any HIP call. */
+int odehip_frame_metrics(const float* pred, const float* truth, int batch, int n_frames, int channels, int height, int width,
+                         float data_range, float* sse, float* ssim, float* mse, float* psnr, float* ssim_t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

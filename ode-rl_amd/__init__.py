@@ -10,5 +10,7 @@ from .helpers.utils import create_convnet  # noqa: F401
 from .modules.DiffEqSolver import DiffEqSolver, ODEFunc  # noqa: F401
 from .modules.ConvGRUCell import ConvGRUCell  # noqa: F401
 from .modules.ODEConvGRUCell import ODEConvGRUCell  # noqa: F401
+from .metrics import frame_metrics, FrameMetrics  # noqa: F401
 
-__all__ = ["odeint", "odeint_adjoint", "DiffEqSolver", "ODEFunc", "create_convnet", "ConvGRUCell", "ODEConvGRUCell"]
+__all__ = ["odeint", "odeint_adjoint", "DiffEqSolver", "ODEFunc", "create_convnet", "ConvGRUCell", "ODEConvGRUCell", "frame_metrics",
+           "FrameMetrics"]

@@ -1,6 +1,8 @@
 """Training-step harness around the HIP hot path: the ODEConvGRU branch of the reference's
 `train_batch` (train_test.py:169-207) and its checkpoint format (helpers/utils.py:212-252), without the per-step host copies
-of the reference's loop (train_test.py:50 `pred.detach().cpu()`) and with anomaly detection off (train_test.py:5)."""
+of the reference's loop (train_test.py:50 `pred.detach().cpu()`) and with anomaly detection off (train_test.py:5).  Evaluation
+(SURVEY.md section 8 f5): `test_batch` and `evaluate`, the ODEConv branch of the reference's `test_batch` / `test`
+(train_test.py:78-165) with the per-frame metrics computed on the device (metrics.py)."""
 import os
 import pickle
 
@@ -70,6 +72,53 @@ def _set_async_quietly(hip_ops, on):
         hip_ops.set_async_dopri5(on)
     except Exception:
         pass
+
+
+def test_batch(model, batch_dict):
+    """The ODEConv branch of the reference's `test_batch` (train_test.py:146-167) for one batch as `data.get_next_batch` builds it:
+    frames in [-0.5, 0.5] are shifted to [0, 1] for the model and its loss and back for the result.  Returns (pred - 0.5,
+    truth - 0.5, loss) with the loss left on the device.  Gradient mode and model.eval() are the caller's business (`evaluate`)."""
+    dev = next(model.parameters()).device
+    inp = batch_dict["observed_data"].to(dev) + 0.5
+    truth = batch_dict["data_to_predict"].to(dev) + 0.5
+    pred = model.get_prediction(inp, batch_dict=batch_dict)
+    loss = model.get_loss(pred, truth)
+    return pred - 0.5, truth - 0.5, loss
+
+
+def evaluate(model, batches):
+    """The reference's `test()` loop (train_test.py:78-144) without wandb, prints and the video: model.eval() under no_grad, and per
+    batch `test_batch`, then MSE, PSNR and SSIM of every predicted frame from ONE `frame_metrics` call where the reference runs
+    `F.mse_loss(...).item()`, `math.log10` and `utils.get_normalized_ssim` (a host copy and B scikit-image calls) per frame.  The
+    frames go to it in [0, 1] with data_range 1: that is the reference's SSIM of the x 255 frames with data_range 255, and its MSE
+    of the [-0.5, 0.5] frames (a shift cancels in the difference), so its `10 log10(1 / mse)` too.  Everything accumulates on the
+    device; the single host transfer is at the end.  `batches`: an iterable of batch dicts, at least one.
+
+    Returns a dict: 'mse', 'psnr', 'ssim' -- (T_out,) CPU tensors, the means over the batches per predicted frame (PSNR is the mean
+    of the per-batch PSNRs, as the reference averages them, not the PSNR of the mean MSE) -- 'loss' (mean over the batches, a
+    float) and 'avg_mse', 'avg_psnr', 'avg_ssim': the last frame's values, which the reference logs as its final metrics
+    (train_test.py:143).  The model's training mode is restored on the way out, also when a batch raises."""
+    from . import metrics
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            total, loss_sum, n = None, None, 0
+            for batch_dict in batches:
+                pred, truth, loss = test_batch(model, batch_dict)
+                m = metrics.frame_metrics(pred + 0.5, truth + 0.5, data_range=1.0)
+                per_frame = torch.stack([m.mse, m.psnr, m.ssim])
+                total = per_frame if total is None else total + per_frame
+                loss_sum = loss if loss_sum is None else loss_sum + loss
+                n += 1
+            if n == 0:
+                raise ValueError("evaluate: no batches")
+            host = torch.cat([(total / n).reshape(-1), torch.as_tensor(loss_sum / n, dtype=total.dtype, device=total.device).reshape(1)]).cpu()
+    finally:
+        model.train(was_training)
+    mse, psnr, ssim = host[:-1].view(3, -1)
+    return {"mse": mse, "psnr": psnr, "ssim": ssim, "loss": float(host[-1]),
+            "avg_mse": float(mse[-1]), "avg_psnr": float(psnr[-1]), "avg_ssim": float(ssim[-1])}
 
 
 def checkpoint_name(ckpt_id, step):

@@ -41,7 +41,12 @@ SED[act_bwd_launders_nan]='s/    g.x = y.x <= 0.0f ? 0.0f : g.x; g.y = y.y <= 0.
 SED[bn_bwd_launders_nan]='s/      const float gv = pre <= 0.0f ? 0.0f : grad_at<UP>(g, pl, y, xx, H, W);/      const float gv = pre > 0.0f ? grad_at<UP>(g, pl, y, xx, H, W) : 0.0f;/'   # fused BatchNorm + ReLU backward: NaN -> 0
 SED[bf16_mask_launders_nan]='s/          v.x = m.x <= 0.f ? 0.f : v.x; v.y = m.y <= 0.f ? 0.f : v.y; v.z = m.z <= 0.f ? 0.f : v.z; v.w = m.w <= 0.f ? 0.f : v.w;/          v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;/'   # bf16 per-evaluation mask: NaN -> 0
 SED[btraj_mask_drops_negative_nan]='s/__device__ __forceinline__ bool bf16_relu_pass(unsigned f32_bits) { return !(__uint_as_float(f32_bits) <= 0.0f); }/__device__ __forceinline__ bool bf16_relu_pass(unsigned f32_bits) { return (int)f32_bits > 0; }/'   # bf16 reverse sweep: the old sign-bit test, a NaN with its sign bit set -> 0
-TESTS="tests/test_hip_backward.py::test_backward_strict_on_kink_free_dynamics tests/test_hip_frame_codec.py::test_encoder_matches_reference_fixture tests/test_hip_frame_codec.py::test_decoder_matches_reference_fixture tests/test_hip_conv.py::test_winograd5_conv_matches_torch tests/test_hip_full_size.py::test_cell_and_encoder_full_channels tests/test_hip_odeint.py::test_fixed_grid_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_dopri5_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_fixed_grid_matches_golden_and_oracle tests/test_hip_odeint.py::test_full_size_against_oracle tests/test_hip_backward.py::test_dopri5_backward_matches_autograd_through_oracle tests/test_hip_backward.py::test_dopri5_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_dopri5_saving_forward_equals_reintegration tests/test_hip_reference_configs.py::test_config0_as_stated_b4 tests/test_hip_encoder_backward.py::test_convgru_cell_backward_matches_autograd_through_oracle tests/test_hip_frame_codec.py::test_backward_matches_fp64_autograd tests/test_hip_vidode.py::test_upsample2x_matches_torch tests/test_hip_vidode.py::test_bn_relu_up_matches_torch tests/test_hip_backward.py::test_async_dopri5_forward_matches_the_synchronous_one tests/test_hip_errors.py::test_a_non_finite_state_is_not_laundered tests/test_hip_errors.py::test_a_lost_partner_in_a_single_evaluation_walk_is_loud tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[max_num_steps-no_grad] tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[overflow-saving] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[euler-3-per_layer] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[rk4-20-persistent] tests/test_hip_relu_nan_backward.py::test_bf16_backward_passes_the_gradient_of_a_nan_channel tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-True-True-x] tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-False-False-gamma]"
+# ---- evaluation metrics (frame_metrics.hip): the window, the interior, the constants, the covariance
+SED[ssim_sigma]='s/  const double sigma = 1.5;/  const double sigma = 1.4;/'                                   # Gaussian taps of sigma 1.4
+SED[ssim_interior_shift]='s/^constexpr int kFirstRow = kWinRadius; /constexpr int kFirstRow = kWinRadius + 1; /'   # S averaged over rows 6..59 (row 64 = the words behind each plane in LDS: still inside the allocation)
+SED[ssim_c2]='s/  const double k1 = 0.01, k2 = 0.03, range = (double)data_range;/  const double k1 = 0.01, k2 = 0.02, range = (double)data_range;/'   # C2 = (0.02 R)^2
+SED[ssim_covariance]='s/        const float vxy = uxy - ux \* uy;/        const float vxy = uxy - ux * ux;/'       # vxy = uxy - ux ux
+TESTS="tests/test_hip_backward.py::test_backward_strict_on_kink_free_dynamics tests/test_hip_frame_codec.py::test_encoder_matches_reference_fixture tests/test_hip_frame_codec.py::test_decoder_matches_reference_fixture tests/test_hip_conv.py::test_winograd5_conv_matches_torch tests/test_hip_full_size.py::test_cell_and_encoder_full_channels tests/test_hip_odeint.py::test_fixed_grid_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_dopri5_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_fixed_grid_matches_golden_and_oracle tests/test_hip_odeint.py::test_full_size_against_oracle tests/test_hip_backward.py::test_dopri5_backward_matches_autograd_through_oracle tests/test_hip_backward.py::test_dopri5_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_dopri5_saving_forward_equals_reintegration tests/test_hip_reference_configs.py::test_config0_as_stated_b4 tests/test_hip_encoder_backward.py::test_convgru_cell_backward_matches_autograd_through_oracle tests/test_hip_frame_codec.py::test_backward_matches_fp64_autograd tests/test_hip_vidode.py::test_upsample2x_matches_torch tests/test_hip_vidode.py::test_bn_relu_up_matches_torch tests/test_hip_backward.py::test_async_dopri5_forward_matches_the_synchronous_one tests/test_hip_errors.py::test_a_non_finite_state_is_not_laundered tests/test_hip_errors.py::test_a_lost_partner_in_a_single_evaluation_walk_is_loud tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[max_num_steps-no_grad] tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[overflow-saving] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[euler-3-per_layer] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[rk4-20-persistent] tests/test_hip_relu_nan_backward.py::test_bf16_backward_passes_the_gradient_of_a_nan_channel tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-True-True-x] tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-False-False-gamma] tests/test_hip_frame_metrics.py::test_matches_the_fp64_restatement[3-5-3] tests/test_hip_frame_metrics.py::test_matches_the_fp64_restatement[64-10-1] tests/test_hip_frame_metrics.py::test_evaluate_end_to_end"
 case "${1:-}" in
 build)
   for m in "${!SED[@]}"; do
