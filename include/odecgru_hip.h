@@ -273,6 +273,47 @@ int odehip_convgru_cell_backward(const odehip_convgru_cell* c, const odehip_conv
                                  const odehip_convgru_cell_grads* grads, int batch, void* workspace, size_t workspace_bytes,
                                  void* stream);
 
+/* ---- a whole ConvGRU sequence: ConvGRUCell.forward(input_tensor, h_cur, seq_len) (modules/ConvGRUCell.py:55-86) as the ConvGRU
+ * baseline drives it (models/ConvGRU.py:133-149 encoder: frames from a zero state; :225-242 decoder: zero input from a state) ----
+ * x_seq (n_steps, batch, input, 16, 16) or NULL = zero input; h0 (batch, hidden, 16, 16) or NULL = zero state; not both NULL.
+ * h_seq (n_steps, batch, hidden, 16, 16) is written in place by the step epilogues (slot t = the state after step t; the last
+ * state is the view h_seq[n_steps - 1]).  Steps are launches in stream order; enqueue-only, no host synchronisation.
+ *   zero input:  the gates and candidate convolutions are ONE-source launches over the state half of the weights (hv->wino[1],
+ *                hv->wino[3]; the split-launch choice follows K = hidden * 25); no zero frame is allocated, read or transformed
+ *   zero state:  the first step runs over the frame half alone (hv->wino[0], hv->wino[2]) and r * h is not formed
+ *   both given:  the two-source launches of odehip_convgru_cell_forward (w_gates_wino / w_can_wino)
+ * ks = 5, input % 8 == 0, hidden % 32 == 0 (what the F(2x2,5x5) kernels serve); _train / _backward: both multiples of 64.
+ * Arguments are checked before any HIP call (ODEHIP_EINVAL).  Pure additions: no existing struct or signature changes, so
+ * ODEHIP_ABI_VERSION stays (as for odehip_frame_metrics).
+ * Workspace: odehip_convgru_sequence_workspace_bytes(c, n_steps, batch, has_x, train); forward (train = 0) keeps two states and one
+ * step's conv outputs (+ the Q4 frames), train keeps per step h, gates_raw, z, r*h, cand_raw and the backward's gradients of the two
+ * conv outputs and the gradient arriving at the step: 10 state-sized Q4 tensors per step (+ 2 frame-sized with has_x), i.e. 40 MiB
+ * per step at batch 64, hidden 64.
+ * odehip_convgru_sequence_train = _forward that keeps those tensors; the workspace must stay untouched until _backward.
+ * odehip_convgru_sequence_backward: back-propagation through time in one call.  grad_h_seq (n_steps, batch, hidden, 16, 16) = the
+ * gradient arriving at every h_seq slot (a gradient of the last state is added to slot n_steps - 1 by the caller).  has_x / has_h0
+ * as in the train call; grad_x_seq (x_seq's shape) is written iff has_x, grad_h0 iff has_h0 (else pass NULL).  Reverse sweep
+ * t = n_steps-1 .. 0 with the cell backward kernels (one-source input-gradient launches without x: no gradient is formed for the
+ * zero frame), then per weight half and 64 x 64 channel tile ONE weight-gradient launch over all steps (steps are one more batch
+ * axis; slabs summed in a fixed order), GroupNorm affine and bias gradients summed in a fixed order: bitwise reproducible.  Without
+ * x the frame half of grads->w_gates / w_can is written as exact zeros (what autograd gives for a zero input). */
+typedef struct odehip_convgru_cell_halves {
+  /* forward images of the two HALVES of the two 5x5 weights, in the order conv_gates.0.weight[:, :input], conv_gates.0.weight[:, input:],
+   * conv_can.0.weight[:, :input], conv_can.0.weight[:, input:] (each slice made contiguous, then packed with transpose_flip = 0): a step
+   * with one source runs over its half alone.  Entries a call does not need may be NULL. */
+  const float* wino[4];        /* odehip_pack_conv_weight_winograd5 (fp32 mode)                                              */
+  const void* bf16[4];         /* odehip_pack_conv_weight_bf16_ks (bf16 mode, i.e. odehip_convgru_cell.w_gates_bf16 != NULL) */
+} odehip_convgru_cell_halves;
+size_t odehip_convgru_sequence_workspace_bytes(const odehip_convgru_cell* c, int n_steps, int batch, int has_x, int train);
+int odehip_convgru_sequence_forward(const odehip_convgru_cell* c, const odehip_convgru_cell_halves* hv, const float* x_seq_nchw, const float* h0_nchw, int n_steps,
+                                    int batch, float* h_seq_nchw, void* workspace, size_t workspace_bytes, void* stream);
+int odehip_convgru_sequence_train(const odehip_convgru_cell* c, const odehip_convgru_cell_halves* hv, const float* x_seq_nchw, const float* h0_nchw, int n_steps, int batch,
+                                  float* h_seq_nchw, void* workspace, size_t workspace_bytes, void* stream);
+int odehip_convgru_sequence_backward(const odehip_convgru_cell* c, const odehip_convgru_cell_halves* hv, const odehip_convgru_cell_bwd* cb, int has_x, int has_h0,
+                                     int n_steps, int batch, const float* grad_h_seq_nchw, float* grad_x_seq_nchw,
+                                     float* grad_h0_nchw, const odehip_convgru_cell_grads* grads, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+
 /* ---- training path of the encoder: `loss.backward()` through ODEConvGRUCell.forward (train_test.py:204) ---------------- */
 
 typedef struct odehip_encoder_bwd {

@@ -63,6 +63,10 @@ class ConvGRUCellDesc(ctypes.Structure):
                 ("w_gates_wino", ctypes.c_void_p), ("w_can_wino", ctypes.c_void_p)]
 
 
+class ConvGRUCellHalves(ctypes.Structure):   # odehip_convgru_cell_halves: frame / state halves of the two 5x5 weights, packed on their own
+    _fields_ = [("wino", ctypes.c_void_p * 4), ("bf16", ctypes.c_void_p * 4)]
+
+
 class EncoderDesc(ctypes.Structure):
     _fields_ = [("f_enc", ConvStack), ("cell", ConvGRUCellDesc), ("head_hidden", ctypes.c_int), ("out_ch", ctypes.c_int),
                 ("w_head0", ctypes.c_void_p), ("b_head0", ctypes.c_void_p), ("w_head1", ctypes.c_void_p),
@@ -208,6 +212,14 @@ SIGNATURES = {
     "odehip_convgru_cell_forward": (ctypes.c_int, [ctypes.POINTER(ConvGRUCellDesc), ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
                                                    ctypes.c_void_p]),
+    "odehip_convgru_sequence_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ConvGRUCellDesc)] + [ctypes.c_int] * 4),
+    "odehip_convgru_sequence_forward": (ctypes.c_int, [ctypes.POINTER(ConvGRUCellDesc), ctypes.POINTER(ConvGRUCellHalves), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                       ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "odehip_convgru_sequence_train": (ctypes.c_int, [ctypes.POINTER(ConvGRUCellDesc), ctypes.POINTER(ConvGRUCellHalves), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                     ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "odehip_convgru_sequence_backward": (ctypes.c_int, [ctypes.POINTER(ConvGRUCellDesc), ctypes.POINTER(ConvGRUCellHalves), ctypes.POINTER(ConvGRUCellBwd)] + [ctypes.c_int] * 4 +
+                                         [ctypes.c_void_p] * 3 + [ctypes.POINTER(ConvGRUCellGrads), ctypes.c_void_p, ctypes.c_size_t,
+                                                                  ctypes.c_void_p]),
     "odehip_encoder_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(EncoderDesc), ctypes.c_int, ctypes.c_int]),
     "odehip_odeconvgru_encode": (ctypes.c_int, [ctypes.POINTER(EncoderDesc), ctypes.c_void_p,
                                                 ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_int,

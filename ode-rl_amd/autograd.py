@@ -118,6 +118,39 @@ def cell_with_grad(packed, x, h):
     return _CellFn.apply(x, h, packed, *packed._params())
 
 
+class _SequenceFn(torch.autograd.Function):
+    """A whole ConvGRU sequence under autograd (csrc/convgru_sequence.hip): the saving forward, back-propagation through time in one
+    call.  x_seq / h0 may be None (zero input / zero state); the gradient of the last state arrives through the view h_seq[-1]."""
+
+    @staticmethod
+    def forward(ctx, x_seq, h0, n_steps, packed, *params):
+        ctx.mode = hip_ops.current_compute_dtype()
+        h_seq, ctx.saved = hip_ops.convgru_sequence(packed, x_seq, h0, n_steps, save=True)
+        ctx.packed = packed
+        ctx.n_in = None if x_seq is None else x_seq.shape[0]
+        ctx.versions = tuple(p._version for p in params)
+        ctx.params = params
+        return h_seq
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    @_pinned
+    def backward(ctx, grad_h_seq):
+        if tuple(p._version for p in ctx.params) != ctx.versions:
+            raise RuntimeError("a ConvGRUCell parameter was modified in place between forward and backward")
+        if ctx.saved is None:
+            raise RuntimeError("the sequence's saved activations were already consumed (backward called twice)")
+        gx, gh0, grads = hip_ops.convgru_sequence_backward(ctx.packed, ctx.saved, grad_h_seq)
+        ctx.saved = None
+        if gx is not None and ctx.n_in > gx.shape[0]:   # frames behind seq_len were never read
+            gx = torch.cat([gx, gx.new_zeros((ctx.n_in - gx.shape[0],) + tuple(gx.shape[1:]))])
+        return (gx, gh0, None, None) + tuple(grads)
+
+
+def sequence_with_grad(packed, x_seq, h0, n_steps):
+    return _SequenceFn.apply(x_seq, h0, n_steps, packed, *packed._params())
+
+
 class _EncodeFn(torch.autograd.Function):
     """ODEConvGRUCell.forward / run_ode_conv_gru under autograd: csrc/convgru_backward.hip keeps the per-frame conv outputs and
     sweeps back; the gradient may arrive through (mean, std) and, when latent_ys was asked for, through latent_ys."""

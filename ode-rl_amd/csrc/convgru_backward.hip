@@ -346,6 +346,23 @@ __global__ __launch_bounds__(256) void add_nchw_slice_to_q4_kernel(const float* 
   *d += f32x4{s[0], s[kPix], s[2 * kPix], s[3 * kPix]};
 }
 
+// host-side handles of the cell backward kernels for the sequence driver (convgru_sequence.hip)
+void launch_gn_update_bwd(const float* cand_raw, const float* gamma, const float* beta, const float* gh, const float* z, const float* h_prev,
+                          float* g_cand_raw, float* gz_pre, float* gh_prev, float* dgamma_part, float* dbeta_part, int hidden, int batch,
+                          hipStream_t stream) {
+  hipLaunchKernelGGL(gn_update_bwd_kernel, dim3(hidden / 32, batch), dim3(256), 0, stream, cand_raw, gamma, beta, gh, z, h_prev, g_cand_raw,
+                     gz_pre, gh_prev, dgamma_part, dbeta_part, hidden / 32);
+}
+void launch_gn_gates_bwd(const float* gates_raw, const float* gamma, const float* beta, const float* gz_pre, const float* g_rh,
+                         const float* h_prev, float* gh_prev, float* g_gates_raw, float* dgamma_part, float* dbeta_part, int hidden,
+                         int batch, hipStream_t stream) {
+  hipLaunchKernelGGL(gn_gates_bwd_kernel, dim3(2 * hidden / 32, batch), dim3(256), 0, stream, gates_raw, gamma, beta, gz_pre, g_rh, h_prev,
+                     gh_prev, g_gates_raw, dgamma_part, dbeta_part, hidden / 32);
+}
+void launch_reduce_rows(const float* part, int n_rows, int n_cols, float* out, hipStream_t stream) {
+  hipLaunchKernelGGL(reduce_rows_kernel, dim3(n_cols), dim3(256), 0, stream, part, n_rows, n_cols, out);
+}
+
 }  // namespace odehip
 
 using namespace odehip;

@@ -953,6 +953,111 @@ def convgru_cell_backward(packed_cell, x, h, grad_h_next):
     return gx, gh, grads
 
 
+def _cell_seq_desc(packed_cell):
+    """(cell descriptor, odehip_convgru_cell_halves): the images of the two halves (frame, state) of the two 5x5 weights, each slice packed on its own: what
+    the one-source steps of odehip_convgru_sequence_* run over.  Packed once per parameter version and compute dtype."""
+    d = packed_cell.refresh()
+    cached = getattr(packed_cell, "_seq", None)
+    if cached is not None and cached[0] == packed_cell._stamp:
+        return d, cached[1]
+    mode, cell = packed_cell._stamp[0], packed_cell.cell
+    if d.ks != 5 or d.input % 8 or d.hidden % 32:
+        raise ValueError(f"ConvGRU sequence: the 5x5 Winograd kernels serve kernel_size 5, input_dim % 8 == 0, hidden_dim % 32 == 0 "
+                         f"(got {d.ks}, {d.input}, {d.hidden})")
+    wg, wc = cell.conv_gates[0].weight.detach(), cell.conv_can[0].weight.detach()
+    slices = [w.contiguous() for w in (wg[:, :d.input], wg[:, d.input:], wc[:, :d.input], wc[:, d.input:])]
+    hv = _lib.ConvGRUCellHalves()
+    if mode == "bf16":
+        if not (_bf16_cell_ok(d.input, d.hidden, d.ks) and d.w_gates_bf16):
+            raise ValueError(f"ConvGRU sequence: bf16 compute needs input_dim % 16 == 0, hidden_dim % 32 == 0 and input_dim + hidden_dim <= 128 "
+                             f"(got {d.input}, {d.hidden})")
+        keep = [pack_conv_weight_bf16_ks(w) for w in slices]
+        for j in range(4):
+            hv.bf16[j] = keep[j].data_ptr()
+    else:
+        if not d.w_gates_wino:
+            raise ValueError("ConvGRU sequence: needs the F(2x2,5x5) form of the cell's weights (ODEHIP_WINO5=0 switches it off)")
+        keep = pack_conv_weights_many([(w, 2, False) for w in slices])
+        for j in range(4):
+            hv.wino[j] = keep[j].data_ptr()
+    packed_cell._seq = (packed_cell._stamp, hv, keep)
+    return d, hv
+
+
+def _check_sequence_args(d, x_seq, h0, n_steps):
+    if x_seq is None and h0 is None:
+        raise ValueError("ConvGRU sequence: input_tensor and h_cur are both None")
+    n_steps = int(n_steps)
+    if n_steps < 1:
+        raise ValueError(f"ConvGRU sequence: seq_len must be at least 1 (got {n_steps})")
+    b = None
+    if x_seq is not None:
+        require_device_tensor(x_seq, "input_tensor")
+        if x_seq.dim() != 5 or x_seq.shape[0] < n_steps or tuple(x_seq.shape[2:]) != (d.input, 16, 16):
+            raise ValueError(f"ConvGRU sequence: input_tensor must be (>= {n_steps},B,{d.input},16,16); got {tuple(x_seq.shape)}")
+        b = x_seq.shape[1]
+        x_seq = x_seq[:n_steps].detach().contiguous()
+    if h0 is not None:
+        require_device_tensor(h0, "h_cur")
+        if h0.dim() != 4 or tuple(h0.shape[1:]) != (d.hidden, 16, 16) or (b is not None and h0.shape[0] != b):
+            raise ValueError(f"ConvGRU sequence: h_cur must be (B,{d.hidden},16,16); got {tuple(h0.shape)}")
+        b = h0.shape[0]
+        h0 = h0.detach().contiguous()
+    return x_seq, h0, n_steps, b
+
+
+def convgru_sequence(packed_cell, x_seq, h0, n_steps, save=False):
+    """n_steps ConvGRU steps in one call (csrc/convgru_sequence.hip).  x_seq (T,B,input,16,16) or None = zero input (one-source
+    launches over the state half of the weights), h0 (B,hidden,16,16) or None = zero state.  Returns h_seq (T,B,hidden,16,16), written in
+    place by the steps (the last state is h_seq[-1]); with save=True also what convgru_sequence_backward needs."""
+    d, hv = _cell_seq_desc(packed_cell)
+    x_seq, h0, n_steps, b = _check_sequence_args(d, x_seq, h0, n_steps)
+    dev = (x_seq if x_seq is not None else h0).device
+    lib = _lib.load()
+    nbytes = lib.odehip_convgru_sequence_workspace_bytes(ctypes.byref(d), n_steps, b, int(x_seq is not None), int(bool(save)))
+    if nbytes == 0:
+        raise ValueError("ConvGRU sequence: bad sizes")
+    # a training-mode forward owns its workspace until the backward pass has run
+    ws = alloc_workspace(nbytes, dev) if save else workspace(("cgru_seq", n_steps, b, d.input, d.hidden, x_seq is not None), nbytes, dev)
+    h_seq = torch.empty((n_steps, b, d.hidden, 16, 16), dtype=torch.float32, device=dev)
+    fn = lib.odehip_convgru_sequence_train if save else lib.odehip_convgru_sequence_forward
+    _lib.check(fn(ctypes.byref(d), ctypes.byref(hv), _ptr(x_seq), _ptr(h0), n_steps, b, _ptr(h_seq), _ptr(ws), ws.numel(), _stream()))
+    if save:
+        return h_seq, (ws, x_seq is not None, h0 is not None, n_steps, b, packed_cell._stamp)
+    return h_seq
+
+
+def convgru_sequence_backward(packed_cell, saved, grad_h_seq):
+    """BPTT over a sequence convgru_sequence(save=True) ran: (grad_x_seq or None, grad_h0 or None, [gradients of packed_cell._params()]).
+    Without x the frame half of the two conv weight gradients is exact zeros."""
+    ws, has_x, has_h0, n_steps, b, stamp = saved
+    require_device_tensor(grad_h_seq, "grad_h_seq")
+    d, hv = _cell_seq_desc(packed_cell)
+    if packed_cell._stamp != stamp:
+        raise RuntimeError("a ConvGRUCell parameter (or the compute dtype) changed between the sequence's forward and its backward")
+    cached = getattr(packed_cell, "_bwd", None)
+    if cached is None or cached[0] != packed_cell._stamp:
+        keep, bf, wino = _cell_bwd_packs(packed_cell.cell, d, packed_cell._stamp[0])
+        bw = _lib.ConvGRUCellBwd(*[k.data_ptr() for k in keep])
+        for j in range(4):
+            bw.bf16[j] = bf[j].data_ptr() if bf[j] is not None else None
+            bw.wino[j] = wino[j].data_ptr() if wino[j] is not None else None
+        cached = packed_cell._bwd = (packed_cell._stamp, bw, keep, bf, wino)
+    bw = cached[1]
+    grad_h_seq = grad_h_seq.contiguous()
+    if tuple(grad_h_seq.shape) != (n_steps, b, d.hidden, 16, 16):
+        raise ValueError(f"grad_h_seq must be ({n_steps},{b},{d.hidden},16,16); got {tuple(grad_h_seq.shape)}")
+    dev = grad_h_seq.device
+    grads = [torch.empty_like(p) for p in packed_cell._params()]
+    g = _lib.ConvGRUCellGrads(*[t_.data_ptr() for t_ in grads])
+    gx = torch.empty((n_steps, b, d.input, 16, 16), dtype=torch.float32, device=dev) if has_x else None
+    gh0 = torch.empty((b, d.hidden, 16, 16), dtype=torch.float32, device=dev) if has_h0 else None
+    _lib.check(_lib.load().odehip_convgru_sequence_backward(ctypes.byref(d), ctypes.byref(hv), ctypes.byref(bw), int(has_x), int(has_h0), n_steps, b,
+                                                            _ptr(grad_h_seq), _ptr(gx), _ptr(gh0), ctypes.byref(g), _ptr(ws), ws.numel(),
+                                                            _stream()))
+    return gx, gh0, grads
+
+
 class PackedEncoder:
     """Everything `ODEConvGRUCell.forward` needs on the device: encoder dynamics, cell, 1x1 head."""
 

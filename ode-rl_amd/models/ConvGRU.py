@@ -1,0 +1,153 @@
+"""Harness for the reference's ConvGRU baseline (`models/ConvGRU.py`: conv encoder -> ConvGRU over the observed frames from a
+zero state -> autonomous ConvGRU rollout -> transposed-conv decoder -> sigmoid), the model every ODEConvGRU number is read against
+(`model: "ConvGRU"` is the reference's default, configs.yaml:4).
+
+Same constructor, `forward`, `get_prediction`, `get_loss` and the same module names, so a reference checkpoint loads key for key:
+`encoder.conv_encoders.0.{0,2}`, `encoder.conv_gru_cells.0.conv_gates.{0,1}` / `conv_can.{0,1}`, `decoder.conv_gru_cells.0.*`,
+`decoder.conv_decoders.0.{0,2}`.
+
+Both cells run as ONE sequence call each (`ConvGRUCell.rollout`, csrc/convgru_sequence.hip): the encoder cell driven over the
+encoded frames from a zero state, the decoder cell with no input at all (its 5x5 convolutions run over the state half of their
+weights).  Frame encoder and decoder are the fused launches of csrc/frame_codec.hip where their structure checks pass (the default
+configuration: leaky_relu, one frame channel, 64 latent channels); otherwise library calls, as in ODEConvGRU.
+
+Scope: depth == 1.  The reference's depth > 1 branches read `resize` and `self.hiddens` before they exist and cannot run; they
+raise NotImplementedError here.  `decODE` is stored and ignored, as in the reference (its DecODEr is commented out).  Kept quirks:
+the decoder's views take their batch size from opt.batch_size, and the output is a sigmoid."""
+import torch
+import torch.nn as nn
+
+from .. import hip_ops
+from ..modules.ConvGRUCell import ConvGRUCell
+
+
+def _wants_grad(module, x):
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
+
+
+class ConvGRU(nn.Module):
+    def __init__(self, opt, device, activation='leaky_relu', decODE=False):
+        super().__init__()
+        self.opt = opt
+        self.decODE = decODE
+        self.device = device
+        self.encoder_out_channels = opt.convgru_out_ch
+        self.decoder_out_channels = opt.in_channels
+        if activation == 'relu':
+            nonlinear = nn.ReLU()
+        elif activation == 'tanh':
+            nonlinear = nn.Tanh()
+        elif activation == 'leaky_relu':
+            nonlinear = nn.LeakyReLU(negative_slope=0.2, inplace=True)
+        elif activation == 'elu':
+            nonlinear = nn.ELU()
+        else:   # the reference falls through to a NameError here
+            raise NotImplementedError('Wrong activation function')
+        if opt.phase == 'train':
+            self.n_input_frames, self.n_output_frames = opt.train_in_seq, opt.train_out_seq
+        else:
+            self.n_input_frames, self.n_output_frames = opt.test_in_seq, opt.test_out_seq
+        self.encoder = Encoder(in_channels=opt.in_channels, out_channels=self.encoder_out_channels, n_frames=self.n_input_frames,
+                               act=nonlinear, opt=opt, device=device).to(device)
+        self.hidden_state_channels = self.encoder.get_hidden_state_channels()
+        self.decoder = Decoder(in_channels=self.encoder_out_channels, out_channels=self.decoder_out_channels,
+                               hidden_state_channels=self.hidden_state_channels, act=nonlinear, opt=opt, device=device,
+                               resolution=self.encoder.resolution, n_frames=self.n_output_frames).to(device)
+
+    def forward(self, inputs, batch_dict=None):
+        _, last_state_list = self.encoder(inputs)
+        return self.decoder(last_state_list)   # the sigmoid of the reference's forward is folded into the decoder's last launch
+
+    def get_prediction(self, inputs, batch_dict=None):
+        return self(inputs, batch_dict)
+
+    def get_loss(self, pred_frames, truth, loss='MSE'):
+        b, t, c, h, w = truth.size()
+        return nn.functional.mse_loss(pred_frames.reshape(b * t, c, h, w), truth.reshape(b * t, c, h, w))
+
+
+class Encoder(nn.Module):
+    def __init__(self, in_channels=1, out_channels=96, n_frames=10, act=None, dtype=None, opt=None, device=None):
+        super().__init__()
+        self.opt = opt
+        self.n_frames = n_frames
+        self.depth = opt.depth
+        if self.depth != 1:
+            raise NotImplementedError("ConvGRU: depth > 1 cannot run in the reference either (its branches read `resize` and `self.hiddens` "
+                                      "before they exist); only depth == 1 is implemented")
+        h, w = opt.resolution, opt.resolution
+        self.out_channels = out_channels
+        self.device = device
+        chan, resize = 16, 4
+        self.resolution = h // resize, w // resize
+        self.conv_encoders = nn.ModuleList([nn.Sequential(nn.Conv2d(in_channels, chan, 3, 2, 1), act,
+                                                          nn.Conv2d(chan, opt.conv_encoder_out_ch, 3, 2, 1), act)])
+        self.conv_gru_cells = nn.ModuleList([ConvGRUCell(self.resolution, opt.conv_encoder_out_ch, opt.convgru_out_ch, 5, bias=True,
+                                                         dtype=dtype)])
+        self.hidden_state_channels = [opt.convgru_out_ch]
+        self.init_hidden_state_channels = self.hidden_state_channels.copy()
+
+    def get_hidden_state_channels(self):
+        return self.hidden_state_channels[::-1]
+
+    def _encode_time_first(self, inputs):
+        """(B,T,c,H,W) -> conv_encoders[0] per frame, as (T,B,C',H/4,W/4)."""
+        seq = self.conv_encoders[0]
+        if inputs.is_cuda and tuple(inputs.shape[-2:]) == (64, 64) and hip_ops.frame_encoder_supported(seq):
+            if not _wants_grad(seq, inputs):
+                return hip_ops.frame_encode(seq, inputs)
+            if hip_ops.codec_backward_enabled() and not inputs.requires_grad and hip_ops.frame_encoder_backward_supported(seq):
+                return hip_ops.frame_encode_autograd(seq, inputs)
+        b, t, c, h, w = inputs.size()
+        enc = seq(inputs.reshape(-1, c, h, w))
+        _, c_, h_, w_ = enc.size()
+        return enc.view(b, t, c_, h_, w_).permute(1, 0, 2, 3, 4)
+
+    def forward(self, inputs):
+        self.hidden_state_channels = self.init_hidden_state_channels.copy()
+        hip_ops.require_device_tensor(inputs, "inputs")
+        encoded = self._encode_time_first(inputs)   # t, b, c, h, w
+        hiddens, h_next = self.conv_gru_cells[0].rollout(encoded, None, self.n_frames)
+        return hiddens, [h_next]
+
+
+class Decoder(nn.Module):
+    def __init__(self, in_channels, out_channels, hidden_state_channels, n_frames, act=None, dtype=None, opt=None, device=None,
+                 resolution=(16, 16)):
+        super().__init__()
+        assert in_channels == hidden_state_channels[0]
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        hidden_state_channels.append(out_channels)
+        self.hidden_state_channels = hidden_state_channels
+        self.opt = opt
+        self.device = device
+        self.depth = opt.depth
+        if self.depth != 1:
+            raise NotImplementedError("ConvGRU: only depth == 1 is implemented (the reference's depth > 1 decoder cannot run)")
+        self.encoder_resolution = resolution
+        self.n_frames = n_frames
+        chan = 16
+        conv_gru_ch, last_ch = self.hidden_state_channels[0], self.hidden_state_channels[1]
+        self.conv_gru_cells = nn.ModuleList([ConvGRUCell(resolution, conv_gru_ch, conv_gru_ch, 5, bias=True, dtype=dtype)])
+        self.conv_decoders = nn.ModuleList([nn.Sequential(nn.ConvTranspose2d(conv_gru_ch, chan * 2, 4, 2, 1), act,
+                                                          nn.ConvTranspose2d(chan * 2, last_ch, 4, 2, 1))])
+
+    def _decode_sigmoid(self, hiddens):
+        """(N,C,16,16) -> sigmoid(conv_decoders[0](.)) (N,c,64,64)."""
+        seq = self.conv_decoders[0]
+        if hiddens.is_cuda and tuple(hiddens.shape[-2:]) == (16, 16) and hip_ops.frame_decoder_supported(seq):
+            if not _wants_grad(seq, hiddens):
+                return hip_ops.frame_decode(seq, hiddens, True)
+            if hip_ops.codec_backward_enabled() and hip_ops.frame_decoder_backward_supported(seq):
+                return hip_ops.frame_decode_autograd(seq, hiddens, True)
+        return torch.sigmoid(seq(hiddens))
+
+    def forward(self, hidden_states):
+        assert len(hidden_states) == self.depth
+        b = self.opt.batch_size   # (the reference's choice: not the batch the tensors carry)
+        e_h, e_w = self.encoder_resolution
+        hiddens, _ = self.conv_gru_cells[0].rollout(None, hidden_states[0], seq_len=self.n_frames)   # t, b, c, h, w
+        outputs = self._decode_sigmoid(hiddens.reshape(b * self.n_frames, -1, e_h, e_w))
+        _, c, h, w = outputs.size()
+        return outputs.view(self.n_frames, b, c, h, w).permute(1, 0, 2, 3, 4)

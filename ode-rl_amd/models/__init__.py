@@ -1,0 +1,1 @@
+from .ConvGRU import ConvGRU  # noqa: F401

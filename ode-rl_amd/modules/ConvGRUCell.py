@@ -52,3 +52,21 @@ class ConvGRUCell(nn.Module):
                 h_cur = hip_ops.convgru_cell_forward(self._packed(), x, h_cur)
             outs.append(h_cur)
         return torch.stack(outs, dim=dim), h_cur
+
+    def rollout(self, input_tensor=None, h_cur=None, seq_len=10, dim=0):
+        """The contract of `forward` -- (stack of h over `dim`, last h) -- as ONE call of the sequence path
+        (csrc/convgru_sequence.hip): the steps write their states straight into the stacked tensor, input_tensor=None is a zero
+        input that is never materialised (both 5x5 convolutions run over the state half of their weights), h_cur=None a zero
+        state whose first step skips the state half.  Under autograd the backward is one BPTT call.  `forward` stays the
+        step-by-step route."""
+        if input_tensor is None and h_cur is None:
+            raise ValueError("ConvGRUCell.rollout: input_tensor and h_cur are both None")
+        wants_grad = torch.is_grad_enabled() and ((input_tensor is not None and input_tensor.requires_grad) or
+                                                  (h_cur is not None and h_cur.requires_grad) or
+                                                  any(p.requires_grad for p in self.parameters()))
+        if wants_grad:
+            from ..autograd import sequence_with_grad
+            h_seq = sequence_with_grad(self._packed(), input_tensor, h_cur, seq_len)
+        else:
+            h_seq = hip_ops.convgru_sequence(self._packed(), input_tensor, h_cur, seq_len)
+        return (h_seq if dim == 0 else h_seq.movedim(0, dim)), h_seq[-1]
