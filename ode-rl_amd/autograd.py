@@ -15,27 +15,46 @@ def _pinned(fn):
     return wrapper
 
 
+def _stack_params(stack):
+    """The parameters of the dynamics in the order the solver Functions take them and return their gradients: w0, b0, w1, b1, ..."""
+    params = []
+    for c in stack.convs:
+        params += [c.weight, c.bias]
+    return params
+
+
+def _solver_backward_result(gz0, gws, gbs):
+    """What the backward of a solver Function(y0, t_host, method or cfg, stack, *_stack_params(stack)) returns."""
+    grads = []
+    for gw, gb in zip(gws, gbs):
+        grads += [gw, gb]
+    return (gz0, None, None, None) + tuple(grads)
+
+
+def _accepted_steps(stats):
+    """The accepted-step log of a finished dopri5 forward, all of it or an error: the backward pass walks these steps."""
+    if stats["n_accept"] > len(stats["accepted"]):
+        raise RuntimeError(f"odeint(HIP, dopri5): {stats['n_accept']} accepted steps exceed the {hip_ops.LOG_CAP} "
+                           "the backward pass can re-integrate")
+    return stats["accepted"]
+
+
 class _FixedGridOdeint(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y0, t_host, method, stack, *params):
         ctx.mode = hip_ops.current_compute_dtype()
         out, ws = hip_ops.odeint_fixed(stack, method, y0.detach(), t_host, save=True)
         ctx.stack, ctx.method, ctx.t_host, ctx.batch, ctx.ws = stack, method, t_host, y0.shape[0], ws
-        ctx.versions = tuple(p._version for p in params)
-        ctx.params = params
+        hip_ops.record_versions(ctx, params)
         return out
 
     @staticmethod
     @_pinned
     def backward(ctx, grad_out):
-        if tuple(p._version for p in ctx.params) != ctx.versions:
-            raise RuntimeError("a parameter of the ODE dynamics was modified in place between forward and backward")
-        gz0, gws, gbs = hip_ops.odeint_fixed_backward(ctx.stack, ctx.method, ctx.t_host, ctx.batch, grad_out, ctx.ws)
+        hip_ops.check_versions(ctx, "a parameter of the ODE dynamics")
+        grads = hip_ops.odeint_fixed_backward(ctx.stack, ctx.method, ctx.t_host, ctx.batch, grad_out, ctx.ws)
         ctx.ws = None
-        grads = []
-        for gw, gb in zip(gws, gbs):
-            grads += [gw, gb]
-        return (gz0, None, None, None) + tuple(grads)
+        return _solver_backward_result(*grads)
 
 
 class _Dopri5Odeint(torch.autograd.Function):
@@ -47,48 +66,30 @@ class _Dopri5Odeint(torch.autograd.Function):
         y0d = y0.detach()
         # the forward keeps the activations of the accepted steps when it can (64-channel fp32 stacks on the adaptive walk): the
         # backward is then the reverse sweep alone; otherwise ctx.saved is None and the backward re-integrates the logged steps
-        out, stats, ctx.saved = hip_ops.odeint_dopri5_saving(stack, y0d, t_host, cfg["rtol"], cfg["atol"], first_step=cfg["first_step"],
-                                                             max_steps=cfg["max_num_steps"])
-        from .odeint import last_stats
+        from .odeint import run_dopri5
+        out, ctx.pending, stats, ctx.saved = run_dopri5(stack, y0d, t_host, cfg, save=True)
         ctx.stack, ctx.t_host = stack, t_host
-        ctx.versions = tuple(p._version for p in params)
-        ctx.params = params
-        if isinstance(stats, hip_ops.PendingDopri5):   # asynchronous solve: nothing is known yet -- the backward pass collects it
-            last_stats._bind(stats)
-            ctx.pending, ctx.accepted = stats, None
-        else:
-            ctx.pending = None
-            last_stats.clear()
-            last_stats.update(stats)
-            if stats["n_accept"] > len(stats["accepted"]):
-                raise RuntimeError(f"odeint(HIP, dopri5): {stats['n_accept']} accepted steps exceed the {hip_ops.LOG_CAP} "
-                                   "the backward pass can re-integrate")
-            ctx.accepted = stats["accepted"]
+        hip_ops.record_versions(ctx, params)
+        # asynchronous solve (ctx.pending): nothing is known yet -- the backward pass collects it
+        ctx.accepted = _accepted_steps(stats) if ctx.pending is None else None
         ctx.save_for_backward(y0d)
         return out
 
     @staticmethod
     @_pinned
     def backward(ctx, grad_out):
-        if tuple(p._version for p in ctx.params) != ctx.versions:
-            raise RuntimeError("a parameter of the ODE dynamics was modified in place between forward and backward")
+        hip_ops.check_versions(ctx, "a parameter of the ODE dynamics")
         (y0,) = ctx.saved_tensors
         if ctx.pending is not None:
             stats, ctx.saved = ctx.pending.collect()
             ctx.pending = None
-            if stats["n_accept"] > len(stats["accepted"]):
-                raise RuntimeError(f"odeint(HIP, dopri5): {stats['n_accept']} accepted steps exceed the {hip_ops.LOG_CAP} "
-                                   "the backward pass can re-integrate")
-            ctx.accepted = stats["accepted"]
+            ctx.accepted = _accepted_steps(stats)
         if ctx.saved is not None and len(ctx.accepted) >= 1:
-            gz0, gws, gbs = hip_ops.odeint_dopri5_backward_saved(ctx.stack, ctx.t_host, ctx.accepted, grad_out, ctx.saved)
+            grads = hip_ops.odeint_dopri5_backward_saved(ctx.stack, ctx.t_host, ctx.accepted, grad_out, ctx.saved)
             ctx.saved = None
         else:
-            gz0, gws, gbs = hip_ops.odeint_dopri5_backward(ctx.stack, ctx.t_host, ctx.accepted, y0, grad_out)
-        grads = []
-        for gw, gb in zip(gws, gbs):
-            grads += [gw, gb]
-        return (gz0, None, None, None) + tuple(grads)
+            grads = hip_ops.odeint_dopri5_backward(ctx.stack, ctx.t_host, ctx.accepted, y0, grad_out)
+        return _solver_backward_result(*grads)
 
 
 class _CellFn(torch.autograd.Function):
@@ -99,16 +100,14 @@ class _CellFn(torch.autograd.Function):
         ctx.mode = hip_ops.current_compute_dtype()
         out = hip_ops.convgru_cell_forward(packed, x.detach(), h.detach())
         ctx.packed = packed
-        ctx.versions = tuple(p._version for p in params)
-        ctx.params = params
+        hip_ops.record_versions(ctx, params)
         ctx.save_for_backward(x.detach(), h.detach())
         return out
 
     @staticmethod
     @_pinned
     def backward(ctx, grad_out):
-        if tuple(p._version for p in ctx.params) != ctx.versions:
-            raise RuntimeError("a ConvGRUCell parameter was modified in place between forward and backward")
+        hip_ops.check_versions(ctx, "a ConvGRUCell parameter")
         x, h = ctx.saved_tensors
         gx, gh, grads = hip_ops.convgru_cell_backward(ctx.packed, x, h, grad_out)
         return (gx, gh, None) + tuple(grads)
@@ -128,16 +127,14 @@ class _SequenceFn(torch.autograd.Function):
         h_seq, ctx.saved = hip_ops.convgru_sequence(packed, x_seq, h0, n_steps, save=True)
         ctx.packed = packed
         ctx.n_in = None if x_seq is None else x_seq.shape[0]
-        ctx.versions = tuple(p._version for p in params)
-        ctx.params = params
+        hip_ops.record_versions(ctx, params)
         return h_seq
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     @_pinned
     def backward(ctx, grad_h_seq):
-        if tuple(p._version for p in ctx.params) != ctx.versions:
-            raise RuntimeError("a ConvGRUCell parameter was modified in place between forward and backward")
+        hip_ops.check_versions(ctx, "a ConvGRUCell parameter")
         if ctx.saved is None:
             raise RuntimeError("the sequence's saved activations were already consumed (backward called twice)")
         gx, gh0, grads = hip_ops.convgru_sequence_backward(ctx.packed, ctx.saved, grad_h_seq)
@@ -160,15 +157,13 @@ class _EncodeFn(torch.autograd.Function):
         ctx.mode = hip_ops.current_compute_dtype()
         mean, std, latent, saved = hip_ops.odeconvgru_encode_train(enc, inputs.detach(), timesteps, want_latent, run_backwards)
         ctx.enc, ctx.saved, ctx.want_latent = enc, saved, want_latent
-        ctx.versions = tuple(p._version for p in params)
-        ctx.params = params
+        hip_ops.record_versions(ctx, params)
         return (mean, std, latent) if want_latent else (mean, std)
 
     @staticmethod
     @_pinned
     def backward(ctx, grad_mean, grad_std, grad_latent=None):
-        if tuple(p._version for p in ctx.params) != ctx.versions:
-            raise RuntimeError("an encoder parameter was modified in place between forward and backward")
+        hip_ops.check_versions(ctx, "an encoder parameter")
         if ctx.saved is None:
             raise RuntimeError("the encoder's saved activations were already consumed (backward called twice)")
         gin, grads = hip_ops.odeconvgru_encode_backward(ctx.enc, ctx.saved, grad_mean, grad_std, grad_latent if ctx.want_latent else None)
@@ -266,22 +261,16 @@ class _AdjointOdeint(torch.autograd.Function):
         ctx.mode = hip_ops.current_compute_dtype()
         out = hip_ops.odeint_fixed(stack, method, y0.detach(), t_host)
         ctx.stack, ctx.method, ctx.t_host = stack, method, t_host
-        ctx.versions = tuple(p._version for p in params)
-        ctx.params = params
+        hip_ops.record_versions(ctx, params)
         ctx.save_for_backward(out)
         return out
 
     @staticmethod
     @_pinned
     def backward(ctx, grad_out):
-        if tuple(p._version for p in ctx.params) != ctx.versions:
-            raise RuntimeError("a parameter of the ODE dynamics was modified in place between forward and backward")
+        hip_ops.check_versions(ctx, "a parameter of the ODE dynamics")
         (y_traj,) = ctx.saved_tensors
-        gz0, gws, gbs = hip_ops.odeint_adjoint_backward(ctx.stack, ctx.method, ctx.t_host, y_traj, grad_out)
-        grads = []
-        for gw, gb in zip(gws, gbs):
-            grads += [gw, gb]
-        return (gz0, None, None, None) + tuple(grads)
+        return _solver_backward_result(*hip_ops.odeint_adjoint_backward(ctx.stack, ctx.method, ctx.t_host, y_traj, grad_out))
 
 
 class _AdjointDopri5(torch.autograd.Function):
@@ -291,44 +280,28 @@ class _AdjointDopri5(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y0, t_host, cfg, stack, *params):
         ctx.mode = hip_ops.current_compute_dtype()
-        from .odeint import last_stats
-        if hip_ops._async_dopri5:
-            out, pending = hip_ops.odeint_dopri5_start(stack, y0.detach(), t_host, cfg["rtol"], cfg["atol"], first_step=cfg["first_step"],
-                                                       max_steps=cfg["max_num_steps"])
-            last_stats._bind(pending)
-            ctx.pending = pending
-        else:
-            out, stats = hip_ops.odeint_dopri5(stack, y0.detach(), t_host, cfg["rtol"], cfg["atol"],
-                                               first_step=cfg["first_step"], max_steps=cfg["max_num_steps"])
-            last_stats.clear()
-            last_stats.update(stats)
-            ctx.pending = None
+        from .odeint import run_dopri5
+        out, ctx.pending, _, _ = run_dopri5(stack, y0.detach(), t_host, cfg)
         ctx.stack, ctx.t_host, ctx.cfg = stack, t_host, cfg
-        ctx.versions = tuple(p._version for p in params)
-        ctx.params = params
+        hip_ops.record_versions(ctx, params)
         ctx.save_for_backward(out)
         return out
 
     @staticmethod
     @_pinned
     def backward(ctx, grad_out):
-        if tuple(p._version for p in ctx.params) != ctx.versions:
-            raise RuntimeError("a parameter of the ODE dynamics was modified in place between forward and backward")
+        hip_ops.check_versions(ctx, "a parameter of the ODE dynamics")
         (y_traj,) = ctx.saved_tensors
         if ctx.pending is not None:   # the forward solve's outcome: an error (or a sealed, unfinished solve) must stop the adjoint here
             ctx.pending.collect()
             ctx.pending = None
         cfg = ctx.cfg
         stats = {}
-        gz0, gws, gbs = hip_ops.odeint_adjoint_dopri5_backward(ctx.stack, ctx.t_host, y_traj, grad_out, cfg["adjoint_rtol"],
-                                                               cfg["adjoint_atol"], max_accept=cfg["max_accept"], stats=stats,
-                                                               mixed_norm=cfg["mixed_norm"])
+        grads = hip_ops.odeint_adjoint_dopri5_backward(ctx.stack, ctx.t_host, y_traj, grad_out, cfg["adjoint_rtol"], cfg["adjoint_atol"],
+                                                       max_accept=cfg["max_accept"], stats=stats, mixed_norm=cfg["mixed_norm"])
         last_adjoint_stats.clear()
         last_adjoint_stats.update(stats)
-        grads = []
-        for gw, gb in zip(gws, gbs):
-            grads += [gw, gb]
-        return (gz0, None, None, None) + tuple(grads)
+        return _solver_backward_result(*grads)
 
 
 last_adjoint_stats = {}
@@ -342,7 +315,7 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
     torchdiffeq's default mixed norm (every parameter tensor's error ratio steers the steps too) or, with
     `adjoint_options={"norm": "seminorm"}`, with the cheaper seminorm; `max_accept` in adjoint_options bounds the accepted
     backward steps whose activations are kept."""
-    from .odeint import FIXED_GRID, _check_monotone, _host_times, check_options, conv_stack_of, odeint
+    from .odeint import FIXED_GRID, _check_monotone, _host_times, check_options, conv_stack_of, dopri5_cfg, odeint
     if method is None:
         method = "dopri5"
     if method not in FIXED_GRID and method != "dopri5":
@@ -363,9 +336,7 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
     if len(th) > 1 and bool(th[0] > th[1]):
         raise NotImplementedError("odeint_adjoint(HIP): decreasing time grids are not supported")
     stack = conv_stack_of(func)
-    params = []
-    for c in stack.convs:
-        params += [c.weight, c.bias]
+    params = _stack_params(stack)
     if method in FIXED_GRID:
         return _AdjointOdeint.apply(y0, th, method, stack, *params)
     adjoint_options = dict(adjoint_options or {})
@@ -375,29 +346,22 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
     unknown = set(adjoint_options) - {"norm", "max_accept"}
     if unknown:
         raise ValueError(f"odeint_adjoint(HIP): unsupported adjoint_options {sorted(unknown)}")
-    options = options or {}
-    cfg = dict(rtol=float(rtol), atol=float(atol), first_step=float(options.get("first_step") or 0.0),
-               max_num_steps=int(options.get("max_num_steps") or 0),
-               adjoint_rtol=float(rtol if adjoint_rtol is None else adjoint_rtol),
+    cfg = dopri5_cfg(rtol, atol, options)
+    cfg.update(adjoint_rtol=float(rtol if adjoint_rtol is None else adjoint_rtol),
                adjoint_atol=float(atol if adjoint_atol is None else adjoint_atol), max_accept=adjoint_options.get("max_accept"),
                mixed_norm=norm != "seminorm")
     return _AdjointDopri5.apply(y0, th, cfg, stack, *params)
 
 
 def odeint_with_grad(func, y0, t, rtol, atol, method, options=None):
-    from .odeint import FIXED_GRID, _check_monotone, _host_times, check_options, conv_stack_of
+    from .odeint import FIXED_GRID, _check_monotone, _host_times, check_options, conv_stack_of, dopri5_cfg
     check_options(method, options)
     th = _host_times(t)
     _check_monotone(th)
     if len(th) > 1 and bool(th[0] > th[1]):
         raise NotImplementedError("odeint(HIP): reversed-time integration is not implemented yet")
     stack = conv_stack_of(func)
-    params = []
-    for c in stack.convs:
-        params += [c.weight, c.bias]
+    params = _stack_params(stack)
     if method in FIXED_GRID:
         return _FixedGridOdeint.apply(y0, th, method, stack, *params)
-    options = options or {}
-    cfg = dict(rtol=float(rtol), atol=float(atol), first_step=float(options.get("first_step") or 0.0),
-               max_num_steps=int(options.get("max_num_steps") or 0))
-    return _Dopri5Odeint.apply(y0, th, cfg, stack, *params)
+    return _Dopri5Odeint.apply(y0, th, dopri5_cfg(rtol, atol, options), stack, *params)

@@ -6,6 +6,7 @@ current stream.  Tensors must be CUDA fp32; anything else raises (there is no CP
 import ctypes
 import os
 import threading
+import weakref
 
 import torch
 
@@ -55,7 +56,6 @@ _guarded = []           # weak references to (full buffer, payload bytes)
 
 def alloc_workspace(nbytes, device):
     """A fresh workspace of `nbytes` with a guard region behind it; returns the payload view (numel() == nbytes)."""
-    import weakref
     nbytes = max(int(nbytes), 1024)
     full = torch.empty(nbytes + _CANARY, dtype=torch.uint8, device=device)
     full[nbytes:].fill_(0xA5)
@@ -97,7 +97,6 @@ def host_times(t):
     """float64 host copy of a 1-D time tensor.  A device-resident `t` costs a device->host copy (a stream synchronisation);
     it is cached per (base tensor OBJECT, version, view geometry): the base is held by weak reference, so a new tensor that
     happens to reuse the address of a freed one can never hit the cache."""
-    import weakref
     if not isinstance(t, torch.Tensor):
         t = torch.as_tensor(t, dtype=torch.float64)
     if t.dim() != 1:
@@ -135,33 +134,33 @@ def q4_to_nchw(x):
     return out
 
 
-def pack_conv_weight(w, transpose_flip=False):
-    """(Cout,Cin,k,k) fp32 -> MFMA-ordered image.  With transpose_flip the result is the packed weight of
-    the input-gradient conv (Cin and Cout swap roles)."""
+def _pack_single(entry, w, transpose_flip, dtype, ks=None, per_pair=None, ks_error=None):
+    """One conv weight through one packing entry point.  ks: the kernel size the entry point is built for (None: any, and the entry
+    point is told the size); per_pair: values of the image per (cout, cin) pair (None: k * k); ks_error: the text raised for a
+    non-square kernel or one of another size than ks (None: not checked)."""
     require_device_tensor(w, "weight")
     w = w.detach().contiguous()
     co, ci, k, k2 = w.shape
-    if k != k2:
-        raise ValueError("square kernels only")
+    if ks_error is not None and (k != k2 or ks not in (None, k)):
+        raise ValueError(ks_error)
     if transpose_flip:
         co, ci = ci, co
-    out = torch.empty(co * ci * k * k, dtype=torch.float32, device=w.device)
-    _lib.check(_lib.load().odehip_pack_conv_weight(_ptr(w), _ptr(out), co, ci, k, int(bool(transpose_flip)), _stream()))
+    out = torch.empty(co * ci * (per_pair or k * k2), dtype=dtype, device=w.device)
+    size = () if ks else (k,)   # an entry point built for one kernel size takes no size argument
+    _lib.check(getattr(_lib.load(), entry)(_ptr(w), _ptr(out), co, ci, *size, int(bool(transpose_flip)), _stream()))
     return out
+
+
+def pack_conv_weight(w, transpose_flip=False):
+    """(Cout,Cin,k,k) fp32 -> MFMA-ordered image.  With transpose_flip the result is the packed weight of
+    the input-gradient conv (Cin and Cout swap roles)."""
+    return _pack_single("odehip_pack_conv_weight", w, transpose_flip, torch.float32, ks_error="square kernels only")
 
 
 def pack_conv_weight_winograd(w, transpose_flip=False):
     """(Cout,Cin,3,3) fp32 -> Winograd F(2x2,3x3) image U = G g G^T (16 values per channel pair)."""
-    require_device_tensor(w, "weight")
-    w = w.detach().contiguous()
-    co, ci, k, k2 = w.shape
-    if (k, k2) != (3, 3):
-        raise ValueError("Winograd form exists for 3x3 kernels only")
-    if transpose_flip:
-        co, ci = ci, co
-    out = torch.empty(co * ci * 16, dtype=torch.float32, device=w.device)
-    _lib.check(_lib.load().odehip_pack_conv_weight_winograd(_ptr(w), _ptr(out), co, ci, int(bool(transpose_flip)), _stream()))
-    return out
+    return _pack_single("odehip_pack_conv_weight_winograd", w, transpose_flip, torch.float32, ks=3, per_pair=16,
+                        ks_error="Winograd form exists for 3x3 kernels only")
 
 
 def pack_conv_weights_many(jobs):
@@ -173,8 +172,6 @@ def pack_conv_weights_many(jobs):
         kind = int(kind)
         require_device_tensor(w, "conv weight")
         w = w.detach().contiguous()
-        if w.dtype != torch.float32:
-            raise ValueError("conv weights must be float32")
         co, ci, k, _ = w.shape
         if tf:
             co, ci = ci, co
@@ -193,16 +190,8 @@ def pack_conv_weights_many(jobs):
 
 def pack_conv_weight_winograd5(w, transpose_flip=False):
     """(Cout,Cin,5,5) fp32 -> Winograd F(2x2,5x5) image U = G g G^T (36 values per channel pair; csrc/conv_wino5.hip)."""
-    require_device_tensor(w, "weight")
-    w = w.detach().contiguous()
-    co, ci, k, k2 = w.shape
-    if (k, k2) != (5, 5):
-        raise ValueError("this Winograd form is for 5x5 kernels")
-    if transpose_flip:
-        co, ci = ci, co
-    out = torch.empty(co * ci * 36, dtype=torch.float32, device=w.device)
-    _lib.check(_lib.load().odehip_pack_conv_weight_winograd5(_ptr(w), _ptr(out), co, ci, int(bool(transpose_flip)), _stream()))
-    return out
+    return _pack_single("odehip_pack_conv_weight_winograd5", w, transpose_flip, torch.float32, ks=5, per_pair=36,
+                        ks_error="this Winograd form is for 5x5 kernels")
 
 
 def winograd5_enabled():
@@ -255,28 +244,13 @@ class compute_mode:
 
 def pack_conv_weight_bf16(w, transpose_flip=False):
     """(Cout,Cin,3,3) fp32 -> bf16 A-operand image of the bf16 MFMA kernel (round to nearest even)."""
-    require_device_tensor(w, "weight")
-    w = w.detach().contiguous()
-    co, ci, k, k2 = w.shape
-    if (k, k2) != (3, 3):
-        raise ValueError("the bf16 kernel serves 3x3 layers only")
-    if transpose_flip:
-        co, ci = ci, co
-    out = torch.empty(co * ci * 9, dtype=torch.bfloat16, device=w.device)
-    _lib.check(_lib.load().odehip_pack_conv_weight_bf16(_ptr(w), _ptr(out), co, ci, int(bool(transpose_flip)), _stream()))
-    return out
+    return _pack_single("odehip_pack_conv_weight_bf16", w, transpose_flip, torch.bfloat16, ks=3, per_pair=9,
+                        ks_error="the bf16 kernel serves 3x3 layers only")
 
 
 def pack_conv_weight_bf16_ks(w, transpose_flip=False):
     """(Cout,Cin,5,5) fp32 -> block-major bf16 image of the 5x5 bf16 ring kernel."""
-    require_device_tensor(w, "weight")
-    w = w.detach().contiguous()
-    co, ci, k, k2 = w.shape
-    if transpose_flip:
-        co, ci = ci, co
-    out = torch.empty(co * ci * k * k2, dtype=torch.bfloat16, device=w.device)
-    _lib.check(_lib.load().odehip_pack_conv_weight_bf16_ks(_ptr(w), _ptr(out), co, ci, k, int(bool(transpose_flip)), _stream()))
-    return out
+    return _pack_single("odehip_pack_conv_weight_bf16_ks", w, transpose_flip, torch.bfloat16)
 
 
 def pack_fused_bf16(convs, reverse_transposed=False):
@@ -331,7 +305,7 @@ class PackedConvStack:
         self.convs = list(convs)
         self.final_tanh = bool(final_tanh)
         self.act = int(act)   # hidden activation (_lib.ACT_RELU / ACT_TANH)
-        self._cache = {}      # compute dtype -> dict(stamp, desc, keep, dgrad)
+        self._cache = {}      # compute dtype -> dict(stamp, desc, keep, bias, dgrad = (desc, keep) of the input-gradient convs)
         self._bias = None
         self.desc = None
 
@@ -365,15 +339,28 @@ class PackedConvStack:
                 raise ValueError("the HIP path supports stride-1 'same' square convs with bias only "
                                  f"(got {c}); downsize=True dynamics are not supported")
             require_device_tensor(c.weight, "conv weight")
+        bias = [c.bias.detach().contiguous() for c in convs]
+        d, keep = self._pack(mode, ks, bias, False)
+        self._cache[mode] = dict(stamp=stamp, desc=d, keep=keep, bias=bias, dgrad=None)
+        self.desc, self._bias = d, bias
+        return d
+
+    def _pack(self, mode, ks, bias, transpose_flip):
+        """(ConvStack, the images it points to) of the convs in one direction: as they are, or transposed + flipped (the
+        input-gradient convs: Cin and Cout swap roles, the fused image holds the layers in reverse order)."""
+        convs = self.convs
+        cin = [c.out_channels if transpose_flip else c.in_channels for c in convs]
+        cout = [c.in_channels if transpose_flip else c.out_channels for c in convs]
         # 3x3 layers with cin % 16 == 0 run the Winograd kernel (2.25x fewer MFMAs, still exact-fp32 arithmetic)
-        want_wino = [ks == 3 and c.in_channels % 16 == 0 for c in convs]
-        both = pack_conv_weights_many([(c.weight, False, False) for c in convs] + [(c.weight, True, False) for c, ww in zip(convs, want_wino) if ww])
+        want_wino = [ks == 3 and ci % 16 == 0 for ci in cin]
+        both = pack_conv_weights_many([(c.weight, False, transpose_flip) for c in convs] +
+                                      [(c.weight, True, transpose_flip) for c, ww in zip(convs, want_wino) if ww])
         packed, rest = both[:len(convs)], iter(both[len(convs):])
         wino = [next(rest) if ww else None for ww in want_wino]
-        bf16 = [pack_conv_weight_bf16(c.weight) if mode == "bf16" and _bf16_ok(c.in_channels, c.out_channels, ks) else None
-                for c in convs]
-        bias = [c.bias.detach().contiguous() for c in convs]
-        fused = pack_fused_bf16(convs) if mode == "bf16" and self.relu_only and _fusable(convs, ks) else None
+        bf16 = [pack_conv_weight_bf16(c.weight, transpose_flip) if mode == "bf16" and _bf16_ok(ci, co, ks) else None
+                for c, ci, co in zip(convs, cin, cout)]
+        fused = (pack_fused_bf16(convs, reverse_transposed=transpose_flip)
+                 if mode == "bf16" and self.relu_only and _fusable(convs, ks) else None)
         d = _lib.ConvStack()
         d.w_fused = fused.data_ptr() if fused is not None else None
         d.n_convs = len(convs)
@@ -387,9 +374,7 @@ class PackedConvStack:
             d.bias[i] = bias[i].data_ptr()
         d.final_tanh = int(self.final_tanh)
         d.act = self.act
-        self._cache[mode] = dict(stamp=stamp, desc=d, keep=(packed, wino, bf16, fused), bias=bias, dgrad=None)
-        self.desc, self._bias = d, bias
-        return d
+        return d, (packed, wino, bf16, fused)
 
     def dgrad_desc(self, mode=None):
         """Stack of the input-gradient convs (weights packed transposed + flipped), built on first use."""
@@ -397,27 +382,7 @@ class PackedConvStack:
         d0 = self.refresh(mode)
         ent = self._cache[mode]
         if ent["dgrad"] is None:
-            want_wino = [d0.ks == 3 and c.out_channels % 16 == 0 for c in self.convs]
-            both = pack_conv_weights_many([(c.weight, False, True) for c in self.convs] +
-                                          [(c.weight, True, True) for c, ww in zip(self.convs, want_wino) if ww])
-            packed, rest = both[:len(self.convs)], iter(both[len(self.convs):])
-            wino = [next(rest) if ww else None for ww in want_wino]
-            bf16 = [pack_conv_weight_bf16(c.weight, transpose_flip=True)
-                    if mode == "bf16" and _bf16_ok(c.out_channels, c.in_channels, d0.ks) else None for c in self.convs]
-            fused = (pack_fused_bf16(self.convs, reverse_transposed=True)
-                     if mode == "bf16" and self.relu_only and _fusable(self.convs, d0.ks) else None)
-            d = _lib.ConvStack()
-            d.w_fused = fused.data_ptr() if fused is not None else None
-            d.n_convs, d.ks = d0.n_convs, d0.ks
-            d.final_tanh, d.act = d0.final_tanh, d0.act
-            for i in range(len(self.convs) + 1):
-                d.channels[i] = d0.channels[i]
-            for i, p in enumerate(packed):
-                d.w_packed[i] = p.data_ptr()
-                d.w_wino[i] = wino[i].data_ptr() if wino[i] is not None else None
-                d.w_bf16[i] = bf16[i].data_ptr() if bf16[i] is not None else None
-                d.bias[i] = ent["bias"][i].data_ptr()
-            ent["dgrad"] = (d, packed, wino, bf16, fused)
+            ent["dgrad"] = self._pack(mode, d0.ks, ent["bias"], True)
         return ent["dgrad"][0]
 
 
@@ -437,17 +402,40 @@ def convstack_forward(stack, y, negate=False):
     return out
 
 
-def odeint_fixed(stack, method, z0, t, save=False, negate=False):
-    """Whole fixed-grid trajectory in one C-ABI call.  Returns (T,B,C,16,16); with save=True also the private
-    workspace holding every saved activation (input of odeint_fixed_backward)."""
+def _c_times(t):
+    """The time grid as the c_double array the C ABI takes (len() of it = the number of time points)."""
+    t64 = host_times(t).tolist()
+    return (ctypes.c_double * len(t64))(*t64)
+
+
+def _solver_inputs(stack, z0, t):
+    """What every solver forward starts from: (refreshed descriptor, contiguous y0, batch, channels, time points, c_double time array)."""
     require_device_tensor(z0, "y0")
     desc = stack.refresh()
     z0 = z0.contiguous()
     b, c = z0.shape[0], z0.shape[1]
     if z0.dim() != 4 or tuple(z0.shape[2:]) != (16, 16) or c != desc.channels[0]:
         raise ValueError(f"y0 must be (B,{desc.channels[0]},16,16) (got {tuple(z0.shape)})")
-    t64 = [float(v) for v in t.detach().to("cpu", torch.float64).tolist()]
-    n = len(t64)
+    tarr = _c_times(t)
+    return desc, z0, b, c, len(tarr), tarr
+
+
+def _stack_grads(stack, batch, device):
+    """Outputs of a solver backward: ((grad_z0, [grad_w...], [grad_b...]) -- what the wrappers return --, and the arrays of the weight
+    and bias gradient pointers the C ABI takes)."""
+    gz0 = torch.empty((batch, stack.desc.channels[0], 16, 16), dtype=torch.float32, device=device)
+    gws = [torch.empty_like(cv.weight) for cv in stack.convs]
+    gbs = [torch.empty_like(cv.bias) for cv in stack.convs]
+    nl = len(gws)
+    gw_arr = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gws])
+    gb_arr = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gbs])
+    return (gz0, gws, gbs), gw_arr, gb_arr
+
+
+def odeint_fixed(stack, method, z0, t, save=False, negate=False):
+    """Whole fixed-grid trajectory in one C-ABI call.  Returns (T,B,C,16,16); with save=True also the private
+    workspace holding every saved activation (input of odeint_fixed_backward)."""
+    desc, z0, b, c, n, tarr = _solver_inputs(stack, z0, t)
     lib = _lib.load()
     m = _lib.METHODS[method]
     nbytes = lib.odehip_odeint_workspace_bytes(ctypes.byref(desc), b, n, m, int(save))
@@ -456,7 +444,6 @@ def odeint_fixed(stack, method, z0, t, save=False, negate=False):
     else:
         ws = workspace(("odeint", b, n, m, tuple(desc.channels)), nbytes, z0.device)
     out = torch.empty((n, b, c, 16, 16), dtype=torch.float32, device=z0.device)
-    tarr = (ctypes.c_double * n)(*t64)
     fmt = ctypes.c_int(0)
     _lib.check(lib.odehip_odeint_fixed(ctypes.byref(desc), m, _ptr(z0), tarr, n, b, _ptr(out), int(save), int(bool(negate)), _ptr(ws),
                                        ws.numel(), ctypes.byref(fmt), _stream()))
@@ -471,51 +458,66 @@ def odeint_fixed_backward(stack, method, t, batch, grad_out, ws):
     desc = stack.refresh()
     dg = stack.dgrad_desc()
     grad_out = grad_out.contiguous()
-    t64 = [float(v) for v in t.detach().to("cpu", torch.float64).tolist()]
-    n = len(t64)
-    c = desc.channels[0]
-    gz0 = torch.empty((batch, c, 16, 16), dtype=torch.float32, device=grad_out.device)
-    gws = [torch.empty_like(cv.weight) for cv in stack.convs]
-    gbs = [torch.empty_like(cv.bias) for cv in stack.convs]
-    nl = len(gws)
-    gw_arr = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gws])
-    gb_arr = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gbs])
-    tarr = (ctypes.c_double * n)(*t64)
-    _lib.check(_lib.load().odehip_odeint_fixed_backward(ctypes.byref(desc), ctypes.byref(dg), _lib.METHODS[method], tarr, n,
-                                                        batch, _ptr(grad_out), _ptr(gz0), gw_arr, gb_arr,
+    tarr = _c_times(t)
+    grads, gw_arr, gb_arr = _stack_grads(stack, batch, grad_out.device)
+    _lib.check(_lib.load().odehip_odeint_fixed_backward(ctypes.byref(desc), ctypes.byref(dg), _lib.METHODS[method], tarr, len(tarr),
+                                                        batch, _ptr(grad_out), _ptr(grads[0]), gw_arr, gb_arr,
                                                         int(getattr(ws, "_odehip_saved_format", 0)), _ptr(ws), ws.numel(), _stream()))
-    return gz0, gws, gbs
+    return grads
 
 
 LOG_CAP = 2048   # accepted steps the forward reports back (the backward pass re-integrates them)
 
 
+def _dopri5_buffers(desc, z0, b, c, n, slots):
+    """(workspace, output) of a dopri5 forward.  With `slots` the workspace also keeps the activations of that many accepted steps and
+    is private (it must survive untouched until backward); without, it is the shared ("dopri5", ...) one."""
+    lib = _lib.load()
+    if slots:
+        ws = alloc_workspace(lib.odehip_dopri5_saving_workspace_bytes(ctypes.byref(desc), b, n, slots), z0.device)
+    else:
+        ws = workspace(("dopri5", b, n, tuple(desc.channels)), lib.odehip_dopri5_workspace_bytes(ctypes.byref(desc), b, n), z0.device)
+    return ws, torch.empty((n, b, c, 16, 16), dtype=torch.float32, device=z0.device)
+
+
+def _dopri5_stats(stats, log, saved=None):
+    """The stats dict of a dopri5 forward from what the library reported; `saved` (a c_int) adds whether activations were kept."""
+    k = min(int(stats[1]), LOG_CAP)
+    st = {"nfe": stats[0], "n_accept": stats[1], "n_reject": stats[2], "attempts_enqueued": stats[3],
+          "accepted": [(log[2 * i], log[2 * i + 1]) for i in range(k)]}
+    if saved is not None:
+        st["saved"] = bool(saved.value)
+    return st
+
+
+def _c_step_log(accepted):
+    """The accepted steps [(t0, dt), ...] as the flat c_double array the backward entry points take."""
+    flat = [v for pair in accepted for v in pair]
+    return (ctypes.c_double * max(len(flat), 1))(*flat)
+
+
 def odeint_dopri5(stack, z0, t, rtol, atol, first_step=0.0, max_steps=0, negate=False):
     """Adaptive dopri5 trajectory; returns ((T,B,C,16,16), stats dict).  stats["accepted"] = [(t0, dt), ...]."""
     collect_pending_solves()   # an asynchronous solve still in flight owns the shared ("dopri5", ...) workspace
-    require_device_tensor(z0, "y0")
-    desc = stack.refresh()
-    z0 = z0.contiguous()
-    b, c = z0.shape[0], z0.shape[1]
-    if z0.dim() != 4 or tuple(z0.shape[2:]) != (16, 16) or c != desc.channels[0]:
-        raise ValueError(f"y0 must be (B,{desc.channels[0]},16,16) (got {tuple(z0.shape)})")
-    t64 = [float(v) for v in t.detach().to("cpu", torch.float64).tolist()]
-    n = len(t64)
-    lib = _lib.load()
-    nbytes = lib.odehip_dopri5_workspace_bytes(ctypes.byref(desc), b, n)
-    ws = workspace(("dopri5", b, n, tuple(desc.channels)), nbytes, z0.device)
-    out = torch.empty((n, b, c, 16, 16), dtype=torch.float32, device=z0.device)
-    tarr = (ctypes.c_double * n)(*t64)
+    desc, z0, b, c, n, tarr = _solver_inputs(stack, z0, t)
+    ws, out = _dopri5_buffers(desc, z0, b, c, n, 0)
     stats = (ctypes.c_int * 4)()
     log = (ctypes.c_double * (2 * LOG_CAP))()
-    _lib.check(lib.odehip_odeint_dopri5(ctypes.byref(desc), _ptr(z0), tarr, n, b, float(rtol), float(atol), float(first_step or 0.0), int(max_steps),
-                                        int(bool(negate)), _ptr(out), stats, log, LOG_CAP, _ptr(ws), ws.numel(), _stream()))
-    k = min(int(stats[1]), LOG_CAP)
-    return out, {"nfe": stats[0], "n_accept": stats[1], "n_reject": stats[2], "attempts_enqueued": stats[3],
-                 "accepted": [(log[2 * i], log[2 * i + 1]) for i in range(k)]}
+    _lib.check(_lib.load().odehip_odeint_dopri5(ctypes.byref(desc), _ptr(z0), tarr, n, b, float(rtol), float(atol), float(first_step or 0.0),
+                                                int(max_steps), int(bool(negate)), _ptr(out), stats, log, LOG_CAP, _ptr(ws), ws.numel(),
+                                                _stream()))
+    return out, _dopri5_stats(stats, log)
 
 
 _dopri5_save_slots = 8   # slots of a saving forward's workspace; doubled (up to 64) after a forward that accepted more steps
+
+
+def _grow_save_slots(slots, n_accept):
+    """After a saving forward with `slots` slots that accepted n_accept steps: the next one gets room for them."""
+    global _dopri5_save_slots
+    if n_accept > slots:
+        _dopri5_save_slots = min(64, max(2 * slots, n_accept + 2))
+
 
 # ---- asynchronous dopri5 (include/odecgru_hip.h: odehip_odeint_dopri5_start / _collect) ------------------------------------------
 # The synchronous entry points return when the device-side controller has reported completion, so the host cannot enqueue what comes
@@ -557,7 +559,7 @@ class PendingDopri5:
 
     def collect(self):
         """(stats dict, saved) -- saved = (workspace, slots) if the activations of the accepted steps were kept, else None."""
-        global _dopri5_save_slots, _async_attempts
+        global _async_attempts
         if isinstance(self._result, BaseException):   # the solve failed: every later look at it raises the same error
             raise self._result
         if self._result is None:
@@ -580,18 +582,15 @@ class PendingDopri5:
                 raise
             finally:
                 self._keep = None
-            k = min(int(stats[1]), LOG_CAP)
-            if self.slots and int(stats[1]) > self.slots:
-                _dopri5_save_slots = min(64, max(2 * self.slots, int(stats[1]) + 2))
+            if self.slots:
+                _grow_save_slots(self.slots, int(stats[1]))
             # what this solve needed plus a margin of a quarter (at least 2): an attempt queued behind `done` costs three empty
             # launches, an attempt too few costs the step (AsyncSolveTruncated).  Never below what the last solve was given unless
             # it used less than half of it -- the count drifts slowly as the dynamics train
             used = int(stats[1]) + int(stats[2])
             want = used + max(2, used // 4)
             _async_attempts = max(4, min(ASYNC_ATTEMPTS_MAX, want if want > _async_attempts or 2 * want < _async_attempts else _async_attempts))
-            st = {"nfe": stats[0], "n_accept": stats[1], "n_reject": stats[2], "attempts_enqueued": stats[3],
-                  "accepted": [(log[2 * i], log[2 * i + 1]) for i in range(k)], "saved": bool(saved.value)}
-            self._result = (st, (self.ws, self.slots) if saved.value else None)
+            self._result = (_dopri5_stats(stats, log, saved), (self.ws, self.slots) if saved.value else None)
             self.ws = None
         return self._result
 
@@ -662,26 +661,13 @@ def odeint_dopri5_start(stack, z0, t, rtol, atol, first_step=0.0, max_steps=0, s
     """Asynchronous dopri5 forward: returns (out, PendingDopri5) at once.  save=True keeps the activations of the accepted steps
     (as odeint_dopri5_saving does) in a private workspace held by the pending object."""
     collect_pending_solves()      # one solve in flight per process: the shared workspaces and the library's slots are free again
-    require_device_tensor(z0, "y0")
-    desc = stack.refresh()
-    z0 = z0.contiguous()
-    b, c = z0.shape[0], z0.shape[1]
-    if z0.dim() != 4 or tuple(z0.shape[2:]) != (16, 16) or c != desc.channels[0]:
-        raise ValueError(f"y0 must be (B,{desc.channels[0]},16,16) (got {tuple(z0.shape)})")
-    t64 = [float(v) for v in t.detach().to("cpu", torch.float64).tolist()]
-    n = len(t64)
-    lib = _lib.load()
+    desc, z0, b, c, n, tarr = _solver_inputs(stack, z0, t)
     slots = _dopri5_save_slots if save and os.environ.get("ODEHIP_DOPRI5_SAVE") != "0" else 0
-    if slots:
-        ws = alloc_workspace(lib.odehip_dopri5_saving_workspace_bytes(ctypes.byref(desc), b, n, slots), z0.device)
-    else:
-        ws = workspace(("dopri5", b, n, tuple(desc.channels)), lib.odehip_dopri5_workspace_bytes(ctypes.byref(desc), b, n), z0.device)
-    out = torch.empty((n, b, c, 16, 16), dtype=torch.float32, device=z0.device)
-    tarr = (ctypes.c_double * n)(*t64)
+    ws, out = _dopri5_buffers(desc, z0, b, c, n, slots)
     token = ctypes.c_int(-1)
-    _lib.check(lib.odehip_odeint_dopri5_start(ctypes.byref(desc), _ptr(z0), tarr, n, b, float(rtol), float(atol), float(first_step or 0.0),
-                                              int(max_steps), _ptr(out), int(slots), int(_async_attempts), ctypes.byref(token), _ptr(ws),
-                                              ws.numel(), _stream()))
+    _lib.check(_lib.load().odehip_odeint_dopri5_start(ctypes.byref(desc), _ptr(z0), tarr, n, b, float(rtol), float(atol),
+                                                      float(first_step or 0.0), int(max_steps), _ptr(out), int(slots), int(_async_attempts),
+                                                      ctypes.byref(token), _ptr(ws), ws.numel(), _stream()))
     return out, PendingDopri5(token.value, (z0, out, ws), slots, ws if slots else None)
 
 
@@ -690,7 +676,6 @@ def odeint_dopri5_saving(stack, z0, t, rtol, atol, first_step=0.0, max_steps=0):
     step in a private workspace, so that the backward pass needs no re-integration.  Returns (out, stats, saved) with saved =
     (workspace, max_accept), or None when nothing was kept (other stacks than 64-channel fp32, persistent walk off, more accepted
     steps than slots): the caller then takes odeint_dopri5_backward."""
-    global _dopri5_save_slots
     if _async_dopri5:   # enqueue only: stats and `saved` are read later (LazyStats / PendingDopri5.collect())
         out, pending = odeint_dopri5_start(stack, z0, t, rtol, atol, first_step=first_step, max_steps=max_steps, save=True)
         return out, pending, pending
@@ -699,32 +684,17 @@ def odeint_dopri5_saving(stack, z0, t, rtol, atol, first_step=0.0, max_steps=0):
         st["saved"] = False
         return out, st, None
     collect_pending_solves()
-    require_device_tensor(z0, "y0")
-    desc = stack.refresh()
-    z0 = z0.contiguous()
-    b, c = z0.shape[0], z0.shape[1]
-    if z0.dim() != 4 or tuple(z0.shape[2:]) != (16, 16) or c != desc.channels[0]:
-        raise ValueError(f"y0 must be (B,{desc.channels[0]},16,16) (got {tuple(z0.shape)})")
-    t64 = [float(v) for v in t.detach().to("cpu", torch.float64).tolist()]
-    n = len(t64)
-    lib = _lib.load()
+    desc, z0, b, c, n, tarr = _solver_inputs(stack, z0, t)
     slots = _dopri5_save_slots
-    nbytes = lib.odehip_dopri5_saving_workspace_bytes(ctypes.byref(desc), b, n, slots)
-    ws = alloc_workspace(nbytes, z0.device)   # private: it must survive untouched until backward
-    out = torch.empty((n, b, c, 16, 16), dtype=torch.float32, device=z0.device)
-    tarr = (ctypes.c_double * n)(*t64)
+    ws, out = _dopri5_buffers(desc, z0, b, c, n, slots)
     stats = (ctypes.c_int * 4)()
     log = (ctypes.c_double * (2 * LOG_CAP))()
     saved = ctypes.c_int(0)
-    _lib.check(lib.odehip_odeint_dopri5_saving(ctypes.byref(desc), _ptr(z0), tarr, n, b, float(rtol), float(atol), float(first_step or 0.0),
-                                               int(max_steps), _ptr(out), stats, log, LOG_CAP, slots, ctypes.byref(saved), _ptr(ws), ws.numel(),
-                                               _stream()))
-    k = min(int(stats[1]), LOG_CAP)
-    if int(stats[1]) > slots:
-        _dopri5_save_slots = min(64, max(2 * slots, int(stats[1]) + 2))
-    st = {"nfe": stats[0], "n_accept": stats[1], "n_reject": stats[2], "attempts_enqueued": stats[3],
-          "accepted": [(log[2 * i], log[2 * i + 1]) for i in range(k)], "saved": bool(saved.value)}
-    return out, st, ((ws, slots) if saved.value else None)
+    _lib.check(_lib.load().odehip_odeint_dopri5_saving(ctypes.byref(desc), _ptr(z0), tarr, n, b, float(rtol), float(atol),
+                                                       float(first_step or 0.0), int(max_steps), _ptr(out), stats, log, LOG_CAP, slots,
+                                                       ctypes.byref(saved), _ptr(ws), ws.numel(), _stream()))
+    _grow_save_slots(slots, int(stats[1]))
+    return out, _dopri5_stats(stats, log, saved), ((ws, slots) if saved.value else None)
 
 
 def odeint_dopri5_backward_saved(stack, t, accepted, grad_out, saved):
@@ -734,21 +704,13 @@ def odeint_dopri5_backward_saved(stack, t, accepted, grad_out, saved):
     desc = stack.refresh()
     dg = stack.dgrad_desc()
     grad_out = grad_out.contiguous()
-    t64 = [float(v) for v in t.detach().to("cpu", torch.float64).tolist()]
-    n, b, c = len(t64), grad_out.shape[1], desc.channels[0]
-    lib = _lib.load()
-    gz0 = torch.empty((b, c, 16, 16), dtype=torch.float32, device=grad_out.device)
-    gws = [torch.empty_like(cv.weight) for cv in stack.convs]
-    gbs = [torch.empty_like(cv.bias) for cv in stack.convs]
-    nl = len(gws)
-    gw_arr = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gws])
-    gb_arr = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gbs])
-    tarr = (ctypes.c_double * n)(*t64)
-    flat = [v for pair in accepted for v in pair]
-    larr = (ctypes.c_double * max(len(flat), 1))(*flat)
-    _lib.check(lib.odehip_odeint_dopri5_backward_saved(ctypes.byref(desc), ctypes.byref(dg), tarr, n, b, larr, len(accepted), _ptr(grad_out),
-                                                       _ptr(gz0), gw_arr, gb_arr, int(slots), _ptr(ws), ws.numel(), _stream()))
-    return gz0, gws, gbs
+    tarr = _c_times(t)
+    b = grad_out.shape[1]
+    grads, gw_arr, gb_arr = _stack_grads(stack, b, grad_out.device)
+    _lib.check(_lib.load().odehip_odeint_dopri5_backward_saved(ctypes.byref(desc), ctypes.byref(dg), tarr, len(tarr), b,
+                                                               _c_step_log(accepted), len(accepted), _ptr(grad_out), _ptr(grads[0]), gw_arr,
+                                                               gb_arr, int(slots), _ptr(ws), ws.numel(), _stream()))
+    return grads
 
 
 def odeint_dopri5_backward(stack, t, accepted, z0, grad_out):
@@ -758,26 +720,17 @@ def odeint_dopri5_backward(stack, t, accepted, z0, grad_out):
     desc = stack.refresh()
     dg = stack.dgrad_desc()
     grad_out, z0 = grad_out.contiguous(), z0.contiguous()
-    t64 = [float(v) for v in t.detach().to("cpu", torch.float64).tolist()]
-    n, b, c = len(t64), z0.shape[0], desc.channels[0]
-    ns = len(accepted)
+    tarr = _c_times(t)
+    n, b, ns = len(tarr), z0.shape[0], len(accepted)
     lib = _lib.load()
     nbytes = lib.odehip_dopri5_backward_workspace_bytes(ctypes.byref(desc), b, n, ns)
     # keyed WITHOUT the accepted-step count: that count drifts as the weights train, and a key per count would leave one
     # multi-GB buffer behind for every count ever seen; workspace() replaces a buffer that has become too small
     ws = workspace(("dopri5_bwd", b, n, tuple(desc.channels)), nbytes, grad_out.device)
-    gz0 = torch.empty((b, c, 16, 16), dtype=torch.float32, device=grad_out.device)
-    gws = [torch.empty_like(cv.weight) for cv in stack.convs]
-    gbs = [torch.empty_like(cv.bias) for cv in stack.convs]
-    nl = len(gws)
-    gw_arr = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gws])
-    gb_arr = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gbs])
-    tarr = (ctypes.c_double * n)(*t64)
-    flat = [v for pair in accepted for v in pair]
-    larr = (ctypes.c_double * max(len(flat), 1))(*flat)
-    _lib.check(lib.odehip_odeint_dopri5_backward(ctypes.byref(desc), ctypes.byref(dg), tarr, n, b, larr, ns, _ptr(z0),
-                                                 _ptr(grad_out), _ptr(gz0), gw_arr, gb_arr, _ptr(ws), ws.numel(), _stream()))
-    return gz0, gws, gbs
+    grads, gw_arr, gb_arr = _stack_grads(stack, b, grad_out.device)
+    _lib.check(lib.odehip_odeint_dopri5_backward(ctypes.byref(desc), ctypes.byref(dg), tarr, n, b, _c_step_log(accepted), ns, _ptr(z0),
+                                                 _ptr(grad_out), _ptr(grads[0]), gw_arr, gb_arr, _ptr(ws), ws.numel(), _stream()))
+    return grads
 
 
 def odeint_adjoint_backward(stack, method, t, y_traj, grad_out):
@@ -787,22 +740,16 @@ def odeint_adjoint_backward(stack, method, t, y_traj, grad_out):
     desc = stack.refresh()
     dg = stack.dgrad_desc()
     grad_out, y_traj = grad_out.contiguous(), y_traj.contiguous()
-    t64 = [float(v) for v in t.detach().to("cpu", torch.float64).tolist()]
-    n, b, c = len(t64), y_traj.shape[1], desc.channels[0]
+    tarr = _c_times(t)
+    n, b = len(tarr), y_traj.shape[1]
     lib = _lib.load()
     m = _lib.METHODS[method]
     nbytes = lib.odehip_odeint_workspace_bytes(ctypes.byref(desc), b, n, m, 1)
     ws = workspace(("adjoint", b, n, m, tuple(desc.channels)), nbytes, grad_out.device)
-    gz0 = torch.empty((b, c, 16, 16), dtype=torch.float32, device=grad_out.device)
-    gws = [torch.empty_like(cv.weight) for cv in stack.convs]
-    gbs = [torch.empty_like(cv.bias) for cv in stack.convs]
-    nl = len(gws)
-    gw_arr = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gws])
-    gb_arr = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gbs])
-    tarr = (ctypes.c_double * n)(*t64)
+    grads, gw_arr, gb_arr = _stack_grads(stack, b, grad_out.device)
     _lib.check(lib.odehip_odeint_adjoint_backward(ctypes.byref(desc), ctypes.byref(dg), m, tarr, n, b, _ptr(y_traj),
-                                                  _ptr(grad_out), _ptr(gz0), gw_arr, gb_arr, _ptr(ws), ws.numel(), _stream()))
-    return gz0, gws, gbs
+                                                  _ptr(grad_out), _ptr(grads[0]), gw_arr, gb_arr, _ptr(ws), ws.numel(), _stream()))
+    return grads
 
 
 def odeint_adjoint_dopri5_backward(stack, t, y_traj, grad_out, rtol, atol, max_accept=None, stats=None, mixed_norm=False):
@@ -814,8 +761,8 @@ def odeint_adjoint_dopri5_backward(stack, t, y_traj, grad_out, rtol, atol, max_a
     desc = stack.refresh()
     dg = stack.dgrad_desc()
     grad_out, y_traj = grad_out.contiguous(), y_traj.contiguous()
-    t64 = [float(v) for v in t.detach().to("cpu", torch.float64).tolist()]
-    n, b, c = len(t64), y_traj.shape[1], desc.channels[0]
+    tarr = _c_times(t)
+    n, b = len(tarr), y_traj.shape[1]
     lib = _lib.load()
     if max_accept is None:  # every accepted step keeps its activations: default to what fits in 32 GiB, at most 256 steps
         per_step = (lib.odehip_adjoint_dopri5_workspace_bytes(ctypes.byref(desc), b, n, 2)
@@ -823,20 +770,14 @@ def odeint_adjoint_dopri5_backward(stack, t, y_traj, grad_out, rtol, atol, max_a
         max_accept = int(max(4 * n, min(256, (32 << 30) // max(per_step, 1))))
     nbytes = lib.odehip_adjoint_dopri5_workspace_bytes(ctypes.byref(desc), b, n, int(max_accept))
     ws = workspace(("adjoint_dopri5", b, n, int(max_accept), tuple(desc.channels)), nbytes, grad_out.device)
-    gz0 = torch.empty((b, c, 16, 16), dtype=torch.float32, device=grad_out.device)
-    gws = [torch.empty_like(cv.weight) for cv in stack.convs]
-    gbs = [torch.empty_like(cv.bias) for cv in stack.convs]
-    nl = len(gws)
-    gw_arr = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gws])
-    gb_arr = (ctypes.c_void_p * nl)(*[g.data_ptr() for g in gbs])
-    tarr = (ctypes.c_double * n)(*t64)
+    grads, gw_arr, gb_arr = _stack_grads(stack, b, grad_out.device)
     st = (ctypes.c_int * 3)()
     _lib.check(lib.odehip_odeint_adjoint_dopri5_backward(ctypes.byref(desc), ctypes.byref(dg), tarr, n, b, float(rtol),
-                                                         float(atol), _ptr(y_traj), _ptr(grad_out), _ptr(gz0), gw_arr, gb_arr,
+                                                         float(atol), _ptr(y_traj), _ptr(grad_out), _ptr(grads[0]), gw_arr, gb_arr,
                                                          int(max_accept), int(bool(mixed_norm)), st, _ptr(ws), ws.numel(), _stream()))
     if stats is not None:
         stats.update(nfe=int(st[0]), n_accept=int(st[1]), n_reject=int(st[2]))
-    return gz0, gws, gbs
+    return grads
 
 
 class PackedCell:
@@ -891,14 +832,34 @@ class PackedCell:
         self._stamp, self.desc = stamp, d
         return d
 
+    def _half_slices(self):
+        """The two 5x5 weights cut into frame half and state half: gates-frame, gates-state, candidate-frame, candidate-state."""
+        i = self.cell.input_channels
+        wg, wc = self.cell.conv_gates[0].weight.detach(), self.cell.conv_can[0].weight.detach()
+        return [w.contiguous() for w in (wg[:, :i], wg[:, i:], wc[:, :i], wc[:, i:])]
 
-def _cell_bwd_packs(cell, d, mode, extra_jobs=()):
+    def bwd_desc(self):
+        """The ConvGRUCellBwd of the entry refresh() returned last, packed once per stamp."""
+        cached = getattr(self, "_bwd", None)
+        if cached is None or cached[0] != self._stamp:
+            keep, bf, wino = _cell_bwd_packs(self, self.desc, self._stamp[0])
+            bw = _lib.ConvGRUCellBwd(*[k.data_ptr() for k in keep])
+            _set_half_images(bw, bf, wino)
+            cached = self._bwd = (self._stamp, bw, keep, bf, wino)
+        return cached[1]
+
+
+def _set_half_images(bw, bf, wino):
+    """The optional bf16 / F(2x2,5x5) images of the four half slices into a backward descriptor (ConvGRUCellBwd, EncoderBwd)."""
+    for j in range(4):
+        bw.bf16[j] = bf[j].data_ptr() if bf[j] is not None else None
+        bw.wino[j] = wino[j].data_ptr() if wino[j] is not None else None
+
+
+def _cell_bwd_packs(packed_cell, d, mode, extra_jobs=()):
     """Transposed + flipped slices of the two 5x5 weights (frame half, state half), fp32 images and, in bf16 mode, bf16 ones; extra_jobs
     (pack_conv_weights_many tuples) ride in the same launch and their results follow the four slices in the first list."""
-    i = d.input
-    wg, wc = cell.conv_gates[0].weight.detach(), cell.conv_can[0].weight.detach()
-    slices = [wg[:, :i], wg[:, i:], wc[:, :i], wc[:, i:]]
-    slices = [w.contiguous() for w in slices]
+    slices = packed_cell._half_slices()
     want_wino = mode == "f32" and d.ks == 5 and winograd5_enabled() and all(w.shape[0] % 8 == 0 and w.shape[1] % 32 == 0 for w in slices)
     packs = pack_conv_weights_many([(w, 0, True) for w in slices] + list(extra_jobs) + ([(w, 2, True) for w in slices] if want_wino else []))
     keep, extra = packs[:4], packs[4:4 + len(extra_jobs)]
@@ -930,15 +891,7 @@ def convgru_cell_backward(packed_cell, x, h, grad_h_next):
     for t_, n_ in ((x, "input_tensor"), (h, "h_cur"), (grad_h_next, "grad_h_next")):
         require_device_tensor(t_, n_)
     d = packed_cell.refresh()
-    cached = getattr(packed_cell, "_bwd", None)
-    if cached is None or cached[0] != packed_cell._stamp:
-        keep, bf, wino = _cell_bwd_packs(packed_cell.cell, d, current_compute_dtype())
-        bw = _lib.ConvGRUCellBwd(*[k.data_ptr() for k in keep])
-        for j in range(4):
-            bw.bf16[j] = bf[j].data_ptr() if bf[j] is not None else None
-            bw.wino[j] = wino[j].data_ptr() if wino[j] is not None else None
-        cached = packed_cell._bwd = (packed_cell._stamp, bw, keep, bf, wino)
-    bw = cached[1]
+    bw = packed_cell.bwd_desc()
     x, h, grad_h_next = x.contiguous(), h.contiguous(), grad_h_next.contiguous()
     b = x.shape[0]
     params = packed_cell._params()
@@ -960,12 +913,11 @@ def _cell_seq_desc(packed_cell):
     cached = getattr(packed_cell, "_seq", None)
     if cached is not None and cached[0] == packed_cell._stamp:
         return d, cached[1]
-    mode, cell = packed_cell._stamp[0], packed_cell.cell
+    mode = packed_cell._stamp[0]
     if d.ks != 5 or d.input % 8 or d.hidden % 32:
         raise ValueError(f"ConvGRU sequence: the 5x5 Winograd kernels serve kernel_size 5, input_dim % 8 == 0, hidden_dim % 32 == 0 "
                          f"(got {d.ks}, {d.input}, {d.hidden})")
-    wg, wc = cell.conv_gates[0].weight.detach(), cell.conv_can[0].weight.detach()
-    slices = [w.contiguous() for w in (wg[:, :d.input], wg[:, d.input:], wc[:, :d.input], wc[:, d.input:])]
+    slices = packed_cell._half_slices()
     hv = _lib.ConvGRUCellHalves()
     if mode == "bf16":
         if not (_bf16_cell_ok(d.input, d.hidden, d.ks) and d.w_gates_bf16):
@@ -1035,15 +987,7 @@ def convgru_sequence_backward(packed_cell, saved, grad_h_seq):
     d, hv = _cell_seq_desc(packed_cell)
     if packed_cell._stamp != stamp:
         raise RuntimeError("a ConvGRUCell parameter (or the compute dtype) changed between the sequence's forward and its backward")
-    cached = getattr(packed_cell, "_bwd", None)
-    if cached is None or cached[0] != packed_cell._stamp:
-        keep, bf, wino = _cell_bwd_packs(packed_cell.cell, d, packed_cell._stamp[0])
-        bw = _lib.ConvGRUCellBwd(*[k.data_ptr() for k in keep])
-        for j in range(4):
-            bw.bf16[j] = bf[j].data_ptr() if bf[j] is not None else None
-            bw.wino[j] = wino[j].data_ptr() if wino[j] is not None else None
-        cached = packed_cell._bwd = (packed_cell._stamp, bw, keep, bf, wino)
-    bw = cached[1]
+    bw = packed_cell.bwd_desc()
     grad_h_seq = grad_h_seq.contiguous()
     if tuple(grad_h_seq.shape) != (n_steps, b, d.hidden, 16, 16):
         raise ValueError(f"grad_h_seq must be ({n_steps},{b},{d.hidden},16,16); got {tuple(grad_h_seq.shape)}")
@@ -1089,14 +1033,10 @@ class PackedEncoder:
 
 def encoder_params(enc):
     """Parameters of the encoder in the order the training path returns their gradients."""
-    cell = enc.packed_cell.cell
     ps = []
     for c in enc.f_stack.convs:
         ps += [c.weight, c.bias]
-    ps += [cell.conv_gates[0].weight, cell.conv_gates[0].bias, cell.conv_gates[1].weight, cell.conv_gates[1].bias,
-           cell.conv_can[0].weight, cell.conv_can[0].bias, cell.conv_can[1].weight, cell.conv_can[1].bias,
-           enc.head[0].weight, enc.head[0].bias, enc.head[2].weight, enc.head[2].bias]
-    return ps
+    return ps + enc.packed_cell._params() + [enc.head[0].weight, enc.head[0].bias, enc.head[2].weight, enc.head[2].bias]
 
 
 def _encoder_bwd_desc(enc):
@@ -1106,45 +1046,52 @@ def _encoder_bwd_desc(enc):
     cached = getattr(enc, "_bwd", None)
     if cached is not None and cached[0] is stamp:
         return cached[1]
-    keep, bf, wino = _cell_bwd_packs(enc.packed_cell.cell, d.cell, current_compute_dtype(),
+    keep, bf, wino = _cell_bwd_packs(enc.packed_cell, d.cell, current_compute_dtype(),
                                      extra_jobs=[(enc.head[0].weight, 0, True), (enc.head[2].weight, 0, True)])
     b = _lib.EncoderBwd()
     b.f_dgrad = enc.f_stack.dgrad_desc()
     b.w_gates_dx, b.w_gates_dh, b.w_can_dx, b.w_can_dh, b.w_head0_t, b.w_head1_t = (k.data_ptr() for k in keep)
-    for j in range(4):
-        b.bf16[j] = bf[j].data_ptr() if bf[j] is not None else None
-        b.wino[j] = wino[j].data_ptr() if wino[j] is not None else None
+    _set_half_images(b, bf, wino)
     keep = keep + bf + wino
     enc._bwd = (stamp, b, keep)
     return b
 
 
-def odeconvgru_encode_train(enc, inputs, timesteps, want_latent=False, run_backwards=True):
-    """Forward of the training path: returns (mean, std, latent_ys or None, saved) -- `saved` holds the workspace the backward
-    call needs."""
+def _encode(enc, inputs, timesteps, want_latent, run_backwards, train):
+    """The encoder forward of both paths: (mean, std, latent_ys or None, what odeconvgru_encode_backward needs).  train: the entry point
+    that keeps the per-frame activations, in a private workspace."""
     require_device_tensor(inputs, "inputs")
     d = enc.refresh()
     inputs = inputs.contiguous()
     t, b, c = inputs.shape[0], inputs.shape[1], inputs.shape[2]
     if inputs.dim() != 5 or tuple(inputs.shape[3:]) != (16, 16) or c != d.cell.hidden:
         raise ValueError(f"inputs must be (T,B,{d.cell.hidden},16,16) time-first (got {tuple(inputs.shape)})")
-    t64 = [float(v) for v in host_times(timesteps).tolist()]
-    assert t == len(t64), "Sequence length should be same as time_steps"
+    tarr = _c_times(timesteps)
+    assert t == len(tarr), "Sequence length should be same as time_steps"
     lib = _lib.load()
-    nbytes = lib.odehip_encoder_train_workspace_bytes(ctypes.byref(d), t, b)
-    ws = alloc_workspace(nbytes, inputs.device)   # owned by this call's graph node
+    if train:
+        ws = alloc_workspace(lib.odehip_encoder_train_workspace_bytes(ctypes.byref(d), t, b), inputs.device)   # owned by this call's graph node
+        fn = lib.odehip_odeconvgru_encode_train
+    else:
+        ws = workspace(("enc", t, b, c), lib.odehip_encoder_workspace_bytes(ctypes.byref(d), t, b), inputs.device)
+        fn = lib.odehip_odeconvgru_encode
     mean = torch.empty((b, d.out_ch, 16, 16), dtype=torch.float32, device=inputs.device)
     std = torch.empty_like(mean)
     latent = torch.empty((b, t, c, 16, 16), dtype=torch.float32, device=inputs.device) if want_latent else None
-    tarr = (ctypes.c_double * t)(*t64)
-    _lib.check(lib.odehip_odeconvgru_encode_train(ctypes.byref(d), _ptr(inputs), tarr, t, b, int(bool(run_backwards)), _ptr(mean),
-                                                  _ptr(std), _ptr(latent), _ptr(ws), ws.numel(), _stream()))
-    return mean, std, latent, (ws, t64, t, b, c, int(bool(run_backwards)))
+    _lib.check(fn(ctypes.byref(d), _ptr(inputs), tarr, t, b, int(bool(run_backwards)), _ptr(mean), _ptr(std), _ptr(latent), _ptr(ws),
+                  ws.numel(), _stream()))
+    return mean, std, latent, (ws, tarr, t, b, c, int(bool(run_backwards)))
+
+
+def odeconvgru_encode_train(enc, inputs, timesteps, want_latent=False, run_backwards=True):
+    """Forward of the training path: returns (mean, std, latent_ys or None, saved) -- `saved` holds the workspace the backward
+    call needs."""
+    return _encode(enc, inputs, timesteps, want_latent, run_backwards, True)
 
 
 def odeconvgru_encode_backward(enc, saved, grad_mean, grad_std, grad_latent=None):
     """(grad_inputs (T,B,C,16,16), [gradient of every tensor of encoder_params(enc)]); grad_latent: what arrives through latent_ys."""
-    ws, t64, t, b, c, run_backwards = saved
+    ws, tarr, t, b, c, run_backwards = saved
     d = enc.refresh()
     bw = _encoder_bwd_desc(enc)
     dev = ws.device
@@ -1167,7 +1114,6 @@ def odeconvgru_encode_backward(enc, saved, grad_mean, grad_std, grad_latent=None
     (g.w_gates, g.b_gates, g.gn_gates_w, g.gn_gates_b, g.w_can, g.b_can, g.gn_can_w, g.gn_can_b, g.w_head0, g.b_head0, g.w_head1,
      g.b_head1) = (x.data_ptr() for x in grads[2 * nl:])
     gin = torch.empty((t, b, c, 16, 16), dtype=torch.float32, device=dev)
-    tarr = (ctypes.c_double * t)(*t64)
     _lib.check(_lib.load().odehip_odeconvgru_encode_backward(ctypes.byref(d), ctypes.byref(bw), tarr, t, b, run_backwards,
                                                              _ptr(grad_mean), _ptr(grad_std), _ptr(grad_latent), _ptr(gin),
                                                              ctypes.byref(g), _ptr(ws), ws.numel(), _stream()))
@@ -1175,24 +1121,7 @@ def odeconvgru_encode_backward(enc, saved, grad_mean, grad_std, grad_latent=None
 
 
 def odeconvgru_encode(enc, inputs, timesteps, want_latent=False, run_backwards=True):
-    require_device_tensor(inputs, "inputs")
-    d = enc.refresh()
-    inputs = inputs.contiguous()
-    t, b, c = inputs.shape[0], inputs.shape[1], inputs.shape[2]
-    if inputs.dim() != 5 or tuple(inputs.shape[3:]) != (16, 16) or c != d.cell.hidden:
-        raise ValueError(f"inputs must be (T,B,{d.cell.hidden},16,16) time-first (got {tuple(inputs.shape)})")
-    t64 = [float(v) for v in host_times(timesteps).tolist()]
-    assert t == len(t64), "Sequence length should be same as time_steps"
-    lib = _lib.load()
-    nbytes = lib.odehip_encoder_workspace_bytes(ctypes.byref(d), t, b)
-    ws = workspace(("enc", t, b, c), nbytes, inputs.device)
-    mean = torch.empty((b, d.out_ch, 16, 16), dtype=torch.float32, device=inputs.device)
-    std = torch.empty_like(mean)
-    latent = torch.empty((b, t, c, 16, 16), dtype=torch.float32, device=inputs.device) if want_latent else None
-    tarr = (ctypes.c_double * t)(*t64)
-    _lib.check(lib.odehip_odeconvgru_encode(ctypes.byref(d), _ptr(inputs), tarr, t, b, int(bool(run_backwards)), _ptr(mean), _ptr(std),
-                                            _ptr(latent), _ptr(ws), ws.numel(), _stream()))
-    return mean, std, latent
+    return _encode(enc, inputs, timesteps, want_latent, run_backwards, False)[:3]
 
 
 # ---- VidODE's warp chain + mask compositing (csrc/warp.hip) ---------------------------------------------------------------
@@ -1352,7 +1281,6 @@ def frame_decoder_supported(seq):
 
 
 def _codec_pack(seq, c1, c2, n_floats, pack_fn, in_ch, out_ch):
-    import weakref
     params = (c1.weight, c1.bias, c2.weight, c2.bias)
     for p in params:
         require_device_tensor(p, "codec parameter")
@@ -1370,6 +1298,18 @@ def _codec_pack(seq, c1, c2, n_floats, pack_fn, in_ch, out_ch):
     return pack
 
 
+def _frame_encoder_pack(seq, c1, c2):
+    lib = _lib.load()
+    return _codec_pack(seq, c1, c2, lib.odehip_frame_encoder_pack_floats(c1.in_channels, c2.out_channels), lib.odehip_pack_frame_encoder,
+                       c1.in_channels, c2.out_channels)
+
+
+def _frame_decoder_pack(seq, c1, c2):
+    lib = _lib.load()
+    return _codec_pack(seq, c1, c2, lib.odehip_frame_decoder_pack_floats(c1.in_channels, c2.out_channels), lib.odehip_pack_frame_decoder,
+                       c1.in_channels, c2.out_channels)
+
+
 def frame_encode(seq, frames):
     """`seq` = the reference Encoder's nn.Sequential (n_downs = 2).  frames (B,T,c,64,64) -> (T,B,out_ch,16,16) contiguous,
     TIME-FIRST: the layout ODEConvGRU.py:64-68 reaches through a permuted view."""
@@ -1381,11 +1321,9 @@ def frame_encode(seq, frames):
         raise ValueError(f"frame_encode: frames must be (B,T,{c1.in_channels},64,64), got {tuple(frames.shape)}")
     frames = frames.detach().contiguous()
     b, t = frames.shape[:2]
-    lib = _lib.load()
-    pack = _codec_pack(seq, c1, c2, lib.odehip_frame_encoder_pack_floats(c1.in_channels, c2.out_channels), lib.odehip_pack_frame_encoder,
-                       c1.in_channels, c2.out_channels)
+    pack = _frame_encoder_pack(seq, c1, c2)
     out = torch.empty((t, b, c2.out_channels, 16, 16), dtype=torch.float32, device=frames.device)
-    _lib.check(lib.odehip_frame_encode(_ptr(pack), _ptr(frames), b, t, c1.in_channels, c2.out_channels, slope, _ptr(out), _stream()))
+    _lib.check(_lib.load().odehip_frame_encode(_ptr(pack), _ptr(frames), b, t, c1.in_channels, c2.out_channels, slope, _ptr(out), _stream()))
     return out
 
 
@@ -1404,13 +1342,11 @@ def frame_decode(seq, latents, apply_sigmoid, save_mid=False):
     n = 1
     for d in lead:
         n *= d
-    lib = _lib.load()
-    pack = _codec_pack(seq, c1, c2, lib.odehip_frame_decoder_pack_floats(c1.in_channels, c2.out_channels), lib.odehip_pack_frame_decoder,
-                       c1.in_channels, c2.out_channels)
+    pack = _frame_decoder_pack(seq, c1, c2)
     out = torch.empty(lead + (c2.out_channels, 64, 64), dtype=torch.float32, device=latents.device)
     mid = torch.empty((n, 32 * 32 * 32), dtype=torch.float32, device=latents.device) if save_mid else None
-    _lib.check(lib.odehip_frame_decode_train(_ptr(pack), _ptr(latents), n, c1.in_channels, c2.out_channels, slope, 1 if apply_sigmoid else 0,
-                                             _ptr(out), _ptr(mid) if save_mid else None, _stream()))
+    _lib.check(_lib.load().odehip_frame_decode_train(_ptr(pack), _ptr(latents), n, c1.in_channels, c2.out_channels, slope,
+                                                     1 if apply_sigmoid else 0, _ptr(out), _ptr(mid) if save_mid else None, _stream()))
     return (out, mid) if save_mid else out
 
 
@@ -1435,6 +1371,24 @@ def frame_decoder_backward_supported(seq):
     return c2.out_channels == 1 and c1.in_channels in (32, 64)
 
 
+def record_versions(ctx, params):
+    """forward of an autograd Function whose backward reads the live parameters (it re-packs from them): remember which they were."""
+    ctx.params = params
+    ctx.versions = tuple(p._version for p in params)
+
+
+def check_versions(ctx, subject):
+    """backward: the parameters record_versions() saw must still be the forward's."""
+    if tuple(p._version for p in ctx.params) != ctx.versions:
+        raise RuntimeError(f"{subject} was modified in place between forward and backward")
+
+
+def _codec_grads(c1, c2, ws_floats):
+    """Outputs of a codec backward: the gradients of (c1.weight, c1.bias, c2.weight, c2.bias) and its float workspace."""
+    grads = [torch.empty_like(p) for p in (c1.weight, c1.bias, c2.weight, c2.bias)]
+    return grads, torch.empty(int(ws_floats), dtype=torch.float32, device=c1.weight.device)
+
+
 class _FrameEncodeFn(torch.autograd.Function):
     """frame_encode under autograd: forward = the fused launch, backward = odehip_frame_encode_backward (gradients of the four
     parameter tensors; the frames carry none -- the caller checks that they do not ask for one)."""
@@ -1443,31 +1397,25 @@ class _FrameEncodeFn(torch.autograd.Function):
     def forward(ctx, seq, frames, w1, b1, w2, b2):
         out = frame_encode(seq, frames)
         ctx.seq = seq
-        ctx.params = (w1, b1, w2, b2)   # the backward re-packs from the live parameters: they must still be the forward's
-        ctx.versions = tuple(p._version for p in ctx.params)
+        record_versions(ctx, (w1, b1, w2, b2))
         ctx.save_for_backward(frames, out, w2)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        if tuple(p._version for p in ctx.params) != ctx.versions:
-            raise RuntimeError("a parameter of the frame encoder was modified in place between forward and backward")
+        check_versions(ctx, "a parameter of the frame encoder")
         frames, out, w2 = ctx.saved_tensors
-        seq = ctx.seq
-        c1, c2, slope = _codec_layers(seq, torch.nn.Conv2d, 3, 16)
+        c1, c2, slope = _codec_layers(ctx.seq, torch.nn.Conv2d, 3, 16)   # one frame channel (frame_encoder_backward_supported)
         lib = _lib.load()
         b, t = frames.shape[:2]
-        pack = _codec_pack(seq, c1, c2, lib.odehip_frame_encoder_pack_floats(1, c2.out_channels), lib.odehip_pack_frame_encoder, 1, c2.out_channels)
+        pack = _frame_encoder_pack(ctx.seq, c1, c2)
         g = g.contiguous()
         frames = frames.detach().contiguous()
-        dev = frames.device
-        dw1, db1 = torch.empty_like(c1.weight), torch.empty_like(c1.bias)
-        dw2, db2 = torch.empty_like(c2.weight), torch.empty_like(c2.bias)
-        nws = int(lib.odehip_frame_encode_backward_workspace_floats(b, t, 1, c2.out_channels))
-        ws = torch.empty(nws, dtype=torch.float32, device=dev)
+        (dw1, db1, dw2, db2), ws = _codec_grads(c1, c2, lib.odehip_frame_encode_backward_workspace_floats(b, t, 1, c2.out_channels))
         _lib.check(lib.odehip_frame_encode_backward(_ptr(pack), _ptr(w2.detach().contiguous()), _ptr(frames), _ptr(out), _ptr(g), b, t, 1,
-                                                    c2.out_channels, slope, _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(ws), nws, _stream()))
+                                                    c2.out_channels, slope, _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(ws), ws.numel(),
+                                                    _stream()))
         return None, None, dw1, db1, dw2, db2
 
 
@@ -1483,34 +1431,28 @@ class _FrameDecodeFn(torch.autograd.Function):
         else:
             pred, mid = frame_decode(seq, latents, apply_sigmoid), None
         ctx.seq, ctx.apply_sigmoid, ctx.has_mid = seq, bool(apply_sigmoid), mid is not None
-        ctx.params = (w1, b1, w2, b2)
-        ctx.versions = tuple(p._version for p in ctx.params)
+        record_versions(ctx, (w1, b1, w2, b2))
         ctx.save_for_backward(latents, pred, w1, *([mid] if mid is not None else []))
         return pred
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        if tuple(p._version for p in ctx.params) != ctx.versions:
-            raise RuntimeError("a parameter of the frame decoder was modified in place between forward and backward")
+        check_versions(ctx, "a parameter of the frame decoder")
         latents, pred, w1 = ctx.saved_tensors[:3]
         mid = ctx.saved_tensors[3] if ctx.has_mid else None
-        seq = ctx.seq
-        c1, c2, slope = _codec_layers(seq, torch.nn.ConvTranspose2d, 4, 32)
+        c1, c2, slope = _codec_layers(ctx.seq, torch.nn.ConvTranspose2d, 4, 32)   # one frame channel (frame_decoder_backward_supported)
         lib = _lib.load()
         lat = latents.detach().contiguous()
         n = lat.numel() // (c1.in_channels * 256)
-        pack = _codec_pack(seq, c1, c2, lib.odehip_frame_decoder_pack_floats(c1.in_channels, 1), lib.odehip_pack_frame_decoder, c1.in_channels, 1)
+        pack = _frame_decoder_pack(ctx.seq, c1, c2)
         g = g.contiguous()
         g_lat = torch.empty_like(lat)
-        dw1, db1 = torch.empty_like(c1.weight), torch.empty_like(c1.bias)
-        dw2, db2 = torch.empty_like(c2.weight), torch.empty_like(c2.bias)
-        nws = int(lib.odehip_frame_decode_backward_workspace_floats(n, c1.in_channels, 1))
-        ws = torch.empty(nws, dtype=torch.float32, device=lat.device)
+        (dw1, db1, dw2, db2), ws = _codec_grads(c1, c2, lib.odehip_frame_decode_backward_workspace_floats(n, c1.in_channels, 1))
         _lib.check(lib.odehip_frame_decode_backward(_ptr(pack), _ptr(w1.detach().contiguous()), _ptr(lat), _ptr(mid) if mid is not None else None,
                                                     _ptr(pred), _ptr(g), n, c1.in_channels, 1,
                                                     slope, 1 if ctx.apply_sigmoid else 0, _ptr(g_lat), _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2),
-                                                    _ptr(ws), nws, _stream()))
+                                                    _ptr(ws), ws.numel(), _stream()))
         return None, g_lat.view_as(latents), None, dw1, db1, dw2, db2
 
 

@@ -99,14 +99,32 @@ def odeint_forward(func, y0, t, rtol, atol, method, options=None):
         check_options(method, options)
         return hip_ops.odeint_fixed(stack, method, y0, th, negate=negate)
     check_options(method, options)
+    return run_dopri5(stack, y0, th, dopri5_cfg(rtol, atol, options), negate=negate)[0]
+
+
+def dopri5_cfg(rtol, atol, options):
+    """Tolerances and the dopri5 `options` this path implements, as run_dopri5 and the autograd Functions take them."""
     options = options or {}
-    if hip_ops._async_dopri5 and not negate:   # enqueue only; the stats are read when somebody looks at them
-        out, pending = hip_ops.odeint_dopri5_start(stack, y0, th, rtol, atol, first_step=float(options.get("first_step") or 0.0),
-                                                   max_steps=int(options.get("max_num_steps") or 0))
-        last_stats._bind(pending)
-        return out
-    out, stats = hip_ops.odeint_dopri5(stack, y0, th, rtol, atol, first_step=float(options.get("first_step") or 0.0),
-                                       max_steps=int(options.get("max_num_steps") or 0), negate=negate)
+    return dict(rtol=float(rtol), atol=float(atol), first_step=float(options.get("first_step") or 0.0),
+                max_num_steps=int(options.get("max_num_steps") or 0))
+
+
+def run_dopri5(stack, y0, th, cfg, save=False, negate=False):
+    """One dopri5 forward -> (out, pending, stats, saved).  With hip_ops.set_async_dopri5 on (and not for the negated dynamics) the
+    solve is only enqueued: `pending` is its PendingDopri5, bound to last_stats -- the stats are read when somebody looks at them --
+    and stats / saved are None.  Otherwise pending is None and last_stats holds the stats.  save: keep the activations of the accepted
+    steps for the backward pass (hip_ops.odeint_dopri5_saving); `saved` is then what odeint_dopri5_backward_saved takes, or None."""
+    steps = dict(first_step=cfg["first_step"], max_steps=cfg["max_num_steps"])
+    saved = None
+    if save:
+        out, stats, saved = hip_ops.odeint_dopri5_saving(stack, y0, th, cfg["rtol"], cfg["atol"], **steps)
+    elif hip_ops._async_dopri5 and not negate:
+        out, stats = hip_ops.odeint_dopri5_start(stack, y0, th, cfg["rtol"], cfg["atol"], **steps)
+    else:
+        out, stats = hip_ops.odeint_dopri5(stack, y0, th, cfg["rtol"], cfg["atol"], negate=negate, **steps)
+    if isinstance(stats, hip_ops.PendingDopri5):
+        last_stats._bind(stats)
+        return out, stats, None, None
     last_stats.clear()
     last_stats.update(stats)
-    return out
+    return out, None, stats, saved
