@@ -42,28 +42,29 @@ __device__ __forceinline__ f32x4 pk_sub(f32x4 a, f32x4 b) {
   return f32x4{lo.x, lo.y, hi.x, hi.y};
 }
 
-// Hand-off between the layers of the persistent trajectory kernel (below): `done` is the sample's line of 16 words, one per
-// consumer wave of its four workgroups; a wave stores the number of layers it has finished (single writer per word: no
-// read-modify-write anywhere).  A layer's input is complete once all 16 words have reached `target`.
+// Hand-off between the rows of the trajectory walks (below): `done` is the sample's flag line, one word per consumer wave of its
+// workgroups (16 words, or 64 on the sixteen-workgroup walk); a wave stores the number of rows it has finished (single writer per
+// word: no read-modify-write anywhere).  A row's input is complete once the words of the workgroups that wrote it have reached
+// `wait_target`.  The sixteen-workgroup walk names the fields it fills and leaves those of the four-workgroup layers (word0, stamps,
+// split_wait) at the defaults below.
 struct PersistHook {
-  unsigned* done;
-  unsigned target;     // epoch base + index of this layer (a launch that does not zero the flags tags them with its epoch)
-  int word0;           // first of this workgroup's four words
-  unsigned* abort_;    // device word: some wait of this launch has given up -- nobody waits any more
-  unsigned* host_err;  // mapped host word: a capped wait gave up (never expected; the kernel then finishes with wrong data)
-  bool fence;          // the sample's workgroups are NOT on one XCD: agent-scope release / acquire around the hand-off
-  float* nchw_base;    // base of the NCHW result tensor (the table holds offsets into it, in `dbg`)
-  unsigned long long* stamps;  // diagnostic (odehip_set_debug_buffer): 8 x 100 MHz timestamps of this layer, or null
-  int batch;
-  unsigned abort_tag;  // value of *abort_ that means "this launch has given up" (epoch + 1)
-  bool first;          // layer 0 of the launch: its input was complete before the launch
-  bool solo;           // the group walks ONE sample: the producers have nothing to prepare while the consumers finish a layer
-  bool announce;       // false: the first of a workgroup's two passes over a 128-channel layer -- its flags are stored after the second
-  bool split_wait;     // the input chunks 0/1 and 2/3 come from the two co tiles of a 64 -> 64 layer: wait for them separately
-  int sleep6;          // solo: s_sleep(6) periods (0.18 us each) in front of the first poll
-  const unsigned long long* reloc;  // adaptive walk: base addresses of the relocation classes (rel() below), or null
-  unsigned wait_target;  // what the partners' flags must have reached before this row's input is loaded (target, or target - 1
-                         // for a row that does not depend on the row in front of it: ConvArgs::dep_back)
+  unsigned* done = nullptr;
+  unsigned target = 0u;  // index of this row in the launch's walk (every launch gets a zeroed flag line)
+  int word0 = 0;         // first of this workgroup's four words
+  unsigned* abort_ = nullptr;    // device word: some wait of this launch has given up -- nobody waits any more
+  unsigned* host_err = nullptr;  // mapped host word: a capped wait gave up (never expected; the kernel then finishes with wrong data)
+  bool fence = false;    // the sample's workgroups are NOT on one XCD: agent-scope release / acquire around the hand-off
+  float* nchw_base = nullptr;    // base of the NCHW result tensor (the table holds offsets into it, in `dbg`)
+  unsigned long long* stamps = nullptr;  // diagnostic (odehip_set_debug_buffer): 8 x 100 MHz timestamps of this layer, or null
+  int batch = 0;
+  bool first = true;     // layer 0 of the launch: its input was complete before the launch
+  bool solo = false;     // the group walks ONE sample: the producers have nothing to prepare while the consumers finish a layer
+  bool announce = true;  // false: the first of a workgroup's two passes over a 128-channel layer -- its flags are stored after the second
+  bool split_wait = false;  // the input chunks 0/1 and 2/3 come from the two co tiles of a 64 -> 64 layer: wait for them separately
+  int sleep6 = 0;        // s_sleep(6) periods (0.18 us each) in front of the first poll (four workgroups: solo only)
+  const unsigned long long* reloc = nullptr;  // adaptive walk: base addresses of the relocation classes (rel() below), or null
+  unsigned wait_target = 0u;  // what the partners' flags must have reached before this row's input is loaded (target, or target - 1
+                              // for a row that does not depend on the row in front of it: ConvArgs::dep_back)
 };
 
 // Relocatable pointers of the adaptive walk's tables.  A driver whose buffers are chosen ON THE DEVICE (the slot an adaptive
@@ -102,9 +103,9 @@ __device__ __forceinline__ void wait_done(const PersistHook& hk, int sel_mask = 
   while (!__all(!mine || __hip_atomic_load(hk.done + (lane & 15), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= hk.wait_target)) {
     __builtin_amdgcn_s_sleep(1);
     if ((++n & 1023) == 0) {
-      if (__hip_atomic_load(hk.abort_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == hk.abort_tag) break;
+      if (__hip_atomic_load(hk.abort_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1u) break;
       if (n > (1 << 23)) {  // seconds: partners lost -- report and stop ALL waiting rather than hang the device
-        __hip_atomic_store(hk.abort_, hk.abort_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(hk.abort_, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         *hk.host_err = 3;
         break;
       }
@@ -112,6 +113,91 @@ __device__ __forceinline__ void wait_done(const PersistHook& hk, int sel_mask = 
   }
   if (hk.fence) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 }
+
+// A wave announces its share of row hk.target: its stores are in L2 once they are acknowledged; then -- behind an agent-scope release
+// if the group spans XCDs -- it stores target + 1 into its own flag word (unless this is the first of two passes over the layer:
+// !hk.announce).  stamp: the diagnostic timestamp 7 is taken between the two.  The four-workgroup elementwise row (ew_row) keeps the
+// sequence written out: through this function the adaptive walk spills two more scalar registers than its ceiling allows.
+__device__ __forceinline__ void announce(const PersistHook& hk, unsigned* done_word, bool stamp = false) {
+  const int lane = threadIdx.x & 63;
+  wait_vmcnt<0>();
+  if (stamp) pstamp(hk, 7, lane);
+  if (hk.fence) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  if (lane == 0 && hk.announce) __hip_atomic_store(done_word, hk.target + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Prologue of a walk, part 1: the GROUP workgroups of a sample (logical ids lid & ~(GROUP - 1) ...) publish the XCD they really run
+// on (XCC_ID + 1; the words are zero on entry) and read each other's; returns the uniform `fence` flag: true if they differ, so the
+// hand-off needs agent-scope fences.  The wait is capped: a partner that never arrives sets the abort word and the host word.
+template <int GROUP>
+__device__ __forceinline__ bool xcc_rendezvous(unsigned* xcc_of, int lid, unsigned* abort_word, unsigned* host_err) {
+  const unsigned my_xcc = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u) + 1u;  // HW_REG_XCC_ID[3:0]
+  if (threadIdx.x == 0) __hip_atomic_store(xcc_of + lid, my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  bool fence = false;
+  for (int p = 0; p < GROUP; ++p) {
+    unsigned v = 0;
+    int n = 0;
+    while ((v = __hip_atomic_load(xcc_of + (lid & ~(GROUP - 1)) + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0) {
+      __builtin_amdgcn_s_sleep(2);
+      if (++n > (1 << 23)) {
+        __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *host_err = 2;
+        break;
+      }
+    }
+    fence |= (v != my_xcc);
+  }
+  return __builtin_amdgcn_readfirstlane(fence);
+}
+
+// Prologue of a walk, part 2 (all of it uniform and constant during the launch): false = nothing to walk -- an adaptive solver that
+// finished while this launch was queued (table[0].skip), or a device-side controller that lost its way.  section: null, or the
+// device-steered {first row, number of rows} of this launch's walk; table and n_layers then become that section.
+__device__ __forceinline__ bool walk_start(const ConvArgs*& table, int& n_layers, const int* section) {
+  typedef const __attribute__((address_space(4))) int ConstI;
+  const int* skip = table[0].skip;
+  if (skip && *(ConstI*)skip) return false;
+  if (section) {
+    const int row0 = ((ConstI*)section)[0], n_dev = ((ConstI*)section)[1];
+    if (row0 < 0 || n_dev <= 0 || row0 + n_dev > n_layers) return false;
+    table += row0;
+    n_layers = n_dev;
+  }
+  return true;
+}
+
+// The row cursor of a walk.  The table is constant for the whole launch and is read in place (a private copy would live in scratch):
+// through address space 4 its fields are fetched with SCALAR loads (as a plain global pointer they become vector loads, each followed
+// by vmcnt(0), because the kernel also stores to global memory).  A row that is first touched when it is needed costs a trip to HBM on
+// the critical path of every layer, so the next row is pulled into L2 a layer ahead and the producers' two pointers (src, u) are
+// fetched a layer ahead.  (The wide walk reads src and u from the current row and keeps its own loop: through this cursor it needs
+// 254 VGPRs and scratch.)
+struct RowCursor {
+  const ConvArgs* table;
+  int n_layers;
+  const float *src, *u, *src_next, *u_next;
+  __device__ __forceinline__ RowCursor(const ConvArgs* t, int n)
+      : table(t), n_layers(n), src(t[0].src1), u(t[0].w_wino), src_next(nullptr), u_next(nullptr) {}
+  __device__ __forceinline__ const ConvArgs& row(int l) {
+    typedef const __attribute__((address_space(4))) ConvArgs ConstArgs;
+    const ConvArgs& a = *(const ConvArgs*)((ConstArgs*)table + l);
+    src_next = src;
+    u_next = u;
+    if (l + 1 < n_layers) {
+      src_next = table[l + 1].src1;
+      u_next = table[l + 1].w_wino;
+      if (threadIdx.x < (sizeof(ConvArgs) + 63) / 64) {
+        const unsigned v = __builtin_nontemporal_load((const unsigned*)&table[l + 1] + threadIdx.x * 16);
+        asm volatile("" ::"v"(v));
+      }
+    }
+    return a;
+  }
+  __device__ __forceinline__ void next() {
+    src = src_next;
+    u = u_next;
+  }
+};
 
 // One 3x3 layer for workgroup (sample b, 32-channel tile ct, image half rh).  PERSIST: called in a loop by
 // wino_persist_kernel -- the input tile is loaded past the per-CU cache (sc0 sc1: it was written by other CUs of this launch),
@@ -614,10 +700,7 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
     }
     // this wave's share of the layer is in L2 once its stores are acknowledged; then it counts itself in
     if (wave == 0) pstamp(hk, 6, lane);
-    wait_vmcnt<0>();
-    if (wave == 0) pstamp(hk, 7, lane);
-    if (hk.fence) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    if (lane == 0 && hk.announce) __hip_atomic_store(hk.done + hk.word0 + wave, hk.target + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    announce(hk, hk.done + hk.word0 + wave, wave == 0);
   } else {
     finish_err(a, esum, wave);
     st.flush(a);
@@ -635,7 +718,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino_kernel(const float* __res
   int lid = blockIdx.x + gridDim.x * blockIdx.y;
   if ((nwg & 7) == 0) lid = (lid & 7) * (nwg >> 3) + (lid >> 3);
   const int rh = lid & 1, ct = (lid >> 1) % (gridDim.x >> 1), b = (lid >> 1) / (gridDim.x >> 1);
-  const PersistHook none = {nullptr, 0u, 0, nullptr, nullptr, false, nullptr, nullptr, 0, 0u, true, false, true, true, 0, nullptr, 0u};
+  const PersistHook none;
   wino_layer<NCHUNK, DBG, false>(p_src, p_u, p_qin, a, b, ct, rh, smem, none);
 }
 
@@ -649,7 +732,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino_kernel(const float* __res
 // runs on (XCC_ID) and a group whose members differ falls back to agent-scope fences: slower, still correct.  All waits are
 // capped (-> *host_err; the grid is one workgroup per CU and the occupancy is checked before the first launch), so a lost
 // partner cannot hang the device.
-constexpr int kDoneStride = 64;
 struct PersistArgs {
   const ConvArgs* table;  // one entry per layer of the whole trajectory, in execution order (library-owned device copy)
   int n_layers, batch;
@@ -661,8 +743,6 @@ struct PersistArgs {
   unsigned long long* stamps;  // diagnostic: [64 layers][8] timestamps of logical workgroup 0, or null
   int sleep6;             // PersistHook::sleep6
   int sleep6_combine;     // added in front of a layer whose input comes out of a stage-combine epilogue
-  unsigned epoch;         // tag of the flag words (flag = epoch << 10 | layers done; xcc = epoch << 4 | id); always 0: every launch
-                          // gets a zeroed flag area
   const int* n_layers_ptr;  // adaptive walk only: if non-null, {first row, number of rows} of this launch's walk are read from the
                             // device (a device-side controller picks the section of the table); n_layers is then the table's size
   const unsigned long long* reloc;  // adaptive walk only: relocation bases (rel()), or null
@@ -750,83 +830,35 @@ __device__ __forceinline__ void persist_walk(const PersistArgs& pa, const ConvAr
   const int nwg = gridDim.x;  // a multiple of 32: every XCD holds whole groups of 4
   const int lid = ((int)blockIdx.x & 7) * (nwg >> 3) + ((int)blockIdx.x >> 3);
   const int rh = lid & 1, ct = (lid >> 1) & 1, group = lid >> 2;
-  const unsigned my_xcc = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u) + 1u;  // HW_REG_XCC_ID[3:0]
-  const unsigned xtag = pa.epoch << 4;
-  if (threadIdx.x == 0) __hip_atomic_store(pa.xcc_of + lid, xtag | my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  bool fence = false;
-  for (int p = 0; p < 4; ++p) {
-    unsigned v = 0;
-    int n = 0;
-    while (((v = __hip_atomic_load(pa.xcc_of + (lid & ~3) + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & ~15u) != xtag || (v & 15u) == 0) {
-      __builtin_amdgcn_s_sleep(2);
-      if (++n > (1 << 23)) {
-        __hip_atomic_store(pa.xcc_of + nwg, pa.epoch + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *pa.host_err = 2;
-        break;
-      }
-    }
-    fence |= ((v & 15u) != my_xcc);
-  }
-  fence = __builtin_amdgcn_readfirstlane(fence);
-  {  // an adaptive solver that finished while this launch was queued: nothing to do (uniform; constant during the launch)
-    typedef const __attribute__((address_space(4))) int ConstI;
-    const int* skip = table[0].skip;
-    if (skip && *(ConstI*)skip) return;
-  }
-  const int n_groups = nwg >> 2;
+  const bool fence = xcc_rendezvous<4>(pa.xcc_of, lid, pa.xcc_of + nwg, pa.host_err);
   int n_layers = pa.n_layers;
-  if constexpr (ADAPT) {
-    typedef const __attribute__((address_space(4))) int ConstI;
-    if (pa.n_layers_ptr) {   // {row0, rows}: walk table[row0 .. row0 + rows)
-      const int row0 = ((ConstI*)pa.n_layers_ptr)[0], n_dev = ((ConstI*)pa.n_layers_ptr)[1];
-      if (row0 < 0 || n_dev <= 0 || row0 + n_dev > n_layers) return;   // (uniform) nothing to do / a controller that lost its way
-      table += row0;
-      n_layers = n_dev;
-    }
-  }
+  if (!walk_start(table, n_layers, ADAPT ? pa.n_layers_ptr : nullptr)) return;
+  const int n_groups = nwg >> 2;
   // A group walks TWO samples at a time, layer by layer in turn (when the batch gives it more than one): the hand-off latency of
   // one sample's layer (stores acknowledged -> flags seen -> next input tile loaded) is then covered by the other sample's layer.
   for (int b = group; b < pa.batch; b += 2 * n_groups) {
     const int n_interleaved = b + n_groups < pa.batch ? 2 : 1;
-    // the table is read in place (uniform loads; a private copy would live in scratch) -- but a row that is first touched when
-    // it is needed costs a trip to HBM on the critical path of every layer, so: the producers' two pointers are fetched a layer
-    // ahead and the next row is pulled into L2 a layer ahead
-    const float* src = table[0].src1;
-    const float* u = table[0].w_wino;
+    RowCursor cur(table, n_layers);
     int prev_combine = 0;  // the layer whose output this one waits for ended in a Runge-Kutta stage combine (a longer epilogue)
     for (int l = 0; l < n_layers; ++l) {
-      // the table is constant for the whole launch: address space 4 lets the compiler fetch its fields with SCALAR loads (as a
-      // plain global pointer they become vector loads, each followed by vmcnt(0), because the kernel also stores to global memory)
-      typedef const __attribute__((address_space(4))) ConvArgs ConstArgs;
-      const ConvArgs& a = *(const ConvArgs*)((ConstArgs*)table + l);
-      const float* src_next = src;
-      const float* u_next = u;
-      if (l + 1 < n_layers) {
-        src_next = table[l + 1].src1;
-        u_next = table[l + 1].w_wino;
-        if (threadIdx.x < (sizeof(ConvArgs) + 63) / 64) {
-          const unsigned v = __builtin_nontemporal_load((const unsigned*)&table[l + 1] + threadIdx.x * 16);
-          asm volatile("" ::"v"(v));
-        }
-      }
+      const ConvArgs& a = cur.row(l);
 #pragma unroll 1
       for (int s = 0; s < n_interleaved; ++s) {
         const int bs = __builtin_amdgcn_readfirstlane(b + s * n_groups);
-        const PersistHook hk = {pa.done + (size_t)bs * kDoneStride, (pa.epoch << 10) + (unsigned)l, (lid & 3) * 4, pa.xcc_of + nwg, pa.host_err, fence,
+        const PersistHook hk = {pa.done + (size_t)bs * kDoneStride, (unsigned)l, (lid & 3) * 4, pa.xcc_of + nwg, pa.host_err, fence,
                                 pa.out_nchw, (pa.stamps && lid == 0 && bs == group && l < 64) ? pa.stamps + l * 8 : nullptr, pa.batch,
-                                pa.epoch + 1u, l == 0, n_interleaved == 1, true, true, pa.sleep6 + (prev_combine == 1 ? pa.sleep6_combine : 0),
+                                l == 0, n_interleaved == 1, true, true, pa.sleep6 + (prev_combine == 1 ? pa.sleep6_combine : 0),
                                 ADAPT ? pa.reloc : nullptr,
-                                (pa.epoch << 10) + (unsigned)(ADAPT && a.dep_back > 0 && l > 0 ? l - 1 : l)};
+                                (unsigned)(ADAPT && a.dep_back > 0 && l > 0 ? l - 1 : l)};
         if constexpr (ADAPT) {
           if (a.combine >= 4) ew_row<16>(a, bs, ct, rh, hk);
-          else wino_layer<4, false, true, 16, true>(uniform_ptr(rel(pa.reloc, src)), uniform_ptr(u), 16, a, bs, ct, rh, smem, hk);
+          else wino_layer<4, false, true, 16, true>(uniform_ptr(rel(pa.reloc, cur.src)), uniform_ptr(cur.u), 16, a, bs, ct, rh, smem, hk);
         } else {
-          wino_layer<4, false, true>(uniform_ptr(src), uniform_ptr(u), 16, a, bs, ct, rh, smem, hk);
+          wino_layer<4, false, true>(uniform_ptr(cur.src), uniform_ptr(cur.u), 16, a, bs, ct, rh, smem, hk);
         }
       }
       prev_combine = a.combine;
-      src = src_next;
-      u = u_next;
+      cur.next();
     }
   }
 }
@@ -848,24 +880,7 @@ __device__ __forceinline__ void persist_walk_v(const PersistArgs& pa, const Conv
   const int nwg = gridDim.x;
   const int lid = ((int)blockIdx.x & 7) * (nwg >> 3) + ((int)blockIdx.x >> 3);
   const int rh = lid & 1, ct = (lid >> 1) & 1, group = lid >> 2;
-  const unsigned my_xcc = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u) + 1u;
-  const unsigned xtag = pa.epoch << 4;
-  if (threadIdx.x == 0) __hip_atomic_store(pa.xcc_of + lid, xtag | my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  bool fence = false;
-  for (int p = 0; p < 4; ++p) {
-    unsigned v = 0;
-    int n = 0;
-    while (((v = __hip_atomic_load(pa.xcc_of + (lid & ~3) + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & ~15u) != xtag || (v & 15u) == 0) {
-      __builtin_amdgcn_s_sleep(2);
-      if (++n > (1 << 23)) {
-        __hip_atomic_store(pa.xcc_of + nwg, pa.epoch + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *pa.host_err = 2;
-        break;
-      }
-    }
-    fence |= ((v & 15u) != my_xcc);
-  }
-  fence = __builtin_amdgcn_readfirstlane(fence);
+  const bool fence = xcc_rendezvous<4>(pa.xcc_of, lid, pa.xcc_of + nwg, pa.host_err);
   {  // an adaptive solver that finished while this launch was queued: nothing to do (uniform; constant during the launch)
     typedef const __attribute__((address_space(4))) int ConstI;
     const int* skip = table[0].skip;
@@ -888,9 +903,9 @@ __device__ __forceinline__ void persist_walk_v(const PersistArgs& pa, const Conv
 #pragma unroll 1
       for (int s = 0; s < n_interleaved; ++s) {
         const int bs = __builtin_amdgcn_readfirstlane(b + s * n_groups);
-        PersistHook hk = {pa.done + (size_t)bs * kDoneStride, (pa.epoch << 10) + (unsigned)l, (lid & 3) * 4, pa.xcc_of + nwg, pa.host_err, fence,
-                          pa.out_nchw, nullptr, pa.batch, pa.epoch + 1u, l == 0, n_interleaved == 1, true, false,
-                          pa.sleep6 + (prev_combine == 1 ? pa.sleep6_combine : 0), nullptr, (pa.epoch << 10) + (unsigned)l};
+        PersistHook hk = {pa.done + (size_t)bs * kDoneStride, (unsigned)l, (lid & 3) * 4, pa.xcc_of + nwg, pa.host_err, fence,
+                          pa.out_nchw, nullptr, pa.batch, l == 0, n_interleaved == 1, true, false,
+                          pa.sleep6 + (prev_combine == 1 ? pa.sleep6_combine : 0), nullptr, (unsigned)l};
         if (qout == 16) {
           if (qin == 16) wino_layer<4, false, true, 16>(src, u, 16, a, bs, ct, rh, smem, hk);
           else           wino_layer<8, false, true, 16>(src, u, 32, a, bs, ct, rh, smem, hk);
@@ -909,26 +924,20 @@ __device__ __forceinline__ void persist_walk_v(const PersistArgs& pa, const Conv
 
 __global__ __launch_bounds__(512, 1) void wino_persist_v_kernel(const PersistArgs pa) { persist_walk_v(pa, pa.table); }
 
-template <int NCHUNK>
-static int launch_wino_n(const ConvArgs& a, hipStream_t stream) {
-  static bool attr_set = false, attr_set_dbg = false;
-  const dim3 grid((a.qout / 8) * 2, a.batch);
-  if (a.debug) {
-    if (!attr_set_dbg) {
-      ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_wino_kernel<NCHUNK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr_set_dbg = true;
-    }
-    hipLaunchKernelGGL((conv3x3_wino_kernel<NCHUNK, true>), grid, dim3(512), kWinoLds, stream, a.src1, a.w_wino, a.qin, a.qout, a);
-    ODEHIP_CHECK_HIP(hipGetLastError());
-    return ODEHIP_OK;
-  }
+template <int NCHUNK, bool DBG>
+static int launch_wino_nd(const ConvArgs& a, hipStream_t stream) {
+  static bool attr_set = false;
   if (!attr_set) {
-    ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_wino_kernel<NCHUNK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_wino_kernel<NCHUNK, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set = true;
   }
-  hipLaunchKernelGGL((conv3x3_wino_kernel<NCHUNK, false>), grid, dim3(512), kWinoLds, stream, a.src1, a.w_wino, a.qin, a.qout, a);
+  hipLaunchKernelGGL((conv3x3_wino_kernel<NCHUNK, DBG>), dim3((a.qout / 8) * 2, a.batch), dim3(512), kWinoLds, stream, a.src1, a.w_wino, a.qin, a.qout, a);
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
+}
+template <int NCHUNK>
+static int launch_wino_n(const ConvArgs& a, hipStream_t stream) {
+  return a.debug ? launch_wino_nd<NCHUNK, true>(a, stream) : launch_wino_nd<NCHUNK, false>(a, stream);
 }
 
 int launch_wino_persist(const ConvArgs* table_dev, int n_layers, int batch, unsigned* done, unsigned* xcc_of, unsigned* host_err_dev,
@@ -956,7 +965,6 @@ int launch_wino_persist(const ConvArgs* table_dev, int n_layers, int batch, unsi
   constexpr int kSleep6Combine = 4;   // sweep: 0: 1.382, 4: 1.367, 6: 1.370, 8: 1.383, 12: 1.404 ms
   pa.sleep6 = kSleep6;
   pa.sleep6_combine = kSleep6Combine;
-  pa.epoch = 0;  // the caller zeroed the flag area
   pa.n_layers_ptr = n_layers_ptr;
   pa.reloc = reloc;
   pa.fault_inject = 0;
@@ -988,19 +996,7 @@ constexpr int k16V = 16 * 1024;    // V chunk: 16 xi x [quad 4][tile 16][4 ci]
 constexpr int k16X = 8 * 1024;     // exchange: [a 2][col 4][lane 64] quads
 constexpr int kWino16Lds = 2 * k16U + 2 * k16Raw + 2 * k16V + k16X;
 
-struct Hook16 {
-  unsigned* done;      // the sample's 64 flag words
-  unsigned target;     // index of this layer
-  unsigned* abort_;
-  unsigned* host_err;
-  bool fence, first;
-  float* nchw_base;
-  int sleep6;
-  const unsigned long long* reloc;   // relocation bases of an adaptive table (rel()), or null
-  unsigned wait_target;              // target, or target - 1 for a row that does not depend on the row in front of it (dep_back)
-};
-
-__device__ __forceinline__ void wait_done16(const Hook16& hk, int lo_word, int hi_word) {
+__device__ __forceinline__ void wait_done16(const PersistHook& hk, int lo_word, int hi_word) {
   int n = 0;
   const int lane = threadIdx.x & 63;
   const bool mine = lane >= lo_word && lane < hi_word;
@@ -1019,7 +1015,7 @@ __device__ __forceinline__ void wait_done16(const Hook16& hk, int lo_word, int h
 }
 
 __device__ __forceinline__ void wino_layer16(const float* __restrict__ p_src, const float* __restrict__ p_u, const ConvArgs& a, int b,
-                                             int cq, int rq, char* smem, const Hook16& hk) {
+                                             int cq, int rq, char* smem, const PersistHook& hk) {
   char* const Ub = smem;
   char* const Rb = smem + 2 * k16U;
   char* const Vb = smem + 2 * k16U + 2 * k16Raw;
@@ -1343,13 +1339,11 @@ __device__ __forceinline__ void wino_layer16(const float* __restrict__ p_src, co
       }
     }
   }
-  wait_vmcnt<0>();
-  if (hk.fence) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  if (lane == 0) __hip_atomic_store(hk.done + (rq * 4 + cq) * 4 + wave, hk.target + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  announce(hk, hk.done + (rq * 4 + cq) * 4 + wave);
 }
 
 // elementwise / norm rows (ConvArgs::combine == 4 / 5) in the sixteen-workgroup layout: a lane's one quad (see ew_row)
-__device__ __forceinline__ void ew_row16(const ConvArgs& a, int b, int cq, int rq, const Hook16& hk) {
+__device__ __forceinline__ void ew_row16(const ConvArgs& a, int b, int cq, int rq, const PersistHook& hk) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (wave >= 4) return;
@@ -1389,9 +1383,7 @@ __device__ __forceinline__ void ew_row16(const ConvArgs& a, int b, int cq, int r
     if (o1) *(f32x4*)(o1 + off) = s1;
     if (o2) *(f32x4*)(o2 + off) = s2;
   }
-  wait_vmcnt<0>();
-  if (hk.fence) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  if (lane == 0) __hip_atomic_store(hk.done + (rq * 4 + cq) * 4 + wave, hk.target + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  announce(hk, hk.done + (rq * 4 + cq) * 4 + wave);
 }
 
 // A wait of this launch gave up (abort word set; never expected): whatever the walk wrote cannot be trusted.  Every workgroup that is
@@ -1437,58 +1429,29 @@ __global__ __launch_bounds__(512, 1) void wino_persist16_kernel(const PersistArg
   const int b = slot * 8 + xcd;
   const int rq = wg >> 2, cq = wg & 3;
   if (b >= pa.batch) return;
-  const unsigned my_xcc = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u) + 1u;
-  if (threadIdx.x == 0) __hip_atomic_store(pa.xcc_of + lid, my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  bool fence = false;
-  for (int p = 0; p < 16; ++p) {
-    unsigned v = 0;
-    int n = 0;
-    while ((v = __hip_atomic_load(pa.xcc_of + (lid & ~15) + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0) {
-      __builtin_amdgcn_s_sleep(2);
-      if (++n > (1 << 23)) {
-        __hip_atomic_store(pa.xcc_of + gridDim.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *pa.host_err = 2;
-        break;
-      }
-    }
-    fence |= (v != my_xcc);
-  }
-  fence = __builtin_amdgcn_readfirstlane(fence);
+  const bool fence = xcc_rendezvous<16>(pa.xcc_of, lid, pa.xcc_of + gridDim.x, pa.host_err);
   const ConvArgs* table = pa.table;
   int n_layers = pa.n_layers;
-  {
-    typedef const __attribute__((address_space(4))) int ConstI;
-    const int* skip = table[0].skip;
-    if (skip && *(ConstI*)skip) return;   // an adaptive solver that finished while this launch was queued (uniform)
-    if (pa.n_layers_ptr) {   // a device-side controller picks the section of the table: {first row, rows}
-      const int row0 = ((ConstI*)pa.n_layers_ptr)[0], n_dev = ((ConstI*)pa.n_layers_ptr)[1];
-      if (row0 < 0 || n_dev <= 0 || row0 + n_dev > n_layers) return;
-      table += row0;
-      n_layers = n_dev;
-    }
-  }
-  const float* src = table[0].src1;
-  const float* u = table[0].w_wino;
+  if (!walk_start(table, n_layers, pa.n_layers_ptr)) return;
+  RowCursor cur(table, n_layers);
   for (int l = 0; l < n_layers; ++l) {
-    typedef const __attribute__((address_space(4))) ConvArgs ConstArgs;
-    const ConvArgs& a = *(const ConvArgs*)((ConstArgs*)table + l);
-    const float* src_next = src;
-    const float* u_next = u;
-    if (l + 1 < n_layers) {
-      src_next = table[l + 1].src1;
-      u_next = table[l + 1].w_wino;
-      if (threadIdx.x < (sizeof(ConvArgs) + 63) / 64) {
-        const unsigned v = __builtin_nontemporal_load((const unsigned*)&table[l + 1] + threadIdx.x * 16);
-        asm volatile("" ::"v"(v));
-      }
-    }
-    const Hook16 hk = {pa.done + (size_t)b * kDoneStride, (unsigned)l, pa.xcc_of + gridDim.x, pa.host_err, fence, l == 0, pa.out_nchw, pa.sleep6,
-                       pa.reloc, (unsigned)(a.dep_back > 0 && l > 0 ? l - 1 : l)};
+    const ConvArgs& a = cur.row(l);
+    PersistHook hk;
+    hk.done = pa.done + (size_t)b * kDoneStride;
+    hk.target = (unsigned)l;
+    hk.wait_target = (unsigned)(a.dep_back > 0 && l > 0 ? l - 1 : l);
+    hk.abort_ = pa.xcc_of + gridDim.x; hk.host_err = pa.host_err;
+    hk.fence = fence;
+    hk.nchw_base = pa.out_nchw;
+    hk.batch = pa.batch;
+    hk.first = l == 0;
+    hk.solo = true;
+    hk.sleep6 = pa.sleep6;
+    hk.reloc = pa.reloc;
     if (pa.fault_inject && lid == 0 && l == 1) return;   // (tests: a lost partner)
     if (a.combine >= 4) ew_row16(a, b, cq, rq, hk);
-    else wino_layer16(uniform_ptr(rel(pa.reloc, src)), uniform_ptr(u), a, b, cq, rq, smem, hk);
-    src = src_next;
-    u = u_next;
+    else wino_layer16(uniform_ptr(rel(pa.reloc, cur.src)), uniform_ptr(cur.u), a, b, cq, rq, smem, hk);
+    cur.next();
   }
   if (__hip_atomic_load(pa.xcc_of + gridDim.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {   // (uniform) some wait gave up
     for (int l = 0; l < n_layers; ++l) {

@@ -132,6 +132,7 @@ struct ConvRecorder {
   int count, capacity;
 };
 extern thread_local ConvRecorder* g_conv_recorder;
+constexpr int kDoneStride = 64;   // words between the per-sample flag lines of the trajectory walks (a 256-byte line each)
 int launch_wino_persist(const ConvArgs* table_dev, int n_layers, int batch, unsigned* done, unsigned* xcc_of, unsigned* host_err_dev,
                         float* out_nchw, int grid, hipStream_t stream, bool wide = false,  // wide: the table has 128-channel layers
                         bool adaptive = false, const int* n_layers_ptr = nullptr,           // adaptive: wino_persist_d_kernel (order-1

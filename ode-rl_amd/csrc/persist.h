@@ -7,9 +7,8 @@
 
 namespace odehip {
 
-constexpr int kPersistDoneStride = 64;  // words between per-sample flag lines (= kDoneStride in conv_wino.hip)
 constexpr int kPersistGrid = 256;       // the persistent kernel holds every CU of an MI355X (one workgroup each)
-inline size_t persist_sync_bytes(int batch) { return ((size_t)batch * kPersistDoneStride + kPersistGrid + 64) * 4; }
+inline size_t persist_sync_bytes(int batch) { return ((size_t)batch * kDoneStride + kPersistGrid + 64) * 4; }
 
 // Records the conv launches of a driver between begin() and finish(); finish() runs them as one persistent launch, or replays
 // them one by one when the persistent path is unavailable.  Nothing but launch_conv calls may be enqueued in between.

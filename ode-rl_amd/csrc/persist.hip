@@ -369,16 +369,16 @@ int PersistScope::finish(const float* hbuf, const float* hdev, float* out_nchw, 
     }
     if (table) {
       if (!sync_is_zero) ODEHIP_CHECK_HIP(hipMemsetAsync(sync, 0, persist_sync_bytes(batch), stream));
-      if (small16) rc = launch_wino_persist16(table, rec_.count, batch, sync, sync + (size_t)batch * kPersistDoneStride, g_persist.host_err_dev, out_nchw, stream,
+      if (small16) rc = launch_wino_persist16(table, rec_.count, batch, sync, sync + (size_t)batch * kDoneStride, g_persist.host_err_dev, out_nchw, stream,
                                               rows_dev_, reloc_dev_);
       else
-      rc = launch_wino_persist(table, rec_.count, batch, sync, sync + (size_t)batch * kPersistDoneStride, g_persist.host_err_dev, out_nchw,
+      rc = launch_wino_persist(table, rec_.count, batch, sync, sync + (size_t)batch * kDoneStride, g_persist.host_err_dev, out_nchw,
                                kPersistGrid, stream, wide, adaptive, rows_dev_, reloc_dev_);
       if (volatile_) persist_table_async_done(stream);
       if (rc == ODEHIP_OK) {
         ++g_persist.launches;
         launched_ = true;
-        abort_word_ = sync + (size_t)batch * kPersistDoneStride + kPersistGrid;   // xcc_of[grid]: zeroed above, epoch 0 => tag 1
+        abort_word_ = sync + (size_t)batch * kDoneStride + kPersistGrid;   // xcc_of[grid]: zeroed above; a wait that gives up stores 1
         table_ = table;
         table_rows_ = rec_.count;
         table_wide_ = wide;
@@ -408,9 +408,9 @@ int PersistScope::relaunch(int batch, unsigned* sync, hipStream_t stream, bool s
   ODEHIP_REQUIRE(launched_ && table_ && !volatile_, "persistent relaunch without a table");
   if (!sync_is_zero) ODEHIP_CHECK_HIP(hipMemsetAsync(sync, 0, persist_sync_bytes(batch), stream));
   const int rc = table_small16_
-                     ? launch_wino_persist16(table_, table_rows_, batch, sync, sync + (size_t)batch * kPersistDoneStride, g_persist.host_err_dev, nullptr,
+                     ? launch_wino_persist16(table_, table_rows_, batch, sync, sync + (size_t)batch * kDoneStride, g_persist.host_err_dev, nullptr,
                                              stream, rows_dev_, reloc_dev_)
-                     : launch_wino_persist(table_, table_rows_, batch, sync, sync + (size_t)batch * kPersistDoneStride, g_persist.host_err_dev, nullptr,
+                     : launch_wino_persist(table_, table_rows_, batch, sync, sync + (size_t)batch * kDoneStride, g_persist.host_err_dev, nullptr,
                                            kPersistGrid, stream, table_wide_, table_adaptive_, rows_dev_, reloc_dev_);
   if (rc == ODEHIP_OK) ++g_persist.launches;
   return rc;

@@ -19,6 +19,7 @@ SED[wgrad_wino_at]='s/\*(f32x4\*)(wr + (4 \* i + 2) \* kW2Plane) = t\[i\]\[0\] -
 # ---- round 3: the adaptive walk, the device-driven adjoint, the saving forward, the 16-workgroup walk
 SED[adapt_combine_ccur]='s/      d_cA = m.c1\[np\];/      d_cA = m.c1[np] * 1.01f;/'                                  # adaptive walk: weight of the stage's own k in an order-1 combine
 SED[adapt_ew_coef]='s/    const float c1 = (m.c_dev ? ((ConstF\*)m.c_dev)\[j\] : m.c1\[j\]) \* hs;/    const float c1 = (m.c_dev ? ((ConstF*)m.c_dev)[j] : m.c1[j]) * hs * 1.01f;/'   # elementwise rows of the walk
+SED[walk16_ew_coef]='s/      s1 = fma4(kv, (m.c_dev ? ((ConstF\*)m.c_dev)\[j\] : m.c1\[j\]) \* hs, s1);/      s1 = fma4(kv, (m.c_dev ? ((ConstF*)m.c_dev)[j] : m.c1[j]) * hs * 1.01f, s1);/'   # ... and their sixteen-workgroup copy (ew_row16)
 SED[adjoint_dense_weight]='s/  const double C2 = d7 - 4.0 \* d1 - 5.0 \* b + 16.0 \* m;\n  return x \* d1/XX/;s/^__device__ double adj_dense_weight(const AdjCtl\* st, int s, double x) {  \/\/ dp5::dense_weight/__device__ double adj_dense_weight(const AdjCtl* st, int s, double x) { x *= 0.97;/'   # device controller: dense-output weights evaluated at the wrong point
 SED[walk16_out_transform]='s/      val = pk_sub(pk_sub(\*(const f32x4\*)(x + 1024) + bias4, \*(const f32x4\*)(x + 2048)), \*(const f32x4\*)(x + 3072));/      val = pk_sub(pk_sub(*(const f32x4*)(x + 1024) + bias4, *(const f32x4*)(x + 3072)), *(const f32x4*)(x + 2048)) * 1.001f;/'   # 16-workgroup walk: second half of the output transform
 SED[saving_slot_offset]='s/  fa.off_y1 = (long long)(6 \* BL.st);/  fa.off_y1 = (long long)(5 * BL.st);/'                # saving forward: y1 read from the wrong stage input of the slot
