@@ -566,6 +566,41 @@ int odehip_mmnist_render(const double* init, const int* digit_ids, const unsigne
 int odehip_frame_metrics(const float* pred, const float* truth, int batch, int n_frames, int channels, int height, int width,
                          float data_range, float* sse, float* ssim, float* mse, float* psnr, float* ssim_t, void* stream);
 
+/* z0 ~ N(mean_z0, std_z0) by the reparameterisation trick and its KL term against N(0, 1) (latent_sample.hip): the `opt.z_sample`
+ * mode the reference declares in configs.yaml and leaves at a TODO (models/ODEConvGRU.py:72-77; the objective is named in
+ * models/ConvGRU.py:285-290).  ONE launch each, enqueue-only on `stream`, caller-provided memory only, arguments checked before any
+ * HIP call (ODEHIP_EINVAL).  Pure additions: ODEHIP_ABI_VERSION stays.
+ * mean, std: (batch, channels, 16, 16) fp32 NCHW, channels % 4 == 0; n_samples = K >= 1.
+ *   z0       (K * batch, channels, 16, 16), sample-major: row k * batch + b = fma(std[b], eps[k][b], mean[b])
+ *   kl       NULL or (batch): kl[b] = sum_{c,h,w} 0.5 (mean^2 + std^2 - 1) - log std, i.e. torch.distributions.kl_divergence(
+ *            Normal(mean, std), Normal(0, 1)) summed per sample; every term and the sum in float64, rounded to fp32 once, fixed order,
+ *            no atomics (two calls are bitwise equal).  No clamp: std == 0 gives +inf, a NaN stays a NaN (in its own sample only).
+ *   eps_out  NULL or z0's shape: the noise that was used.
+ * Noise.  eps_in != NULL (z0's shape): the caller's noise, the generator is not run.  Otherwise a counter-based stream: the element
+ * quad q = ((k * global_batch + batch_offset + b) * channels + c) * 64 + pixel / 4 (pixel = h * 16 + w) of the GLOBAL noise tensor
+ * (K, global_batch, channels, 16, 16) is
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter = (q lo, q hi, offset lo, offset hi), key = (seed lo, seed hi))   [Random123 constants]
+ *   u(w)             = ((w >> 9) + 0.5) * 2^-23            in (0, 1), 24 significant bits: exact in fp32
+ *   r_i              = sqrt(-2 ln u(w_2i)),  i = 0, 1      at most sqrt(48 ln 2) = 5.77
+ *   eps[4 pixels]    = (r_0 cos(2 pi u(w1)), r_0 sin(2 pi u(w1)), r_1 cos(2 pi u(w3)), r_1 sin(2 pi u(w3)))
+ * evaluated in fp32 (logf, sqrtf, sincospif of the exact 2 u).  batch_offset = the first global sample of this shard, global_batch
+ * the size of the whole batch (batch_offset + batch <= global_batch; one device: 0 and batch).  The draw depends on nothing else --
+ * not on the launch geometry, not on the shard: a shard gets the rows of the full draw bit for bit.  `offset` separates the draws of
+ * one seed (the Python binding advances it by one per call).
+ *
+ * odehip_latent_sample_backward: grad_z0 (K * batch, channels, 16, 16); grad_kl NULL (no KL term) or (batch); the forward's mean, std,
+ * K and noise arguments (eps is regenerated from the counter: nothing is stored between forward and backward).  Out:
+ *   grad_mean[b] = sum_k grad_z0[k][b]             + grad_kl[b] mean[b]
+ *   grad_std[b]  = sum_k grad_z0[k][b] eps[k][b]   + grad_kl[b] (std[b] - 1 / std[b])
+ * k in ascending order with explicit fmas: the regenerated-noise call and the eps_in = eps_out call are bitwise equal.  The |.| behind
+ * std_z0 belongs to the encoder's backward (odehip_odeconvgru_encode_backward: grad_std), not to this call. */
+int odehip_latent_sample(const float* mean, const float* std, int batch, int channels, int height, int width, int n_samples,
+                         uint64_t seed, uint64_t offset, int batch_offset, int global_batch, const float* eps_in, float* z0, float* kl,
+                         float* eps_out, void* stream);
+int odehip_latent_sample_backward(const float* grad_z0, const float* grad_kl, const float* mean, const float* std, int batch,
+                                  int channels, int height, int width, int n_samples, uint64_t seed, uint64_t offset, int batch_offset,
+                                  int global_batch, const float* eps_in, float* grad_mean, float* grad_std, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,10 @@ SIGNATURES = {
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p]),
     "odehip_frame_metrics": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 5 + [ctypes.c_float] + [ctypes.c_void_p] * 6),
+    "odehip_latent_sample": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 5 + [ctypes.c_uint64] * 2 + [ctypes.c_int] * 2 +
+                             [ctypes.c_void_p] * 5),
+    "odehip_latent_sample_backward": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_uint64] * 2 + [ctypes.c_int] * 2 +
+                                      [ctypes.c_void_p] * 4),
     "odehip_fused_bf16_weight_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "odehip_pack_convstack_fused_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "odehip_pack_conv_weight_bf16_ks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,

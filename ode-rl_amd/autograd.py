@@ -365,3 +365,110 @@ def odeint_with_grad(func, y0, t, rtol, atol, method, options=None):
     if method in FIXED_GRID:
         return _FixedGridOdeint.apply(y0, th, method, stack, *params)
     return _Dopri5Odeint.apply(y0, th, dopri5_cfg(rtol, atol, options), stack, *params)
+
+
+class _SampleZ0Fn(torch.autograd.Function):
+    """z0 ~ N(mean, std) by the reparameterisation trick, and KL(N(mean, std) || N(0, 1)) per batch row (csrc/latent_sample.hip).  Keeps
+    mean, std and either the caller's eps or the four integers of the counter-based draw: the backward regenerates the noise."""
+
+    @staticmethod
+    def forward(ctx, mean, std, n_samples, eps, noise, want_kl):
+        seed, offset, batch_offset, global_batch = noise
+        z0, kl, _ = hip_ops.latent_sample(mean, std, n_samples, seed, offset, batch_offset, global_batch, eps_in=eps, want_kl=want_kl)
+        ctx.n_samples, ctx.noise, ctx.has_eps = n_samples, noise, eps is not None
+        ctx.set_materialize_grads(False)   # an unused kl arrives as None, not as zeros: no KL term in the backward then
+        ctx.save_for_backward(mean, std, *([eps] if eps is not None else []))   # unpacking them checks their versions
+        return z0, kl
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_z0, grad_kl):
+        mean, std = ctx.saved_tensors[:2]
+        eps = ctx.saved_tensors[2] if ctx.has_eps else None
+        if grad_z0 is None:   # only the KL term was used
+            grad_z0 = torch.zeros((ctx.n_samples * mean.shape[0],) + tuple(mean.shape[1:]), dtype=mean.dtype, device=mean.device)
+        seed, offset, batch_offset, global_batch = ctx.noise
+        gm, gs = hip_ops.latent_sample_backward(grad_z0, grad_kl, mean, std, ctx.n_samples, seed, offset, batch_offset, global_batch, eps_in=eps)
+        return gm, gs, None, None, None, None
+
+
+_explicit_seed = [None, 0]   # the last seed a caller passed to sample_z0 and the offset its next call takes
+_noise_shard = None          # (batch_offset, global_batch) under batch sharding (dist.set_noise_shard), None on one device
+_last_draw = None            # what last_z0_noise() regenerates from
+
+
+def set_noise_shard(batch_offset=None, global_batch=None):
+    """Place this process's batch rows in a global batch for the noise of sample_z0 (dist.set_noise_shard calls this with the
+    shard's bounds); no arguments: back to one device.  Returns the previous setting."""
+    global _noise_shard
+    was = _noise_shard
+    if batch_offset is None and global_batch is None:
+        _noise_shard = None
+        return was
+    batch_offset, global_batch = int(batch_offset), int(global_batch)
+    if not 0 <= batch_offset < global_batch:
+        raise ValueError(f"set_noise_shard: batch_offset {batch_offset} does not lie in a global batch of {global_batch}")
+    _noise_shard = (batch_offset, global_batch)
+    return was
+
+
+def _next_noise_position(seed, device):
+    """(seed, offset) of this call.  seed None: the default CUDA generator's initial_seed(), and the offset lives IN that generator
+    (its Philox offset in units of 4, advanced by one unit here): torch.manual_seed(s) restarts the sequence, torch.cuda.get_rng_state
+    checkpoints the position.  An explicit seed: the library counts the calls and restarts when the seed changes."""
+    if seed is None:
+        gen = torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()]
+        at = gen.get_offset()
+        gen.set_offset(at + 4)
+        return gen.initial_seed() & 0xFFFFFFFFFFFFFFFF, at // 4
+    if _explicit_seed[0] != seed:
+        _explicit_seed[:] = [seed, 0]
+    offset = _explicit_seed[1]
+    _explicit_seed[1] = offset + 1
+    return seed, offset
+
+
+def sample_z0(mean, std, n_samples=1, eps=None, seed=None, return_kl=True):
+    """z0 ~ N(mean, std) and its KL term, on the device in one launch each way (csrc/latent_sample.hip).
+
+    mean, std: (B, C, 16, 16) float32 device tensors, C % 4 == 0 (the encoder head's mean_z0, std_z0).  Returns (z0, kl):
+      z0 (n_samples * B, C, 16, 16), sample-major -- row k * B + b is mean[b] + std[b] * eps[k, b] -- ready for the solver;
+      kl (B,) = sum over (C, 16, 16) of KL(N(mean, std) || N(0, 1)), or None with return_kl=False.  No clamp: std == 0 gives +inf.
+    Differentiable with respect to mean and std (once).  Noise: `eps` (z0's shape), the caller's own, or the counter-based stream of
+    include/odecgru_hip.h with (seed, offset): seed=None takes the default CUDA generator's seed, so torch.manual_seed(s) makes a run
+    reproducible; every call advances the offset by one (see _next_noise_position).  Under batch sharding (dist.set_noise_shard) a
+    rank draws the rows the full batch would have drawn.  Arguments are checked before tensors; there is no CPU fallback."""
+    global _last_draw
+    if isinstance(n_samples, bool) or not isinstance(n_samples, int) or not 1 <= n_samples <= 65535:
+        raise ValueError(f"sample_z0: n_samples must be an int in [1, 65535], got {n_samples!r}")
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64):
+        raise ValueError(f"sample_z0: seed must be None or an int in [0, 2**64), got {seed!r}")
+    if eps is not None and seed is not None:
+        raise ValueError("sample_z0: eps brings its own noise; a seed with it would be ignored")
+    b, c = hip_ops._check_latent_pair(mean, std, "sample_z0")
+    if eps is not None:
+        eps = hip_ops._check_noise_rows(eps, "eps", n_samples * b, c, mean, "sample_z0")
+        noise = (0, 0, 0, b)
+    else:
+        batch_offset, global_batch = _noise_shard if _noise_shard is not None else (0, b)
+        if batch_offset + b > global_batch:
+            raise ValueError(f"sample_z0: rows [{batch_offset}, {batch_offset + b}) exceed the global batch of {global_batch} (set_noise_shard)")
+        noise = _next_noise_position(seed, mean.device) + (batch_offset, global_batch)
+    _last_draw = (eps, noise, n_samples, b, c, mean.device)
+    want_kl = bool(return_kl)
+    if torch.is_grad_enabled() and (mean.requires_grad or std.requires_grad):
+        return _SampleZ0Fn.apply(mean, std, n_samples, eps, noise, want_kl)
+    z0, kl, _ = hip_ops.latent_sample(mean, std, n_samples, *noise, eps_in=eps, want_kl=want_kl)
+    return z0, kl
+
+
+def last_z0_noise():
+    """The noise of the most recent sample_z0 call, (n_samples * B, C, 16, 16): the caller's eps, or the stream regenerated from
+    the call's (seed, offset, batch_offset, global_batch) through `eps_out` -- nothing was stored."""
+    if _last_draw is None:
+        raise RuntimeError("last_z0_noise: sample_z0 has not been called")
+    eps, noise, n_samples, b, c, device = _last_draw
+    if eps is not None:
+        return eps
+    zero = torch.zeros((b, c, 16, 16), dtype=torch.float32, device=device)
+    return hip_ops.latent_sample(zero, zero, n_samples, *noise, want_kl=False, want_eps=True)[2]

@@ -29,6 +29,24 @@ def shard_batch(x, rank=None, world=None, dim=0):
     return x.narrow(dim, lo, hi - lo)
 
 
+def set_noise_shard(global_batch, rank=None, world=None):
+    """Tell `ode_rl_amd.sample_z0` which rows of a global batch of `global_batch` this rank holds (its shard_bounds): the noise is
+    indexed by the GLOBAL sample, so ranks draw different noise and the sharded step sees exactly the noise of the full-batch step
+    (every rank seeds alike and calls sample_z0 equally often).  Returns (batch_offset, global_batch)."""
+    from . import autograd
+    rank = dist.get_rank() if rank is None else rank
+    world = dist.get_world_size() if world is None else world
+    lo, _ = shard_bounds(global_batch, rank, world)
+    autograd.set_noise_shard(lo, global_batch)
+    return lo, global_batch
+
+
+def clear_noise_shard():
+    """Back to one device: sample_z0 draws for its own batch alone."""
+    from . import autograd
+    autograd.set_noise_shard()
+
+
 def allreduce_gradients(params, group=None, average=True):
     """ONE all-reduce over one flattened bucket of every .grad (missing grads count as zeros so that every rank sends
     the same layout).  Returns the number of elements reduced."""

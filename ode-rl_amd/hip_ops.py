@@ -1472,3 +1472,62 @@ def frame_decode_autograd(seq, latents, apply_sigmoid):
         raise ValueError("frame_decode_autograd: one frame channel and 32 / 64 latent channels only")
     c1, c2, _ = _codec_layers(seq, torch.nn.ConvTranspose2d, 4, 32)
     return _FrameDecodeFn.apply(seq, latents, apply_sigmoid, c1.weight, c1.bias, c2.weight, c2.bias)
+
+
+def _check_latent_pair(mean, std, who):
+    """mean, std: (B, C, 16, 16) float32 device tensors, C % 4 == 0 (what the solver takes as z0) -> (B, C)."""
+    require_device_tensor(mean, "mean")
+    require_device_tensor(std, "std")
+    if mean.dim() != 4 or tuple(mean.shape[2:]) != (16, 16) or mean.shape[0] < 1 or mean.shape[1] < 4 or mean.shape[1] % 4:
+        raise ValueError(f"{who}: mean must be (B, C, 16, 16) with C % 4 == 0, got {tuple(mean.shape)}")
+    if std.shape != mean.shape or std.device != mean.device:
+        raise ValueError(f"{who}: std must have mean's shape and device, got {tuple(std.shape)} on {std.device} for {tuple(mean.shape)} "
+                         f"on {mean.device}")
+    return mean.shape[0], mean.shape[1]
+
+
+def _check_noise_rows(t, name, rows, ch, like, who):
+    require_device_tensor(t, name)
+    if tuple(t.shape) != (rows, ch, 16, 16) or t.device != like.device:
+        raise ValueError(f"{who}: {name} must be ({rows}, {ch}, 16, 16) on {like.device}, got {tuple(t.shape)} on {t.device}")
+    return t.detach().contiguous()
+
+
+def latent_sample(mean, std, n_samples=1, seed=0, offset=0, batch_offset=0, global_batch=None, eps_in=None, want_kl=True, want_eps=False):
+    """z0 = mean + std * eps for n_samples draws per batch row, and KL(N(mean, std) || N(0, 1)) per row, in ONE launch
+    (csrc/latent_sample.hip).  Returns (z0 (K * B, C, 16, 16) sample-major, kl (B,) or None, eps (z0's shape) or None).  The noise is
+    the counter-based stream of include/odecgru_hip.h (seed, offset; batch_offset / global_batch place this shard in the full batch)
+    unless eps_in (z0's shape) brings the caller's own."""
+    b, c = _check_latent_pair(mean, std, "latent_sample")
+    k = int(n_samples)
+    mean, std = mean.detach().contiguous(), std.detach().contiguous()
+    if eps_in is not None:
+        eps_in = _check_noise_rows(eps_in, "eps_in", k * b, c, mean, "latent_sample")
+    z0 = torch.empty((k * b, c, 16, 16), dtype=torch.float32, device=mean.device)
+    kl = torch.empty(b, dtype=torch.float32, device=mean.device) if want_kl else None
+    eps = torch.empty_like(z0) if want_eps else None
+    _lib.check(_lib.load().odehip_latent_sample(_ptr(mean), _ptr(std), b, c, 16, 16, k, int(seed), int(offset), int(batch_offset),
+                                                b if global_batch is None else int(global_batch), _ptr(eps_in), _ptr(z0), _ptr(kl),
+                                                _ptr(eps), _stream()))
+    return z0, kl, eps
+
+
+def latent_sample_backward(grad_z0, grad_kl, mean, std, n_samples=1, seed=0, offset=0, batch_offset=0, global_batch=None, eps_in=None):
+    """(grad_mean, grad_std) of latent_sample from grad_z0 (K * B, C, 16, 16) and grad_kl ((B,) or None: no KL term), ONE launch; the
+    noise is regenerated from the forward's (seed, offset, batch_offset, global_batch), or read from eps_in."""
+    b, c = _check_latent_pair(mean, std, "latent_sample_backward")
+    k = int(n_samples)
+    mean, std = mean.detach().contiguous(), std.detach().contiguous()
+    grad_z0 = _check_noise_rows(grad_z0, "grad_z0", k * b, c, mean, "latent_sample_backward")
+    if eps_in is not None:
+        eps_in = _check_noise_rows(eps_in, "eps_in", k * b, c, mean, "latent_sample_backward")
+    if grad_kl is not None:
+        require_device_tensor(grad_kl, "grad_kl")
+        if tuple(grad_kl.shape) != (b,) or grad_kl.device != mean.device:
+            raise ValueError(f"latent_sample_backward: grad_kl must be ({b},) on {mean.device}, got {tuple(grad_kl.shape)} on {grad_kl.device}")
+        grad_kl = grad_kl.detach().contiguous()
+    grad_mean, grad_std = torch.empty_like(mean), torch.empty_like(std)
+    _lib.check(_lib.load().odehip_latent_sample_backward(_ptr(grad_z0), _ptr(grad_kl), _ptr(mean), _ptr(std), b, c, 16, 16, k, int(seed),
+                                                         int(offset), int(batch_offset), b if global_batch is None else int(global_batch),
+                                                         _ptr(eps_in), _ptr(grad_mean), _ptr(grad_std), _stream()))
+    return grad_mean, grad_std

@@ -7,7 +7,10 @@ The strided encoder / transposed-conv decoder either side of the path (SURVEY.md
 frame channel, 32 / 64 latent channels); for other shapes under autograd, and for structures other than the reference's
 n_downs = 2, they are library calls (MIOpen through torch).  Same module names so the reference's state_dict
 loads, including the aliased keys (`diffeq_solver.ode_func.*` == `ode_decoder_func.*`, `ode_convgru_cell.ode_func.*` ==
-`ode_encoder_func.*`)."""
+`ode_encoder_func.*`).
+
+`opt.z_sample` (a defaults key of the reference's configs.yaml; its models/ODEConvGRU.py:72-77 stops at "TODO: reparametrization
+trick") is finished here as the variational model the encoder's `std_z0` output exists for; see the ODEConvGRU docstring."""
 import torch
 import torch.nn as nn
 
@@ -92,9 +95,23 @@ class Decoder(nn.Module):
 
 
 class ODEConvGRU(nn.Module):
+    """The reference's ODEConvGRU.  With `opt.z_sample` False or absent: z0 = mean_z0, the loss is the MSE -- bit for bit what the
+    model computed before the switch existed.
+
+    With `opt.z_sample` True (definitions of this project; the reference leaves the mode at a TODO):
+      train()  z0 ~ N(mean_z0, std_z0) by the reparameterisation trick, `opt.z_n_samples` (default 1) draws per batch row
+               (`ode_rl_amd.sample_z0`: one launch).  Solver and decoder run on the K * B rows; `forward` returns
+               (K * B, T, c, 64, 64), sample-major.  `get_loss` repeats `truth` over K and adds the KL term of the ELBO,
+                   loss = MSE + opt.kl_weight (default 1.0) * mean_b KL(N(mean_z0, std_z0) || N(0, 1)) / (C * 16 * 16)
+               i.e. the KL per latent element averaged over the batch.  `last_loss_terms` = {"mse", "kl"} holds the two terms of the
+               last call as device tensors (the KL already per element, before the weight).
+      eval()   z0 = mean_z0, deterministic; `get_loss` is the MSE: `evaluate` and `test_batch` work unchanged."""
+
     def __init__(self, opt, device):
         super().__init__()
         self.opt, self.device = opt, device
+        self.last_loss_terms = None
+        self._kl = None   # (kl (B,), latent elements per row) of the last sampled forward, consumed by get_loss
         self.resize = 2 ** opt.n_downs
         res = (opt.resolution // self.resize, opt.resolution // self.resize)
         ch = opt.conv_encoder_out_ch
@@ -112,8 +129,15 @@ class ODEConvGRU(nn.Module):
         b, t, c, h, w = inputs.size()
         observed_tp, tp_to_predict = batch_dict['observed_tp'], batch_dict['tp_to_predict']
         enc = self.conv_encoder.encode_time_first(inputs)  # time first
-        first_point_mu, _ = self.ode_convgru_cell(enc, observed_tp)
-        sol_y = self.diffeq_solver(first_point_mu, tp_to_predict)  # (T,B,C,H,W)
+        first_point_mu, first_point_std = self.ode_convgru_cell(enc, observed_tp)
+        self._kl = None
+        if getattr(self.opt, "z_sample", False) and self.training:
+            from ..autograd import sample_z0
+            z0, kl = sample_z0(first_point_mu, first_point_std, n_samples=getattr(self.opt, "z_n_samples", 1))
+            self._kl = (kl, first_point_mu[0].numel())
+        else:
+            z0 = first_point_mu
+        sol_y = self.diffeq_solver(z0, tp_to_predict)  # (T,B,C,H,W)
         return self.conv_decoder.decode_sigmoid(sol_y).permute(1, 0, 2, 3, 4)
 
     def get_prediction(self, inputs, batch_dict=None):
@@ -121,4 +145,13 @@ class ODEConvGRU(nn.Module):
 
     def get_loss(self, pred_frames, truth, loss='MSE'):
         b, t, c, h, w = truth.size()
-        return nn.functional.mse_loss(pred_frames.reshape(b * t, c, h, w), truth.reshape(b * t, c, h, w))
+        if self._kl is None:
+            return nn.functional.mse_loss(pred_frames.reshape(b * t, c, h, w), truth.reshape(b * t, c, h, w))
+        (kl, per_row), self._kl = self._kl, None
+        n = pred_frames.shape[0] // b   # the K draws of the forward pass, sample-major
+        if n > 1:
+            truth = truth.repeat(n, 1, 1, 1, 1)
+        mse = nn.functional.mse_loss(pred_frames.reshape(n * b * t, c, h, w), truth.reshape(n * b * t, c, h, w))
+        kl_term = kl.mean() / per_row
+        self.last_loss_terms = {"mse": mse.detach(), "kl": kl_term.detach()}
+        return mse + getattr(self.opt, "kl_weight", 1.0) * kl_term

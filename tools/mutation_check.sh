@@ -52,7 +52,13 @@ SED[seq_state_half_from_frame_half]='s/    else rc = seq_conv(c, hv, true, 1, h,
 SED[seq_first_step_reads_h0]='s/    const bool has_h = h0 || t > 0;/    const bool has_h = true;/'   # zero state: the first step reads the (unwritten) state slot
 SED[seq_wgrad_drops_step]='s/      const int n_eval = half == 0 ? T : n_state, a_ch = half == 0 ? I : H;/      const int n_eval = (half == 0 ? T : n_state) - 1, a_ch = half == 0 ? I : H;/'   # batched weight gradient: the last step is left out
 SED[seq_slot_off_by_one]='s/    float\* slot = h_seq + (size_t)t \* batch \* H \* kPix;/    float* slot = h_seq + (size_t)(t > 0 ? t - 1 : 0) * batch * H * kPix;/'   # h_seq[t] written to slot t - 1
-TESTS="tests/test_hip_convgru_sequence.py::test_rollout_forward_against_the_float64_restatement[False-True-10-4-64] tests/test_hip_convgru_sequence.py::test_bptt_against_float64_autograd[False-True-10-4] tests/test_hip_convgru_sequence.py::test_bptt_against_float64_autograd[True-False-10-4] tests/test_hip_convgru_sequence.py::test_a_zero_state_reads_nothing_of_the_state_buffers tests/test_hip_convgru_sequence.py::test_rollout_agrees_with_the_step_by_step_forward[False-True-10-4] tests/test_hip_backward.py::test_backward_strict_on_kink_free_dynamics tests/test_hip_frame_codec.py::test_encoder_matches_reference_fixture tests/test_hip_frame_codec.py::test_decoder_matches_reference_fixture tests/test_hip_conv.py::test_winograd5_conv_matches_torch tests/test_hip_full_size.py::test_cell_and_encoder_full_channels tests/test_hip_odeint.py::test_fixed_grid_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_dopri5_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_fixed_grid_matches_golden_and_oracle tests/test_hip_odeint.py::test_full_size_against_oracle tests/test_hip_backward.py::test_dopri5_backward_matches_autograd_through_oracle tests/test_hip_backward.py::test_dopri5_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_dopri5_saving_forward_equals_reintegration tests/test_hip_reference_configs.py::test_config0_as_stated_b4 tests/test_hip_encoder_backward.py::test_convgru_cell_backward_matches_autograd_through_oracle tests/test_hip_frame_codec.py::test_backward_matches_fp64_autograd tests/test_hip_vidode.py::test_upsample2x_matches_torch tests/test_hip_vidode.py::test_bn_relu_up_matches_torch tests/test_hip_backward.py::test_async_dopri5_forward_matches_the_synchronous_one tests/test_hip_errors.py::test_a_non_finite_state_is_not_laundered tests/test_hip_errors.py::test_a_lost_partner_in_a_single_evaluation_walk_is_loud tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[max_num_steps-no_grad] tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[overflow-saving] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[euler-3-per_layer] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[rk4-20-persistent] tests/test_hip_relu_nan_backward.py::test_bf16_backward_passes_the_gradient_of_a_nan_channel tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-True-True-x] tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-False-False-gamma] tests/test_hip_frame_metrics.py::test_matches_the_fp64_restatement[3-5-3] tests/test_hip_frame_metrics.py::test_matches_the_fp64_restatement[64-10-1] tests/test_hip_frame_metrics.py::test_evaluate_end_to_end"
+# ---- sampled z0 (latent_sample.hip and its binding): the KL term, the sign of the noise in grad_std, the offset of consecutive draws
+SED[kl_drops_log_sigma]='s/        acc += 0.5 \* (md \* md + sd \* sd - 1.0) - log(sd);/        acc += 0.5 * (md * md + sd * sd - 1.0);/'   # kl = sum 0.5 (mu^2 + sigma^2 - 1), no - log sigma
+SED[grad_std_eps_sign]='s/      gs\[i\] = k ? fmaf(g\[i\], e\[i\], gs\[i\]) : g\[i\] \* e\[i\];/      gs[i] = k ? fmaf(g[i], -e[i], gs[i]) : g[i] * -e[i];/'   # grad_std = - sum_k g eps
+# mutants of the Python binding, "file|sed script": applied to the tree's own file for the run and restored afterwards (run only)
+declare -A PYSED
+PYSED[z0_offset_stuck]='ode-rl_amd/autograd.py|s/gen.set_offset(at + 4)/gen.set_offset(at)/;s/_explicit_seed\[1\] = offset + 1/_explicit_seed[1] = offset/'   # consecutive sample_z0 calls draw the same noise
+TESTS="tests/test_hip_latent_sample.py tests/test_hip_convgru_sequence.py::test_rollout_forward_against_the_float64_restatement[False-True-10-4-64] tests/test_hip_convgru_sequence.py::test_bptt_against_float64_autograd[False-True-10-4] tests/test_hip_convgru_sequence.py::test_bptt_against_float64_autograd[True-False-10-4] tests/test_hip_convgru_sequence.py::test_a_zero_state_reads_nothing_of_the_state_buffers tests/test_hip_convgru_sequence.py::test_rollout_agrees_with_the_step_by_step_forward[False-True-10-4] tests/test_hip_backward.py::test_backward_strict_on_kink_free_dynamics tests/test_hip_frame_codec.py::test_encoder_matches_reference_fixture tests/test_hip_frame_codec.py::test_decoder_matches_reference_fixture tests/test_hip_conv.py::test_winograd5_conv_matches_torch tests/test_hip_full_size.py::test_cell_and_encoder_full_channels tests/test_hip_odeint.py::test_fixed_grid_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_dopri5_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_fixed_grid_matches_golden_and_oracle tests/test_hip_odeint.py::test_full_size_against_oracle tests/test_hip_backward.py::test_dopri5_backward_matches_autograd_through_oracle tests/test_hip_backward.py::test_dopri5_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_dopri5_saving_forward_equals_reintegration tests/test_hip_reference_configs.py::test_config0_as_stated_b4 tests/test_hip_encoder_backward.py::test_convgru_cell_backward_matches_autograd_through_oracle tests/test_hip_frame_codec.py::test_backward_matches_fp64_autograd tests/test_hip_vidode.py::test_upsample2x_matches_torch tests/test_hip_vidode.py::test_bn_relu_up_matches_torch tests/test_hip_backward.py::test_async_dopri5_forward_matches_the_synchronous_one tests/test_hip_errors.py::test_a_non_finite_state_is_not_laundered tests/test_hip_errors.py::test_a_lost_partner_in_a_single_evaluation_walk_is_loud tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[max_num_steps-no_grad] tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[overflow-saving] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[euler-3-per_layer] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[rk4-20-persistent] tests/test_hip_relu_nan_backward.py::test_bf16_backward_passes_the_gradient_of_a_nan_channel tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-True-True-x] tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-False-False-gamma] tests/test_hip_frame_metrics.py::test_matches_the_fp64_restatement[3-5-3] tests/test_hip_frame_metrics.py::test_matches_the_fp64_restatement[64-10-1] tests/test_hip_frame_metrics.py::test_evaluate_end_to_end"
 [ -n "${MUT_TESTS:-}" ] && TESTS=$MUT_TESTS   # a subset of the tests (a GPU lease is short): e.g. the files that cover the mutants of MUT_ONLY
 case "${1:-}" in
 build)
@@ -96,6 +102,19 @@ run)
     if grep -qE "is missing: build it|reports ABI version|cannot open shared object|undefined symbol|AttributeError: .*odehip_|OSError|Segmentation|core dumped" gpurun_out/mut_$m.log; then
       echo "  !! mutant $m failed for the wrong reason (library not loaded / crash): rebuild the mutants" | tee -a "$out"; bad=1
     fi
+  done
+  logs=$(dirname "$out")   # the logs go next to the summary
+  for m in "${!PYSED[@]}"; do
+    if [ -n "${MUT_ONLY:-}" ] && [[ ! " $MUT_ONLY " =~ " $m " ]]; then continue; fi
+    f=${PYSED[$m]%%|*}; script=${PYSED[$m]#*|}
+    cp -p "$f" "$logs/mut_$m.orig"
+    sed -i "$script" "$f"
+    if cmp -s "$f" "$logs/mut_$m.orig"; then echo "mutant $m: the pattern changed nothing in $f" | tee -a "$out"; bad=1; continue; fi
+    python -m pytest $TESTS -q > $logs/mut_$m.log 2>&1; rc=$?
+    cp -p "$logs/mut_$m.orig" "$f"
+    echo "mutant $m: pytest rc=$rc ($(tail -1 $logs/mut_$m.log)) failed: $(grep -c '^FAILED' $logs/mut_$m.log)" | tee -a "$out"
+    grep '^FAILED' $logs/mut_$m.log | sed 's/ - .*//' >> "$out"
+    [ $rc -eq 0 ] && { echo "  !! mutant $m SURVIVED" | tee -a "$out"; bad=1; }
   done
   exit $bad ;;
 baseline)   # the unmutated library alone (starts a fresh summary; the mutants then follow with MUT_ONLY=... run, one lease at a time)
