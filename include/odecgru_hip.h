@@ -601,6 +601,58 @@ int odehip_latent_sample_backward(const float* grad_z0, const float* grad_kl, co
                                   int channels, int height, int width, int n_samples, uint64_t seed, uint64_t offset, int batch_offset,
                                   int global_batch, const float* eps_in, float* grad_mean, float* grad_std, void* stream);
 
+/* The scalar training losses and their backward (frame_loss.hip): what models/ODEConvGRU.py, models/ConvGRU.py and models/VidODE.py
+ * compute between the forward and the backward pass, as one call each way instead of a chain of small library kernels (and, for the
+ * L1 pair, of host synchronisations).  Enqueue-only on `stream`, caller-provided memory only, arguments checked before any HIP call
+ * (ODEHIP_EINVAL: null pointers, counts below 1, misaligned pointers or strides).  Pure additions: ODEHIP_ABI_VERSION stays.
+ * Arithmetic, both kinds: every difference, square, absolute value and sum in float64 from the fp32 inputs, rounded to fp32 once; the
+ * order of every sum is a function of the sizes alone (thread partials in element order with 16-byte loads, wave xor-shuffles, wave
+ * partials in index order, workgroup partials in workgroup order; no atomics): two calls are bitwise equal, on any machine.  A NaN or
+ * Inf of an input reaches the loss by plain arithmetic.  Forward: two launches (partials into `workspace`, then a one-workgroup
+ * final); backward: one launch.  out: three floats.
+ *
+ * odehip_loss_mse: pred (n_samples * batch, row_elems) sample-major, truth (batch, row_elems), both contiguous and 16-byte aligned,
+ * row_elems % 4 == 0: element i of pred row k * batch + b pairs with element i of truth row b (the truth is not repeated in memory).
+ * kl NULL or (batch).  N = n_samples * batch * row_elems.
+ *   out[1] = mse     = sum (pred - truth)^2 / N
+ *   out[2] = kl_term = kl_scale * sum_b kl[b]           (0 with kl == NULL; the models pass kl_scale = 1 / (batch * latent elements))
+ *   out[0] = loss    = mse + kl_weight * kl_term        (mse with kl == NULL)
+ * workspace: odehip_loss_mse_workspace_bytes(n_samples, batch, row_elems) bytes, 8-byte aligned.
+ * odehip_loss_mse_backward: grad_out = one float ON THE DEVICE (d / d loss; never copied to the host).
+ *   grad_pred = fl32(pred - truth) * fl32(2 grad_out / N)       (pred's shape; a non-finite value stays in its own element)
+ *   grad_kl[b] = fl32(grad_out * kl_weight * kl_scale)          (grad_kl NULL: not written) */
+size_t odehip_loss_mse_workspace_bytes(int n_samples, int batch, long long row_elems);
+int odehip_loss_mse(const float* pred, const float* truth, int n_samples, int batch, long long row_elems, const float* kl, double kl_scale,
+                    float kl_weight, float* out, void* workspace, size_t workspace_bytes, void* stream);
+int odehip_loss_mse_backward(const float* grad_out, const float* pred, const float* truth, int n_samples, int batch, long long row_elems,
+                             double kl_scale, float kl_weight, float* grad_pred, float* grad_kl, void* stream);
+
+/* odehip_loss_vidode_l1: the L1 pair of models/VidODE.py's get_loss (reference :211-226).  frame_elems = P, a multiple of 4.
+ *   pred   (batch, n_sel, P) contiguous
+ *   inter  (batch, n_sel, P) through inter_batch_stride / inter_frame_stride in elements (multiples of 4; P contiguous elements per
+ *          frame): the channel slice [:, :, 2:2+c] of the flow decoder's (batch, n_sel, c + 3, H, W) output as it lies
+ *   truth  (batch, n_frames, P) contiguous;  init (batch, P) through init_batch_stride: the last observed frame, a view as well
+ *   mask   (batch, n_frames), non-zero = selected: float32 (mask_is_byte 0) or uint8 / bool (mask_is_byte 1)
+ * s(b, j) = the j-th selected frame of row b (each workgroup scans its mask row; no prefix tensor, no host count; selected frames
+ * behind the n_sel-th are ignored).  d(b, t) = truth[b][t] - (t > 0 ? truth[b][t - 1] : init[b]).  N = batch * n_sel * P.
+ *   out[1] = l1_pred = sum |pred[b][j] - truth[b][s(b, j)]| / N
+ *   out[2] = l1_diff = sum |inter[b][j] - d(b, s(b, j))| / N
+ *   out[0] = loss    = l1_pred + l1_diff
+ * A row that selects fewer than n_sel frames makes all three NaN; nothing is read for the frames it cannot pair.
+ * workspace: odehip_loss_vidode_l1_workspace_bytes(batch, n_sel, frame_elems) bytes, 8-byte aligned.
+ * odehip_loss_vidode_l1_backward: grad_out = one float on the device; grad_pred, grad_inter (batch, n_sel, P) contiguous:
+ *   grad_pred  = sgn(pred - truth_s) * fl32(grad_out / N),  grad_inter = sgn(inter - d) * fl32(grad_out / N)
+ * sgn as the backward of torch.abs has it: 0 at 0 and at NaN, +-1 at +-inf (the sign of the float64 difference).  The frames of a
+ * row with too few selected frames get NaN. */
+size_t odehip_loss_vidode_l1_workspace_bytes(int batch, int n_sel, int frame_elems);
+int odehip_loss_vidode_l1(const float* pred, const float* inter, long long inter_batch_stride, long long inter_frame_stride,
+                          const float* truth, const float* init, long long init_batch_stride, const void* mask, int mask_is_byte, int batch,
+                          int n_frames, int n_sel, int frame_elems, float* out, void* workspace, size_t workspace_bytes, void* stream);
+int odehip_loss_vidode_l1_backward(const float* grad_out, const float* pred, const float* inter, long long inter_batch_stride,
+                                   long long inter_frame_stride, const float* truth, const float* init, long long init_batch_stride,
+                                   const void* mask, int mask_is_byte, int batch, int n_frames, int n_sel, int frame_elems, float* grad_pred,
+                                   float* grad_inter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,16 @@ SIGNATURES = {
                              [ctypes.c_void_p] * 5),
     "odehip_latent_sample_backward": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 + [ctypes.c_uint64] * 2 + [ctypes.c_int] * 2 +
                                       [ctypes.c_void_p] * 4),
+    "odehip_loss_mse_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_longlong]),
+    "odehip_loss_mse": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_double,
+                                       ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "odehip_loss_mse_backward": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_double,
+                                                ctypes.c_float] + [ctypes.c_void_p] * 3),
+    "odehip_loss_vidode_l1_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "odehip_loss_vidode_l1": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_longlong] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_longlong,
+                                             ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "odehip_loss_vidode_l1_backward": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_longlong] * 2 + [ctypes.c_void_p] * 2 +
+                                       [ctypes.c_longlong, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3),
     "odehip_fused_bf16_weight_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "odehip_pack_convstack_fused_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "odehip_pack_conv_weight_bf16_ks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -472,3 +472,143 @@ def last_z0_noise():
         return eps
     zero = torch.zeros((b, c, 16, 16), dtype=torch.float32, device=device)
     return hip_ops.latent_sample(zero, zero, n_samples, *noise, want_kl=False, want_eps=True)[2]
+
+
+class _MseKlLossFn(torch.autograd.Function):
+    """mean (pred - truth)^2 + kl_weight * kl_scale * sum(kl) (csrc/frame_loss.hip): two launches forward, one backward.  Returns
+    (loss, mse, kl_term), three views of one device buffer; only `loss` is differentiable.  The backward reads pred, truth live."""
+
+    @staticmethod
+    def forward(ctx, pred, truth, kl, kl_weight, kl_scale):
+        hip_ops.record_versions(ctx, tuple(x for x in (pred, truth, kl) if x is not None))
+        ctx.pred, ctx.truth = pred.detach().contiguous(), truth.detach().contiguous()
+        ctx.kl_weight, ctx.kl_scale, ctx.has_kl = kl_weight, kl_scale, kl is not None
+        ctx.set_materialize_grads(False)
+        loss, mse, kl_term = hip_ops.loss_mse(ctx.pred, ctx.truth, kl, kl_weight, kl_scale).unbind(0)
+        ctx.mark_non_differentiable(mse, kl_term)
+        return loss, mse, kl_term
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, _grad_mse, _grad_kl_term):
+        if grad_loss is None:
+            return None, None, None, None, None
+        hip_ops.check_versions(ctx, "an input of mse_kl_loss")
+        grad_pred, grad_kl = hip_ops.loss_mse_backward(grad_loss, ctx.pred, ctx.truth, ctx.kl_weight, ctx.kl_scale, want_kl=ctx.has_kl)
+        ctx.pred = ctx.truth = None
+        return grad_pred, None, grad_kl, None, None
+
+
+class _VidodeL1LossFn(torch.autograd.Function):
+    """The L1 pair of models/VidODE.py's get_loss (csrc/frame_loss.hip): two launches forward, one backward, no host synchronisation.
+    Returns (loss, l1_pred, l1_diff); only `loss` is differentiable, with respect to pred and inter."""
+
+    @staticmethod
+    def forward(ctx, pred, inter, truth, init, mask):
+        hip_ops.record_versions(ctx, (pred, inter, truth, init, mask))
+        ctx.args = (pred.detach(), inter.detach(), truth.detach(), init.detach(), mask.detach())
+        ctx.set_materialize_grads(False)
+        loss, l1_pred, l1_diff = hip_ops.loss_vidode_l1(*ctx.args).unbind(0)
+        ctx.mark_non_differentiable(l1_pred, l1_diff)
+        return loss, l1_pred, l1_diff
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, _grad_l1_pred, _grad_l1_diff):
+        if grad_loss is None:
+            return None, None, None, None, None
+        hip_ops.check_versions(ctx, "an input of vidode_l1_loss")
+        grad_pred, grad_inter = hip_ops.loss_vidode_l1_backward(grad_loss, *ctx.args)
+        ctx.args = None
+        return grad_pred, grad_inter, None, None, None
+
+
+def _constants(who, **tensors):
+    for name, t in tensors.items():
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise NotImplementedError(f"{who}: {name} is treated as a constant; a gradient with respect to it is not implemented")
+
+
+def _fused_loss_ok(row_elems, *tensors):
+    """The fused path of csrc/frame_loss.hip: CUDA float32 tensors, rows of a multiple of 4 elements, ODEHIP_FUSED_LOSS not 0."""
+    return (hip_ops.fused_loss_enabled() and row_elems >= 4 and row_elems % 4 == 0 and
+            all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in tensors))
+
+
+def mse_kl_loss(pred, truth, kl=None, kl_weight=1.0, latent_elems=None):
+    """The training loss of ODEConvGRU / ConvGRU: (loss, mse, kl_term) with
+        mse = mean (pred - truth)^2,  kl_term = mean_b kl[b] / latent_elems,  loss = mse + kl_weight * kl_term.
+    pred (K * B, ...) holds K draws per truth row, sample-major: row k * B + b pairs with truth row b (B, ...); the truth is not
+    repeated in memory.  kl (B,): the KL term per batch row (`sample_z0`), latent_elems the latent elements per row; kl=None: loss =
+    mse and kl_term is None.  `loss` carries the graph (to pred and kl); mse and kl_term are detached scalars.  truth is a constant.
+    CUDA float32 tensors with a row size that is a multiple of 4: one C ABI call each way (csrc/frame_loss.hip: float64 sums in a
+    fixed order, two launches forward, one backward).  Anything else, or ODEHIP_FUSED_LOSS=0: the torch composition."""
+    if not isinstance(pred, torch.Tensor) or not isinstance(truth, torch.Tensor):
+        raise TypeError("mse_kl_loss: pred and truth must be torch.Tensors")
+    if kl is not None and not isinstance(kl, torch.Tensor):
+        raise TypeError("mse_kl_loss: kl must be a torch.Tensor or None")
+    _constants("mse_kl_loss", truth=truth)
+    if truth.dim() < 1 or pred.dim() != truth.dim() or truth.shape[0] < 1 or pred.shape[0] < 1 or pred.shape[0] % truth.shape[0] or \
+            pred.shape[1:] != truth.shape[1:]:
+        raise ValueError(f"mse_kl_loss: pred must be (K * B, ...) with truth's (B, ...) trailing shape, got {tuple(pred.shape)} for "
+                         f"{tuple(truth.shape)}")
+    b = truth.shape[0]
+    n = pred.shape[0] // b
+    if kl is not None:
+        if isinstance(latent_elems, bool) or not isinstance(latent_elems, int) or latent_elems < 1:
+            raise ValueError(f"mse_kl_loss: with kl, latent_elems must be a positive int (the latent elements per batch row), got {latent_elems!r}")
+        if tuple(kl.shape) != (b,):
+            raise ValueError(f"mse_kl_loss: kl must be ({b},), got {tuple(kl.shape)}")
+    kl_weight = float(kl_weight)
+    if _fused_loss_ok(truth[0].numel(), pred, truth, *([kl] if kl is not None else [])):
+        kl_scale = 1.0 / (b * latent_elems) if kl is not None else 0.0
+        if torch.is_grad_enabled() and (pred.requires_grad or (kl is not None and kl.requires_grad)):
+            loss, mse, kl_term = _MseKlLossFn.apply(pred, truth, kl, kl_weight, kl_scale)
+        else:
+            loss, mse, kl_term = hip_ops.loss_mse(pred, truth, kl, kl_weight, kl_scale).unbind(0)
+        return loss, mse, (kl_term if kl is not None else None)
+    if n > 1:
+        truth = truth.repeat(n, *([1] * (truth.dim() - 1)))
+    mse = torch.nn.functional.mse_loss(pred, truth)
+    if kl is None:
+        return mse, mse.detach(), None
+    kl_term = kl.mean() / latent_elems
+    return mse + kl_weight * kl_term, mse.detach(), kl_term.detach()
+
+
+def vidode_l1_loss(pred, inter, truth, init, mask):
+    """The training loss of VidODE (reference models/VidODE.py:211-226): (loss, l1_pred, l1_diff) with
+        l1_pred = mean |pred - truth[selected]|,  l1_diff = mean |inter - d[selected]|,  loss = l1_pred + l1_diff,
+    d[:, t] = truth[:, t] - truth[:, t - 1] and truth[:, -1] = init, the last observed frame.  pred, inter (B, n, c, H, W) -- inter
+    may be a channel slice --, truth (B, T, c, H, W), init (B, c, H, W), mask (B, T) or (B, T, 1): non-zero selects a frame, the first
+    n selected frames of every row count; a row with fewer makes the result NaN on the fused path (the torch composition raises).
+    `loss` carries the graph (to pred and inter); the two terms are detached scalars.  truth, init and mask are constants.
+    CUDA float32 tensors with a frame size that is a multiple of 4: one C ABI call each way, no host synchronisation
+    (csrc/frame_loss.hip).  Anything else, or ODEHIP_FUSED_LOSS=0: the torch composition (its boolean indexing synchronises)."""
+    for name, t in (("pred", pred), ("inter", inter), ("truth", truth), ("init", init), ("mask", mask)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"vidode_l1_loss: {name} must be a torch.Tensor")
+    _constants("vidode_l1_loss", truth=truth, init=init, mask=mask)
+    if pred.dim() < 3 or truth.dim() != pred.dim() or truth.shape[0] != pred.shape[0] or truth.shape[2:] != pred.shape[2:] or \
+            not 1 <= pred.shape[1] <= truth.shape[1]:
+        raise ValueError(f"vidode_l1_loss: pred must be (B, n, ...) and truth (B, T >= n, ...) with the same frames, got {tuple(pred.shape)} "
+                         f"and {tuple(truth.shape)}")
+    if inter.shape != pred.shape:
+        raise ValueError(f"vidode_l1_loss: inter must have pred's shape {tuple(pred.shape)}, got {tuple(inter.shape)}")
+    if tuple(init.shape) != (pred.shape[0],) + tuple(pred.shape[2:]):
+        raise ValueError(f"vidode_l1_loss: init must be {(pred.shape[0],) + tuple(pred.shape[2:])}, got {tuple(init.shape)}")
+    if tuple(mask.shape) not in (tuple(truth.shape[:2]), tuple(truth.shape[:2]) + (1,)):
+        raise ValueError(f"vidode_l1_loss: mask must be {tuple(truth.shape[:2])} (or with a trailing 1), got {tuple(mask.shape)}")
+    if _fused_loss_ok(pred[0, 0].numel(), pred, inter, truth, init) and mask.is_cuda:
+        if torch.is_grad_enabled() and (pred.requires_grad or inter.requires_grad):
+            return _VidodeL1LossFn.apply(pred, inter, truth, init, mask)
+        return tuple(hip_ops.loss_vidode_l1(pred, inter, truth, init, mask).unbind(0))
+    b, n = pred.shape[0], pred.shape[1]
+    sel = (mask.squeeze(-1) if mask.dim() == 3 else mask).bool()
+    data = torch.cat([init.unsqueeze(1), truth], dim=1)
+    d = data[:, 1:, ...] - data[:, :-1, ...]
+    count = pred[0].numel() * b
+    data_diff = d[sel].view((b, n) + tuple(pred.shape[2:]))
+    l1_pred = torch.mean(torch.sum(torch.abs(pred - truth[sel].view((b, n) + tuple(pred.shape[2:])))) / count)
+    l1_diff = torch.mean(torch.sum(torch.abs(inter - data_diff)) / count)
+    return torch.mean(l1_pred + l1_diff), l1_pred.detach(), l1_diff.detach()

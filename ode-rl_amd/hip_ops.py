@@ -1531,3 +1531,141 @@ def latent_sample_backward(grad_z0, grad_kl, mean, std, n_samples=1, seed=0, off
                                                          int(offset), int(batch_offset), b if global_batch is None else int(global_batch),
                                                          _ptr(eps_in), _ptr(grad_mean), _ptr(grad_std), _stream()))
     return grad_mean, grad_std
+
+
+def fused_loss_enabled():
+    """ODEHIP_FUSED_LOSS=0: the models' get_loss runs its torch composition on the GPU too (A/B against csrc/frame_loss.hip)."""
+    return os.environ.get("ODEHIP_FUSED_LOSS", "1") != "0"
+
+
+def _check_mse_pair(pred, truth, who):
+    """pred (K * B, ...) and truth (B, ...) float32 device tensors with the same trailing shape, its size a multiple of 4
+    -> (K, B, elements per row)."""
+    require_device_tensor(pred, "pred")
+    require_device_tensor(truth, "truth")
+    if truth.dim() < 2 or truth.shape[0] < 1 or truth[0].numel() < 4 or truth[0].numel() % 4:
+        raise ValueError(f"{who}: truth must be (B, ...) with a row size that is a positive multiple of 4, got {tuple(truth.shape)}")
+    if pred.dim() != truth.dim() or pred.shape[1:] != truth.shape[1:] or pred.shape[0] < 1 or pred.shape[0] % truth.shape[0] or \
+            pred.device != truth.device:
+        raise ValueError(f"{who}: pred must be (K * B, ...) on truth's device with truth's trailing shape, got {tuple(pred.shape)} on "
+                         f"{pred.device} for {tuple(truth.shape)} on {truth.device}")
+    return pred.shape[0] // truth.shape[0], truth.shape[0], truth[0].numel()
+
+
+def _check_device_scalar(t, name, like, who):
+    require_device_tensor(t, name)
+    if t.numel() != 1 or t.device != like.device:
+        raise ValueError(f"{who}: {name} must hold one float on {like.device}, got {tuple(t.shape)} on {t.device}")
+    return t.detach().contiguous()
+
+
+def _check_kl(kl, b, like, who):
+    require_device_tensor(kl, "kl")
+    if tuple(kl.shape) != (b,) or kl.device != like.device:
+        raise ValueError(f"{who}: kl must be ({b},) on {like.device}, got {tuple(kl.shape)} on {kl.device}")
+    return kl.detach().contiguous()
+
+
+def loss_mse(pred, truth, kl=None, kl_weight=1.0, kl_scale=0.0):
+    """{loss, mse, kl_term} as a (3,) device tensor, two launches (csrc/frame_loss.hip): mse = mean (pred - truth)^2 with pred
+    (K * B, ...) sample-major against truth (B, ...) -- row k * B + b against row b, the truth is not repeated --, kl_term =
+    kl_scale * sum(kl) for kl (B,) or 0, loss = mse + kl_weight * kl_term.  Sums in float64, fixed order."""
+    k, b, f = _check_mse_pair(pred, truth, "loss_mse")
+    pred, truth = pred.detach().contiguous(), truth.detach().contiguous()
+    if kl is not None:
+        kl = _check_kl(kl, b, pred, "loss_mse")
+    lib = _lib.load()
+    ws = workspace("loss_mse", lib.odehip_loss_mse_workspace_bytes(k, b, f), pred.device)
+    out = torch.empty(3, dtype=torch.float32, device=pred.device)
+    _lib.check(lib.odehip_loss_mse(_ptr(pred), _ptr(truth), k, b, f, _ptr(kl), float(kl_scale), float(kl_weight), _ptr(out), _ptr(ws),
+                                   ws.numel(), _stream()))
+    return out
+
+
+def loss_mse_backward(grad_out, pred, truth, kl_weight=1.0, kl_scale=0.0, want_kl=False):
+    """(grad_pred, grad_kl or None) of loss_mse from grad_out, one float on the device, in ONE launch: grad_pred = (pred - truth) *
+    (2 grad_out / N), grad_kl[b] = grad_out * kl_weight * kl_scale."""
+    k, b, f = _check_mse_pair(pred, truth, "loss_mse_backward")
+    pred, truth = pred.detach().contiguous(), truth.detach().contiguous()
+    grad_out = _check_device_scalar(grad_out, "grad_out", pred, "loss_mse_backward")
+    grad_pred = torch.empty_like(pred)
+    grad_kl = torch.empty(b, dtype=torch.float32, device=pred.device) if want_kl else None
+    _lib.check(_lib.load().odehip_loss_mse_backward(_ptr(grad_out), _ptr(pred), _ptr(truth), k, b, f, float(kl_scale), float(kl_weight),
+                                                    _ptr(grad_pred), _ptr(grad_kl), _stream()))
+    return grad_pred, grad_kl
+
+
+def _frame_rows(t, name, lead, frame, who):
+    """A float32 device tensor of shape lead + frame whose frames lie contiguous in memory, its leading strides multiples of 4 and
+    its first element 16-byte aligned: as it is (a view is not copied), otherwise made contiguous."""
+    require_device_tensor(t, name)
+    if tuple(t.shape) != tuple(lead) + tuple(frame):
+        raise ValueError(f"{who}: {name} must be {tuple(lead) + tuple(frame)}, got {tuple(t.shape)}")
+    t = t.detach()
+    n = len(lead)
+    inner = t[(0,) * n]
+    ok = inner.is_contiguous() and t.data_ptr() % 16 == 0 and all(s % 4 == 0 and s >= inner.numel() for s in t.stride()[:n])
+    if ok and n == 2:   # frames of one batch row must not overlap the next row's
+        ok = t.stride(0) >= t.stride(1) * (t.shape[1] - 1) + inner.numel()
+    return t if ok else t.contiguous()
+
+
+def _check_l1_args(pred, inter, truth, init, mask, who):
+    """The tensors of the VidODE L1 pair, checked and laid out for the C ABI -> (pred, inter, truth, init, mask, mask_is_byte, B, T, n, P)."""
+    require_device_tensor(pred, "pred")
+    if pred.dim() < 3 or pred.shape[0] < 1 or pred.shape[1] < 1 or pred[0, 0].numel() < 4 or pred[0, 0].numel() % 4:
+        raise ValueError(f"{who}: pred must be (B, n, ...) with a frame size that is a positive multiple of 4, got {tuple(pred.shape)}")
+    b, n, frame = pred.shape[0], pred.shape[1], tuple(pred.shape[2:])
+    require_device_tensor(truth, "truth")
+    if truth.dim() != pred.dim() or truth.shape[0] != b or tuple(truth.shape[2:]) != frame or truth.shape[1] < n:
+        raise ValueError(f"{who}: truth must be ({b}, T >= {n}) + {frame}, got {tuple(truth.shape)}")
+    t = truth.shape[1]
+    if not isinstance(mask, torch.Tensor):
+        raise TypeError("mask must be a torch.Tensor")
+    if mask.dim() == 3 and mask.shape[2] == 1:   # the loaders' (B, T, 1)
+        mask = mask[:, :, 0]
+    if tuple(mask.shape) != (b, t):
+        raise ValueError(f"{who}: mask must be ({b}, {t}) or ({b}, {t}, 1), got {tuple(mask.shape)}")
+    for name, x in (("inter", inter), ("init", init), ("mask", mask)):
+        if isinstance(x, torch.Tensor) and x.device != pred.device:
+            raise ValueError(f"{who}: {name} is on {x.device}, pred on {pred.device}")
+    if not mask.is_cuda:
+        raise RuntimeError(f"mask is on {mask.device}: the HIP path needs CUDA (ROCm) tensors and has no CPU fallback")
+    mask = mask.detach()
+    if mask.dtype not in (torch.float32, torch.uint8, torch.bool):
+        mask = mask != 0
+    mask = mask.contiguous()
+    pred = _frame_rows(pred, "pred", (b, n), frame, who).contiguous()
+    inter = _frame_rows(inter, "inter", (b, n), frame, who)
+    truth = _frame_rows(truth, "truth", (b, t), frame, who).contiguous()
+    init = _frame_rows(init, "init", (b,), frame, who)
+    return pred, inter, truth, init, mask, 0 if mask.dtype == torch.float32 else 1, b, t, n, pred[0, 0].numel()
+
+
+def _l1_call_args(pred, inter, truth, init, mask, mask_is_byte, b, t, n, p):
+    """The arguments both VidODE L1 entry points take between grad_out and their outputs."""
+    return (_ptr(pred), _ptr(inter), inter.stride(0), inter.stride(1), _ptr(truth), _ptr(init), init.stride(0), _ptr(mask), mask_is_byte,
+            b, t, n, p)
+
+
+def loss_vidode_l1(pred, inter, truth, init, mask):
+    """{loss, l1_pred, l1_diff} of models/VidODE.py's get_loss as a (3,) device tensor, two launches, no host synchronisation
+    (csrc/frame_loss.hip).  pred, inter (B, n, ...) -- inter may be a channel slice, it is not copied --, truth (B, T, ...), init
+    (B, ...) the last observed frame (a view is fine), mask (B, T) or (B, T, 1), non-zero = selected, float32 / uint8 / bool as it is.
+    l1_pred = mean |pred - truth[selected]|, l1_diff = mean |inter - (truth[t] - truth[t - 1])[selected]| with truth[-1] = init."""
+    args = _check_l1_args(pred, inter, truth, init, mask, "loss_vidode_l1")
+    b, n, p = args[6], args[8], args[9]
+    lib = _lib.load()
+    ws = workspace("loss_vidode_l1", lib.odehip_loss_vidode_l1_workspace_bytes(b, n, p), args[0].device)
+    out = torch.empty(3, dtype=torch.float32, device=args[0].device)
+    _lib.check(lib.odehip_loss_vidode_l1(*_l1_call_args(*args), _ptr(out), _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def loss_vidode_l1_backward(grad_out, pred, inter, truth, init, mask):
+    """(grad_pred, grad_inter), both (B, n, ...) contiguous, of loss_vidode_l1 from grad_out (one float on the device), ONE launch."""
+    args = _check_l1_args(pred, inter, truth, init, mask, "loss_vidode_l1_backward")
+    grad_out = _check_device_scalar(grad_out, "grad_out", args[0], "loss_vidode_l1_backward")
+    grad_pred, grad_inter = torch.empty_like(args[0]), torch.empty_like(args[0])
+    _lib.check(_lib.load().odehip_loss_vidode_l1_backward(_ptr(grad_out), *_l1_call_args(*args), _ptr(grad_pred), _ptr(grad_inter), _stream()))
+    return grad_pred, grad_inter

@@ -101,7 +101,7 @@ class ODEConvGRU(nn.Module):
     With `opt.z_sample` True (definitions of this project; the reference leaves the mode at a TODO):
       train()  z0 ~ N(mean_z0, std_z0) by the reparameterisation trick, `opt.z_n_samples` (default 1) draws per batch row
                (`ode_rl_amd.sample_z0`: one launch).  Solver and decoder run on the K * B rows; `forward` returns
-               (K * B, T, c, 64, 64), sample-major.  `get_loss` repeats `truth` over K and adds the KL term of the ELBO,
+               (K * B, T, c, 64, 64), sample-major.  `get_loss` pairs the K draws with `truth` and adds the KL term of the ELBO,
                    loss = MSE + opt.kl_weight (default 1.0) * mean_b KL(N(mean_z0, std_z0) || N(0, 1)) / (C * 16 * 16)
                i.e. the KL per latent element averaged over the batch.  `last_loss_terms` = {"mse", "kl"} holds the two terms of the
                last call as device tensors (the KL already per element, before the weight).
@@ -144,14 +144,15 @@ class ODEConvGRU(nn.Module):
         return self(inputs, batch_dict)
 
     def get_loss(self, pred_frames, truth, loss='MSE'):
+        """Through `ode_rl_amd.mse_kl_loss`: one call each way on the device (csrc/frame_loss.hip; the K draws of a sampled forward pair
+        with the truth rows as they lie, nothing is repeated), the torch composition elsewhere."""
+        from ..autograd import mse_kl_loss
         b, t, c, h, w = truth.size()
         if self._kl is None:
-            return nn.functional.mse_loss(pred_frames.reshape(b * t, c, h, w), truth.reshape(b * t, c, h, w))
+            return mse_kl_loss(pred_frames.reshape(b * t, c, h, w), truth.reshape(b * t, c, h, w))[0]
         (kl, per_row), self._kl = self._kl, None
-        n = pred_frames.shape[0] // b   # the K draws of the forward pass, sample-major
-        if n > 1:
-            truth = truth.repeat(n, 1, 1, 1, 1)
-        mse = nn.functional.mse_loss(pred_frames.reshape(n * b * t, c, h, w), truth.reshape(n * b * t, c, h, w))
-        kl_term = kl.mean() / per_row
-        self.last_loss_terms = {"mse": mse.detach(), "kl": kl_term.detach()}
-        return mse + getattr(self.opt, "kl_weight", 1.0) * kl_term
+        # (K * B, T, ...) against (B, T, ...): the rows are the batch rows kl (B,) counts, so the frames are not folded into them here
+        loss, mse, kl_term = mse_kl_loss(pred_frames.contiguous(), truth.contiguous(), kl=kl,
+                                         kl_weight=getattr(self.opt, "kl_weight", 1.0), latent_elems=per_row)
+        self.last_loss_terms = {"mse": mse, "kl": kl_term}
+        return loss

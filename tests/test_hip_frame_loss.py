@@ -1,0 +1,355 @@
+"""The training losses on the device (csrc/frame_loss.hip through `hip_ops.loss_*`, `ode_rl_amd.mse_kl_loss`, `vidode_l1_loss` and the
+three models' get_loss) against the float64 restatements of tests/_loss_ref.py on the same fp32 inputs.
+
+Bounds (from the arithmetic include/odecgru_hip.h prescribes; none is calibrated on what the kernels give).
+  loss and its two terms   |got - ref| <= 2^-23 |ref|: the sums are float64, the only fp32 rounding is the last one (2^-24); the bound
+                           is two half-ulps, to allow the mse + kl addition.
+  grad_pred, grad_inter    elementwise <= 4 * 2^-24 |ref| + 2^-149: one fp32 subtraction, one fp32 scale and one product (three half-ulps
+                           and their second-order terms), plus one denormal step.  grad_kl: the same bound.
+  against the torch composition (fp32 sums in an order torch chooses): 1e-5 relative, the loss bound of
+                           tests/test_hip_train_end_to_end.py; the models: its bounds (loss 1e-5 relative, gradients 1e-3 rel-L2).
+
+No host synchronisation: test_no_host_synchronisation runs both public functions forward and backward under
+torch.cuda.set_sync_debug_mode("error").  The torch composition of VidODE.get_loss does not pass it: each int(mask[0].sum()) and each
+boolean-mask index (nonzero) copies to the host -- four synchronisations per call."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+import _loss_ref as lr
+from conftest import procedural_tensor, rel_l2
+
+pytestmark = pytest.mark.gpu
+
+SCALAR_REL = 2.0 ** -23
+GRAD_REL, GRAD_ABS = 4 * 2.0 ** -24, 2.0 ** -149
+
+
+@pytest.fixture(autouse=True)
+def _fused_path(monkeypatch):
+    """These tests are about csrc/frame_loss.hip: an ODEHIP_FUSED_LOSS=0 of the environment does not reach them (the model tests set it)."""
+    monkeypatch.delenv("ODEHIP_FUSED_LOSS", raising=False)
+
+
+def _check_scalar(name, got, ref):
+    got, err = float(got), abs(float(got) - ref)
+    print(f"{name}: got {got!r} ref {ref!r} |err| / |ref| = {err / abs(ref) if ref else err:.3e} (bound {SCALAR_REL:.3e})")
+    assert err <= SCALAR_REL * abs(ref), (name, got, ref)
+
+
+def _check_grad(name, got, ref):
+    got = got.detach().cpu().numpy().astype(np.float64)
+    assert got.shape == ref.shape, (name, got.shape, ref.shape)
+    excess = np.abs(got - ref) - (GRAD_REL * np.abs(ref) + GRAD_ABS)
+    worst = float(np.max(np.abs(got - ref) / np.maximum(np.abs(ref), 1e-300)))
+    print(f"{name}: worst elementwise relative error {worst:.3e} (bound {GRAD_REL:.3e})")
+    assert float(excess.max()) <= 0.0, (name, worst)
+
+
+# ---- the MSE (+ KL) kind --------------------------------------------------------------------------------------------------------------
+
+MSE_CASES = [(1, 1, 1, 1, 64, 64), (3, 2, 3, 1, 64, 64), (1, 5, 7, 3, 64, 64), (1, 2, 3, 1, 8, 12), (1, 64, 10, 1, 64, 64)]
+LATENT = 64 * 256
+
+
+def _mse_inputs(k, b, t, c, h, w, cuda):
+    pred = procedural_tensor((k * b, t, c, h, w), 7 * k + b, 0.0, 1.0)
+    truth = procedural_tensor((b, t, c, h, w), 11 * t + b, -0.5, 0.5)
+    kl = procedural_tensor((b,), 13 + b, 5.0, 300.0)
+    return pred.to(cuda), truth.to(cuda), kl.to(cuda)
+
+
+@pytest.mark.parametrize("kl_weight", [None, 0.0, 2.5], ids=["no_kl", "kw0", "kw2.5"])
+@pytest.mark.parametrize("k,b,t,c,h,w", MSE_CASES)
+def test_mse_kl_against_the_float64_restatement(cuda, k, b, t, c, h, w, kl_weight):
+    import ode_rl_amd
+    from ode_rl_amd import hip_ops
+    pred, truth, kl = _mse_inputs(k, b, t, c, h, w, cuda)
+    with_kl = kl_weight is not None
+    kw = dict(kl=kl.clone().requires_grad_(True), kl_weight=kl_weight, latent_elems=LATENT) if with_kl else {}
+    p = pred.clone().requires_grad_(True)
+    loss, mse, kl_term = ode_rl_amd.mse_kl_loss(p, truth, **kw)
+    assert loss.requires_grad and not mse.requires_grad and (kl_term is None or not kl_term.requires_grad)
+    (3.0 * loss).backward()                                             # grad_out != 1
+    ref = lr.mse_kl(pred.cpu().numpy(), truth.cpu().numpy(), kl.cpu().numpy() if with_kl else None, kl_weight, LATENT, grad_out=3.0)
+    _check_scalar("loss", loss, ref["loss"])
+    _check_scalar("mse", mse, ref["mse"])
+    _check_grad("grad_pred", p.grad, ref["grad_pred"])
+    if with_kl:
+        _check_scalar("kl_term", kl_term, ref["kl_term"])
+        _check_grad("grad_kl", kw["kl"].grad, ref["grad_kl"])
+    # the entry points themselves: the same numbers without autograd, two calls bitwise equal
+    scale = 1.0 / (b * LATENT) if with_kl else 0.0
+    out = hip_ops.loss_mse(pred, truth, kl if with_kl else None, kl_weight or 0.0, scale)
+    assert torch.equal(out[0], loss.detach()) and torch.equal(out[1], mse) and (not with_kl or torch.equal(out[2], kl_term))
+    assert torch.equal(hip_ops.loss_mse(pred, truth, kl if with_kl else None, kl_weight or 0.0, scale), out)
+    three = torch.full((1,), 3.0, device=cuda)
+    gp, gk = hip_ops.loss_mse_backward(three, pred, truth, kl_weight or 0.0, scale, want_kl=with_kl)
+    assert torch.equal(gp, p.grad) and (not with_kl or torch.equal(gk, kw["kl"].grad))
+    # 3 x the backward of loss, within the bound
+    one = lr.mse_kl(pred.cpu().numpy(), truth.cpu().numpy(), grad_out=1.0)
+    g1, _ = hip_ops.loss_mse_backward(torch.ones(1, device=cuda), pred, truth)
+    _check_grad("grad_pred at grad_out 1", g1, one["grad_pred"])
+    # the torch composition with the truth repeated over the K draws
+    comp = torch.nn.functional.mse_loss(pred, truth.repeat(k, 1, 1, 1, 1))
+    if with_kl:
+        comp = comp + kl_weight * (kl.mean() / LATENT)
+    assert abs(float(loss) - float(comp)) <= 1e-5 * abs(float(comp)), (float(loss), float(comp))
+
+
+def test_mse_rows_pair_with_the_truth_rows_as_they_lie(cuda):
+    """K = 3, B = 2: pred row k B + b is the truth row b plus a constant that depends on (k, b) alone, so every wrong pairing shows."""
+    from ode_rl_amd import hip_ops
+    k, b = 3, 2
+    truth = procedural_tensor((b, 3, 1, 64, 64), 3, -0.5, 0.5).to(cuda)
+    shift = torch.tensor([0.25, -0.5, 1.0, 2.0, -0.125, 0.75], device=cuda).view(k * b, 1, 1, 1, 1)
+    pred = truth.repeat(k, 1, 1, 1, 1) + shift
+    out = hip_ops.loss_mse(pred, truth)
+    _check_scalar("mse of shifted rows", out[1], lr.mse_kl(pred.cpu().numpy(), truth.cpu().numpy())["mse"])
+    assert abs(float(out[1]) - float((shift.double() ** 2).mean())) <= 1e-6
+
+
+# ---- the VidODE L1 pair ---------------------------------------------------------------------------------------------------------------
+
+HOLED = [[1, 0, 1, 1, 0], [0, 1, 1, 0, 1]]
+L1_CASES = [(2, 4, 4, 1, None), (2, 5, 3, 1, HOLED), (3, 6, 2, 3, [[0, 1, 0, 0, 1, 0], [1, 1, 0, 0, 0, 0], [0, 0, 0, 1, 0, 1]])]
+
+
+def _l1_inputs(b, t, n, c, rows, cuda, mask_dtype=torch.float32):
+    pred = procedural_tensor((b, n, c, 64, 64), 31 + b, -0.5, 0.5).to(cuda)
+    outputs = procedural_tensor((b, n, c + 3, 64, 64), 37 + t, -0.5, 0.5).to(cuda)
+    truth = procedural_tensor((b, t, c, 64, 64), 41 + n, -0.5, 0.5).to(cuda)
+    observed = procedural_tensor((b, 3, c, 64, 64), 43 + c, -0.5, 0.5).to(cuda)
+    mask = torch.ones(b, t, 1) if rows is None else torch.tensor(rows, dtype=torch.float32).view(b, t, 1)
+    inter, init = outputs[:, :, 2:2 + c], observed[:, -1]              # views, as VidODE hands them over
+    assert not inter.is_contiguous() and not init.is_contiguous()
+    return pred, inter, truth, init, mask.to(cuda).to(mask_dtype)
+
+
+def _np(*tensors):
+    return [x.detach().float().cpu().numpy() for x in tensors]
+
+
+@pytest.mark.parametrize("mask_dtype", [torch.float32, torch.bool], ids=["f32mask", "boolmask"])
+@pytest.mark.parametrize("b,t,n,c,rows", L1_CASES, ids=["ones", "holed", "c3"])
+def test_vidode_l1_against_the_float64_restatement(cuda, b, t, n, c, rows, mask_dtype):
+    import ode_rl_amd
+    from ode_rl_amd import hip_ops
+    pred, inter, truth, init, mask = _l1_inputs(b, t, n, c, rows, cuda, mask_dtype)
+    p, x = pred.clone().requires_grad_(True), inter.detach().requires_grad_(True)
+    loss, l1_pred, l1_diff = ode_rl_amd.vidode_l1_loss(p, x, truth, init, mask)
+    assert loss.requires_grad and not l1_pred.requires_grad and not l1_diff.requires_grad
+    (3.0 * loss).backward()
+    ref = lr.vidode_l1(*_np(pred, inter, truth, init, mask), grad_out=3.0)
+    for name, got in (("loss", loss), ("l1_pred", l1_pred), ("l1_diff", l1_diff)):
+        _check_scalar(name, got, ref[name])
+    _check_grad("grad_pred", p.grad, ref["grad_pred"])
+    _check_grad("grad_inter", x.grad, ref["grad_inter"])
+    out = hip_ops.loss_vidode_l1(pred, inter, truth, init, mask)
+    assert torch.equal(out[0], loss.detach()) and torch.equal(out[1], l1_pred) and torch.equal(out[2], l1_diff)
+    assert torch.equal(hip_ops.loss_vidode_l1(pred, inter, truth, init, mask[:, :, 0]), out)          # (B, T) as well as (B, T, 1)
+    gp, gx = hip_ops.loss_vidode_l1_backward(torch.ones(1, device=cuda), pred, inter, truth, init, mask)
+    one = lr.vidode_l1(*_np(pred, inter, truth, init, mask))
+    _check_grad("grad_pred at grad_out 1", gp, one["grad_pred"])
+    _check_grad("grad_inter at grad_out 1", gx, one["grad_inter"])
+    # the composition the model ran before (it selects with a boolean index, i.e. with host synchronisations)
+    sel = mask[:, :, 0].bool()
+    data = torch.cat([init.unsqueeze(1), truth], dim=1)
+    d = (data[:, 1:] - data[:, :-1])[sel].view(b, n, c, 64, 64)
+    comp = (pred - truth[sel].view(b, n, c, 64, 64)).abs().sum() / pred.numel() + (inter - d).abs().sum() / pred.numel()
+    assert abs(float(loss) - float(comp)) <= 1e-5 * abs(float(comp)), (float(loss), float(comp))
+
+
+def test_a_row_with_too_few_selected_frames_gives_nan(cuda):
+    from ode_rl_amd import hip_ops
+    pred, inter, truth, init, _ = _l1_inputs(2, 5, 3, 1, HOLED, cuda)
+    mask = torch.tensor([[1, 0, 1, 1, 0], [0, 0, 1, 0, 1]], dtype=torch.float32, device=cuda)        # row 1 selects two frames, n = 3
+    out = hip_ops.loss_vidode_l1(pred, inter, truth, init, mask)
+    assert torch.isnan(out).all(), out
+    gp, gx = hip_ops.loss_vidode_l1_backward(torch.ones(1, device=cuda), pred, inter, truth, init, mask)
+    ref = lr.vidode_l1(*_np(pred, inter, truth, init, torch.tensor(HOLED)))
+    _check_grad("grad_pred of the complete row", gp[0], ref["grad_pred"][0])                          # row 0 is whole
+    assert torch.isnan(gp[1, 2]).all() and torch.isnan(gx[1, 2]).all()                                # the frame that has no partner
+    assert np.all(np.isnan(list(lr.vidode_l1(*_np(pred, inter, truth, init, mask)).values())[:3]))
+
+
+# ---- repeatability ------------------------------------------------------------------------------------------------------------------
+
+def test_results_do_not_depend_on_what_ran_before(cuda):
+    from ode_rl_amd import hip_ops
+    pred, truth, kl = _mse_inputs(1, 64, 10, 1, 64, 64, cuda)
+    a = _l1_inputs(3, 6, 2, 3, L1_CASES[2][4], cuda)
+    first = hip_ops.loss_mse(pred, truth, kl, 2.5, 1.0 / (64 * LATENT)).clone(), hip_ops.loss_vidode_l1(*a).clone()
+    g_first = hip_ops.loss_mse_backward(torch.ones(1, device=cuda), pred, truth)[0]
+    # unrelated device work in front: other sizes through the same workspaces, and a matmul that fills the device
+    other = _mse_inputs(3, 2, 3, 1, 64, 64, cuda)
+    hip_ops.loss_mse(other[0], other[1])
+    hip_ops.loss_vidode_l1(*_l1_inputs(2, 4, 4, 1, None, cuda))
+    m = torch.randn(2048, 2048, device=cuda)
+    (m @ m).sum()
+    again = hip_ops.loss_mse(pred, truth, kl, 2.5, 1.0 / (64 * LATENT)), hip_ops.loss_vidode_l1(*a)
+    assert torch.equal(first[0], again[0]) and torch.equal(first[1], again[1])
+    assert torch.equal(g_first, hip_ops.loss_mse_backward(torch.ones(1, device=cuda), pred, truth)[0])
+
+
+# ---- non-finite inputs -----------------------------------------------------------------------------------------------------------------
+
+def _cls(t):
+    """finiteness class per element: 0 finite, 1 +inf, 2 -inf, 3 NaN"""
+    t = t.detach().float()
+    return (torch.isposinf(t) * 1 + torch.isneginf(t) * 2 + torch.isnan(t) * 3).cpu()
+
+
+@pytest.mark.parametrize("where", ["pred", "truth"])
+def test_mse_non_finite_inputs_behave_as_in_torch(cuda, where):
+    import ode_rl_amd
+    pred, truth, _ = _mse_inputs(2, 2, 3, 1, 64, 64, cuda)
+    for value in (float("nan"), float("inf")):
+        pred, truth = pred.clone(), truth.clone()
+        (pred if where == "pred" else truth)[1, 2, 0, 5, 9] = value
+        p = pred.clone().requires_grad_(True)
+        loss = ode_rl_amd.mse_kl_loss(p, truth)[0]
+        loss.backward()
+        q = pred.clone().requires_grad_(True)
+        comp = torch.nn.functional.mse_loss(q, truth.repeat(2, 1, 1, 1, 1))   # the composition on the same device tensors
+        comp.backward()
+        assert torch.equal(_cls(loss), _cls(comp)), (where, value, float(loss), float(comp))
+        assert torch.equal(_cls(p.grad), _cls(q.grad)), (where, value)
+        assert int((_cls(p.grad) != 0).sum()) == (1 if where == "pred" else 2)        # it stays in its own element (of both draws)
+
+
+@pytest.mark.parametrize("where", ["pred", "truth"])
+def test_l1_non_finite_inputs_and_zero_differences_behave_as_in_torch(cuda, where):
+    import ode_rl_amd
+    b, t, n, c = 2, 4, 4, 1
+    pred, inter, truth, init, mask = _l1_inputs(b, t, n, c, None, cuda)
+    pred, inter = pred.clone(), inter.clone()
+    pred[0, 1, 0, 3, 4] = truth[0, 1, 0, 3, 4]                                     # zero differences: sgn(0) is torch's
+    truth[1, 0, 0, 7, 7], init[1, 0, 7, 7], inter[1, 0, 0, 7, 7] = 0.25, 0.125, 0.125   # (a frame difference that is exact in fp32)
+    for value in (None, float("nan"), float("inf")):
+        pred, truth = pred.clone(), truth.clone()
+        if value is not None:
+            (pred if where == "pred" else truth)[1, 1, 0, 5, 9] = value
+        p, x = pred.clone().requires_grad_(True), inter.clone().requires_grad_(True)
+        loss = ode_rl_amd.vidode_l1_loss(p, x, truth, init, mask)[0]
+        loss.backward()
+        q, y = pred.clone().requires_grad_(True), inter.clone().requires_grad_(True)
+        data = torch.cat([init.unsqueeze(1), truth], dim=1)
+        comp = (q - truth).abs().sum() / q.numel() + (y - (data[:, 1:] - data[:, :-1])).abs().sum() / q.numel()
+        comp.backward()
+        assert torch.equal(_cls(loss), _cls(comp)), (where, value, float(loss), float(comp))
+        assert torch.equal(_cls(p.grad), _cls(q.grad)) and torch.equal(_cls(x.grad), _cls(y.grad)), (where, value)
+        assert torch.equal(torch.sign(p.grad), torch.sign(q.grad)), (where, value)   # (pred - truth has the same sign in fp32 and float64)
+        assert float(p.grad[0, 1, 0, 3, 4]) == float(q.grad[0, 1, 0, 3, 4]) and float(x.grad[1, 0, 0, 7, 7]) == float(y.grad[1, 0, 0, 7, 7])
+        assert float(q.grad[0, 1, 0, 3, 4]) == 0.0 and float(y.grad[1, 0, 0, 7, 7]) == 0.0
+
+
+# ---- no host synchronisation ----------------------------------------------------------------------------------------------------------
+
+def test_no_host_synchronisation(cuda):
+    """Forward and backward of both public functions under set_sync_debug_mode("error").  (The torch composition of VidODE.get_loss
+    trips it: int(mask[0].sum()) twice and nonzero behind each boolean index.)"""
+    import ode_rl_amd
+    pred, truth, kl = _mse_inputs(2, 2, 3, 1, 64, 64, cuda)
+    a = _l1_inputs(2, 5, 3, 1, HOLED, cuda)
+
+    def step():
+        p, k = pred.clone().requires_grad_(True), kl.clone().requires_grad_(True)
+        ode_rl_amd.mse_kl_loss(p, truth, kl=k, kl_weight=0.5, latent_elems=LATENT)[0].backward()
+        q, x = a[0].clone().requires_grad_(True), a[1].detach().requires_grad_(True)
+        ode_rl_amd.vidode_l1_loss(q, x, *a[2:])[0].backward()
+        return p.grad, k.grad, q.grad, x.grad
+
+    warm = step()                                                       # library load, workspaces
+    torch.cuda.synchronize()
+    was = torch.cuda.get_sync_debug_mode()
+    try:
+        torch.cuda.set_sync_debug_mode("error")
+    except Exception as e:                                              # noqa: BLE001
+        pytest.skip(f"torch.cuda.set_sync_debug_mode('error') is not available on this build: {e}")
+    try:
+        got = step()
+    finally:
+        torch.cuda.set_sync_debug_mode(was)
+    assert all(torch.equal(g, w) for g, w in zip(got, warm))
+
+
+# ---- the models ------------------------------------------------------------------------------------------------------------------------
+
+def _loss_and_grads(model, run, fused, monkeypatch):
+    monkeypatch.setenv("ODEHIP_FUSED_LOSS", "1" if fused else "0")
+    model.zero_grad(set_to_none=True)
+    model.last_loss_terms = None
+    torch.manual_seed(21)                                               # the noise of a sampled forward
+    loss = run(model)
+    loss.backward()
+    return loss.detach(), {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None}, getattr(model, "last_loss_terms", None)
+
+
+def _compare(model, run, monkeypatch, launches):
+    fused = _loss_and_grads(model, run, True, monkeypatch)
+    n_fused = launches["n"]
+    comp = _loss_and_grads(model, run, False, monkeypatch)
+    assert n_fused > 0 and launches["n"] == n_fused, "ODEHIP_FUSED_LOSS=1 must take csrc/frame_loss.hip, =0 must not"
+    assert abs(float(fused[0]) - float(comp[0])) <= 1e-5 * abs(float(comp[0])) + 1e-7, (float(fused[0]), float(comp[0]))
+    assert fused[1].keys() == comp[1].keys() and len(fused[1]) > 0
+    bad = {n: rel_l2(g, comp[1][n]) for n, g in fused[1].items() if float(comp[1][n].norm()) > 0 and rel_l2(g, comp[1][n]) > 1e-3}
+    assert not bad, bad
+    return fused, comp
+
+
+@pytest.fixture
+def launches(monkeypatch):
+    """Counts the calls of the two forward entry points."""
+    from ode_rl_amd import hip_ops
+    count = {"n": 0}
+    for name in ("loss_mse", "loss_vidode_l1"):
+        real = getattr(hip_ops, name)
+
+        def counted(*a, _real=real, **kw):
+            count["n"] += 1
+            return _real(*a, **kw)
+        monkeypatch.setattr(hip_ops, name, counted)
+    return count
+
+
+@pytest.mark.parametrize("z_sample", [False, True], ids=["mean_z0", "sampled_k2"])
+def test_odeconvgru_get_loss_is_wired_to_the_kernels(cuda, monkeypatch, launches, z_sample):
+    from test_hip_latent_sample import _data, _model
+    model = _model(**({"z_sample": True, "z_n_samples": 2, "kl_weight": 0.5} if z_sample else {})).to(cuda).train()
+    frames, truth, ts = _data()
+    bd = {"observed_tp": ts[:3].to(cuda), "tp_to_predict": ts[3:].to(cuda)}
+    fused, comp = _compare(model, lambda m: m.get_loss(m(frames.to(cuda), bd), truth.to(cuda)), monkeypatch, launches)
+    if z_sample:
+        for key in ("mse", "kl"):
+            a, b = float(fused[2][key]), float(comp[2][key])
+            assert abs(a - b) <= 1e-5 * abs(b) + 1e-7 and not fused[2][key].requires_grad, (key, a, b)
+        assert abs(float(fused[2]["mse"]) + 0.5 * float(fused[2]["kl"]) - float(fused[0])) <= 1e-6 * abs(float(fused[0]))
+
+
+def test_convgru_get_loss_is_wired_to_the_kernels(cuda, monkeypatch, launches):
+    from test_hip_convgru_model import _model
+    model, _ = _model(cuda, 23, train_in_seq=3, train_out_seq=3)
+    model.train()
+    frames = procedural_tensor((2, 3, 1, 64, 64), 5, 0.0, 1.0).to(cuda)
+    truth = procedural_tensor((2, 3, 1, 64, 64), 6, 0.0, 1.0).to(cuda)
+    _compare(model, lambda m: m.get_loss(m(frames), truth), monkeypatch, launches)
+
+
+def test_vidode_get_loss_is_wired_to_the_kernels(cuda, monkeypatch, launches):
+    from test_hip_vidode import _model
+    model = _model(cuda).train()
+    B, Tin, Tout = 4, 3, 3
+    frames = procedural_tensor((B, Tin + Tout, 1, 64, 64), 150, 0, 1).to(cuda)
+    ts = torch.tensor(np.arange(Tin + Tout) / (Tin + Tout)).to(cuda)
+    bd = {"observed_tp": ts[:Tin], "tp_to_predict": ts[Tin:], "observed_mask": torch.ones(B, Tin, 1, device=cuda),
+          "mask_predicted_data": torch.ones(B, Tout, 1, device=cuda), "observed_data": frames[:, :Tin], "data_to_predict": frames[:, Tin:]}
+    state = copy.deepcopy(model.state_dict())                           # BatchNorm's running statistics move with every forward
+
+    def run(m):
+        m.load_state_dict(state)
+        return m.get_loss(m.get_prediction(frames[:, :Tin], bd), torch.zeros_like(frames[:, Tin:]))   # the truth is the batch dict's
+
+    _compare(model, run, monkeypatch, launches)
