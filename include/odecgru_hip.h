@@ -434,6 +434,32 @@ int odehip_adam_step(float* const* params, const float* const* grads, float* con
                      const long long* numel, int n_tensors, float lr, float beta1, float beta2, float eps, float weight_decay,
                      int step, void* stream);
 
+/* Gradient clipping by global L2 norm (train_test.py:187-195: torch.nn.utils.clip_grad_norm_(model.parameters(), opt.clip)) without a
+ * host read and without a grid-wide barrier: stream order between plain launches is the barrier.  Pure additions: ODEHIP_ABI_VERSION
+ * stays.  Enqueue-only on `stream`, caller-provided memory only, arguments checked before any HIP call (ODEHIP_EINVAL: null pointers,
+ * a negative or NaN max_norm, a workspace that is too small).  Host arrays of n_tensors device pointers / element counts as for
+ * odehip_adam_step; a tensor of 0 elements may have a null pointer.
+ *
+ * odehip_grad_norm: ceil(n_tensors / 24) launches write one float64 partial sum of g*g per workgroup to partials_ws (plain stores, no
+ * atomics: two calls are bitwise equal), a one-workgroup launch adds them in index order and writes three floats to out3 (device):
+ *   out3[0] = total_norm   = (float)sqrt(sum)
+ *   out3[1] = coef         = clamp(reciprocal(total_norm + 1e-6f) * max_norm, max = 1), every step rounded to fp32: torch's
+ *                            `max_norm / (total_norm + 1e-6)` is that product; a NaN norm gives a NaN coefficient
+ *                            (error_if_nonfinite=False), an Inf norm gives 0
+ *   out3[2] = clipped_norm = total_norm * coef
+ * partials_ws: odehip_grad_norm_workspace_bytes(n_tensors, numel) bytes, 8-byte aligned.
+ * odehip_grad_scale: g *= *coef_dev for every tensor (the stand-alone clip_grad_norm_), ceil(n_tensors / 24) launches.
+ * odehip_adam_step_clipped: odehip_adam_step on g * *coef_dev; the scaled gradient is also written back to `grads`, so the caller's
+ * gradients end as torch's clip_grad_norm_ would leave them.  With *coef_dev == 1 parameters, moments and gradients get
+ * odehip_adam_step's bits. */
+size_t odehip_grad_norm_workspace_bytes(int n_tensors, const long long* numel);
+int odehip_grad_norm(const float* const* grads, const long long* numel, int n_tensors, float max_norm, void* partials_ws, size_t ws_bytes,
+                     float* out3, void* stream);
+int odehip_grad_scale(float* const* grads, const long long* numel, int n_tensors, const float* coef_dev, void* stream);
+int odehip_adam_step_clipped(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                             const long long* numel, int n_tensors, float lr, float beta1, float beta2, float eps, float weight_decay,
+                             int step, const float* coef_dev, void* stream);
+
 /* ---- VidODE's warp chain + mask compositing (models/VidODE.py:119-140, get_warped_images :160-186) -------------------------- */
 
 /* pred_outputs (B,T,c+3,H,W) = the flow decoder's output per predicted frame: channels [0:2] optical flow (x, y) in pixels,

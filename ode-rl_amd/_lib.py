@@ -124,6 +124,16 @@ SIGNATURES = {
                                         ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                         ctypes.POINTER(ctypes.c_longlong), ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                         ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_void_p]),
+    "odehip_grad_norm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]),
+    "odehip_grad_norm": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_longlong), ctypes.c_int, ctypes.c_float,
+                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "odehip_grad_scale": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_longlong), ctypes.c_int, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
+    "odehip_adam_step_clipped": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                                ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                                ctypes.POINTER(ctypes.c_longlong), ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                                ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_void_p,
+                                                ctypes.c_void_p]),
     "odehip_set_persistent_trajectory": (ctypes.c_int, [ctypes.c_int]),
     "odehip_persistent_trajectory_launches": (ctypes.c_longlong, []),
     "odehip_persistent_error": (ctypes.c_int, [ctypes.c_int]),

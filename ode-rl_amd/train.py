@@ -9,7 +9,7 @@ import pickle
 import torch
 
 
-def train_batch(model, batch_dict, optimizer, async_solver=False):
+def train_batch(model, batch_dict, optimizer, async_solver=False, clip=None):
     """One optimisation step.  batch_dict: 'observed_data' (B,T_in,C,H,W) and 'data_to_predict' (B,T_out,C,H,W) in [-0.5, 0.5] as the
     reference's loaders deliver them, plus 'observed_tp' / 'tp_to_predict'.  Returns (pred * 255, truth * 255, loss tensor, loss_dict)
     -- the loss stays on the device (no .item() synchronisation here).
@@ -22,7 +22,14 @@ def train_batch(model, batch_dict, optimizer, async_solver=False):
     module buffers (BatchNorm statistics, which may have folded in the NaN frames) are restored to their values of before the pass.
     An AsyncSolveTruncated is then handled here: the step is repeated on the synchronous path, whatever the caller's setting (the next
     asynchronous solve enqueues more attempts); any other error is re-raised.  The caller's asynchronous setting is restored
-    afterwards, and an error from collecting the solves still pending on the way out never replaces the error of the pass."""
+    afterwards, and an error from collecting the solves still pending on the way out never replaces the error of the pass.
+
+    clip: the reference's `opt.clip` (train_test.py:187-195).  None or -1: no clipping, and loss_dict has the keys it always had.
+    Otherwise the gradients are clipped to that global L2 norm before the update -- a FusedAdam does it inside its step
+    (`step(max_grad_norm=clip)`: norm, coefficient and update stay on the device), any other optimizer gets
+    torch.nn.utils.clip_grad_norm_ in front of its step() -- and loss_dict['Gradient Norm'] is the norm AFTER clipping as a device
+    scalar (the reference logs it from one .item() per parameter tensor).  A batch-sharded loop that all-reduces the gradients itself
+    (dist.allreduce_gradients) clips after that: every rank then computes the same coefficient without another collective."""
     dev = next(model.parameters()).device
     inp = batch_dict["observed_data"].to(dev) + 0.5          # train_test.py:180: [-0.5, 0.5] -> [0, 1]
     out = batch_dict["data_to_predict"].to(dev) + 0.5
@@ -61,8 +68,19 @@ def train_batch(model, batch_dict, optimizer, async_solver=False):
                 _set_async_quietly(hip_ops, was)
     else:
         pred, loss = step()
-    optimizer.step()
-    return pred.detach() * 255.0, out * 255.0, loss.detach(), {"Per Step Loss": loss.detach()}
+    loss_dict = {"Per Step Loss": loss.detach()}
+    if clip is None or clip == -1:
+        optimizer.step()
+    else:
+        from .optim import FusedAdam
+        if isinstance(optimizer, FusedAdam):
+            optimizer.step(max_grad_norm=float(clip))
+            loss_dict["Gradient Norm"] = optimizer.last_clipped_norm
+        else:
+            total = torch.nn.utils.clip_grad_norm_(model.parameters(), float(clip))
+            optimizer.step()
+            loss_dict["Gradient Norm"] = total * torch.clamp(float(clip) / (total + 1e-6), max=1.0)   # the coefficient it applied
+    return pred.detach() * 255.0, out * 255.0, loss.detach(), loss_dict
 
 
 def _set_async_quietly(hip_ops, on):
