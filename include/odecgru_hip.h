@@ -679,6 +679,38 @@ int odehip_loss_vidode_l1_backward(const float* grad_out, const float* pred, con
                                    const void* mask, int mask_is_byte, int batch, int n_frames, int n_sel, int frame_elems, float* grad_pred,
                                    float* grad_inter, void* stream);
 
+/* Fixed-grid solvers on an internal grid (grid_interp.hip): torchdiffeq 0.2.1's options={"grid_constructor": fn} / "step_size".  The
+ * solver runs on a grid of n_grid points chosen by the caller (odehip_odeint_fixed with the grid as its time array) and the n_times
+ * requested times are filled by linear interpolation, as FixedGridODESolver.integrate does:
+ *   j = 1;  for n = 0 .. n_grid-2, (t0, t1) = (grid[n], grid[n+1]):  while j < n_times and t1 >= t[j]:  emit j from interval n;  j += 1
+ * with every comparison in float64.  Pure additions: ODEHIP_ABI_VERSION stays.
+ *
+ * odehip_grid_emit_table: HOST ONLY (touches no device).  grid and t strictly increasing with grid[0] == t[0] and grid[n_grid-1] ==
+ * t[n_times-1] (else ODEHIP_EINVAL); n_grid >= 2 unless n_times == 1.  Out, host arrays:
+ *   first (n_grid)   interval n emits the outputs first[n] <= j < first[n+1]; first[0] = 1, first[n_grid-1] = n_times
+ *   exact (n_times)  1 if t[j] == t1 of its interval (solution[j] is that grid state itself, no arithmetic), else 0; exact[0] = 1
+ *   slope (n_times)  fl32((t[j] - t0) / (t1 - t0)), the quotient taken in float64; 1 for an exact hit, 0 for j = 0
+ *
+ * odehip_grid_emit: grid_states (n_grid, state_floats) as the solver wrote them -> out (n_times, state_floats), one launch:
+ *   out[0] = Y[0];   out[j] = Y[n+1] for an exact hit, else Y[n] + slope[j] * (Y[n+1] - Y[n])    (n = the interval of j)
+ * difference, product and sum rounded one after the other (no contraction): the expression order of torchdiffeq's _linear_interp.
+ * odehip_grid_scatter: its backward, grad_out (n_times, state_floats) -> grad_grid (n_grid, state_floats), one launch written as a
+ * gather per grid point, so that every sum has a fixed order and nothing is atomic:
+ *   grad_grid[n] = [n == 0] grad_out[0] + sum_{j in interval n-1} w1_j grad_out[j] + sum_{j in interval n} w0_j grad_out[j]
+ * (w1, w0) = (1, 0) for an exact hit (the w0 term is left out), else (slope, 1 - slope) with 1 - slope taken in fp32; j ascending,
+ * explicit fmas.  grad_grid is what odehip_odeint_fixed_backward takes as grad_out on the grid.
+ * Both: state_floats a positive multiple of 4, device pointers 16-byte aligned; first / slope / exact are the HOST arrays of
+ * odehip_grid_emit_table; table_dev is odehip_grid_table_bytes(n_grid, n_times) bytes of the caller's device memory, into which the
+ * table travels in one asynchronous staged upload.  Enqueue-only on `stream`, no hidden allocation; null pointers, a table that does
+ * not cover the n_times outputs, n_grid < 2 with n_times > 1 and more than 4096 points either way are refused before anything is
+ * enqueued (ODEHIP_EINVAL). */
+size_t odehip_grid_table_bytes(int n_grid, int n_times);
+int odehip_grid_emit_table(const double* grid, int n_grid, const double* t, int n_times, int* first, float* slope, int* exact);
+int odehip_grid_emit(const float* grid_states, float* out, const int* first, const float* slope, const int* exact, int n_grid,
+                     int n_times, long long state_floats, void* table_dev, size_t table_bytes, void* stream);
+int odehip_grid_scatter(const float* grad_out, float* grad_grid, const int* first, const float* slope, const int* exact, int n_grid,
+                        int n_times, long long state_floats, void* table_dev, size_t table_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,6 +183,15 @@ SIGNATURES = {
                                              ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]),
     "odehip_loss_vidode_l1_backward": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_longlong] * 2 + [ctypes.c_void_p] * 2 +
                                        [ctypes.c_longlong, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3),
+    "odehip_grid_table_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "odehip_grid_emit_table": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]),
+    "odehip_grid_emit": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float),
+                                        ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p,
+                                        ctypes.c_size_t, ctypes.c_void_p]),
+    "odehip_grid_scatter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float),
+                                           ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p,
+                                           ctypes.c_size_t, ctypes.c_void_p]),
     "odehip_fused_bf16_weight_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "odehip_pack_convstack_fused_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "odehip_pack_conv_weight_bf16_ks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -57,6 +57,29 @@ class _FixedGridOdeint(torch.autograd.Function):
         return _solver_backward_result(*grads)
 
 
+class _GriddedOdeint(torch.autograd.Function):
+    """A fixed-grid method on an internal grid (options={"grid_constructor": fn}) under autograd: the saving forward walks the grid and
+    one launch interpolates the outputs; the backward turns grad_out into a gradient over the grid points with one launch
+    (csrc/grid_interp.hip) and runs the reverse sweep of _FixedGridOdeint on the grid."""
+
+    @staticmethod
+    def forward(ctx, y0, t_host, method, stack, grid, *params):
+        ctx.mode = hip_ops.current_compute_dtype()
+        out, ws = hip_ops.odeint_fixed_on_grid(stack, method, y0.detach(), t_host, grid, save=True)
+        ctx.stack, ctx.method, ctx.t_host, ctx.grid, ctx.batch, ctx.ws = stack, method, t_host, grid, y0.shape[0], ws
+        hip_ops.record_versions(ctx, params)
+        return out
+
+    @staticmethod
+    @_pinned
+    def backward(ctx, grad_out):
+        hip_ops.check_versions(ctx, "a parameter of the ODE dynamics")
+        grads = hip_ops.odeint_fixed_on_grid_backward(ctx.stack, ctx.method, ctx.t_host, ctx.grid, ctx.batch, grad_out, ctx.ws)
+        ctx.ws = None
+        res = _solver_backward_result(*grads)
+        return res[:4] + (None,) + res[4:]
+
+
 class _Dopri5Odeint(torch.autograd.Function):
     """odeint(method="dopri5") under autograd: the gradient of the accepted steps (csrc/dopri5_backward.hip)."""
 
@@ -311,7 +334,8 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
                    adjoint_method=None, adjoint_options=None, adjoint_params=None):
     """`torchdiffeq.odeint_adjoint(func, y0, t, rtol=, atol=, method=, adjoint_options=)`.
 
-    Fixed-grid methods: one backward step of the same method per interval.  dopri5: adaptive backward solve with
+    Fixed-grid methods: one backward step of the same method per interval; the internal grids of `odeint` (grid_constructor) are
+    refused here -- torchdiffeq's adjoint builds a new grid for every backward interval, which this path does not do.  dopri5: adaptive backward solve with
     torchdiffeq's default mixed norm (every parameter tensor's error ratio steers the steps too) or, with
     `adjoint_options={"norm": "seminorm"}`, with the cheaper seminorm; `max_accept` in adjoint_options bounds the accepted
     backward steps whose activations are kept."""
@@ -354,7 +378,7 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
 
 
 def odeint_with_grad(func, y0, t, rtol, atol, method, options=None):
-    from .odeint import FIXED_GRID, _check_monotone, _host_times, check_options, conv_stack_of, dopri5_cfg
+    from .odeint import FIXED_GRID, _check_monotone, _host_times, check_options, conv_stack_of, dopri5_cfg, internal_grid
     check_options(method, options)
     th = _host_times(t)
     _check_monotone(th)
@@ -363,6 +387,9 @@ def odeint_with_grad(func, y0, t, rtol, atol, method, options=None):
     stack = conv_stack_of(func)
     params = _stack_params(stack)
     if method in FIXED_GRID:
+        grid = internal_grid(func, y0, th, options)
+        if grid is not None:
+            return _GriddedOdeint.apply(y0, th, method, stack, grid, *params)
         return _FixedGridOdeint.apply(y0, th, method, stack, *params)
     return _Dopri5Odeint.apply(y0, th, dopri5_cfg(rtol, atol, options), stack, *params)
 

@@ -466,6 +466,100 @@ def odeint_fixed_backward(stack, method, t, batch, grad_out, ws):
     return grads
 
 
+GRID_MAX_POINTS = 4096   # points of a time array the fixed-grid drivers take (csrc/fixed_grid.hip: check_common)
+GRID_MAX_EVALS = 2048    # evaluations of f a saved trajectory may hold (the weight-gradient tables: csrc/fixed_grid.hip)
+_STAGES = {"euler": 1, "midpoint": 2, "rk4": 4}
+
+
+class EmitTable:
+    """Which grid interval emits which output, as csrc/grid_interp.hip takes it (odehip_grid_emit_table).  Interval n = (grid[n],
+    grid[n + 1]) emits the outputs first[n] <= j < first[n + 1]; exact[j]: t[j] is that interval's end point, the output is the grid
+    state itself; slope[j]: fp32 weight of the interval's end state otherwise."""
+
+    def __init__(self, n_grid, n_times):
+        self.n_grid, self.n_times = n_grid, n_times
+        self._first = (ctypes.c_int * n_grid)()
+        self._slope = (ctypes.c_float * n_times)()
+        self._exact = (ctypes.c_int * n_times)()
+
+    first = property(lambda self: list(self._first))
+    slope = property(lambda self: list(self._slope))
+    exact = property(lambda self: [bool(e) for e in self._exact])
+
+
+def grid_emit_table(grid, t):
+    """The emit table of torchdiffeq's FixedGridODESolver.integrate for the internal `grid` and the requested (increasing) times `t`,
+    built on the host by the library.  The grid must be one-dimensional, strictly increasing and run from t[0] to t[-1]:
+    AssertionError otherwise, as torchdiffeq asserts."""
+    gh, th = host_times(grid), host_times(t)
+    if len(th) < 1 or len(gh) < 1:
+        raise AssertionError("t and the grid must hold at least one point")
+    if len(th) > 1 and not bool((th[1:] > th[:-1]).all()):
+        raise AssertionError("t must be strictly increasing")
+    if len(gh) > 1 and not bool((gh[1:] > gh[:-1]).all()):
+        raise AssertionError("the grid of grid_constructor must be strictly increasing")
+    if not (bool(gh[0] == th[0]) and bool(gh[-1] == th[-1])):
+        raise AssertionError(f"the grid of grid_constructor must start at t[0] and end at t[-1] (grid {float(gh[0])} .. {float(gh[-1])}, "
+                             f"t {float(th[0])} .. {float(th[-1])})")
+    table = EmitTable(len(gh), len(th))
+    _lib.check(_lib.load().odehip_grid_emit_table(_c_times(gh), len(gh), _c_times(th), len(th), table._first, table._slope, table._exact))
+    return table
+
+
+def _grid_call(fn, src, dst, table, state_floats):
+    """One of the two launches of csrc/grid_interp.hip; the table travels into a workspace of its own."""
+    lib = _lib.load()
+    tab = workspace("grid_table", lib.odehip_grid_table_bytes(table.n_grid, table.n_times), src.device)
+    _lib.check(getattr(lib, fn)(_ptr(src), _ptr(dst), table._first, table._slope, table._exact, table.n_grid, table.n_times, state_floats,
+                                _ptr(tab), tab.numel(), _stream()))
+
+
+def _same_times(grid, t):
+    return grid.shape == t.shape and torch.equal(grid, t)
+
+
+def odeint_fixed_on_grid(stack, method, z0, t, grid, save=False, negate=False):
+    """odeint_fixed on an internal grid (torchdiffeq's grid_constructor): the solver steps through `grid`, the requested times `t`
+    are filled by linear interpolation between the grid states around them -- one more launch (csrc/grid_interp.hip).  Returns what
+    odeint_fixed returns, (T,B,C,16,16) and with save=True the workspace odeint_fixed_on_grid_backward takes.  A grid that equals t
+    element for element is the plain call itself: no scratch, no extra launch.  The limits of the plain path hold for the G grid
+    points: ValueError before any launch."""
+    th, gh = host_times(t), host_times(grid)
+    if _same_times(gh, th):
+        return odeint_fixed(stack, method, z0, th, save=save, negate=negate)
+    table = grid_emit_table(gh, th)
+    g = len(gh)
+    if g > GRID_MAX_POINTS:
+        raise ValueError(f"odeint(HIP): a grid of G = {g} points exceeds the limit of {GRID_MAX_POINTS} points")
+    if save and (g - 1) * _STAGES[method] > GRID_MAX_EVALS:
+        raise ValueError(f"odeint(HIP): a grid of G = {g} points needs {(g - 1) * _STAGES[method]} evaluations of f under autograd; the "
+                         f"backward pass keeps at most {GRID_MAX_EVALS} ((G - 1) * {_STAGES[method]} stages of {method})")
+    res = odeint_fixed(stack, method, z0, gh, save=save, negate=negate)
+    states = res[0] if save else res
+    out = torch.empty((len(th),) + tuple(states.shape[1:]), dtype=torch.float32, device=states.device)
+    _grid_call("odehip_grid_emit", states, out, table, states[0].numel())
+    if save:
+        res[1]._odehip_emit_table = table
+        return out, res[1]
+    return out
+
+
+def odeint_fixed_on_grid_backward(stack, method, t, grid, batch, grad_out, ws):
+    """Gradients of odeint_fixed_on_grid: grad_out over the T outputs becomes a gradient over the G grid points (one launch, a gather
+    per grid point: fixed order, no atomics), then the backward of the plain path runs on the grid with the saved workspace."""
+    th, gh = host_times(t), host_times(grid)
+    if _same_times(gh, th):
+        return odeint_fixed_backward(stack, method, th, batch, grad_out, ws)
+    require_device_tensor(grad_out, "grad_out")
+    table = getattr(ws, "_odehip_emit_table", None) or grid_emit_table(gh, th)
+    grad_out = grad_out.contiguous()
+    if grad_out.shape[0] != len(th):
+        raise ValueError(f"grad_out must hold {len(th)} frames (got {tuple(grad_out.shape)})")
+    grad_grid = torch.empty((len(gh),) + tuple(grad_out.shape[1:]), dtype=torch.float32, device=grad_out.device)
+    _grid_call("odehip_grid_scatter", grad_out, grad_grid, table, grad_out[0].numel())
+    return odeint_fixed_backward(stack, method, gh, batch, grad_grid, ws)
+
+
 LOG_CAP = 2048   # accepted steps the forward reports back (the backward pass re-integrates them)
 
 

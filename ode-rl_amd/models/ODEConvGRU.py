@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import hip_ops
-from ..modules.DiffEqSolver import DiffEqSolver, ODEFunc
+from ..modules.DiffEqSolver import DiffEqSolver, ODEFunc, decode_options
 from ..modules.ODEConvGRUCell import ODEConvGRUCell
 
 
@@ -122,7 +122,8 @@ class ODEConvGRU(nn.Module):
         self.ode_decoder_func = ODEFunc(n_inputs=ch, n_outputs=opt.neural_ode_decoder_out_ch, n_layers=opt.n_ode_layers,
                                         n_units=opt.neural_ode_n_units, downsize=False, nonlinear='relu', device=device,
                                         final_act=False)
-        self.diffeq_solver = DiffEqSolver(self.ode_decoder_func, opt.decode_diff_method, device=device, memory=opt.mem)
+        self.diffeq_solver = DiffEqSolver(self.ode_decoder_func, opt.decode_diff_method, device=device, memory=opt.mem,
+                                          options=decode_options(opt))
         self.conv_decoder = Decoder(opt.neural_ode_decoder_out_ch, opt.in_channels, opt.n_downs, nonlinear='leaky_relu').to(device)
 
     def forward(self, inputs, batch_dict):

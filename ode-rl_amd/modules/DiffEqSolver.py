@@ -5,12 +5,12 @@ import torch
 import torch.nn as nn
 
 from ..helpers import utils
-from ..odeint import odeint, conv_stack_of
+from ..odeint import odeint, conv_stack_of, step_size_grid
 from .. import hip_ops
 
 
 class DiffEqSolver(nn.Module):
-    def __init__(self, ode_func, method, odeint_rtol=1e-4, odeint_atol=1e-5, device=torch.device("cpu"), memory=False):
+    def __init__(self, ode_func, method, odeint_rtol=1e-4, odeint_atol=1e-5, device=torch.device("cpu"), memory=False, options=None):
         super().__init__()
         self.ode_func = ode_func
         self.ode_method = method
@@ -18,6 +18,7 @@ class DiffEqSolver(nn.Module):
         self.memory = memory
         self.odeint_rtol = odeint_rtol
         self.odeint_atol = odeint_atol
+        self.options = options   # torchdiffeq's `options` of odeint (e.g. {"grid_constructor": step_size_grid(h)}); not used with memory=True
 
     def forward(self, first_point, time_steps_to_predict, backwards=False):
         """Integrate z0 over `time_steps_to_predict`; returns (T,B,C,H,W) time-first, out[0] == z0."""
@@ -33,10 +34,17 @@ class DiffEqSolver(nn.Module):
                 y_is.append(h_prev + pred_m.view(b, c, h, w))
             return torch.stack(y_is[1:]).permute(1, 0, 2, 3, 4)
         pred_y = odeint(self.ode_func, first_point, time_steps_to_predict, rtol=self.odeint_rtol,
-                        atol=self.odeint_atol, method=self.ode_method)
+                        atol=self.odeint_atol, method=self.ode_method, options=self.options)
         if pred_y.dim() == 3:
             pred_y = None  # reference :48-49
         return pred_y
+
+
+def decode_options(opt):
+    """The solver options of a model's decoder: an optional `opt.decode_step_size` h makes its fixed-grid solver step by h on an
+    internal grid (torchdiffeq's step_size), whatever the output frames are; absent or None: one step per frame, as ever."""
+    h = getattr(opt, "decode_step_size", None)
+    return None if h is None else {"grid_constructor": step_size_grid(h)}
 
 
 class ODEFunc(nn.Module):

@@ -7,7 +7,8 @@ Supported `func`: an `ODEFunc` (or any module exposing `gradient_net`, an nn.Seq
 autonomous (`ODEFunc.forward` ignores t: modules/DiffEqSolver.py:77), so `t` only sets step sizes.
 
 Semantics follow torchdiffeq 0.2.1: solution[0] = y0, float64 time, 'rk4' = 3/8 rule with one step per
-output interval, strictly decreasing t integrates the negated dynamics on -t.
+output interval -- or, with options={"grid_constructor": fn}, steps on the grid fn(func, y0, t) with the outputs interpolated
+linearly --, strictly decreasing t integrates the negated dynamics on -t.
 """
 import torch
 import torch.nn as nn
@@ -65,13 +66,60 @@ def conv_stack_of(func):
 
 
 def check_options(method, options, where="odeint"):
-    """torchdiffeq's `options` that this path implements: none for the fixed-grid methods (one step per output interval; `step_size`,
-    `grid_constructor`, `perturb` and `interp` would change the result and are refused rather than ignored), `first_step` and
-    `max_num_steps` for dopri5."""
-    known = set() if method in FIXED_GRID else {"first_step", "max_num_steps"}
-    unknown = set(options or {}) - known
+    """torchdiffeq's `options` that this path implements.  Fixed-grid methods, in `odeint` only: `grid_constructor` (an internal grid
+    of the caller's; the requested times are filled by linear interpolation) and `interp: "linear"` next to it; `step_size` stays
+    refused -- `step_size_grid(step_size)` builds torchdiffeq's grid for it --, as do `perturb` and any other `interp`: they would
+    change the result and are refused rather than ignored.  dopri5: `first_step` and `max_num_steps`.  Looks at no tensor."""
+    options = options or {}
+    if method in FIXED_GRID:
+        known = {"grid_constructor", "interp"} if where == "odeint" else set()
+    else:
+        known = {"first_step", "max_num_steps"}
+    unknown = set(options) - known
     if unknown:
-        raise ValueError(f"{where}(HIP): unsupported {method} options {sorted(unknown)}")
+        hint = ""
+        if "step_size" in unknown and where == "odeint":
+            hint = ': for a step size pass options={"grid_constructor": ode_rl_amd.step_size_grid(step_size)}'
+        elif method in FIXED_GRID and where != "odeint" and unknown & {"step_size", "grid_constructor", "interp"}:
+            hint = (": internal grids are implemented for odeint only (torchdiffeq's adjoint builds a new grid for every backward "
+                    "interval, which this path does not do)")
+        raise ValueError(f"{where}(HIP): unsupported {method} options {sorted(unknown)}{hint}")
+    if method in FIXED_GRID:
+        if "grid_constructor" in options and not callable(options["grid_constructor"]):
+            raise TypeError(f"{where}(HIP): options['grid_constructor'] must be callable as grid_constructor(func, y0, t), got "
+                            f"{type(options['grid_constructor']).__name__}")
+        if options.get("interp", "linear") != "linear":
+            raise ValueError(f"{where}(HIP): unsupported interp {options['interp']!r}: only \"linear\" is implemented")
+
+
+def step_size_grid(step_size):
+    """The grid constructor of torchdiffeq's `options={"step_size": h}` (_grid_constructor_from_step_size), for
+    `options={"grid_constructor": step_size_grid(h)}`: steps of h from t[0], the last one cut short at t[-1]; float64."""
+    step_size = float(step_size)
+    if not step_size > 0:
+        raise ValueError(f"step_size_grid: step_size must be positive, got {step_size!r}")
+
+    def grid_constructor(func, y0, t):
+        t = torch.as_tensor(t).detach().to("cpu", torch.float64)
+        niters = torch.ceil((t[-1] - t[0]) / step_size + 1).item()
+        grid = torch.arange(0, niters, dtype=torch.float64) * step_size + t[0]
+        grid[-1] = t[-1]
+        return grid
+    return grid_constructor
+
+
+def internal_grid(func, y0, th, options):
+    """The float64 host grid the fixed-grid solver steps through, from options["grid_constructor"](func, y0, t) with the (already
+    increasing) host times `th`, checked as torchdiffeq asserts; None without a constructor."""
+    ctor = (options or {}).get("grid_constructor")
+    if ctor is None:
+        return None
+    grid = hip_ops.host_times(ctor(func, y0, th))
+    if len(grid) < 1 or not bool(grid[0] == th[0]) or not bool(grid[-1] == th[-1]):
+        raise AssertionError("the grid of grid_constructor must start at t[0] and end at t[-1]")
+    if len(grid) > 1 and not bool((grid[1:] > grid[:-1]).all()):
+        raise AssertionError("the grid of grid_constructor must be strictly increasing")
+    return grid
 
 
 def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
@@ -97,6 +145,9 @@ def odeint_forward(func, y0, t, rtol, atol, method, options=None):
     stack = conv_stack_of(func)
     if method in FIXED_GRID:
         check_options(method, options)
+        grid = internal_grid(func, y0, th, options)   # of -t for a decreasing t: torchdiffeq flips time before it builds the solver
+        if grid is not None:
+            return hip_ops.odeint_fixed_on_grid(stack, method, y0, th, grid, negate=negate)
         return hip_ops.odeint_fixed(stack, method, y0, th, negate=negate)
     check_options(method, options)
     return run_dopri5(stack, y0, th, dopri5_cfg(rtol, atol, options), negate=negate)[0]
