@@ -297,7 +297,7 @@ struct EncLayout {
     off_pgg = take((size_t)2 * T * B * 2 * C * 4);
     off_pgc = take((size_t)2 * T * B * C * 4);
     off_tab = take((size_t)(ODEHIP_MAX_LAYERS + 6) * T * sizeof(WgradPair));  // every weight-gradient table of a backward pass: ONE upload
-    off_slab = take(((size_t)B * wgrad_esplit_max(B) + 1) * kWgradSlabFloats * 4);
+    off_slab = take(wgrad_slab_bytes(B));
     total = o;
   }
   float* p(void* ws, size_t off) const { return (float*)((char*)ws + off); }
@@ -580,34 +580,17 @@ extern "C" int odehip_odeconvgru_encode_backward(const odehip_encoder* e, const 
     const CatJob& J = jobs[j];
     for (int half = 0; half < 2; ++half) {
       const WgradPair* const table = table0 + (size_t)(NL + 2 * j + half) * T;
-      for (int co0 = 0; co0 < J.g_ch; co0 += 64)
-        for (int ci0 = 0; ci0 < C; ci0 += 64) {
-          if (ks == 5 && e->cell.w_gates_bf16)  // bf16 compute mode: operands rounded to bf16, fp32 accumulation
-            rc = launch_wgrad_tile_bf16_5x5(table, T, batch, 4, slabs, J.dw, J.db, 2 * C, co0, half * C + ci0, J.g_ch / 4, co0 / 4, C / 4,
-                                            ci0 / 4, half == 0 && ci0 == 0, stream);
-          else
-            rc = launch_wgrad_tile(table, T, batch, wgrad_esplit(batch, T), slabs, J.dw, J.db, ks, 2 * C, co0, half * C + ci0, J.g_ch / 4, co0 / 4, C / 4,
-                                   ci0 / 4, half == 0 && ci0 == 0, stream);
-          if (rc != ODEHIP_OK) return rc;
-        }
+      const bool bf16 = ks == 5 && e->cell.w_gates_bf16;  // bf16 compute mode: operands rounded to bf16, fp32 accumulation
+      rc = launch_wgrad_layer(table, T, batch, bf16 ? 4 : wgrad_esplit(batch, T), slabs, J.dw, J.db, ks, J.g_ch, C, 2 * C, half * C, bf16,
+                              half == 0, stream);
+      if (rc != ODEHIP_OK) return rc;
     }
   }
-  {
-    const WgradPair* table = table0 + (size_t)(NL + 4) * T;
-    for (int co0 = 0; co0 < OUT2; co0 += 64)
-      for (int ci0 = 0; ci0 < HH; ci0 += 64) {
-        rc = launch_wgrad_tile(table, 1, batch, 4, slabs, gr->w_head1, gr->b_head1, 1, HH, co0, ci0, OUT2 / 4, co0 / 4, HH / 4, ci0 / 4,
-                               ci0 == 0, stream);
-        if (rc != ODEHIP_OK) return rc;
-      }
-    table = table0 + (size_t)(NL + 5) * T;
-    for (int co0 = 0; co0 < HH; co0 += 64)
-      for (int ci0 = 0; ci0 < C; ci0 += 64) {
-        rc = launch_wgrad_tile(table, 1, batch, 4, slabs, gr->w_head0, gr->b_head0, 1, C, co0, ci0, HH / 4, co0 / 4, C / 4, ci0 / 4,
-                               ci0 == 0, stream);
-        if (rc != ODEHIP_OK) return rc;
-      }
-  }
+  // head 1x1 convs
+  rc = launch_wgrad_layer(table0 + (size_t)(NL + 4) * T, 1, batch, 4, slabs, gr->w_head1, gr->b_head1, 1, OUT2, HH, HH, 0, false, true, stream);
+  if (rc != ODEHIP_OK) return rc;
+  rc = launch_wgrad_layer(table0 + (size_t)(NL + 5) * T, 1, batch, 4, slabs, gr->w_head0, gr->b_head0, 1, HH, C, C, 0, false, true, stream);
+  if (rc != ODEHIP_OK) return rc;
   // GroupNorm affine parameters
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(2 * C), dim3(256), 0, stream, pgg, T * batch, 2 * C, gr->gn_gates_w);
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(2 * C), dim3(256), 0, stream, pgg + pgg_half, T * batch, 2 * C, gr->gn_gates_b);
@@ -632,7 +615,7 @@ struct CellBwdLayout {
     g_cand = take(hs); g_gates = take(2 * hs); gz_pre = take(hs); gh_ode = take(hs); g_rh = take(hs); gh = take(hs);
     pg = take((size_t)6 * batch * c->hidden * 4);  // [dgamma_g | dbeta_g] (2H each) then [dgamma_c | dbeta_c] (H each), per sample
     table = take(sizeof(WgradPair));
-    slabs = take(((size_t)batch * wgrad_esplit_max(batch) + 1) * kWgradSlabFloats * 4);
+    slabs = take(wgrad_slab_bytes(batch));
     total = o;
   }
 };
@@ -717,16 +700,9 @@ extern "C" int odehip_convgru_cell_backward(const odehip_convgru_cell* c, const 
       pr.a = half == 0 ? x : jobs[j].a2;
       if ((rc = upload_bytes(table, &pr, sizeof(pr), stream)) != ODEHIP_OK) return rc;
       const int a_ch = half == 0 ? I : H;
-      for (int co0 = 0; co0 < jobs[j].g_ch; co0 += 64)
-        for (int ci0 = 0; ci0 < a_ch; ci0 += 64) {
-          if (ks == 5 && c->w_gates_bf16)
-            rc = launch_wgrad_tile_bf16_5x5(table, 1, batch, 4, slabs, jobs[j].dw, jobs[j].db, I + H, co0, half * I + ci0,
-                                            jobs[j].g_ch / 4, co0 / 4, a_ch / 4, ci0 / 4, half == 0 && ci0 == 0, stream);
-          else
-            rc = launch_wgrad_tile(table, 1, batch, 4, slabs, jobs[j].dw, jobs[j].db, ks, I + H, co0, half * I + ci0, jobs[j].g_ch / 4,
-                                   co0 / 4, a_ch / 4, ci0 / 4, half == 0 && ci0 == 0, stream);
-          if (rc != ODEHIP_OK) return rc;
-        }
+      rc = launch_wgrad_layer(table, 1, batch, 4, slabs, jobs[j].dw, jobs[j].db, ks, jobs[j].g_ch, a_ch, I + H, half * I,
+                              ks == 5 && c->w_gates_bf16, half == 0, stream);
+      if (rc != ODEHIP_OK) return rc;
     }
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(2 * H), dim3(256), 0, stream, pgg, batch, 2 * H, gr->gn_gates_w);
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(2 * H), dim3(256), 0, stream, pgg + (size_t)batch * 2 * H, batch, 2 * H,

@@ -131,7 +131,7 @@ struct SeqLayout {
       off_pgg = take((size_t)2 * T * B * 2 * H * 4);   // [dgamma | dbeta][T*B][2H]
       off_pgc = take((size_t)2 * T * B * H * 4);
       off_tab = take((size_t)4 * T * sizeof(WgradPair));
-      off_slab = take(((size_t)B * wgrad_esplit_max(B) + 1) * kWgradSlabFloats * 4);
+      off_slab = take(wgrad_slab_bytes(B));
     }
     total = o;
   }
@@ -376,16 +376,9 @@ extern "C" int odehip_convgru_sequence_backward(const odehip_convgru_cell* c, co
       const WgradPair* const table = table0 + (size_t)(2 * j + half) * T + (half == 1 ? t_first : 0);
       const int n_eval = half == 0 ? T : n_state, a_ch = half == 0 ? I : H;
       const bool bias_here = half == 0 || !has_x;   // the launches over ALL steps carry the bias sums
-      for (int co0 = 0; co0 < g_ch; co0 += 64)
-        for (int ci0 = 0; ci0 < a_ch; ci0 += 64) {
-          if (bf)
-            rc = launch_wgrad_tile_bf16_5x5(table, n_eval, batch, 4, slabs, dw, db, I + H, co0, half * I + ci0, g_ch / 4, co0 / 4, a_ch / 4,
-                                            ci0 / 4, bias_here && ci0 == 0, stream);
-          else
-            rc = launch_wgrad_tile(table, n_eval, batch, wgrad_esplit(batch, n_eval), slabs, dw, db, 5, I + H, co0, half * I + ci0, g_ch / 4,
-                                   co0 / 4, a_ch / 4, ci0 / 4, bias_here && ci0 == 0, stream);
-          if (rc != ODEHIP_OK) return rc;
-        }
+      rc = launch_wgrad_layer(table, n_eval, batch, bf ? 4 : wgrad_esplit(batch, n_eval), slabs, dw, db, 5, g_ch, a_ch, I + H, half * I, bf,
+                              bias_here, stream);
+      if (rc != ODEHIP_OK) return rc;
     }
   }
   launch_reduce_rows(pgg, T * batch, 2 * H, gr->gn_gates_w, stream);

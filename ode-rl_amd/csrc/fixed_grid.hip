@@ -59,7 +59,7 @@ struct FixedLayout {
       off_gy = take(st);
       off_g2 = take(2 * st);
       off_tab = take(ne * sizeof(WgradPair) * ODEHIP_MAX_LAYERS);   // one table per layer, uploaded together
-      off_slab = take(((size_t)B * wgrad_esplit_max(B) + 1) * kWgradSlabFloats * 4);
+      off_slab = take(wgrad_slab_bytes(B));
     }
     total = o;
   }

@@ -213,7 +213,6 @@ struct WgradPair {
   float scale;     // weight of this evaluation in the sum (1 for discretise-then-optimise; dt*b_s for the adjoint)
   float pad_[3];
 };
-// bf16 = true: operands rounded to bf16 (fp32 accumulation), for stacks running in bf16 compute mode
 // floats per workgroup slab of the weight-gradient kernels: the Winograd-domain tile [16 positions][64][64] + 64 bias sums is the
 // largest; every slab region holds batch * esplit of them PLUS ONE (the fixed-order sum before the final G^T . G)
 constexpr int kWgradSlabFloats = 16 * 64 * 64 + 64;
@@ -226,12 +225,46 @@ inline int wgrad_esplit(int batch, int n_eval) {
   return e < 4 ? 4 : e;
 }
 inline int wgrad_esplit_max(int batch) { return batch >= 64 ? 4 : (256 / batch < 4 ? 4 : 256 / batch); }
-int launch_wgrad_wino(const WgradPair* table_dev, int n_eval, int batch, int esplit, float* slabs, float* dw, float* db, int cout,
-                      int cin, hipStream_t stream);  // wgrad_wino.hip; 1 = switched off
-int launch_wgrad(const WgradPair* table_dev, int n_eval, int batch, int esplit, float* slabs, float* dw, float* db, int cout,
-                 int cin, hipStream_t stream, bool bf16 = false);
+// bytes of the slab area of every weight-gradient caller: the slabs of the largest esplit and the one of the sum
+inline size_t wgrad_slab_bytes(int batch) { return ((size_t)batch * wgrad_esplit_max(batch) + 1) * kWgradSlabFloats * 4; }
+
+// One 64 x 64 tile of dW (cout_total, cin_total, ks, ks): output channels co0.. from G tensors with g_quads quads per sample (tile at
+// quad g_quad0), input channels ci0.. of the WEIGHT from A tensors with a_quads quads per sample (tile at a_quad0) -- the A tensor may be
+// one half of a concatenated conv input.  esplit workgroups per sample share the n_eval table entries; slabs: wgrad_slab_bytes(batch).
+struct WgradTile {
+  const WgradPair* table;
+  int n_eval, batch, esplit;
+  float* slabs;
+  float* dw;
+  float* db;
+  int ks, cin_total, co0, ci0;
+  int g_quads, g_quad0, a_quads, a_quad0;
+  bool write_bias;
+};
+// The weight gradient of one conv operand (wgrad.hip), walked in 64 x 64 tiles: G has cout channels, A the cin channels that sit at
+// ci_off of the conv's cin_total input channels (a plain layer: cin_total = cin, ci_off = 0).  bias: these launches carry the bias sums
+// (db is written with the tiles ci0 == 0).  bf16: operands rounded to bf16 (fp32 accumulation; 3x3 and 5x5), for layers in bf16 compute
+// mode.  fp32 3x3 whole layers and fp32 5x5 tiles run in the Winograd domain unless switched off.
+int launch_wgrad_layer(const WgradPair* table_dev, int n_eval, int batch, int esplit, float* slabs, float* dw, float* db, int ks, int cout,
+                       int cin, int cin_total, int ci_off, bool bf16, bool bias, hipStream_t stream);
+// a plain 3x3 layer
+inline int launch_wgrad(const WgradPair* table_dev, int n_eval, int batch, int esplit, float* slabs, float* dw, float* db, int cout,
+                        int cin, hipStream_t stream, bool bf16 = false) {
+  return launch_wgrad_layer(table_dev, n_eval, batch, esplit, slabs, dw, db, 3, cout, cin, cin, 0, bf16, true, stream);
+}
 int launch_wgrad_q4h(const WgradPair* table_dev, int n_eval, int batch, int esplit, float* slabs, float* dw, int accumulate,
                      hipStream_t stream);
+// the fp32 3x3 layer in the Winograd F(2x2,3x3) domain (wgrad_wino.hip); 1 = switched off
+int launch_wgrad_wino(const WgradPair* table_dev, int n_eval, int batch, int esplit, float* slabs, float* dw, float* db, int cout,
+                      int cin, hipStream_t stream);
+// a 64 x 64 tile of a 5x5 weight gradient in the Winograd F(2x2,5x5) domain (wgrad_wino5.hip); 1 = switched off
+int launch_wgrad_wino5(const WgradTile& t, hipStream_t stream);
+// sum[i] = sum over k < n_slabs of slabs[k * stride + i], i < n_vals, in a fixed order (16 interleaved partial sums of 4 chains each,
+// 16-byte loads: bitwise reproducible).  stride and n_vals multiples of 4 floats, slabs and sum 16-byte aligned.  (wgrad.hip)
+void launch_slab_sum4(const float* slabs, int n_slabs, int stride, int n_vals, float* sum, hipStream_t stream);
+// raises the dynamic-LDS limit of a weight-gradient kernel to 160 KiB, once per kernel (wgrad.hip)
+int wgrad_raise_lds(const void* kernel);
+
 int launch_ftraj_bf16_saving(const odehip_convstack* f, const float* z0_nchw, float* out_nchw, const float* hdev, int n_times, int batch,
                              void* save_x, size_t stride_x, void* save_h, size_t stride_h_eval, size_t stride_h_layer,
                              hipStream_t stream);
@@ -243,19 +276,6 @@ int launch_btraj_bf16_rk4(const odehip_convstack* f_dgrad, const float* grad_out
                           hipStream_t stream);
 // grad_b[l][ch] = sum over segments and samples of bias_part[seg][b][l][ch], in order
 int launch_bias_reduce(const float* bias_part, int n_parts, int n_layers, float* const* grad_b, hipStream_t stream);
-int launch_wgrad_tile(const WgradPair* table_dev, int n_eval, int batch, int esplit, float* slabs, float* dw, float* db, int ks,
-                      int cin_total, int co0, int ci0, int g_quads, int g_quad0, int a_quads, int a_quad0, bool write_bias,
-                      hipStream_t stream);
-
-// a 64 x 64 tile of a 5x5 weight gradient in the Winograd F(2x2,5x5) domain (wgrad_wino5.hip); 1 = switched off
-// sum[i] = sum over k < n_slabs of slabs[k * stride + i], i < n_vals, in a fixed order (16 interleaved partial sums of 4 chains each,
-// 16-byte loads: bitwise reproducible).  stride and n_vals multiples of 4 floats, slabs and sum 16-byte aligned.  (wgrad.hip)
-void launch_slab_sum4(const float* slabs, int n_slabs, int stride, int n_vals, float* sum, hipStream_t stream);
-int launch_wgrad_wino5(const WgradPair* table_dev, int n_eval, int batch, int esplit, float* slabs, float* dw, float* db, int cin_total,
-                       int co0, int ci0, int g_quads, int g_quad0, int a_quads, int a_quad0, bool write_bias, hipStream_t stream);
-int launch_wgrad_tile_bf16_5x5(const WgradPair* table_dev, int n_eval, int batch, int esplit, float* slabs, float* dw, float* db,
-                               int cin_total, int co0, int ci0, int g_quads, int g_quad0, int a_quads, int a_quad0, bool write_bias,
-                               hipStream_t stream);
 
 // Dormand-Prince 5(4) tableau as torchdiffeq 0.2.1 holds it (_impl/dopri5.py): beta rows, c_sol (= last beta row, padded),
 // c_error = c_sol - 4th-order weights, c_mid (dense-output midpoint weights)

@@ -3,8 +3,8 @@
 //   dg[co][ci] = G^T [ sum over evaluations e, samples b, tiles  (A dY A^T)[co] .* (B^T d B)[ci] ] G
 // (dY: the gradient w.r.t. the layer's output, d: the layer's saved input, both Q4; tools/experiments/winograd_wgrad_check.py:
 // identity 1e-15 in fp64, fp32 error 4.9e-7 rel-L2 against 5.5e-7 for the direct sum).  Y is linear in g, so the 16 multiplies of
-// the forward tile become 16 multiplies of the gradient tile: 2.25x fewer than the 36 of the direct sum (wgrad64_kernel), and the
-// contraction index is the TILE (64 per sample) instead of the pixel.  Same contract as wgrad64_kernel: one launch per layer and
+// the forward tile become 16 multiplies of the gradient tile: 2.25x fewer than the 36 of the direct sum (wgrad_tile_kernel<3, 0, 3>), and the
+// contraction index is the TILE (64 per sample) instead of the pixel.  Same contract as the direct kernel: one launch per layer and
 // 64x64 channel tile, workgroup (sample b, split s) walks its share of the evaluations and keeps the whole gradient tile -- here
 // 16 positions x 64 x 64 -- in MFMA accumulators (8 waves x 128 VGPRs); one slab per workgroup at the end, summed in a fixed order
 // (bitwise reproducible, no float atomics), then G^T . G per channel pair.
@@ -221,16 +221,13 @@ __global__ __launch_bounds__(256) void wgrad_wino_finish_kernel(const float* __r
   if (ci == 0 && ci0 == 0) db[co0 + co] = sum[16 * 64 * 64 + co];
 }
 
-// the fp32 3x3 weight gradient of launch_wgrad (wgrad.hip); returns 1 if switched off (ODEHIP_WGRAD_WINO=0: the direct kernel)
+// the fp32 3x3 weight gradient of a whole layer (launch_wgrad_layer, wgrad.hip); returns 1 if switched off (ODEHIP_WGRAD_WINO=0: the direct kernel)
 int launch_wgrad_wino(const WgradPair* table_dev, int n_eval, int batch, int esplit, float* slabs, float* dw, float* db, int cout,
                       int cin, hipStream_t stream) {
   static const bool off = [] { const char* e = getenv("ODEHIP_WGRAD_WINO"); return e && e[0] == '0'; }();
   if (off) return 1;
-  static bool attr_set = false;
-  if (!attr_set) {
-    ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad64_wino2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  const int rc = wgrad_raise_lds((const void*)wgrad64_wino2_kernel);
+  if (rc != ODEHIP_OK) return rc;
   float* const sum = slabs + (size_t)batch * esplit * kWgradSlabFloats;  // the slab region is sized for one more slab
   for (int co0 = 0; co0 < cout; co0 += 64)
     for (int ci0 = 0; ci0 < cin; ci0 += 64) {

@@ -265,26 +265,23 @@ __global__ __launch_bounds__(256) void wgrad_wino5_finish_kernel(const float* __
   if (write_bias && ci == 0) db[co0 + co] = sum[36 * 32 * 32 + co];
 }
 
-// One 64 x 64 tile of a 5x5 weight gradient (the contract of launch_wgrad_tile, wgrad.hip) as four 32 x 32 launches in the Winograd
-// domain.  Returns 1 if switched off (ODEHIP_WGRAD_WINO5=0: the direct kernel).  slabs: (batch * esplit + 1) * kWgradSlabFloats floats.
-int launch_wgrad_wino5(const WgradPair* table_dev, int n_eval, int batch, int esplit, float* slabs, float* dw, float* db, int cin_total,
-                       int co0, int ci0, int g_quads, int g_quad0, int a_quads, int a_quad0, bool write_bias, hipStream_t stream) {
+// One 64 x 64 tile of a 5x5 weight gradient (WgradTile, odehip_internal.h) as four 32 x 32 launches in the Winograd domain.  Returns 1
+// if switched off (ODEHIP_WGRAD_WINO5=0: the direct kernel).  slabs: (batch * esplit + 1) * kWgradSlabFloats floats.
+int launch_wgrad_wino5(const WgradTile& t, hipStream_t stream) {
   static const bool off = [] { const char* e = getenv("ODEHIP_WGRAD_WINO5"); return e && e[0] == '0'; }();
   if (off) return 1;
   static_assert(kW5Slab <= kWgradSlabFloats, "a slab of this kernel must fit the callers' slab allocation");
-  static bool attr_set = false;
-  if (!attr_set) {
-    ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)wgrad32_wino5_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
-  float* const sum = slabs + (size_t)batch * esplit * kWgradSlabFloats;  // the slab region is sized for one more slab
+  const int rc = wgrad_raise_lds((const void*)wgrad32_wino5_kernel);
+  if (rc != ODEHIP_OK) return rc;
+  const int n_slabs = t.batch * t.esplit;
+  float* const sum = t.slabs + (size_t)n_slabs * kWgradSlabFloats;  // the slab region is sized for one more slab
   for (int cs = 0; cs < 2; ++cs)
     for (int as = 0; as < 2; ++as) {
-      hipLaunchKernelGGL(wgrad32_wino5_kernel, dim3(batch, esplit), dim3(512), kW5Lds, stream, table_dev, n_eval, esplit, slabs, kWgradSlabFloats,
-                         g_quad0 + 8 * cs, g_quads, a_quad0 + 8 * as, a_quads);
-      launch_slab_sum4(slabs, batch * esplit, kWgradSlabFloats, kW5Slab, sum, stream);
-      hipLaunchKernelGGL(wgrad_wino5_finish_kernel, dim3(4), dim3(256), 0, stream, sum, dw, db, cin_total, co0 + 32 * cs, ci0 + 32 * as,
-                         (int)(write_bias && as == 0));
+      hipLaunchKernelGGL(wgrad32_wino5_kernel, dim3(t.batch, t.esplit), dim3(512), kW5Lds, stream, t.table, t.n_eval, t.esplit, t.slabs,
+                         kWgradSlabFloats, t.g_quad0 + 8 * cs, t.g_quads, t.a_quad0 + 8 * as, t.a_quads);
+      launch_slab_sum4(t.slabs, n_slabs, kWgradSlabFloats, kW5Slab, sum, stream);
+      hipLaunchKernelGGL(wgrad_wino5_finish_kernel, dim3(4), dim3(256), 0, stream, sum, t.dw, t.db, t.cin_total, t.co0 + 32 * cs,
+                         t.ci0 + 32 * as, (int)(t.write_bias && as == 0));
     }
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
