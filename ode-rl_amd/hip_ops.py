@@ -958,7 +958,8 @@ def _cell_bwd_packs(packed_cell, d, mode, extra_jobs=()):
     packs = pack_conv_weights_many([(w, 0, True) for w in slices] + list(extra_jobs) + ([(w, 2, True) for w in slices] if want_wino else []))
     keep, extra = packs[:4], packs[4:4 + len(extra_jobs)]
     bf = [None] * 4
-    if mode == "bf16" and d.ks == 5 and all(w.shape[0] <= 128 and w.shape[0] % 16 == 0 and w.shape[1] % 32 == 0 for w in slices):
+    # only where the forward runs in bf16 too (_bf16_cell_ok): a cell the bf16 kernels do not serve stays fp32 in both directions
+    if mode == "bf16" and d.ks == 5 and d.w_gates_bf16 and all(w.shape[0] <= 128 and w.shape[0] % 16 == 0 and w.shape[1] % 32 == 0 for w in slices):
         bf = [pack_conv_weight_bf16_ks(w, True) for w in slices]
     wino = packs[4 + len(extra_jobs):] if want_wino else [None] * 4
     return keep + extra, bf, wino

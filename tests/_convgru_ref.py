@@ -8,10 +8,10 @@ from conftest import procedural_state_dict, rel_l2
 from oracle import reference_modules as rm
 
 
-def cell_state_dict(input_dim, hidden, seed):
-    shapes = {"conv_gates.0.weight": (2 * hidden, input_dim + hidden, 5, 5), "conv_gates.0.bias": (2 * hidden,),
+def cell_state_dict(input_dim, hidden, seed, ks=5):
+    shapes = {"conv_gates.0.weight": (2 * hidden, input_dim + hidden, ks, ks), "conv_gates.0.bias": (2 * hidden,),
               "conv_gates.1.weight": (2 * hidden,), "conv_gates.1.bias": (2 * hidden,),
-              "conv_can.0.weight": (hidden, input_dim + hidden, 5, 5), "conv_can.0.bias": (hidden,),
+              "conv_can.0.weight": (hidden, input_dim + hidden, ks, ks), "conv_can.0.bias": (hidden,),
               "conv_can.1.weight": (hidden,), "conv_can.1.bias": (hidden,)}
     return procedural_state_dict({k: torch.zeros(s) for k, s in shapes.items()}, seed)
 

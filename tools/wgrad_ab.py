@@ -5,27 +5,25 @@
                                                                         weight gradients switched off (the direct fp32 kernels)
   python tools/wgrad_ab.py compare <a.pt> <b.pt>                        torch.equal on every tensor; exit status 1 on a difference
 
-Cases are built the way the tests build theirs (test_hip_backward, test_hip_bf16, test_hip_convgru_sequence, test_hip_encoder_backward) at
-the smallest shapes at which each path can still go wrong; the sums are deterministic by design, so there is no tolerance."""
+Cases run through the builders of tests/_wgrad_cases.py (shared with tests/test_hip_wgrad.py) at the smallest shapes at which each
+path can still go wrong; the sums are deterministic by design, so there is no tolerance."""
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import _wgrad_cases as wc   # noqa: E402  (the one set of case builders, shared with tests/test_hip_wgrad.py)
 
 
-def _stack_grads(dev, n_units, method, T, B, seed, n_layers=3):
+def _stack_grads(dev, n_units, method, T, B, seed, n_layers=3):   # the module's own initialisation under a fixed seed
     import torch
-    import ode_rl_amd
     torch.manual_seed(seed)
-    f = ode_rl_amd.ODEFunc(64, 64, n_layers, n_units, False, "relu", final_act=False).to(dev)
     g = torch.Generator().manual_seed(seed + 1)
-    z = (torch.randn(B, 64, 16, 16, generator=g) * 0.5).to(dev).requires_grad_(True)
-    t = torch.arange(T, 2 * T, dtype=torch.float64) / (2 * T)
-    gout = torch.randn(T, B, 64, 16, 16, generator=g).to(dev)
-    ode_rl_amd.odeint(f, z, t, method=method).backward(gout)
-    convs = [m for m in f.gradient_net if isinstance(m, torch.nn.Conv2d)]
-    return [z.grad] + [c.weight.grad for c in convs] + [c.bias.grad for c in convs]
+    spec = {"n_layers": n_layers, "n_units": n_units, "method": method, "sd": None, "z0": torch.randn(B, 64, 16, 16, generator=g) * 0.5,
+            "t": torch.arange(T, 2 * T, dtype=torch.float64) / (2 * T), "gout": torch.randn(T, B, 64, 16, 16, generator=g)}
+    return list(wc.stack_grads(dev, spec).values())
 
 
 def _module_grads(module, inputs, outputs):
@@ -47,27 +45,14 @@ def _encoder_grads(dev, T=2, B=2, ch=64):   # ODE-ConvGRU encoder: 3x3 dynamics,
     return _module_grads(enc, [x], [mean, std])
 
 
-def _cell(dev, ch=64):
+def _cell_grads(dev, driver, ch=64):   # "step": the per-step driver (convgru_backward.hip); "rollout": the whole-sequence one (convgru_sequence.hip)
     import torch
-    import ode_rl_amd
     torch.manual_seed(5)
-    cell = ode_rl_amd.ConvGRUCell((16, 16), ch, ch, 5).to(dev)
     g = torch.Generator().manual_seed(6)
-    xs = (torch.randn(2, 2, ch, 16, 16, generator=g) * 0.5).to(dev).requires_grad_(True)
-    h0 = (torch.randn(2, ch, 16, 16, generator=g) * 0.5).to(dev).requires_grad_(True)
-    return cell, xs, h0
-
-
-def _cell_step_grads(dev):       # the per-step driver (convgru_backward.hip), two chained steps
-    cell, xs, h0 = _cell(dev)
-    _, out = cell(input_tensor=xs, h_cur=h0, seq_len=2)
-    return _module_grads(cell, [xs, h0], [out])
-
-
-def _cell_sequence_grads(dev):   # the whole-sequence driver (convgru_sequence.hip)
-    cell, xs, h0 = _cell(dev)
-    hs, last = cell.rollout(xs, h0, 2)
-    return _module_grads(cell, [xs, h0], [hs, last])
+    spec = {"I": ch, "H": ch, "ks": 5, "driver": driver, "T": 2, "sd": None, "x": torch.randn(2, 2, ch, 16, 16, generator=g) * 0.5,
+            "h0": torch.randn(2, ch, 16, 16, generator=g) * 0.5, "gw": torch.randn(2, 2, ch, 16, 16, generator=g),
+            "gl": torch.randn(2, ch, 16, 16, generator=g)}
+    return list(wc.cell_grads(dev, spec).values())
 
 
 def run(out_path, off):
@@ -83,8 +68,8 @@ def run(out_path, off):
     # a 128-channel hidden layer: the co0 and ci0 loops take two steps each
     res["stack128.euler.T2.B1"] = _stack_grads(dev, 128, "euler", 2, 1, 22, n_layers=1)
     res["encoder.C64.T2.B2"] = _encoder_grads(dev)
-    res["cell_step.C64.B2"] = _cell_step_grads(dev)
-    res["cell_sequence.C64.T2.B2"] = _cell_sequence_grads(dev)
+    res["cell_step.C64.B2"] = _cell_grads(dev, "step")
+    res["cell_sequence.C64.T2.B2"] = _cell_grads(dev, "rollout")
     if not off:
         res["stack64.rk4.T3.B20"] = _stack_grads(dev, 64, "rk4", 3, 20, 21)   # esplit = 8 = n_eval
         ode_rl_amd.set_compute_dtype("bf16")
@@ -94,8 +79,8 @@ def run(out_path, off):
             lib.odehip_set_persistent_trajectory(1)
             res["bf16.stack64.whole_trajectory.T17.B3"] = _stack_grads(dev, 64, "rk4", 17, 3, 24)   # Q4h operands, two segments: accumulate
             res["bf16.encoder.C64.T2.B2"] = _encoder_grads(dev)
-            res["bf16.cell_step.C64.B2"] = _cell_step_grads(dev)
-            res["bf16.cell_sequence.C64.T2.B2"] = _cell_sequence_grads(dev)
+            res["bf16.cell_step.C64.B2"] = _cell_grads(dev, "step")
+            res["bf16.cell_sequence.C64.T2.B2"] = _cell_grads(dev, "rollout")
         finally:
             lib.odehip_set_persistent_trajectory(was)
             ode_rl_amd.set_compute_dtype(None)
