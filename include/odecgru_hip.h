@@ -247,11 +247,22 @@ size_t odehip_encoder_workspace_bytes(const odehip_encoder* e, int n_frames, int
 /* inputs (T,B,C,16,16) time-first NCHW, t_host[T] float64 -> mean_z0, std_z0 (B,out_ch,16,16); latent (B,T,C,16,16) or NULL
  * (slot k of a sample = the state after the k-th VISITED frame, as the reference stacks them, ODEConvGRUCell.py:74,76).
  * ODEConvGRUCell.forward / run_ode_conv_gru: run_backwards != 0 visits the frames T-1 .. 0 (what forward() does, :33),
- * 0 visits them 0 .. T-1 with the step sizes the reference's loop then produces (:47,73); `mask` is ignored as in the
- * reference (ConvGRUCell.py:55-86). */
+ * 0 visits them 0 .. T-1 with the step sizes the reference's loop then produces (:47,73).  This entry point has no observation
+ * mask, as the reference's cell takes one and forgets it (ConvGRUCell.py:55-86): it is odehip_odeconvgru_encode_masked with NULL. */
 int odehip_odeconvgru_encode(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames, int batch,
                              int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw, void* workspace,
                              size_t workspace_bytes, void* stream);
+/* The same with the observation mask of upstream Vid-ODE (models/base_conv_gru.py:66-70).  mask_tb: (T, B) float32 on the device,
+ * mask_tb[i*B + b] = m belongs to FRAME i of sample b whenever that frame is visited (run_backwards changes the visiting order,
+ * not the indexing), or NULL = every frame observed = exactly the launches of odehip_odeconvgru_encode.  Per step, with h_ode the
+ * Euler-advanced state and h' the cell's result:  m == 1: h', bit for bit what the unmasked call writes;  m == 0: h_ode, copied --
+ * nothing the cell computed for that sample is read, so a non-finite unobserved frame stays out of the result;  otherwise
+ * m h' + (1 - m) h_ode in fp32.  The step's latent slot receives the blended state.  The mask is read on the device (one scalar per
+ * workgroup of the update kernel); the convolutions run for every sample either way.  Workspace: odehip_encoder_workspace_bytes.
+ * Arguments are checked before any HIP call (ODEHIP_EINVAL).  Pure additions: ODEHIP_ABI_VERSION stays. */
+int odehip_odeconvgru_encode_masked(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames, int batch,
+                                    int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw, void* workspace,
+                                    size_t workspace_bytes, void* stream, const float* mask_tb);
 
 /* Backward of one ConvGRU step (ConvGRUCell.forward with seq_len = 1): grad_h_next -> grad_x, grad_h and the gradients of
  * the cell's eight parameters.  Stateless: the step is recomputed from (x, h) inside the call.  input_dim and hidden_dim
@@ -349,6 +360,20 @@ int odehip_odeconvgru_encode_backward(const odehip_encoder* e, const odehip_enco
                                       int batch, int run_backwards, const float* grad_mean_nchw, const float* grad_std_nchw,
                                       const float* grad_latent_nchw, float* grad_inputs_nchw, const odehip_encoder_grads* grads,
                                       void* workspace, size_t workspace_bytes, void* stream);
+/* The pair with the observation mask of odehip_odeconvgru_encode_masked (mask_tb (T, B) on the device or NULL; the two calls above
+ * are these with NULL).  Nothing of the mask is kept in the workspace (odehip_encoder_train_workspace_bytes as before): the backward
+ * call is handed the SAME pointer, whose contents must not have changed.  With g the gradient at the blended state of a step, the
+ * cell's chain is fed m g and h_ode additionally receives (1 - m) g: nothing is added for m == 1; for m == 0 the chain is fed exact
+ * zeros, stored as such and not as products with what the forward kept.  So with finite frames an unobserved (frame, sample) has
+ * an exactly zero grad_inputs slice and contributes exact zeros to every weight, bias and GroupNorm-affine gradient.  A NON-FINITE
+ * unobserved frame is contained by the forward only: the weight-gradient products multiply it by those zeros. */
+int odehip_odeconvgru_encode_train_masked(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames,
+                                          int batch, int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw,
+                                          void* workspace, size_t workspace_bytes, void* stream, const float* mask_tb);
+int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e, const odehip_encoder_bwd* eb, const double* t_host, int n_frames,
+                                             int batch, int run_backwards, const float* grad_mean_nchw, const float* grad_std_nchw,
+                                             const float* grad_latent_nchw, float* grad_inputs_nchw, const odehip_encoder_grads* grads,
+                                             void* workspace, size_t workspace_bytes, void* stream, const float* mask_tb);
 
 /* ---- odeint, adaptive dopri5 (torchdiffeq Dopri5Solver; the reference's default method, configs.yaml:79) ------ */
 

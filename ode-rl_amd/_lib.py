@@ -258,6 +258,10 @@ SIGNATURES = {
                                                 ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_size_t, ctypes.c_void_p]),
+    "odehip_odeconvgru_encode_masked": (ctypes.c_int, [ctypes.POINTER(EncoderDesc), ctypes.c_void_p,
+                                                       ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     "odehip_dopri5_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ConvStack), ctypes.c_int, ctypes.c_int]),
     "odehip_convgru_cell_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ConvGRUCellDesc), ctypes.c_int]),
     "odehip_convgru_cell_backward": (ctypes.c_int, [ctypes.POINTER(ConvGRUCellDesc), ctypes.POINTER(ConvGRUCellBwd),
@@ -274,6 +278,15 @@ SIGNATURES = {
                                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                          ctypes.POINTER(EncoderGrads), ctypes.c_void_p, ctypes.c_size_t,
                                                          ctypes.c_void_p]),
+    "odehip_odeconvgru_encode_train_masked": (ctypes.c_int, [ctypes.POINTER(EncoderDesc), ctypes.c_void_p,
+                                                             ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                             ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "odehip_odeconvgru_encode_backward_masked": (ctypes.c_int, [ctypes.POINTER(EncoderDesc), ctypes.POINTER(EncoderBwd),
+                                                                ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                                ctypes.POINTER(EncoderGrads), ctypes.c_void_p, ctypes.c_size_t,
+                                                                ctypes.c_void_p, ctypes.c_void_p]),
     "odehip_odeint_dopri5": (ctypes.c_int, [ctypes.POINTER(ConvStack), ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
                                             ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_double, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),

@@ -13,6 +13,9 @@
 //   gn_gates_kernel: GroupNorm + sigmoid; writes z and r*h_ode                one workgroup per (sample, 32-ch group)
 //   conv5x5(cat(x, r*h_ode)) -> cand_raw
 //   gn_update_kernel: GroupNorm + tanh + h' = (1-z) h_ode + z cand
+// Observation mask (odehip_odeconvgru_encode_masked; upstream Vid-ODE models/base_conv_gru.py:66-70, which the reference's cell takes
+// and forgets): the state a step leaves is m h' + (1-m) h_ode with m = mask[frame, sample], decided inside gn_update_kernel<true>
+// per workgroup.  The convolutions above run for every sample either way; without a mask the launches are gn_update_kernel<false>.
 // In the Q4 layout a 32-channel group of one sample is 32 KiB contiguous, so a workgroup holds its whole group in
 // registers (32 floats per thread): statistics are exact two-pass fp32, one HBM read, one write.
 #include <string.h>
@@ -44,13 +47,33 @@ __global__ __launch_bounds__(256) void gn_gates_kernel(const float* __restrict__
 }
 
 // cand_raw: (B,hid) Q4.  h' = (1 - z) h + z tanh(GN(cand_raw)); optionally also written to an NCHW slot (latent_ys).
+// kMasked: mask_b[b] = m, the observation mask of this step's frame for sample b (one scalar per workgroup, so the branches
+// are uniform).  m == 1: h' as above, bit for bit what the unmasked instantiation writes; m == 0: h is copied and nothing the
+// cell computed is read; otherwise m h' + (1 - m) h.  The unmasked instantiation never reads mask_b.
+template <bool kMasked>
 __global__ __launch_bounds__(256) void gn_update_kernel(const float* __restrict__ cand_raw, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, const float* __restrict__ h,
                                                         const float* __restrict__ z, float* __restrict__ h_out,
                                                         float* __restrict__ h_out_nchw, long long nchw_batch_stride,
-                                                        int hid_groups) {
+                                                        int hid_groups, const float* __restrict__ mask_b) {
   __shared__ float sh[4];
   const int g = blockIdx.x, b = blockIdx.y;
+  const float m = kMasked ? mask_b[b] : 1.0f;
+  if (kMasked && m == 0.0f) {  // unobserved: the Euler-advanced state goes on unchanged
+    const size_t base = ((size_t)(b * hid_groups + g) * 8) * kPix;
+    const f32x4* hp = (const f32x4*)h + base + threadIdx.x;
+    f32x4* op = (f32x4*)h_out + base + threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const f32x4 o = hp[q * kPix];
+      op[q * kPix] = o;
+      if (h_out_nchw) {
+        float* n = h_out_nchw + (size_t)b * nchw_batch_stride + (size_t)(g * 32 + q * 4) * kPix + threadIdx.x;
+        n[0] = o.x; n[kPix] = o.y; n[2 * kPix] = o.z; n[3 * kPix] = o.w;
+      }
+    }
+    return;
+  }
   f32x4 v[8];
   load_group(cand_raw, b, hid_groups, g, v);
   group_norm(v, gamma, beta, g, 1e-5f, sh);
@@ -62,7 +85,8 @@ __global__ __launch_bounds__(256) void gn_update_kernel(const float* __restrict_
   for (int q = 0; q < 8; ++q) {
     const f32x4 c = {tanhf(v[q].x), tanhf(v[q].y), tanhf(v[q].z), tanhf(v[q].w)};
     const f32x4 zz = zp[q * kPix], hh = hp[q * kPix];
-    const f32x4 o = (1.0f - zz) * hh + zz * c;
+    f32x4 o = (1.0f - zz) * hh + zz * c;
+    if (kMasked && m != 1.0f) o = m * o + (1.0f - m) * hh;
     op[q * kPix] = o;
     if (h_out_nchw) {
       float* n = h_out_nchw + (size_t)b * nchw_batch_stride + (size_t)(g * 32 + q * 4) * kPix + threadIdx.x;
@@ -130,10 +154,11 @@ static int check_cell(const odehip_convgru_cell* c) {
   return ODEHIP_OK;
 }
 
-// one ConvGRU step on Q4 tensors; scratch: gates_raw (B,2H), z (B,H), rh (B,H), cand_raw (B,H)
+// one ConvGRU step on Q4 tensors; scratch: gates_raw (B,2H), z (B,H), rh (B,H), cand_raw (B,H); mask_b: the step's B observation
+// mask values on the device, or null (every sample observed)
 static int cell_step(const odehip_convgru_cell* c, const float* x, const float* h, float* h_out, float* h_out_nchw,
                      long long nchw_batch_stride, int batch, float* gates_raw, float* z, float* rh, float* cand_raw,
-                     hipStream_t stream) {
+                     hipStream_t stream, const float* mask_b = nullptr) {
   const int H = c->hidden, I = c->input;
   int rc = conv_layer(x, h, I, I + H, 2 * H, c->ks, c->w_gates, c->b_gates, gates_raw, 0, batch, stream, c->w_gates_bf16, c->w_gates_wino);
   if (rc != ODEHIP_OK) return rc;
@@ -141,8 +166,12 @@ static int cell_step(const odehip_convgru_cell* c, const float* x, const float* 
                      rh, H / 32);
   rc = conv_layer(x, rh, I, I + H, H, c->ks, c->w_can, c->b_can, cand_raw, 0, batch, stream, c->w_can_bf16, c->w_can_wino);
   if (rc != ODEHIP_OK) return rc;
-  hipLaunchKernelGGL(gn_update_kernel, dim3(H / 32, batch), dim3(256), 0, stream, cand_raw, c->gn_can_w, c->gn_can_b, h, z, h_out,
-                     h_out_nchw, nchw_batch_stride, H / 32);
+  if (mask_b)
+    hipLaunchKernelGGL(gn_update_kernel<true>, dim3(H / 32, batch), dim3(256), 0, stream, cand_raw, c->gn_can_w, c->gn_can_b, h, z, h_out,
+                       h_out_nchw, nchw_batch_stride, H / 32, mask_b);
+  else
+    hipLaunchKernelGGL(gn_update_kernel<false>, dim3(H / 32, batch), dim3(256), 0, stream, cand_raw, c->gn_can_w, c->gn_can_b, h, z, h_out,
+                       h_out_nchw, nchw_batch_stride, H / 32, nullptr);
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
 }
@@ -155,8 +184,9 @@ extern "C" size_t odehip_convgru_cell_workspace_bytes(const odehip_convgru_cell*
 
 namespace odehip {  // shared with the training path (convgru_backward.hip)
 int cell_step_q4(const odehip_convgru_cell* c, const float* x, const float* h, float* h_out, float* h_out_nchw,
-                 long long nchw_batch_stride, int batch, float* gates_raw, float* z, float* rh, float* cand_raw, hipStream_t stream) {
-  return cell_step(c, x, h, h_out, h_out_nchw, nchw_batch_stride, batch, gates_raw, z, rh, cand_raw, stream);
+                 long long nchw_batch_stride, int batch, float* gates_raw, float* z, float* rh, float* cand_raw, hipStream_t stream,
+                 const float* mask_b) {
+  return cell_step(c, x, h, h_out, h_out_nchw, nchw_batch_stride, batch, gates_raw, z, rh, cand_raw, stream, mask_b);
 }
 int conv_layer_q4(const float* src1, const float* src2, int cin1, int cin, int cout, int ks, const float* wp, const float* bias,
                   float* dst, int relu, int batch, hipStream_t stream) {
@@ -209,6 +239,14 @@ extern "C" size_t odehip_encoder_workspace_bytes(const odehip_encoder* e, int n_
 extern "C" int odehip_odeconvgru_encode(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames,
                                         int batch, int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw,
                                         void* workspace, size_t workspace_bytes, void* stream_) {
+  return odehip_odeconvgru_encode_masked(e, inputs_nchw, t_host, n_frames, batch, run_backwards, mean_nchw, std_nchw, latent_nchw, workspace,
+                                         workspace_bytes, stream_, nullptr);
+}
+
+// mask_tb: (T, B) on the device, row i = the observation mask of FRAME i (whenever it is visited), or null = all observed
+extern "C" int odehip_odeconvgru_encode_masked(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames,
+                                               int batch, int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw,
+                                               void* workspace, size_t workspace_bytes, void* stream_, const float* mask_tb) {
   ODEHIP_REQUIRE(e, "odeconvgru_encode: null descriptor");
   int rc = check_stack(&e->f_enc);
   if (rc != ODEHIP_OK) return rc;
@@ -271,7 +309,7 @@ extern "C" int odehip_odeconvgru_encode(const odehip_encoder* e, const float* in
     if (rc != ODEHIP_OK) return rc;
     float* lat = latent_nchw ? latent_nchw + (size_t)idx * C * kPix : nullptr;  // latent_ys (B,T,C,H,W): slot idx of each sample
     rc = cell_step(&e->cell, frames + (size_t)i * hf, h_ode, hbuf[cur ^ 1], lat, (long long)n_frames * C * kPix, batch, gates, z,
-                   rh, cand, stream);
+                   rh, cand, stream, mask_tb ? mask_tb + (size_t)i * batch : nullptr);
     if (rc != ODEHIP_OK) return rc;
     cur ^= 1;
   }

@@ -15,6 +15,11 @@
 // GroupNorm statistics, sigmoid/tanh outputs are recomputed from the saved pre-normalisation tensors inside the fused
 // backward kernels (a 32-channel group of one sample lives in the registers of one workgroup) -- nothing but conv
 // outputs is stored.  Deterministic: no float atomics.
+// Observation mask (the *_masked entry points): the forward blends  state = m h' + (1-m) h_ode  in gn_update_kernel<true>; the sweep
+// feeds the cell's chain m gh and adds (1-m) gh to gh_ode in gn_update_bwd_kernel<true>, nothing else changes.  For m == 0 that
+// kernel stores exact zeros, so every later product of an unobserved (frame, sample) is 0 * (what the forward kept): exactly zero
+// for finite frames.  Containment of a NON-FINITE unobserved frame is promised for the forward only -- here the input-gradient and
+// weight-gradient products would multiply it by those zeros.
 #include <string.h>
 
 #include <vector>
@@ -116,19 +121,43 @@ __device__ __forceinline__ void gn_backward(f32x4 (&gy)[8], const f32x4 (&xh)[8]
 }
 
 // backward of  h' = (1-z) h_ode + z tanh(GN(cand_raw))  for one (sample, group of 32 hidden channels)
+// kMasked: mask_b[b] = m of the forward's blend  state = m h' + (1-m) h_ode  (uniform per workgroup); gh is the gradient at the
+// blended state.  The cell's chain is fed m gh and h_ode receives (1-m) gh on top.  m == 1: the unmasked arithmetic, nothing
+// added.  m == 0: gh_ode = gh itself and every other output of this workgroup (g_cand_raw, gz_pre, its dgamma / dbeta partial rows)
+// is stored as exact zeros -- not as a product with what the forward kept, which may be non-finite for an unobserved frame.
+template <bool kMasked>
 __global__ __launch_bounds__(256) void gn_update_bwd_kernel(const float* __restrict__ cand_raw, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, const float* __restrict__ gh,
                                                             const float* __restrict__ z, const float* __restrict__ h_ode,
                                                             float* __restrict__ g_cand_raw, float* __restrict__ gz_pre,
                                                             float* __restrict__ gh_ode, float* __restrict__ dgamma_part,
-                                                            float* __restrict__ dbeta_part, int hid_groups) {
+                                                            float* __restrict__ dbeta_part, int hid_groups,
+                                                            const float* __restrict__ mask_b) {
   __shared__ float sh[4];
   __shared__ float shc[256];
   const int g = blockIdx.x, b = blockIdx.y;
+  const int H = hid_groups * 32;
   f32x4 xh[8], gy[8], t[8];
+  const float m = kMasked ? mask_b[b] : 1.0f;
+  if (kMasked && m == 0.0f) {
+    load_grp(gh, b, hid_groups, g, gy);
+    store_grp(gh_ode, b, hid_groups, g, gy);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) t[q] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    store_grp(gz_pre, b, hid_groups, g, t);
+    store_grp(g_cand_raw, b, hid_groups, g, t);
+    if (threadIdx.x < 32) dgamma_part[(size_t)b * H + g * 32 + threadIdx.x] = 0.0f;
+    else if (threadIdx.x < 64) dbeta_part[(size_t)b * H + g * 32 + threadIdx.x - 32] = 0.0f;
+    return;
+  }
   load_grp(cand_raw, b, hid_groups, g, xh);
   const float rstd = normalise(xh, sh);
   load_grp(gh, b, hid_groups, g, gy);
+  const bool blend = kMasked && m != 1.0f;
+  if (blend) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) gy[q] *= m;  // what the cell's chain is fed
+  }
   f32x4 zz[8], hh[8];
   load_grp(z, b, hid_groups, g, zz);
   load_grp(h_ode, b, hid_groups, g, hh);
@@ -144,9 +173,14 @@ __global__ __launch_bounds__(256) void gn_update_bwd_kernel(const float* __restr
   }
   store_grp(gz_pre, b, hid_groups, g, t);
   store_grp(gh_ode, b, hid_groups, g, hh);
-  const int H = hid_groups * 32;
   gn_backward(gy, xh, gamma, g, rstd, dgamma_part + (size_t)b * H, dbeta_part + (size_t)b * H, sh, shc);
   store_grp(g_cand_raw, b, hid_groups, g, gy);
+  if (blend) {  // the part of the blend that bypasses the cell: gh_ode += (1-m) gh, once the group's registers are free again
+    const f32x4* gp = (const f32x4*)(gh + ((size_t)(b * hid_groups + g) * 8) * kPix * 4) + threadIdx.x;
+    f32x4* p = (f32x4*)(gh_ode + ((size_t)(b * hid_groups + g) * 8) * kPix * 4) + threadIdx.x;  // this thread's own stores above
+#pragma unroll
+    for (int q = 0; q < 8; ++q) p[q * kPix] += (1.0f - m) * gp[q * kPix];
+  }
 }
 
 // backward of  (z, r) = sigmoid(GN(gates_raw)), rh = r*h_ode  for one (sample, group of the 2*hidden gate channels)
@@ -245,7 +279,8 @@ static int upload_bytes(void* dst, const void* src, size_t bytes, hipStream_t st
 
 // forward pieces shared with the inference path (convgru.hip)
 int cell_step_q4(const odehip_convgru_cell* c, const float* x, const float* h, float* h_out, float* h_out_nchw,
-                 long long nchw_batch_stride, int batch, float* gates_raw, float* z, float* rh, float* cand_raw, hipStream_t stream);
+                 long long nchw_batch_stride, int batch, float* gates_raw, float* z, float* rh, float* cand_raw, hipStream_t stream,
+                 const float* mask_b = nullptr);
 int conv_layer_q4(const float* src1, const float* src2, int cin1, int cin, int cout, int ks, const float* wp, const float* bias,
                   float* dst, int relu, int batch, hipStream_t stream);
 void launch_split_mean_std(const float* head_out, float* mean, float* stdv, int batch, int out_ch, hipStream_t stream);
@@ -350,8 +385,8 @@ __global__ __launch_bounds__(256) void add_nchw_slice_to_q4_kernel(const float* 
 void launch_gn_update_bwd(const float* cand_raw, const float* gamma, const float* beta, const float* gh, const float* z, const float* h_prev,
                           float* g_cand_raw, float* gz_pre, float* gh_prev, float* dgamma_part, float* dbeta_part, int hidden, int batch,
                           hipStream_t stream) {
-  hipLaunchKernelGGL(gn_update_bwd_kernel, dim3(hidden / 32, batch), dim3(256), 0, stream, cand_raw, gamma, beta, gh, z, h_prev, g_cand_raw,
-                     gz_pre, gh_prev, dgamma_part, dbeta_part, hidden / 32);
+  hipLaunchKernelGGL(gn_update_bwd_kernel<false>, dim3(hidden / 32, batch), dim3(256), 0, stream, cand_raw, gamma, beta, gh, z, h_prev, g_cand_raw,
+                     gz_pre, gh_prev, dgamma_part, dbeta_part, hidden / 32, nullptr);
 }
 void launch_gn_gates_bwd(const float* gates_raw, const float* gamma, const float* beta, const float* gz_pre, const float* g_rh,
                          const float* h_prev, float* gh_prev, float* g_gates_raw, float* dgamma_part, float* dbeta_part, int hidden,
@@ -375,6 +410,15 @@ extern "C" size_t odehip_encoder_train_workspace_bytes(const odehip_encoder* e, 
 extern "C" int odehip_odeconvgru_encode_train(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames,
                                               int batch, int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw,
                                               void* workspace, size_t workspace_bytes, void* stream_) {
+  return odehip_odeconvgru_encode_train_masked(e, inputs_nchw, t_host, n_frames, batch, run_backwards, mean_nchw, std_nchw, latent_nchw,
+                                               workspace, workspace_bytes, stream_, nullptr);
+}
+
+// mask_tb: (T, B) on the device, row i = the observation mask of FRAME i, or null = all observed.  Nothing of it is kept in the
+// workspace: the backward call is handed the same pointer.
+extern "C" int odehip_odeconvgru_encode_train_masked(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames,
+                                                     int batch, int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw,
+                                                     void* workspace, size_t workspace_bytes, void* stream_, const float* mask_tb) {
   int rc = check_encoder(e, "odeconvgru_encode_train");
   if (rc != ODEHIP_OK) return rc;
   ODEHIP_REQUIRE(inputs_nchw && t_host && mean_nchw && std_nchw && workspace, "odeconvgru_encode_train: null pointer");
@@ -408,7 +452,7 @@ extern "C" int odehip_odeconvgru_encode_train(const odehip_encoder* e, const flo
     float* lat = latent_nchw ? latent_nchw + (size_t)idx * C * kPix : nullptr;  // latent_ys (B,T,C,H,W): slot idx of each sample
     rc = cell_step_q4(&e->cell, L.frame(ws, i), L.per(ws, L.off_hode, idx, L.hs), L.hstate(ws, idx + 1), lat, (long long)n_frames * C * kPix, batch,
                       L.per(ws, L.off_gates, idx, 2 * L.hs), L.per(ws, L.off_z, idx, L.hs), L.per(ws, L.off_rh, idx, L.hs),
-                      L.per(ws, L.off_cand, idx, L.hs), stream);
+                      L.per(ws, L.off_cand, idx, L.hs), stream, mask_tb ? mask_tb + (size_t)i * batch : nullptr);
     if (rc != ODEHIP_OK) return rc;
   }
   rc = conv_layer_q4(L.hstate(ws, n_frames), nullptr, C, C, e->head_hidden, 1, e->w_head0, e->b_head0, L.p(ws, L.off_headhid), 1, batch,
@@ -426,6 +470,18 @@ extern "C" int odehip_odeconvgru_encode_backward(const odehip_encoder* e, const 
                                                  int n_frames, int batch, int run_backwards, const float* grad_mean_nchw,
                                                  const float* grad_std_nchw, const float* grad_latent_nchw, float* grad_inputs_nchw,
                                                  const odehip_encoder_grads* gr, void* workspace, size_t workspace_bytes, void* stream_) {
+  return odehip_odeconvgru_encode_backward_masked(e, eb, t_host, n_frames, batch, run_backwards, grad_mean_nchw, grad_std_nchw,
+                                                  grad_latent_nchw, grad_inputs_nchw, gr, workspace, workspace_bytes, stream_, nullptr);
+}
+
+// mask_tb: the pointer the forward call (odehip_odeconvgru_encode_train_masked) was given.  An unobserved (frame, sample) feeds the
+// cell's chain exact zeros, so with finite frames its grad_inputs slice and its share of every parameter gradient are exact zeros.
+// A NON-FINITE unobserved frame is contained by the forward only: the weight-gradient products multiply it by those zeros.
+extern "C" int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e, const odehip_encoder_bwd* eb, const double* t_host,
+                                                        int n_frames, int batch, int run_backwards, const float* grad_mean_nchw,
+                                                        const float* grad_std_nchw, const float* grad_latent_nchw,
+                                                        float* grad_inputs_nchw, const odehip_encoder_grads* gr, void* workspace,
+                                                        size_t workspace_bytes, void* stream_, const float* mask_tb) {
   int rc = check_encoder(e, "odeconvgru_encode_backward");
   if (rc != ODEHIP_OK) return rc;
   ODEHIP_REQUIRE(eb && t_host && grad_mean_nchw && grad_std_nchw && grad_inputs_nchw && gr && workspace,
@@ -491,9 +547,14 @@ extern "C" int odehip_odeconvgru_encode_backward(const odehip_encoder* e, const 
     float* g_cand = L.per(ws, L.off_gcand, idx, L.hs);
     float* g_gates = L.per(ws, L.off_ggates, idx, 2 * L.hs);
     const float* h_ode = L.per(ws, L.off_hode, idx, L.hs);
-    hipLaunchKernelGGL(gn_update_bwd_kernel, dim3(HG, batch), dim3(256), 0, stream, L.per(ws, L.off_cand, idx, L.hs), e->cell.gn_can_w,
-                       e->cell.gn_can_b, gh, L.per(ws, L.off_z, idx, L.hs), h_ode, g_cand, gz_pre, gh_ode,
-                       pgc + (size_t)idx * batch * C, pgc + pgc_half + (size_t)idx * batch * C, HG);
+    if (mask_tb)
+      hipLaunchKernelGGL(gn_update_bwd_kernel<true>, dim3(HG, batch), dim3(256), 0, stream, L.per(ws, L.off_cand, idx, L.hs), e->cell.gn_can_w,
+                         e->cell.gn_can_b, gh, L.per(ws, L.off_z, idx, L.hs), h_ode, g_cand, gz_pre, gh_ode,
+                         pgc + (size_t)idx * batch * C, pgc + pgc_half + (size_t)idx * batch * C, HG, mask_tb + (size_t)i * batch);
+    else
+      hipLaunchKernelGGL(gn_update_bwd_kernel<false>, dim3(HG, batch), dim3(256), 0, stream, L.per(ws, L.off_cand, idx, L.hs), e->cell.gn_can_w,
+                         e->cell.gn_can_b, gh, L.per(ws, L.off_z, idx, L.hs), h_ode, g_cand, gz_pre, gh_ode,
+                         pgc + (size_t)idx * batch * C, pgc + pgc_half + (size_t)idx * batch * C, HG, nullptr);
     if ((rc = conv_bwd(g_cand, C, C, ks, eb->w_can_dx, 0, nullptr, gx_c, eb->bf16[2], eb->wino[2])) != ODEHIP_OK) return rc;
     if ((rc = conv_bwd(g_cand, C, C, ks, eb->w_can_dh, 0, nullptr, g_rh, eb->bf16[3], eb->wino[3])) != ODEHIP_OK) return rc;
     hipLaunchKernelGGL(gn_gates_bwd_kernel, dim3(2 * HG, batch), dim3(256), 0, stream, L.per(ws, L.off_gates, idx, 2 * L.hs),
@@ -669,8 +730,8 @@ extern "C" int odehip_convgru_cell_backward(const odehip_convgru_cell* c, const 
     a.dst = dst;
     return launch_conv(a, ks, stream);
   };
-  hipLaunchKernelGGL(gn_update_bwd_kernel, dim3(HG, batch), dim3(256), 0, stream, cand, c->gn_can_w, c->gn_can_b, ghn, z, h, g_cand,
-                     gz_pre, gh_ode, pgc, pgc + (size_t)batch * H, HG);
+  hipLaunchKernelGGL(gn_update_bwd_kernel<false>, dim3(HG, batch), dim3(256), 0, stream, cand, c->gn_can_w, c->gn_can_b, ghn, z, h, g_cand,
+                     gz_pre, gh_ode, pgc, pgc + (size_t)batch * H, HG, nullptr);
   if ((rc = conv_bwd(g_cand, H, I, cb->w_can_dx, nullptr, gx_c, cb->bf16[2], cb->wino[2])) != ODEHIP_OK) return rc;
   if ((rc = conv_bwd(g_cand, H, H, cb->w_can_dh, nullptr, g_rh, cb->bf16[3], cb->wino[3])) != ODEHIP_OK) return rc;
   hipLaunchKernelGGL(gn_gates_bwd_kernel, dim3(2 * HG, batch), dim3(256), 0, stream, gates, c->gn_gates_w, c->gn_gates_b, gz_pre, g_rh, h,

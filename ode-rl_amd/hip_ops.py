@@ -1152,9 +1152,31 @@ def _encoder_bwd_desc(enc):
     return b
 
 
-def _encode(enc, inputs, timesteps, want_latent, run_backwards, train):
+def encoder_mask(mask, n_frames, batch, device, who="odeconvgru_encode"):
+    """The observation mask as the library reads it: one contiguous float32 (T, B) tensor on `device`, or None.  mask: (B, T) or
+    (B, T, 1), batch-first as the loaders make it, on the host or the device; mask[b, i] belongs to frame i of the time-first inputs.
+    float32 values are used as they are (fractional masks blend), any other dtype is taken as mask != 0.  A constant: nothing is read
+    back from it (no frame count, no host synchronisation), and a mask that requires grad is refused."""
+    if mask is None:
+        return None
+    if not isinstance(mask, torch.Tensor):
+        raise TypeError(f"{who}: mask must be a torch.Tensor or None (got {type(mask).__name__})")
+    if mask.is_complex():
+        raise TypeError(f"{who}: mask must be a real or boolean tensor (got {mask.dtype})")
+    if mask.requires_grad:
+        raise NotImplementedError(f"{who}: mask is treated as a constant; a gradient with respect to it is not implemented")
+    if tuple(mask.shape) not in ((batch, n_frames), (batch, n_frames, 1)):
+        raise ValueError(f"{who}: mask must be (B, T) = ({batch}, {n_frames}) (or with a trailing 1), batch-first; got {tuple(mask.shape)}")
+    if mask.dtype != torch.float32:
+        mask = mask != 0
+    return mask.reshape(batch, n_frames).to(device=device, dtype=torch.float32).t().contiguous()
+
+
+def _encode(enc, inputs, timesteps, want_latent, run_backwards, train, mask=None):
     """The encoder forward of both paths: (mean, std, latent_ys or None, what odeconvgru_encode_backward needs).  train: the entry point
-    that keeps the per-frame activations, in a private workspace."""
+    that keeps the per-frame activations, in a private workspace.  mask: see encoder_mask; None = every frame observed."""
+    if isinstance(inputs, torch.Tensor) and inputs.dim() == 5:   # (the mask is refused before anything is built or launched)
+        mask = encoder_mask(mask, inputs.shape[0], inputs.shape[1], inputs.device)
     require_device_tensor(inputs, "inputs")
     d = enc.refresh()
     inputs = inputs.contiguous()
@@ -1166,27 +1188,30 @@ def _encode(enc, inputs, timesteps, want_latent, run_backwards, train):
     lib = _lib.load()
     if train:
         ws = alloc_workspace(lib.odehip_encoder_train_workspace_bytes(ctypes.byref(d), t, b), inputs.device)   # owned by this call's graph node
-        fn = lib.odehip_odeconvgru_encode_train
+        fn = lib.odehip_odeconvgru_encode_train_masked
     else:
         ws = workspace(("enc", t, b, c), lib.odehip_encoder_workspace_bytes(ctypes.byref(d), t, b), inputs.device)
-        fn = lib.odehip_odeconvgru_encode
+        fn = lib.odehip_odeconvgru_encode_masked
     mean = torch.empty((b, d.out_ch, 16, 16), dtype=torch.float32, device=inputs.device)
     std = torch.empty_like(mean)
     latent = torch.empty((b, t, c, 16, 16), dtype=torch.float32, device=inputs.device) if want_latent else None
     _lib.check(fn(ctypes.byref(d), _ptr(inputs), tarr, t, b, int(bool(run_backwards)), _ptr(mean), _ptr(std), _ptr(latent), _ptr(ws),
-                  ws.numel(), _stream()))
-    return mean, std, latent, (ws, tarr, t, b, c, int(bool(run_backwards)))
+                  ws.numel(), _stream(), _ptr(mask)))
+    return mean, std, latent, (ws, tarr, t, b, c, int(bool(run_backwards)), mask)
 
 
-def odeconvgru_encode_train(enc, inputs, timesteps, want_latent=False, run_backwards=True):
+def odeconvgru_encode_train(enc, inputs, timesteps, want_latent=False, run_backwards=True, mask=None):
     """Forward of the training path: returns (mean, std, latent_ys or None, saved) -- `saved` holds the workspace the backward
-    call needs."""
-    return _encode(enc, inputs, timesteps, want_latent, run_backwards, True)
+    call needs and the (T, B) device image of `mask`."""
+    return _encode(enc, inputs, timesteps, want_latent, run_backwards, True, mask)
 
 
-def odeconvgru_encode_backward(enc, saved, grad_mean, grad_std, grad_latent=None):
-    """(grad_inputs (T,B,C,16,16), [gradient of every tensor of encoder_params(enc)]); grad_latent: what arrives through latent_ys."""
-    ws, tarr, t, b, c, run_backwards = saved
+def odeconvgru_encode_backward(enc, saved, grad_mean, grad_std, grad_latent=None, mask=None):
+    """(grad_inputs (T,B,C,16,16), [gradient of every tensor of encoder_params(enc)]); grad_latent: what arrives through latent_ys.
+    mask: the forward call's mask; None = the image of it that `saved` holds (none if the forward had none)."""
+    ws, tarr, t, b, c, run_backwards, mask_tb = saved
+    if mask is not None:
+        mask_tb = encoder_mask(mask, t, b, ws.device, "odeconvgru_encode_backward")
     d = enc.refresh()
     bw = _encoder_bwd_desc(enc)
     dev = ws.device
@@ -1209,14 +1234,14 @@ def odeconvgru_encode_backward(enc, saved, grad_mean, grad_std, grad_latent=None
     (g.w_gates, g.b_gates, g.gn_gates_w, g.gn_gates_b, g.w_can, g.b_can, g.gn_can_w, g.gn_can_b, g.w_head0, g.b_head0, g.w_head1,
      g.b_head1) = (x.data_ptr() for x in grads[2 * nl:])
     gin = torch.empty((t, b, c, 16, 16), dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().odehip_odeconvgru_encode_backward(ctypes.byref(d), ctypes.byref(bw), tarr, t, b, run_backwards,
-                                                             _ptr(grad_mean), _ptr(grad_std), _ptr(grad_latent), _ptr(gin),
-                                                             ctypes.byref(g), _ptr(ws), ws.numel(), _stream()))
+    _lib.check(_lib.load().odehip_odeconvgru_encode_backward_masked(ctypes.byref(d), ctypes.byref(bw), tarr, t, b, run_backwards,
+                                                                    _ptr(grad_mean), _ptr(grad_std), _ptr(grad_latent), _ptr(gin),
+                                                                    ctypes.byref(g), _ptr(ws), ws.numel(), _stream(), _ptr(mask_tb)))
     return gin, grads
 
 
-def odeconvgru_encode(enc, inputs, timesteps, want_latent=False, run_backwards=True):
-    return _encode(enc, inputs, timesteps, want_latent, run_backwards, False)[:3]
+def odeconvgru_encode(enc, inputs, timesteps, want_latent=False, run_backwards=True, mask=None):
+    return _encode(enc, inputs, timesteps, want_latent, run_backwards, False, mask)[:3]
 
 
 # ---- VidODE's warp chain + mask compositing (csrc/warp.hip) ---------------------------------------------------------------

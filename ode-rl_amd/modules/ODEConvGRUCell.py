@@ -1,5 +1,9 @@
 """Drop-in for the reference's `modules/ODEConvGRUCell.py:9-78`: same constructor and attribute names (`ode_func`,
-`cgru_cell`, `transform_z0`, `z0_dim`), whole reverse-time Euler + ConvGRU loop in ONE C-ABI call."""
+`cgru_cell`, `transform_z0`, `z0_dim`), whole reverse-time Euler + ConvGRU loop in ONE C-ABI call.
+
+`mask` (B, T) or (B, T, 1), the loaders' `observed_mask`: honoured as upstream Vid-ODE does (models/base_conv_gru.py:66-70) -- after
+the cell's update of frame i, sample b keeps `mask[b, i] * h_next + (1 - mask[b, i]) * h_ode`, so an unobserved frame leaves the
+Euler-advanced state as it is.  The reference's cell takes the mask and forgets it; pass `mask=None` for that behaviour."""
 import torch
 import torch.nn as nn
 
@@ -34,12 +38,13 @@ class ODEConvGRUCell(nn.Module):
         return p
 
     def forward(self, inputs, timesteps, mask=None):
-        """inputs (T,B,C,H,W) time-first -> (mean_z0, std_z0), each (B, z0_dim, H, W); std is |.| (reference :32-37)."""
+        """inputs (T,B,C,H,W) time-first -> (mean_z0, std_z0), each (B, z0_dim, H, W); std is |.| (reference :32-37).
+        mask: see the module docstring; indexed by frame, not by visiting order."""
         enc = self._packed()
         if torch.is_grad_enabled() and (inputs.requires_grad or any(p.requires_grad for p in hip_ops.encoder_params(enc))):
             from ..autograd import encode_with_grad
-            return encode_with_grad(enc, inputs, timesteps)
-        mean, std, _ = hip_ops.odeconvgru_encode(enc, inputs, timesteps)
+            return encode_with_grad(enc, inputs, timesteps, mask=mask)
+        mean, std, _ = hip_ops.odeconvgru_encode(enc, inputs, timesteps, mask=mask)
         if DEBUG_NAN:   # the reference asserts on NaN inside its loop (:56,59); here once per call, and only on request (it syncs)
             assert not torch.isnan(mean).any() and not torch.isnan(std).any(), "NaN in the encoder output"
         return mean, std
@@ -50,7 +55,8 @@ class ODEConvGRUCell(nn.Module):
         autograd the training kernels (csrc/convgru_backward.hip) take the gradient that arrives through latent_ys."""
         if torch.is_grad_enabled() and (inputs.requires_grad or any(p.requires_grad for p in self.parameters())):
             from ..autograd import encode_with_grad
-            _, _, latent = encode_with_grad(self._packed(), inputs, timesteps, want_latent=True, run_backwards=run_backwards)
+            _, _, latent = encode_with_grad(self._packed(), inputs, timesteps, want_latent=True, run_backwards=run_backwards,
+                                             mask=mask)
             return latent[:, -1], latent
-        _, _, latent = hip_ops.odeconvgru_encode(self._packed(), inputs, timesteps, want_latent=True, run_backwards=run_backwards)
+        _, _, latent = hip_ops.odeconvgru_encode(self._packed(), inputs, timesteps, want_latent=True, run_backwards=run_backwards, mask=mask)
         return latent[:, -1], latent
