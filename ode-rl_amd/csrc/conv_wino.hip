@@ -9,15 +9,21 @@
 // Workgroup = (sample, 32 output channels, 8 output rows = 4x8 tiles of 2x2), 512 threads, ROLE-SPECIALISED waves
 // (two per SIMD: one of each role):
 //   waves 0-3  CONSUMERS: wave w owns the (16 co x 16 tiles) block (w>>1, w&1) for ALL 16 xi -- 16 accumulators of
-//              v_mfma_f32_16x16x4_f32 (64 AGPRs).  Per 16-channel chunk: 32 ds_read_b128 feed 64 MFMAs.  Because a
-//              lane ends up holding M_xi[4 consecutive co][its tile] for every xi, the output transform A^T M A is
-//              register-only and its result is exactly one Q4 channel quad per pixel: no LDS exchange.
-//   waves 4-7  PRODUCERS: LDS-DMA of the next chunk's pre-transformed weights U (32 KiB) and of the raw input tile
-//              two chunks ahead (4 quads x 10 rows x 18 cols, zero-PADDED BY THE DMA: per-lane source offsets, out-of-
-//              image slots get an out-of-range offset and the buffer range check writes zeros), then the input
-//              transform V = B^T d B of the next chunk (12 ds_read_b128 + 8 ds_write_b128 + float4 VALU per thread).
-// One s_barrier per chunk hands U_c / V_c to the consumers and the freed buffers back to the producers.
-// LDS: U[2] 64 KiB + raw[2] 32 KiB + V[2] 64 KiB = 160 KiB.
+//              v_mfma_f32_16x16x4_f32 (64 AGPRs).  Per 16-channel chunk 64 MFMAs, fed by 16 ds_read_b128 (the V fragments) and
+//              16 buffer_load_dwordx4 (the U fragments).  The pre-transformed weights U are a packed constant that nothing in
+//              the CU produces: a lane's A operand of position xi is 16 contiguous bytes of the packed tensor, so it goes from
+//              L2 / the vector L1 straight into VGPRs, kUAhead positions ahead of the MFMAs that use it, across chunk
+//              boundaries, and never through LDS; a layer's first kUAhead positions are requested on entry, in front of the
+//              first barrier (in a walk: while the producers still wait for the partners).  (The two waves with the same
+//              w>>1 load the same addresses.)  Because a lane ends up holding M_xi[4 consecutive co][its tile]
+//              for every xi, the output transform A^T M A is register-only and its result is exactly one Q4 channel quad per
+//              pixel: no LDS exchange.
+//   waves 4-7  PRODUCERS: LDS-DMA of the raw input tile two chunks ahead (4 quads x 10 rows x 18 cols, zero-PADDED BY THE
+//              DMA: per-lane source offsets, out-of-image slots get an out-of-range offset and the buffer range check writes
+//              zeros), then the input transform V = B^T d B of the next chunk (12 ds_read_b128 + 8 ds_write_b128 + float4 VALU
+//              per thread).
+// One s_barrier per chunk hands V_c to the consumers and the freed buffers back to the producers.
+// LDS: raw[2] 32 KiB + V[2] 64 KiB = 96 KiB.
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
@@ -26,10 +32,17 @@
 
 namespace odehip {
 
-constexpr int kWU = 32 * 1024;        // U chunk: 16 xi x [quad 4][co 32][4 ci]
+constexpr int kWU = 32 * 1024;        // U chunk in the packed tensor: 16 xi x [quad 4][co 32][4 ci] (never staged in LDS)
 constexpr int kWRaw = 16 * 1024;      // raw chunk: 4 quads x 4 KiB: 10 rows x 20 slots of 16 B (18 padded cols, de-interleaved)
 constexpr int kWV = 32 * 1024;        // V chunk: 16 xi x [quad 4][tile 32][4 ci]
-constexpr int kWinoLds = 2 * kWU + 2 * kWRaw + 2 * kWV;  // 160 KiB
+constexpr int kWinoLds = 2 * kWRaw + 2 * kWV;  // 96 KiB
+constexpr int kUAhead = 8;            // U fragments (positions xi) a consumer wave keeps in flight ahead of its MFMAs: a position is
+                                      // 128 matrix cycles, so 8 cover ~1,000 cycles of L2-hit latency under load, in 32 VGPRs (kept
+                                      // in flight from one layer into the next as well, the fixed-grid walk spills 68 VGPRs)
+
+__device__ __forceinline__ f32x4 load_u(__amdgpu_buffer_rsrc_t r, int voffset, int soffset) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voffset, soffset, 0));
+}
 
 // a - b on 4 floats as two v_pk_add_f32 with the negate modifier (hipcc emits four v_sub_f32 otherwise; every VALU
 // cycle here is taken from the fp32 MFMAs of the consumer wave on the same SIMD)
@@ -211,10 +224,10 @@ template <int NCHUNK, bool DBG, bool PERSIST, int QOUT = 16, bool ADAPT = false>
 __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, const float* __restrict__ p_u, int p_qin, const ConvArgs& a,
                                            int b, int ct, int rh, char* smem, const PersistHook& hk) {
   static_assert(!PERSIST || (NCHUNK % 2 == 0), "the layer-to-layer LDS hand-over assumes an even chunk count");
+  static_assert(kUAhead % 2 == 0 && kUAhead <= 16, "the U ring is refilled a pair of positions at a time");
   constexpr int kRawAux = PERSIST ? 16 : 0;  // sc1 (agent scope): never served from this CU's vector cache
-  char* const Ub = smem;
-  char* const Rb = smem + 2 * kWU;
-  char* const Vb = smem + 2 * kWU + 2 * kWRaw;
+  char* const Rb = smem;
+  char* const Vb = smem + 2 * kWRaw;
   Stamps st(a, (DBG && (a.debug & 16)) ? 256 : (DBG ? 0 : -1));  // debug 16: stamps from a producer wave instead of a consumer
   st.take(0);
   const int tid = threadIdx.x;
@@ -229,8 +242,6 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
   if (wave >= 4) {
     // =========================================== PRODUCERS ===========================================
     const int pw = wave - 4, ptid = tid - 256;
-    const unsigned u_tile_bytes = (unsigned)nchunk * kWU;
-    const __amdgpu_buffer_rsrc_t ru = make_rsrc((const char*)p_u + (size_t)ct * u_tile_bytes, u_tile_bytes);
     const __amdgpu_buffer_rsrc_t rx = make_rsrc((const char*)p_src + (size_t)b * p_qin * kQuadBytes, (unsigned)p_qin * kQuadBytes);
     // Raw tile in LDS: row r (image row r0 - 1 + r) = 20 slots of 16 B: [even padded cols 0,2,..,16 | odd padded cols
     // 1,3,..,17 | 2 unused]; padded col pc = image col + 1.  A 4x4 patch reads cols 2tx + j: for a fixed j the 8 tiles of a
@@ -245,14 +256,6 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
       const int irow = r0 - 1 + row, col = pc - 1;
       vr[p] = (s < 200 && w < 18 && irow >= 0 && irow < kHW && col >= 0 && col < kHW) ? irow * 256 + col * 16 : kOobOffset;
     }
-    const int vw = lane * 16;
-    auto issue_u = [&](int c, int buf) {
-#pragma unroll
-      for (int g = 0; g < 8; ++g) {
-        const int p = pw * 8 + g;
-        dma16(ru, Ub + buf * kWU + p * 1024, vw, (c * 32 + p) * 1024);
-      }
-    };
     auto issue_raw = [&](int c, int buf) {
 #pragma unroll
       for (int p = 0; p < 4; ++p)
@@ -307,11 +310,10 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
       }
     };
 
-    // DMA issue order per wave: raw_0 (4) | U_0 (8) | raw_1 (4) | then per iteration c: U_{c+1} (8) | raw_{c+2} (4).
+    // DMA issue order per wave: raw_0 (4) | raw_1 (4) | then per iteration c: raw_{c+2} (4).
     // Counted waits (vmcnt counts this wave's DMAs in issue order) leave the younger ones in flight.
     if (PERSIST) {
       if (pw == 0) pstamp(hk, 0, lane);
-      issue_u(0, 0);                   // weights do not depend on the partners: requested before the wait
       // chunks 0 and 1 are the channels of co tile 0: only ITS two workgroups must be done before they are loaded; co tile 1's are
       // waited for in front of chunk 2 (same-box A/B over 10 alternations: median 1.4152 -> 1.4076 ms per trajectory; a wait per
       // chunk -- four polls per layer -- costs more than it saves: 1.53 ms)
@@ -322,7 +324,7 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
         // 2: 1.504, 3: 1.435, 4: 1.401, 5: 1.389, 6: 1.409, 8: 1.452; forward + backward 0: 4.75, 4: 4.57, 5: 4.55, 6: 4.54, 8: 4.60;
         // dopri5 forward 0: 0.799, 4: 0.783, 5: 0.777, 8: 0.796; 128-channel-ended stack 0: 1.640, 4: 1.627, 5: 1.638.  A barrier that
         // releases the producers exactly when the consumers' last MFMA has issued is worse than the fixed sleep (it also holds back
-        // the next layer's first weight chunk).
+        // the next layer's start).
         if (hk.solo && hk.wait_target == hk.target)   // (a row with a relaxed dependency has nothing to sleep for)
           for (int i = 0; i < hk.sleep6; ++i) __builtin_amdgcn_s_sleep(6);
         if (hk.split_wait) wait_done(hk, 0x8, 0x0); else wait_done(hk);
@@ -330,33 +332,29 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
       if (pw == 0) pstamp(hk, 1, lane);
       issue_raw(0, 0);
       issue_raw(1, 1);
-      wait_vmcnt<4>();                 // U_0 and raw_0 landed (raw_1 still in flight)
+      wait_vmcnt<4>();                 // raw_0 landed (raw_1 still in flight)
       if (pw == 0) pstamp(hk, 2, lane);
       transform(0, 0);
       if (pw == 0) pstamp(hk, 3, lane);
     } else if (!skip && !dbg_noprod) {
       issue_raw(0, 0);
-      issue_u(0, 0);
       if (nchunk > 1) issue_raw(1, 1);
-      if (nchunk > 1) wait_vmcnt<12>(); else wait_vmcnt<8>();  // raw_0 landed (U_0, raw_1 still in flight)
+      if (nchunk > 1) wait_vmcnt<4>(); else wait_vmcnt<0>();   // raw_0 landed (raw_1 still in flight)
       transform(0, 0);
-      if (nchunk > 1) wait_vmcnt<4>(); else wait_vmcnt<0>();   // U_0 landed
     }
     st.take(2);
 #pragma unroll
     for (int c = 0; c < nchunk; ++c) {
-      __builtin_amdgcn_s_barrier();  // [c] V_c and U_c ready for the consumers; they are done with chunk c-1
+      __builtin_amdgcn_s_barrier();  // [c] V_c ready for the consumers; they are done with chunk c-1
       if (!skip && !dbg_noprod && c + 1 < nchunk) {
-        if (!dbg_nodma) issue_u(c + 1, (c + 1) & 1);      // U buffer last read by the MFMAs of chunk c-1
         if (c + 2 < nchunk) {
           if (PERSIST && c == 0 && !hk.first && hk.split_wait) wait_done(hk, 0x8, 0x8);   // chunks 2 and 3: co tile 1's workgroups
           if (!dbg_nodma) issue_raw(c + 2, c & 1);        // raw buffer consumed by this wave's transform of chunk c
-          wait_vmcnt<12>();                               // raw_{c+1} landed
+          wait_vmcnt<4>();                                // raw_{c+1} landed (raw_{c+2} still in flight)
         } else {
-          wait_vmcnt<8>();
+          wait_vmcnt<0>();                                // raw_{c+1}, the last one
         }
         if (!dbg_notr) transform((c + 1) & 1, (c + 1) & 1);  // V buffer last read by the MFMAs of chunk c-1
-        if (c + 2 < nchunk) wait_vmcnt<4>(); else wait_vmcnt<0>();  // U_{c+1} landed
       }
       if (c < 4) st.take(3 + c);
     }
@@ -370,8 +368,19 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
   f32x4 acc[16];
 #pragma unroll
   for (int x = 0; x < 16; ++x) acc[x] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int u_off = kq * 512 + (ch * 16 + i16) * 16;
+  const int u_off = kq * 512 + (ch * 16 + i16) * 16;  // this lane's 16 bytes of a position's 2 KiB block [quad 4][co 32][4 ci]
   const int v_off = kq * 512 + (thh * 16 + i16) * 16;
+  // U ring: slot g % kUAhead holds position g of the layer (g = 16 c + xi); the request for g + kUAhead goes out with the MFMAs of g.
+  // Buffer loads: the range check keeps every address inside this tile.
+  constexpr int kG = 16 * NCHUNK;
+  const bool dbg_nou = dbg_noprod || dbg_nodma;     // the ablations without memory traffic: U fragments are constants
+  const __amdgpu_buffer_rsrc_t ru = make_rsrc((const char*)p_u + (size_t)ct * (NCHUNK * kWU), (unsigned)NCHUNK * kWU);
+  f32x4 uw[kUAhead];
+#pragma unroll
+  for (int g = 0; g < kUAhead; ++g) {
+    if (skip || dbg_nou) uw[g] = f32x4{1.f, 1.f, 1.f, 1.f};
+    else uw[g] = load_u(ru, u_off, g * 2048);
+  }
   const int Q = ct * 8 + ch * 4 + kq;
   f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
   if (a.bias) bias4 = *(const f32x4*)(a.bias + Q * 4);  // loaded now, used after the last MFMA
@@ -542,19 +551,22 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
     __builtin_amdgcn_s_barrier();  // [c]
     if (PERSIST && c == 0 && wave == 0) pstamp(hk, 4, lane);
     if (!skip && !dbg_nomfma) {
-      const char* u = Ub + (c & 1) * kWU + u_off;
       const char* v = Vb + (c & 1) * kWV + v_off;
       // two xi at a time: consecutive MFMAs hit different accumulators (a dependent 16x16x4 issues 8 cycles late);
-      // the fragments of the next pair are read while this pair's 8 MFMAs run
-      f32x4 w0 = *(const f32x4*)(u), x0 = *(const f32x4*)(v), w1 = *(const f32x4*)(u + 2048), x1 = *(const f32x4*)(v + 2048);
-      f32x4 w0n, x0n, w1n, x1n;
+      // the V fragments of the next pair are read, and the U fragments kUAhead positions on requested, while this pair's 8 MFMAs run
+      f32x4 x0 = *(const f32x4*)(v), x1 = *(const f32x4*)(v + 2048);
+      f32x4 x0n, x1n;
 #pragma unroll
       for (int x = 0; x < 16; x += 2) {
+        const int g = c * 16 + x, s0 = g % kUAhead, s1 = (g + 1) % kUAhead;
+        const f32x4 w0 = uw[s0], w1 = uw[s1];
         if (x + 2 < 16) {
-          w0n = *(const f32x4*)(u + (x + 2) * 2048);
           x0n = *(const f32x4*)(v + (x + 2) * 2048);
-          w1n = *(const f32x4*)(u + (x + 3) * 2048);
           x1n = *(const f32x4*)(v + (x + 3) * 2048);
+        }
+        if (g + kUAhead < kG && !dbg_nou) {
+          uw[s0] = load_u(ru, u_off, (g + kUAhead) * 2048);
+          uw[s1] = load_u(ru, u_off, (g + kUAhead + 1) * 2048);
         }
         acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, x0.x, acc[x], 0, 0, 0);
         acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, x1.x, acc[x + 1], 0, 0, 0);
@@ -564,9 +576,10 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
         acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, x1.z, acc[x + 1], 0, 0, 0);
         acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, x0.w, acc[x], 0, 0, 0);
         acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, x1.w, acc[x + 1], 0, 0, 0);
-        w0 = w0n; x0 = x0n; w1 = w1n; x1 = x1n;
+        x0 = x0n; x1 = x1n;
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 7, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -949,7 +962,7 @@ int launch_wino_persist(const ConvArgs* table_dev, int n_layers, int batch, unsi
     ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)wino_persist_d_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)wino_persist_v_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)wino_persist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    // every workgroup must be resident at once: one per CU (160 KiB of LDS each), `grid` <= number of CUs (checked by the caller)
+    // every workgroup must be resident at once: one per CU (96 KiB of LDS each: two do not fit), `grid` <= number of CUs (checked by the caller)
     int per_cu = 0;
     ODEHIP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)wino_persist_kernel, 512, kWinoLds));
     ODEHIP_REQUIRE(per_cu >= 1, "wino_persist: the kernel does not fit a CU");

@@ -1,5 +1,5 @@
 """Diagnostic: per-layer timeline of logical workgroup 0 inside the persistent trajectory launch (conv_wino.hip).
-Stamps (100 MHz): 0 layer start (producer), 1 partners' previous layer seen, 2 first input chunk + weights landed, 3 first input
+Stamps (100 MHz): 0 layer start (producer), 1 partners' previous layer seen, 2 first input chunk landed (the weights go straight to the consumers' registers), 3 first input
 transform done, 4 consumers past the first barrier, 5 last MFMA issued, 6 stores issued, 7 stores acknowledged.
   python tools/persist_stamps.py"""
 import os
