@@ -485,6 +485,22 @@ int odehip_adam_step_clipped(float* const* params, float* const* grads, float* c
                              const long long* numel, int n_tensors, float lr, float beta1, float beta2, float eps, float weight_decay,
                              int step, const float* coef_dev, void* stream);
 
+/* Adamax (adamax.hip): Vid-ODE's optimizer (Vid-ODE/main.py:187: optim.Adamax(netG.parameters(), lr)) on the tables, the grid and the
+ * argument checks of the Adam pair above.  Pure additions: ODEHIP_ABI_VERSION stays.  torch.optim.Adamax arithmetic (single-tensor
+ * path, maximize off; weight_decay is the L2 form and is skipped when 0), `step` counts from 1 and lr / (1 - beta1^step) is computed
+ * on the host in float64:
+ *   g += wd p;  exp_avg = b1 exp_avg + (1 - b1) g;  exp_inf = max(b2 exp_inf, |g| + eps);  p -= lr / (1 - b1^step) * exp_avg / exp_inf
+ * exp_inf is torch's bit for bit (every operation a single fp32 rounding), and its maximum propagates NaN as torch.maximum does: a
+ * non-finite gradient never becomes a finite update.  ceil(n_tensors / 24) plain launches, no atomics: two calls are bitwise equal.
+ * odehip_adamax_step_clipped: the same on g * *coef_dev (out3 + 1 of odehip_grad_norm), rounded on its own and written back to
+ * `grads`; with *coef_dev == 1 everything gets odehip_adamax_step's bits.  A tensor of 0 elements may have null pointers there. */
+int odehip_adamax_step(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_inf,
+                       const long long* numel, int n_tensors, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       int step, void* stream);
+int odehip_adamax_step_clipped(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_inf,
+                               const long long* numel, int n_tensors, float lr, float beta1, float beta2, float eps, float weight_decay,
+                               int step, const float* coef_dev, void* stream);
+
 /* ---- VidODE's warp chain + mask compositing (models/VidODE.py:119-140, get_warped_images :160-186) -------------------------- */
 
 /* pred_outputs (B,T,c+3,H,W) = the flow decoder's output per predicted frame: channels [0:2] optical flow (x, y) in pixels,

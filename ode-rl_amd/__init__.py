@@ -11,6 +11,8 @@ from .modules.DiffEqSolver import DiffEqSolver, ODEFunc  # noqa: F401
 from .modules.ConvGRUCell import ConvGRUCell  # noqa: F401
 from .modules.ODEConvGRUCell import ODEConvGRUCell  # noqa: F401
 from .metrics import frame_metrics, FrameMetrics  # noqa: F401
+from .optim import FusedAdam, FusedAdamax, decay_learning_rate  # noqa: F401
 
 __all__ = ["odeint", "odeint_adjoint", "DiffEqSolver", "ODEFunc", "create_convnet", "ConvGRUCell", "ODEConvGRUCell", "frame_metrics",
-           "FrameMetrics", "sample_z0", "last_z0_noise", "mse_kl_loss", "vidode_l1_loss", "step_size_grid"]
+           "FrameMetrics", "sample_z0", "last_z0_noise", "mse_kl_loss", "vidode_l1_loss", "step_size_grid", "FusedAdam", "FusedAdamax",
+           "decay_learning_rate"]

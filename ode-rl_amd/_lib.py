@@ -134,6 +134,10 @@ SIGNATURES = {
                                                 ctypes.POINTER(ctypes.c_longlong), ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                                 ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_void_p,
                                                 ctypes.c_void_p]),
+    "odehip_adamax_step": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p)] * 4 + [ctypes.POINTER(ctypes.c_longlong), ctypes.c_int] +
+                           [ctypes.c_float] * 5 + [ctypes.c_int, ctypes.c_void_p]),
+    "odehip_adamax_step_clipped": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p)] * 4 + [ctypes.POINTER(ctypes.c_longlong), ctypes.c_int] +
+                                   [ctypes.c_float] * 5 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "odehip_set_persistent_trajectory": (ctypes.c_int, [ctypes.c_int]),
     "odehip_persistent_trajectory_launches": (ctypes.c_longlong, []),
     "odehip_persistent_error": (ctypes.c_int, [ctypes.c_int]),

@@ -14,18 +14,10 @@
 #include <math.h>
 #include <string.h>
 
+#include "adam_table.h"
 #include "odehip_internal.h"
 
 namespace odehip {
-
-constexpr int kAdamChunk = 24;  // tensors per launch (pointers travel as kernel arguments)
-struct AdamTable {
-  float* p[kAdamChunk];
-  const float* g[kAdamChunk];
-  float* m[kAdamChunk];
-  float* v[kAdamChunk];
-  long long n[kAdamChunk];
-};
 
 __global__ __launch_bounds__(256) void adam_kernel(AdamTable t, float lr_over_bc1, float inv_sqrt_bc2, float b1, float b2, float eps,
                                                    float wd) {
@@ -149,12 +141,6 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(GradTable t, const floa
   const long long n = t.n[k];
   const float coef = coef_dev[0];
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) g[i] = __fmul_rn(g[i], coef);
-}
-
-// workgroups per tensor of an elementwise launch over a chunk whose largest tensor has nmax elements (adam_kernel's grid)
-static inline int update_blocks(long long nmax) {
-  const long long b = (nmax + 255) / 256;
-  return b < 1 ? 1 : (b > 1024 ? 1024 : (int)b);
 }
 
 // one chunk of a gradient table; a tensor of 0 elements may have a null pointer (torch hands out none for it)

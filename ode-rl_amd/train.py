@@ -25,7 +25,7 @@ def train_batch(model, batch_dict, optimizer, async_solver=False, clip=None):
     afterwards, and an error from collecting the solves still pending on the way out never replaces the error of the pass.
 
     clip: the reference's `opt.clip` (train_test.py:187-195).  None or -1: no clipping, and loss_dict has the keys it always had.
-    Otherwise the gradients are clipped to that global L2 norm before the update -- a FusedAdam does it inside its step
+    Otherwise the gradients are clipped to that global L2 norm before the update -- a FusedAdam or FusedAdamax does it inside its step
     (`step(max_grad_norm=clip)`: norm, coefficient and update stay on the device), any other optimizer gets
     torch.nn.utils.clip_grad_norm_ in front of its step() -- and loss_dict['Gradient Norm'] is the norm AFTER clipping as a device
     scalar (the reference logs it from one .item() per parameter tensor).  A batch-sharded loop that all-reduces the gradients itself
@@ -72,8 +72,8 @@ def train_batch(model, batch_dict, optimizer, async_solver=False, clip=None):
     if clip is None or clip == -1:
         optimizer.step()
     else:
-        from .optim import FusedAdam
-        if isinstance(optimizer, FusedAdam):
+        from .optim import _FusedOptimizer
+        if isinstance(optimizer, _FusedOptimizer):   # FusedAdam, FusedAdamax: the clip is part of their step
             optimizer.step(max_grad_norm=float(clip))
             loss_dict["Gradient Norm"] = optimizer.last_clipped_norm
         else:
