@@ -204,6 +204,11 @@ class _WarpCompositeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred_outputs, start_image, grid_x, grid_y):
+        if pred_outputs.dim() == 5:   # refuse up front what the backward does not implement, not from inside loss.backward()
+            c, h, w = pred_outputs.shape[2] - 3, pred_outputs.shape[3], pred_outputs.shape[4]
+            if not hip_ops.warp_composite_backward_supported(c, h, w):
+                raise ValueError(f"warp_composite: the backward of a {c}x{h}x{w} image needs {hip_ops.warp_backward_lds_bytes(c, h, w) // 1024} KiB "
+                                 f"of LDS ({hip_ops.WARP_LDS_BYTES // 1024} KiB available); run it under torch.no_grad() or on detached inputs")
         po, st = pred_outputs.detach().contiguous(), start_image.detach().contiguous()
         gx, gy = grid_x.detach().contiguous(), grid_y.detach().contiguous()
         pred_x, warped, masks = hip_ops.warp_composite(po, st, gx, gy)

@@ -1262,6 +1262,20 @@ def warp_composite(pred_outputs, start_image, grid_x, grid_y):
     return pred_x, warped, masks
 
 
+WARP_LDS_BYTES = 160 * 1024   # check_warp of csrc/warp.hip
+
+
+def warp_backward_lds_bytes(channels, height, width):
+    """LDS of csrc/warp.hip's backward: three (c, H, W) fp32 images -- the gradient that later steps produced, the one this step
+    scatters, and the image the step sampled from (the forward holds two)."""
+    return 3 * channels * height * width * 4
+
+
+def warp_composite_backward_supported(channels, height, width):
+    """Whether the backward runs where the forward does: at c = 4, 64 x 64 the forward's 128 KiB fit and the backward's 192 KiB do not."""
+    return warp_backward_lds_bytes(channels, height, width) <= WARP_LDS_BYTES
+
+
 def warp_composite_backward(pred_outputs, start_image, warped, grid_x, grid_y, g_pred_x, g_warped, g_masks, want_start_grad):
     b, t, cc, h, w = pred_outputs.shape
     c = cc - 3
