@@ -4,13 +4,15 @@
 // transposed + flipped 3x3 convs on the matrix cores, the ReLU replaced by the mask of the activation the forward saved) followed
 // by the reverse Runge-Kutta bookkeeping -- which here happens in REGISTERS: the running gradient w.r.t. y and the gradients
 // w.r.t. k1, k2, k3 never leave the lane that owns their pixel and channels (the per-launch path keeps them in HBM and threads
-// them through the conv epilogues, fixed_grid.hip: odehip_odeint_fixed_backward; same expressions in the same order here).
+// them through the conv epilogues, fixed_grid.hip: odehip_odeint_fixed_backward).  The bookkeeping mirrors reverse_targets() of
+// fixed_tableau.h for the 3/8 rule, target by target, in the same expressions and the same order, on the tableau's named entries.
 // What goes to HBM: the gradient w.r.t. every conv output, as bf16 "Q4h" (the weight-gradient kernel's operand; it is also what
 // the next conv of the chain multiplies), asynchronously; what comes from HBM: the saved masks (bf16, prefetched a layer ahead,
 // counted in the weight ring's vmcnt waits) and grad_out of the interval's left end.  The bias gradients are summed on the way
 // from the UNROUNDED fp32 gradients, in a fixed order (row sums by DPP, then LDS): deterministic.
 #include <string.h>
 
+#include "fixed_tableau.h"
 #include "fused_bf16.h"
 
 namespace odehip {
@@ -53,6 +55,8 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = blockIdx.x;
+  constexpr FixedTableau Tb = kFixedTableau[ODEHIP_RK4];   // the stage loop below is written out for its four stages
+  static_assert(Tb.S == 4, "btraj_bf16_kernel is the 3/8 rule's reverse sweep");
   const int NL = ba.n_layers, UE = NL * 3, S = 4;
   const long long U = (long long)(ba.n_hi - ba.n_lo) * S * UE;
 
@@ -161,8 +165,8 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
   };
   if (ba.n_hi == ba.n_steps) {
     load_go(ba.n_steps, G);
-    // seed of the last interval: (0 + wlast * h) * grad_out[T-1]   (fixed_grid.hip: scale_kernel)
-    const float c = 0.0f + 0.125f * ba.hdev[ba.n_steps - 1];
+    // seed of the last interval: (0 + b[3] * h) * grad_out[T-1]   (fixed_grid.hip: scale_kernel)
+    const float c = 0.0f + Tb.b[3] * ba.hdev[ba.n_steps - 1];
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
@@ -182,7 +186,7 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
       const size_t ev = (size_t)n * S + s;
       const char* const hs = wave_uniform(save_h + ev * ba.stride_h_eval);
       char* const gs = wave_uniform(save_g + ev * ba.stride_g_eval);
-      // ---- seed of this stage's chain: dL/dk_s (fixed_grid.hip: the seeds / targets of the reverse sweep)
+      // ---- seed of this stage's chain: dL/dk_s (fixed_tableau.h: the seeds / targets of the reverse sweep)
       // (stage 4's seed gk4 = (h/8) g(y_{n+1}) was formed when g(y_{n+1}) was -- at the close of interval n+1, or before the
       // loop -- and waits in gk[0], which is dead between an interval's close and its stage-4 bookkeeping)
       constexpr int kSeedSlot[4] = {0, 1, 2, 0};
@@ -270,8 +274,7 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
         }
         bias_rows(acc0, acc1, l - 1);
       }
-      // ---- acc = gx_s = J_f(x_s)^T gk_s: the reverse Runge-Kutta bookkeeping (targets of fixed_grid.hip, same expressions)
-      const float third = 1.0f / 3.0f;
+      // ---- acc = gx_s = J_f(x_s)^T gk_s: the reverse Runge-Kutta bookkeeping (reverse_targets() of fixed_tableau.h, same expressions)
       if (s == 3) {
         // gy = g + gx4; gk3 = (3h/8) g + h gx4; gk2 = (3h/8) g - h gx4; gk1 = (h/8) g + h gx4
 #pragma unroll
@@ -280,9 +283,9 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             const float g = G[nb][i];
-            const float o3 = __builtin_fmaf(g, 0.f + 0.375f * h, gx[i] * (0.f + 1.f * h));
-            const float o2 = __builtin_fmaf(g, 0.f + 0.375f * h, gx[i] * (0.f + -1.f * h));
-            const float o1 = __builtin_fmaf(g, 0.f + 0.125f * h, gx[i] * (0.f + 1.f * h));
+            const float o3 = __builtin_fmaf(g, 0.f + Tb.b[2] * h, gx[i] * (0.f + Tb.a[3][2] * h));
+            const float o2 = __builtin_fmaf(g, 0.f + Tb.b[1] * h, gx[i] * (0.f + Tb.a[3][1] * h));
+            const float o1 = __builtin_fmaf(g, 0.f + Tb.b[0] * h, gx[i] * (0.f + Tb.a[3][0] * h));
             const float oy = __builtin_fmaf(g, 1.f + 0.f * h, gx[i] * (1.f + 0.f * h));
             gk[2][nb][i] = o3; gk[1][nb][i] = o2; gk[0][nb][i] = o1; G[nb][i] = oy;
           }
@@ -295,8 +298,8 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             const float oy = __builtin_fmaf(G[nb][i], 1.f + 0.f * h, gx[i] * (1.f + 0.f * h));
-            const float o2 = __builtin_fmaf(gk[1][nb][i], 1.f + 0.f * h, gx[i] * (0.f + 1.f * h));
-            const float o1 = __builtin_fmaf(gk[0][nb][i], 1.f + 0.f * h, gx[i] * (0.f + -third * h));
+            const float o2 = __builtin_fmaf(gk[1][nb][i], 1.f + 0.f * h, gx[i] * (0.f + Tb.a[2][1] * h));
+            const float o1 = __builtin_fmaf(gk[0][nb][i], 1.f + 0.f * h, gx[i] * (0.f + Tb.a[2][0] * h));
             G[nb][i] = oy; gk[1][nb][i] = o2; gk[0][nb][i] = o1;
           }
         }
@@ -308,7 +311,7 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             const float oy = __builtin_fmaf(G[nb][i], 1.f + 0.f * h, gx[i] * (1.f + 0.f * h));
-            const float o1 = __builtin_fmaf(gk[0][nb][i], 1.f + 0.f * h, gx[i] * (0.f + third * h));
+            const float o1 = __builtin_fmaf(gk[0][nb][i], 1.f + 0.f * h, gx[i] * (0.f + Tb.a[1][0] * h));
             G[nb][i] = oy; gk[0][nb][i] = o1;
           }
         }
@@ -318,7 +321,7 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
         f32x16 go[2];
         load_go(n, go);
         const float hb = n > 0 ? ba.hdev[n - 1] : 0.0f;
-        const float cs = 0.f + 0.125f * hb;
+        const float cs = 0.f + Tb.b[3] * hb;
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
           const f32x16& gx = nb ? acc1 : acc0;

@@ -1,5 +1,9 @@
 // fixed_grid.hip -- euler / midpoint / rk4(3/8) trajectories (torchdiffeq FixedGridODESolver, one step per output
-// interval; call sites /root/reference/modules/DiffEqSolver.py:37,45-46) and their BACKWARD pass.
+// interval; call sites modules/DiffEqSolver.py:37,45-46 of the reference) and their BACKWARD passes.
+//
+// The methods live in ONE place, fixed_tableau.h: the tableaus and the three plans derived from them (stage combines, reverse-sweep
+// targets, adjoint targets).  The drivers below are loops over stages that turn a plan's slots into workspace pointers; the bf16
+// whole-trajectory kernels (fstack_bf16.hip, btraj_bf16.hip) read the same header.
 //
 // Backward = what the reference gets from `loss.backward()` (train_test.py:204): reverse-mode differentiation
 // through every op of the discrete solver ("discretise-then-optimise"; the reference imports `odeint`, not
@@ -17,16 +21,18 @@
 #include <mutex>
 #include <vector>
 
+#include "fixed_tableau.h"
 #include "odehip_internal.h"
 #include "persist.h"
 
 namespace odehip {
 
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-static int n_stages(int method) { return method == ODEHIP_RK4 ? 4 : (method == ODEHIP_MIDPOINT ? 2 : 1); }
 constexpr int kEsplit = 4;
+constexpr int kMaxTimes = 4096;           // output times of one call (the step sizes travel in a stack buffer)
+constexpr int kMaxWgradEvals = 32 * 64;   // evaluations one weight-gradient table (and the adjoint's weight list) holds
+static_assert(kFixedMaxStages - 1 == 3, "the workspace keeps three stage derivatives (off_k) and three partial sums (off_gy, off_g2)");
 
 // Everything lives in the caller's workspace; this is the one place that knows where.
 struct FixedLayout {
@@ -103,10 +109,9 @@ __global__ void wgrad_table_kernel(WgradPair* table, int n_eval, const char* g0,
 static int check_common(const odehip_convstack* f, int method, const double* t_host, int n_times, int batch, const char* who) {
   int rc = check_stack(f);
   if (rc != ODEHIP_OK) return rc;
-  ODEHIP_REQUIRE(method == ODEHIP_EULER || method == ODEHIP_MIDPOINT || method == ODEHIP_RK4,
-                 "%s: method %d is not a fixed-grid method", who, method);
+  ODEHIP_REQUIRE(is_fixed_method(method), "%s: method %d is not a fixed-grid method", who, method);
   ODEHIP_REQUIRE(t_host, "%s: null t", who);
-  ODEHIP_REQUIRE(n_times >= 1 && n_times <= 4096 && batch > 0, "%s: bad sizes (n_times %d, batch %d)", who, n_times, batch);
+  ODEHIP_REQUIRE(n_times >= 1 && n_times <= kMaxTimes && batch > 0, "%s: bad sizes (n_times %d, batch %d)", who, n_times, batch);
   ODEHIP_REQUIRE(f->channels[0] == f->channels[f->n_convs], "%s: f must map C -> C channels (%d -> %d)", who, f->channels[0],
                  f->channels[f->n_convs]);
   for (int i = 1; i < n_times; ++i)
@@ -122,7 +127,7 @@ static int wgrad_all_layers(const odehip_convstack* f, const FixedLayout& L, voi
                             float* const* grad_b, hipStream_t stream) {
   const int S = L.S, NL = f->n_convs;
   const int n_eval = (n_times - 1) * S;
-  ODEHIP_REQUIRE(n_eval <= 32 * 64, "odeint backward: too many evaluations (%d)", n_eval);
+  ODEHIP_REQUIRE(n_eval <= kMaxWgradEvals, "odeint backward: too many evaluations (%d)", n_eval);
   WgradPair* table = (WgradPair*)L.p(ws, L.off_tab);
   float* slabs = L.p(ws, L.off_slab);
   // the NL tables (g, a, scale per evaluation) travel in ONE asynchronous staged upload (25 kernel-argument uploads per training step before)
@@ -147,6 +152,45 @@ static int wgrad_all_layers(const odehip_convstack* f, const FixedLayout& L, voi
   return ODEHIP_OK;
 }
 
+// step sizes: dt = t1 - t0 in float64, rounded to fp32 when it meets the state (torchdiffeq semantics)
+static void fill_step_sizes(float* hbuf, const double* t_host, int n_times) {
+  for (int i = 0; i + 1 < n_times; ++i) hbuf[i] = (float)(t_host[i + 1] - t_host[i]);
+}
+
+// The CombineArgs of stage s from its plan: `base` carries y, h_ptr and k_scale, k[j] is where k_j is kept, x_next the next stage's
+// input; the last stage writes the step result instead.
+static CombineArgs stage_combine(const FixedCombine& p, int s, const CombineArgs& base, float* const* k, float* x_next, float* ynew,
+                                 float* ynew_nchw) {
+  CombineArgs c = base;
+  c.n_prev = p.n_prev;
+  for (int i = 0; i < p.n_prev; ++i) c.k_prev[i] = k[p.prev[i]];
+  float* w = p.result ? c.c2 : c.c1;
+  for (int i = 0; i <= p.n_prev; ++i) w[i] = p.c[i];
+  if (p.keep_k) c.k_out = k[s];
+  c.out1 = p.result ? nullptr : x_next;
+  c.out2 = p.result ? ynew : nullptr;
+  c.out2_nchw = p.result ? ynew_nchw : nullptr;
+  return c;
+}
+
+// The BwdArgs of a chain from its plan: slot(i) resolves a plan's slot to its tensor; the interval's result (kSlotOut) also takes
+// grad_out[n] = `go`, weighted like its source
+template <class Slot>
+static BwdArgs resolve_targets(const FixedTargets& p, const float* h_ptr, const float* go, Slot slot) {
+  BwdArgs w;
+  memset(&w, 0, sizeof(w));
+  w.h_ptr = h_ptr;
+  w.n_targets = p.n;
+  for (int i = 0; i < p.n; ++i) {
+    const FixedTarget& t = p.t[i];
+    BwdTarget& b = w.tgt[i];
+    b.out = slot(t.out); b.srcA = slot(t.src);
+    b.a_c = t.a_c; b.a_h = t.a_h; b.g_c = t.g_c; b.g_h = t.g_h;
+    if (t.out == kSlotOut) { b.srcB = go; b.b_c = t.a_c; b.b_h = t.a_h; }
+  }
+  return w;
+}
+
 }  // namespace odehip
 
 using namespace odehip;
@@ -163,9 +207,8 @@ static bool bf16_trajectory_ok(const odehip_convstack* f, int method) {
   if (!f->w_fused || f->ks != 3 || g_debug_flags || !persist_switch_on()) return false;
   for (int l = 0; l <= f->n_convs; ++l)
     if (f->channels[l] != 64) return false;
-  return method == ODEHIP_EULER || method == ODEHIP_MIDPOINT || method == ODEHIP_RK4;
+  return is_fixed_method(method);
 }
-constexpr int kMaxWgradEvals = 32 * 64;   // evaluations one weight-gradient table holds
 
 extern "C" int odehip_odeint_fixed(const odehip_convstack* f, int method, const float* z0_nchw, const double* t_host,
                                    int n_times, int batch, float* out_nchw, int save_for_backward, int negate,
@@ -182,13 +225,11 @@ extern "C" int odehip_odeint_fixed(const odehip_convstack* f, int method, const 
   void* ws = workspace;
   const size_t st_b = (size_t)batch * L.C * kPix * 4, st_f = st_b / 4;
   float* hdev = L.p(ws, L.off_h);
-  float* ping = L.p(ws, L.off_ping);
-  float* pong = L.p(ws, L.off_pong);
+  float *ping = L.p(ws, L.off_ping), *pong = L.p(ws, L.off_pong);
   float* k[3] = {L.p(ws, L.off_k), L.p(ws, L.off_k + L.st), L.p(ws, L.off_k + 2 * L.st)};
 
-  // step sizes: dt = t1 - t0 in float64, rounded to fp32 when it meets the state (torchdiffeq semantics)
-  float hbuf[4096];
-  for (int i = 0; i + 1 < n_times; ++i) hbuf[i] = (float)(t_host[i + 1] - t_host[i]);
+  float hbuf[kMaxTimes];
+  fill_step_sizes(hbuf, t_host, n_times);
   // ONE prologue launch: solution[0] = y0, y0 in the kernels' layout, the step sizes on the device, the persistent launch's flags zeroed
   const bool h_in_prologue = n_times - 1 <= 64;
   unsigned* psync = (unsigned*)L.p(ws, L.off_psync);
@@ -204,7 +245,7 @@ extern "C" int odehip_odeint_fixed(const odehip_convstack* f, int method, const 
   // bf16 compute, 64-channel stack: the whole trajectory as ONE launch with one workgroup per sample -- state and stage derivatives
   // in registers, activations in LDS (fstack_bf16.hip: ftraj_bf16_kernel).  A training forward (rk4) also saves every stage input
   // and hidden activation as bf16 for the one-launch reverse sweep (btraj_bf16.hip): saved format 1.
-  if (bf16_trajectory_ok(f, method) && (!save_for_backward || (method == ODEHIP_RK4 && (n_times - 1) * 4 <= kMaxWgradEvals))) {
+  if (bf16_trajectory_ok(f, method) && (!save_for_backward || (method == ODEHIP_RK4 && (n_times - 1) * L.S <= kMaxWgradEvals))) {
     if (save_for_backward) {
       rc = launch_ftraj_bf16_saving(f, z0_nchw, out_nchw, hdev, n_times, batch, L.p(ws, L.off_xin), L.st, L.p(ws, L.off_hid),
                                     (size_t)L.NH * L.hid, L.hid, stream);
@@ -221,6 +262,8 @@ extern "C" int odehip_odeint_fixed(const odehip_convstack* f, int method, const 
   PersistScope persist;
   if ((rc = persist.begin(f, nullptr, (n_times - 1) * L.S * f->n_convs)) != ODEHIP_OK) return rc;
   float* hidv[ODEHIP_MAX_LAYERS];
+  FixedCombine plan[kFixedMaxStages];
+  for (int s = 0; s < L.S; ++s) plan[s] = fixed_combine(fixed_tableau(method), s);
   auto enqueue_steps = [&]() -> int {
   for (int n = 0; n + 1 < n_times; ++n) {
     const float* y = L.y(ws, n);
@@ -228,66 +271,16 @@ extern "C" int odehip_odeint_fixed(const odehip_convstack* f, int method, const 
     float* ynew_nchw = out_nchw + (size_t)(n + 1) * st_f;
     // stage input / hidden-activation buffers of stage s (distinct per evaluation when saving)
     auto xin = [&](int s) { return save_for_backward ? L.xin(ws, n, s) : L.p(ws, L.off_xs); };
-    auto run = [&](int s, const float* x, const CombineArgs& c) {
-      float* const* hp = nullptr;
-      if (save_for_backward) {
-        for (int l = 0; l < L.NH; ++l) hidv[l] = L.hidden(ws, n, s, l);
-        hp = hidv;
-      }
-      return enqueue_f_saving(f, x, batch, hp, ping, pong, &c, nullptr, nullptr, stream);
-    };
-    CombineArgs c;
-    memset(&c, 0, sizeof(c));
-    c.y = y;
-    c.h_ptr = hdev + n;
-    c.k_scale = negate ? -1.0f : 1.0f;
-    if (method == ODEHIP_EULER) {  // y1 = y + h*f(y)
-      c.c2[0] = 1.0f;
-      c.out2 = ynew;
-      c.out2_nchw = ynew_nchw;
-      if ((rc = run(0, y, c)) != ODEHIP_OK) return rc;
-    } else if (method == ODEHIP_MIDPOINT) {  // x = y + h/2*k1 ; y1 = y + h*f(x)
-      c.c1[0] = 0.5f;
-      c.out1 = xin(1);
-      if ((rc = run(0, y, c)) != ODEHIP_OK) return rc;
-      c.c1[0] = 0.0f;
-      c.out1 = nullptr;
-      c.c2[0] = 1.0f;
-      c.out2 = ynew;
-      c.out2_nchw = ynew_nchw;
-      if ((rc = run(1, xin(1), c)) != ODEHIP_OK) return rc;
-    } else {  // 3/8 rule (torchdiffeq rk4_alt_step_func)
-      const float third = 1.0f / 3.0f;
-      c.k_out = k[0];  // k1 = f(y); x2 = y + h*(k1/3)
-      c.c1[0] = third;
-      c.out1 = xin(1);
-      if ((rc = run(0, y, c)) != ODEHIP_OK) return rc;
-      c.n_prev = 1;  // k2 = f(x2); x3 = y + h*(k2 - k1/3)
-      c.k_prev[0] = k[0];
-      c.k_out = k[1];
-      c.c1[0] = -third;
-      c.c1[1] = 1.0f;
-      c.out1 = xin(2);
-      if ((rc = run(1, xin(1), c)) != ODEHIP_OK) return rc;
-      c.n_prev = 2;  // k3 = f(x3); x4 = y + h*(k1 - k2 + k3)
-      c.k_prev[1] = k[1];
-      c.k_out = k[2];
-      c.c1[0] = 1.0f;
-      c.c1[1] = -1.0f;
-      c.c1[2] = 1.0f;
-      c.out1 = xin(3);
-      if ((rc = run(2, xin(2), c)) != ODEHIP_OK) return rc;
-      c.n_prev = 3;  // k4 = f(x4); y1 = y + h*(k1 + 3(k2+k3) + k4)/8
-      c.k_prev[2] = k[2];
-      c.k_out = nullptr;
-      c.out1 = nullptr;
-      c.c2[0] = 0.125f;
-      c.c2[1] = 0.375f;
-      c.c2[2] = 0.375f;
-      c.c2[3] = 0.125f;
-      c.out2 = ynew;
-      c.out2_nchw = ynew_nchw;
-      if ((rc = run(3, xin(3), c)) != ODEHIP_OK) return rc;
+    CombineArgs base;
+    memset(&base, 0, sizeof(base));
+    base.y = y;
+    base.h_ptr = hdev + n;
+    base.k_scale = negate ? -1.0f : 1.0f;
+    for (int s = 0; s < L.S; ++s) {   // k_s = f(x_s); its epilogue forms x_{s+1}, or y[n+1] behind the last stage
+      const CombineArgs c = stage_combine(plan[s], s, base, k, s + 1 < L.S ? xin(s + 1) : nullptr, ynew, ynew_nchw);
+      for (int l = 0; l < L.NH && save_for_backward; ++l) hidv[l] = L.hidden(ws, n, s, l);
+      rc = enqueue_f_saving(f, s == 0 ? y : xin(s), batch, save_for_backward ? hidv : nullptr, ping, pong, &c, nullptr, nullptr, stream);
+      if (rc != ODEHIP_OK) return rc;
     }
   }
   return ODEHIP_OK;
@@ -303,52 +296,95 @@ extern "C" int odehip_odeint_fixed(const odehip_convstack* f, int method, const 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Backward of odehip_odeint_fixed(save_for_backward = 1) on the SAME workspace.
+// What the two backward entries (reverse sweep, adjoint) share: the argument checks, the trivial one-time call, the input-gradient
+// chain of one evaluation, and the tail behind the sweep.
 //   f_dgrad: the stack of input-gradient convs, f_dgrad->w_packed[l] = pack(W_l, transpose_flip = 1), in the
 //            forward layer order; bias pointers unused.
 //   grad_out (T,B,C,16,16) NCHW -> grad_z0 (B,C,16,16) NCHW, grad_w[l] (OIHW), grad_b[l].
-// behind the last kernel of a backward pass whose sweep ran as a persistent launch: NaN-fill every gradient if that launch gave up
-static int guard_gradients(PersistScope& persist, const odehip_convstack* f, int batch, float* grad_z0, float* const* grad_w,
-                           float* const* grad_b, hipStream_t stream) {
-  float* regions[1 + 2 * ODEHIP_MAX_LAYERS];
-  size_t floats[1 + 2 * ODEHIP_MAX_LAYERS];
-  int n = 0;
-  regions[n] = grad_z0;
-  floats[n++] = (size_t)batch * f->channels[0] * kPix;
-  for (int l = 0; l < f->n_convs; ++l) {
-    regions[n] = grad_w ? grad_w[l] : nullptr;
-    floats[n++] = (size_t)f->channels[l + 1] * f->channels[l] * f->ks * f->ks;
-    regions[n] = grad_b ? grad_b[l] : nullptr;
-    floats[n++] = (size_t)f->channels[l + 1];
-  }
-  return persist.guard(regions, floats, n, stream);
+static int check_backward_args(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method, const double* t_host, int n_times,
+                               int batch, bool pointers, float* const* grad_w, float* const* grad_b, const char* who) {
+  int rc = check_common(f, method, t_host, n_times, batch, who);
+  if (rc != ODEHIP_OK) return rc;
+  ODEHIP_REQUIRE(f_dgrad && pointers && grad_w && grad_b, "%s: null pointer", who);
+  for (int l = 0; l <= f->n_convs; ++l)
+    ODEHIP_REQUIRE(f->channels[l] % 64 == 0, "%s: channel counts must be multiples of 64 (channels[%d] = %d)", who, l, f->channels[l]);
+  ODEHIP_REQUIRE(f->ks == 3, "%s: 3x3 dynamics only", who);
+  for (int l = 0; l < f->n_convs; ++l)
+    ODEHIP_REQUIRE(f_dgrad->w_packed[l] && grad_w[l] && grad_b[l], "%s: layer %d has null pointers", who, l);
+  return ODEHIP_OK;
 }
 
+struct BackwardPass {
+  const odehip_convstack *f, *f_dgrad;
+  const FixedLayout& L;
+  void* ws;
+  int n_times, batch;
+  float* grad_z0_nchw;
+  float* const* grad_w;
+  float* const* grad_b;
+  hipStream_t stream;
+  float hbuf[kMaxTimes];   // the step sizes as the forward pass uploaded them
+
+  // n_times == 1: the solution is y0 itself
+  int trivial(const float* grad_out_nchw) const {
+    ODEHIP_CHECK_HIP(hipMemcpyAsync(grad_z0_nchw, grad_out_nchw, (size_t)batch * L.C * kPix * 4, hipMemcpyDeviceToDevice, stream));
+    for (int l = 0; l < f->n_convs; ++l) {
+      ODEHIP_CHECK_HIP(hipMemsetAsync(grad_w[l], 0, (size_t)f->channels[l + 1] * f->channels[l] * 9 * 4, stream));
+      ODEHIP_CHECK_HIP(hipMemsetAsync(grad_b[l], 0, (size_t)f->channels[l + 1] * 4, stream));
+    }
+    return ODEHIP_OK;
+  }
+  // input-gradient chain of evaluation (n, s): GP[n][s][NH] (the seed: gradient w.r.t. k_s / the adjoint A_s) -> ... -> gx = J_f(x_s)^T
+  // seed, consumed by the targets of `last`
+  int dgrad_chain(int n, int s, const BwdArgs& last) const {
+    float* gpv[ODEHIP_MAX_LAYERS + 1];
+    const float* hv[ODEHIP_MAX_LAYERS];
+    for (int l = 0; l < L.NG; ++l) gpv[l] = L.gp(ws, n, s, l);
+    for (int l = 0; l + 1 < f->n_convs; ++l) hv[l] = L.hidden(ws, n, s, l);
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.combine = 3;
+    a.bwd = last;
+    return enqueue_dgrad_chain(f, f_dgrad, batch, gpv, hv, a, stream);
+  }
+  // behind the sweep (rc: what recording it returned): the recorded launch, grad_z0 from the Q4 tensor `g`, the weight / bias
+  // gradients -- one launch per layer over all (T-1)*S evaluations -- and the guard: every gradient is NaN-filled if the sweep ran
+  // as a persistent launch that gave up
+  int finish(PersistScope& persist, int rc, const float* g, bool adjoint, const float* eval_scale) const {
+    const int rc2 = persist.finish(hbuf, L.p(ws, L.off_h), nullptr, batch, (unsigned*)L.p(ws, L.off_psync), f->ks, stream);
+    if (rc != ODEHIP_OK || rc2 != ODEHIP_OK) return rc != ODEHIP_OK ? rc : rc2;
+    rc = odehip_q4_to_nchw(g, grad_z0_nchw, batch, L.C, stream);
+    if (rc != ODEHIP_OK) return rc;
+    rc = wgrad_all_layers(f, L, ws, n_times, batch, adjoint, eval_scale, grad_w, grad_b, stream);
+    if (rc != ODEHIP_OK) return rc;
+    float* regions[1 + 2 * ODEHIP_MAX_LAYERS] = {grad_z0_nchw};
+    size_t floats[1 + 2 * ODEHIP_MAX_LAYERS] = {(size_t)batch * L.C * kPix};
+    for (int l = 0; l < f->n_convs; ++l) {
+      regions[1 + 2 * l] = grad_w[l];
+      floats[1 + 2 * l] = (size_t)f->channels[l + 1] * f->channels[l] * f->ks * f->ks;
+      regions[2 + 2 * l] = grad_b[l];
+      floats[2 + 2 * l] = (size_t)f->channels[l + 1];
+    }
+    return persist.guard(regions, floats, 1 + 2 * f->n_convs, stream);
+  }
+};
+
 // ---------------------------------------------------------------------------------------------------------------
+// Backward of odehip_odeint_fixed(save_for_backward = 1) on the SAME workspace.
 extern "C" int odehip_odeint_fixed_backward(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method,
                                             const double* t_host, int n_times, int batch, const float* grad_out_nchw,
                                             float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, int saved_format,
                                             void* workspace, size_t workspace_bytes, void* stream_) {
-  int rc = check_common(f, method, t_host, n_times, batch, "odeint_fixed_backward");
-  ODEHIP_REQUIRE(saved_format == 0 || saved_format == 1, "odeint_fixed_backward: unknown saved format %d", saved_format);
+  int rc = check_backward_args(f, f_dgrad, method, t_host, n_times, batch, grad_out_nchw && grad_z0_nchw && workspace, grad_w, grad_b,
+                               "odeint_fixed_backward");
   if (rc != ODEHIP_OK) return rc;
-  ODEHIP_REQUIRE(f_dgrad && grad_out_nchw && grad_z0_nchw && grad_w && grad_b && workspace, "odeint_fixed_backward: null pointer");
-  for (int l = 0; l <= f->n_convs; ++l)
-    ODEHIP_REQUIRE(f->channels[l] % 64 == 0, "odeint_fixed_backward: channel counts must be multiples of 64 (channels[%d] = %d)", l,
-                   f->channels[l]);
-  ODEHIP_REQUIRE(f->ks == 3, "odeint_fixed_backward: 3x3 dynamics only");
-  for (int l = 0; l < f->n_convs; ++l)
-    ODEHIP_REQUIRE(f_dgrad->w_packed[l] && grad_w[l] && grad_b[l], "odeint_fixed_backward: layer %d has null pointers", l);
+  ODEHIP_REQUIRE(saved_format == 0 || saved_format == 1, "odeint_fixed_backward: unknown saved format %d", saved_format);
   const FixedLayout L(f, batch, n_times, method, 1);
   ODEHIP_REQUIRE(workspace_bytes >= L.total, "odeint_fixed_backward: workspace too small");
   hipStream_t stream = (hipStream_t)stream_;
   void* ws = workspace;
   const int NH = L.NH, S = L.S, NL = f->n_convs;
-  const size_t st_b = (size_t)batch * L.C * kPix * 4;
-  const long long n4 = (long long)(st_b / 16);
   float* hdev = L.p(ws, L.off_h);
-  float* gy = L.p(ws, L.off_gy);
-  float* gbuf[2] = {L.p(ws, L.off_g2), L.p(ws, L.off_g2 + L.st)};
 
   if (saved_format == 1 && n_times > 1) {
     // ---- the forward was the whole-trajectory bf16 launch: ONE launch for the reverse sweep (gradient state in registers, every
@@ -438,121 +474,50 @@ extern "C" int odehip_odeint_fixed_backward(const odehip_convstack* f, const ode
   ODEHIP_REQUIRE(saved_format == 0 || n_times == 1, "odeint_fixed_backward: bad saved format");
   rc = odehip_nchw_to_q4(grad_out_nchw, L.go(ws, 0), n_times * batch, L.C, stream);
   if (rc != ODEHIP_OK) return rc;
-  if (n_times == 1) {
-    ODEHIP_CHECK_HIP(hipMemcpyAsync(grad_z0_nchw, grad_out_nchw, st_b, hipMemcpyDeviceToDevice, stream));
-    for (int l = 0; l < NL; ++l) {
-      ODEHIP_CHECK_HIP(hipMemsetAsync(grad_w[l], 0, (size_t)f->channels[l + 1] * f->channels[l] * 9 * 4, stream));
-      ODEHIP_CHECK_HIP(hipMemsetAsync(grad_b[l], 0, (size_t)f->channels[l + 1] * 4, stream));
-    }
-    return ODEHIP_OK;
-  }
+  BackwardPass bp = {f, f_dgrad, L, ws, n_times, batch, grad_z0_nchw, grad_w, grad_b, stream, {}};
+  if (n_times == 1) return bp.trivial(grad_out_nchw);
+  fill_step_sizes(bp.hbuf, t_host, n_times);
 
-  // dgrad chain of evaluation (n, s): GP[n][s][NH] (gradient w.r.t. k) -> ... -> gx, consumed by `targets`
-  auto chain = [&](int n, int s, const BwdArgs& last) -> int {
-    float* gpv[ODEHIP_MAX_LAYERS + 1];
-    const float* hv[ODEHIP_MAX_LAYERS];
-    for (int l = 0; l < L.NG; ++l) gpv[l] = L.gp(ws, n, s, l);
-    for (int l = 0; l + 1 < NL; ++l) hv[l] = L.hidden(ws, n, s, l);
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.combine = 3;
-    a.bwd = last;
-    return enqueue_dgrad_chain(f, f_dgrad, batch, gpv, hv, a, stream);
-  };
-  auto tgt = [](float* out, const float* sa, float a_c, float a_h, const float* sb, float b_c, float b_h, float g_c, float g_h) {
-    BwdTarget t;
-    t.out = out; t.srcA = sa; t.srcB = sb;
-    t.a_c = a_c; t.a_h = a_h; t.b_c = b_c; t.b_h = b_h; t.g_c = g_c; t.g_h = g_h;
-    return t;
-  };
-
-  float hbuf[4096];
-  for (int i = 0; i + 1 < n_times; ++i) hbuf[i] = (float)(t_host[i + 1] - t_host[i]);  // as uploaded by the forward pass
-  const int last_s = S - 1;
-  const float wlast = method == ODEHIP_RK4 ? 0.125f : 1.0f;  // weight of the last stage's k in the step
+  const FixedTableau& tab = fixed_tableau(method);
+  FixedTargets plan[kFixedMaxStages];
+  for (int s = 0; s < S; ++s) plan[s] = reverse_targets(tab, s);
+  const float wlast = fixed_seed_weight(tab);   // weight of the last stage's k in the step
+  float* gy = L.p(ws, L.off_gy);
+  float* gbuf[2] = {L.p(ws, L.off_g2), L.p(ws, L.off_g2 + L.st)};
   // seed: gradient w.r.t. the last stage's k of the last interval = wlast * h * grad_out[T-1]
-  hipLaunchKernelGGL(scale_kernel, dim3(1024), dim3(256), 0, stream, L.gp(ws, n_times - 2, last_s, NH), L.go(ws, n_times - 1), 0.0f,
-                     wlast, hdev + (n_times - 2), n4);
-  const float* g = L.go(ws, n_times - 1);  // total gradient w.r.t. y[n+1]
+  hipLaunchKernelGGL(scale_kernel, dim3(1024), dim3(256), 0, stream, L.gp(ws, n_times - 2, S - 1, NH), L.go(ws, n_times - 1), 0.0f,
+                     wlast, hdev + (n_times - 2), (long long)batch * L.C * kPix / 4);
+  float* g = L.go(ws, n_times - 1);  // total gradient w.r.t. y[n+1]
   // the reverse sweep is nothing but conv launches (all bookkeeping lives in their epilogues): one persistent launch
   PersistScope persist;
   if ((rc = persist.begin(f, f_dgrad, (n_times - 1) * S * NL)) != ODEHIP_OK) return rc;
   auto sweep = [&]() -> int {
-  for (int n = n_times - 2; n >= 0; --n) {
-    float* gnext = gbuf[n & 1];
-    // epilogue of the FIRST stage's chain: closes the interval and seeds the next one (which uses h[n-1])
-    auto close_interval = [&](const float* gy_src) {
-      BwdArgs w;
-      memset(&w, 0, sizeof(w));
-      if (n > 0) {
-        w.h_ptr = hdev + (n - 1);
-        w.n_targets = 2;
-        w.tgt[0] = tgt(gnext, gy_src, 1.f, 0.f, L.go(ws, n), 1.f, 0.f, 1.f, 0.f);
-        w.tgt[1] = tgt(L.gp(ws, n - 1, last_s, NH), gy_src, 0.f, wlast, L.go(ws, n), 0.f, wlast, 0.f, wlast);
-      } else {
-        w.n_targets = 1;
-        w.tgt[0] = tgt(gnext, gy_src, 1.f, 0.f, L.go(ws, 0), 1.f, 0.f, 1.f, 0.f);
+    for (int n = n_times - 2; n >= 0; --n) {
+      float* gnext = gbuf[n & 1];
+      auto slot = [&](int sl) -> float* {
+        return sl >= 0 ? L.gp(ws, n, sl, NH) : sl == kSlotGy ? gy : sl == kSlotState ? g : sl == kSlotOut ? gnext : nullptr;
+      };
+      for (int s = S - 1; s >= 0; --s) {
+        BwdArgs w = resolve_targets(plan[s], hdev + n, L.go(ws, n), slot);
+        if (s == 0) {
+          // the first stage's chain closes the interval, g(y[n]) = gy + gx + grad_out[n], and seeds the next one, which uses h[n-1]:
+          // the same three terms, each weighted wlast * h
+          w.h_ptr = n > 0 ? hdev + (n - 1) : nullptr;
+          if (n > 0) {
+            BwdTarget& seed = w.tgt[w.n_targets++] = w.tgt[0];
+            seed.out = L.gp(ws, n - 1, S - 1, NH);
+            seed.a_c = seed.b_c = seed.g_c = 0.0f;
+            seed.a_h = seed.b_h = seed.g_h = wlast;
+          }
+        }
+        if ((rc = bp.dgrad_chain(n, s, w)) != ODEHIP_OK) return rc;
       }
-      return w;
-    };
-    BwdArgs w;
-    if (method == ODEHIP_EULER) {
-      // y1 = y + h k1:  gk1 = h g (already seeded), gy = g
-      w = close_interval(g);
-      if ((rc = chain(n, 0, w)) != ODEHIP_OK) return rc;
-    } else if (method == ODEHIP_MIDPOINT) {
-      // x = y + h/2 k1, y1 = y + h k2:  gk2 = h g (seeded); gx2 -> gy = g + gx2, gk1 = h/2 gx2
-      memset(&w, 0, sizeof(w));
-      w.h_ptr = hdev + n;
-      w.n_targets = 2;
-      w.tgt[0] = tgt(gy, g, 1.f, 0.f, nullptr, 0.f, 0.f, 1.f, 0.f);
-      w.tgt[1] = tgt(L.gp(ws, n, 0, NH), nullptr, 0.f, 0.f, nullptr, 0.f, 0.f, 0.f, 0.5f);
-      if ((rc = chain(n, 1, w)) != ODEHIP_OK) return rc;
-      w = close_interval(gy);
-      if ((rc = chain(n, 0, w)) != ODEHIP_OK) return rc;
-    } else {
-      const float third = 1.0f / 3.0f;
-      float* gk1 = L.gp(ws, n, 0, NH);
-      float* gk2 = L.gp(ws, n, 1, NH);
-      float* gk3 = L.gp(ws, n, 2, NH);
-      // stage 4 (gk4 = h/8 g seeded): gx4 -> gy = g + gx4; gk3 = 3h/8 g + h gx4; gk2 = 3h/8 g - h gx4; gk1 = h/8 g + h gx4
-      memset(&w, 0, sizeof(w));
-      w.h_ptr = hdev + n;
-      w.n_targets = 4;
-      w.tgt[0] = tgt(gy, g, 1.f, 0.f, nullptr, 0.f, 0.f, 1.f, 0.f);
-      w.tgt[1] = tgt(gk3, g, 0.f, 0.375f, nullptr, 0.f, 0.f, 0.f, 1.f);
-      w.tgt[2] = tgt(gk2, g, 0.f, 0.375f, nullptr, 0.f, 0.f, 0.f, -1.f);
-      w.tgt[3] = tgt(gk1, g, 0.f, 0.125f, nullptr, 0.f, 0.f, 0.f, 1.f);
-      if ((rc = chain(n, 3, w)) != ODEHIP_OK) return rc;
-      // stage 3: gx3 -> gy += gx3; gk2 += h gx3; gk1 -= h/3 gx3
-      w.n_targets = 3;
-      w.tgt[0] = tgt(gy, gy, 1.f, 0.f, nullptr, 0.f, 0.f, 1.f, 0.f);
-      w.tgt[1] = tgt(gk2, gk2, 1.f, 0.f, nullptr, 0.f, 0.f, 0.f, 1.f);
-      w.tgt[2] = tgt(gk1, gk1, 1.f, 0.f, nullptr, 0.f, 0.f, 0.f, -third);
-      if ((rc = chain(n, 2, w)) != ODEHIP_OK) return rc;
-      // stage 2: gx2 -> gy += gx2; gk1 += h/3 gx2
-      w.n_targets = 2;
-      w.tgt[0] = tgt(gy, gy, 1.f, 0.f, nullptr, 0.f, 0.f, 1.f, 0.f);
-      w.tgt[1] = tgt(gk1, gk1, 1.f, 0.f, nullptr, 0.f, 0.f, 0.f, third);
-      if ((rc = chain(n, 1, w)) != ODEHIP_OK) return rc;
-      // stage 1: gx1 -> g(y[n]) = gy + gx1 + grad_out[n]
-      w = close_interval(gy);
-      if ((rc = chain(n, 0, w)) != ODEHIP_OK) return rc;
+      g = gnext;
     }
-    g = gnext;
-  }
-  return ODEHIP_OK;
+    return ODEHIP_OK;
   };
-  rc = sweep();
-  const int rc2 = persist.finish(hbuf, hdev, nullptr, batch, (unsigned*)L.p(ws, L.off_psync), f->ks, stream);
-  if (rc != ODEHIP_OK || rc2 != ODEHIP_OK) return rc != ODEHIP_OK ? rc : rc2;
-  rc = odehip_q4_to_nchw(g, grad_z0_nchw, batch, L.C, stream);
-  if (rc != ODEHIP_OK) return rc;
-
-  // ---- weight / bias gradients: one launch per layer over all (T-1)*S evaluations
-  rc = wgrad_all_layers(f, L, ws, n_times, batch, /*adjoint=*/false, nullptr, grad_w, grad_b, stream);
-  if (rc != ODEHIP_OK) return rc;
-  return guard_gradients(persist, f, batch, grad_z0_nchw, grad_w, grad_b, stream);
+  rc = sweep();   // moves g: read it only afterwards
+  return bp.finish(persist, rc, g, /*adjoint=*/false, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -569,171 +534,75 @@ extern "C" int odehip_odeint_adjoint_backward(const odehip_convstack* f, const o
                                               const double* t_host, int n_times, int batch, const float* y_traj_nchw,
                                               const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w,
                                               float* const* grad_b, void* workspace, size_t workspace_bytes, void* stream_) {
-  int rc = check_common(f, method, t_host, n_times, batch, "odeint_adjoint_backward");
+  int rc = check_backward_args(f, f_dgrad, method, t_host, n_times, batch, y_traj_nchw && grad_out_nchw && grad_z0_nchw && workspace,
+                               grad_w, grad_b, "odeint_adjoint_backward");
   if (rc != ODEHIP_OK) return rc;
-  ODEHIP_REQUIRE(f_dgrad && y_traj_nchw && grad_out_nchw && grad_z0_nchw && grad_w && grad_b && workspace,
-                 "odeint_adjoint_backward: null pointer");
-  for (int l = 0; l <= f->n_convs; ++l)
-    ODEHIP_REQUIRE(f->channels[l] % 64 == 0, "odeint_adjoint_backward: channel counts must be multiples of 64 (channels[%d] = %d)", l,
-                   f->channels[l]);
-  ODEHIP_REQUIRE(f->ks == 3, "odeint_adjoint_backward: 3x3 dynamics only");
   const FixedLayout L(f, batch, n_times, method, 1);
   ODEHIP_REQUIRE(workspace_bytes >= L.total, "odeint_adjoint_backward: workspace too small");
+  ODEHIP_REQUIRE((n_times - 1) * L.S <= kMaxWgradEvals, "odeint_adjoint_backward: too many evaluations (%d)", (n_times - 1) * L.S);
   hipStream_t stream = (hipStream_t)stream_;
   void* ws = workspace;
   const int NH = L.NH, S = L.S, NL = f->n_convs;
-  const size_t st_b = (size_t)batch * L.C * kPix * 4;
   float* hdev = L.p(ws, L.off_h);
-  float* ping = L.p(ws, L.off_ping);
-  float* pong = L.p(ws, L.off_pong);
+  float *ping = L.p(ws, L.off_ping), *pong = L.p(ws, L.off_pong);
   float* k[3] = {L.p(ws, L.off_k), L.p(ws, L.off_k + L.st), L.p(ws, L.off_k + 2 * L.st)};
-  float* q3 = L.p(ws, L.off_gy);             // partial sums of the a_y stages (see below)
-  float* q4 = L.p(ws, L.off_g2);
-  float* rr = L.p(ws, L.off_g2 + L.st);
+  float* sums[3] = {L.p(ws, L.off_gy), L.p(ws, L.off_g2), L.p(ws, L.off_g2 + L.st)};   // Q_2, Q_3 and R: partial sums of the a_y stages
 
   rc = odehip_nchw_to_q4(y_traj_nchw, L.y(ws, 0), n_times * batch, L.C, stream);
   if (rc != ODEHIP_OK) return rc;
   rc = odehip_nchw_to_q4(grad_out_nchw, L.go(ws, 0), n_times * batch, L.C, stream);
   if (rc != ODEHIP_OK) return rc;
-  if (n_times == 1) {
-    ODEHIP_CHECK_HIP(hipMemcpyAsync(grad_z0_nchw, grad_out_nchw, st_b, hipMemcpyDeviceToDevice, stream));
-    for (int l = 0; l < NL; ++l) {
-      ODEHIP_CHECK_HIP(hipMemsetAsync(grad_w[l], 0, (size_t)f->channels[l + 1] * f->channels[l] * 9 * 4, stream));
-      ODEHIP_CHECK_HIP(hipMemsetAsync(grad_b[l], 0, (size_t)f->channels[l + 1] * 4, stream));
-    }
-    return ODEHIP_OK;
-  }
-  float hbuf[4096];
-  for (int i = 0; i + 1 < n_times; ++i) hbuf[i] = (float)(t_host[i + 1] - t_host[i]);  // dt of the flipped grid, > 0
-  rc = upload_floats(hdev, hbuf, n_times - 1, stream);
+  BackwardPass bp = {f, f_dgrad, L, ws, n_times, batch, grad_z0_nchw, grad_w, grad_b, stream, {}};
+  if (n_times == 1) return bp.trivial(grad_out_nchw);
+  fill_step_sizes(bp.hbuf, t_host, n_times);   // dt of the flipped grid, > 0
+  rc = upload_floats(hdev, bp.hbuf, n_times - 1, stream);
   if (rc != ODEHIP_OK) return rc;
 
-  float* hidv[ODEHIP_MAX_LAYERS];
-  auto run_f = [&](int n, int s, const float* x, const CombineArgs& c) {  // f at stage s, activations kept
-    for (int l = 0; l < NH; ++l) hidv[l] = L.hidden(ws, n, s, l);
-    return enqueue_f_saving(f, x, batch, hidv, ping, pong, &c, nullptr, nullptr, stream);
-  };
-  auto chain = [&](int n, int s, const BwdArgs& last) -> int {  // K^a = J_f(Y_s)^T A_s, A_s = GP[n][s][NH]
-    float* gpv[ODEHIP_MAX_LAYERS + 1];
-    const float* hv[ODEHIP_MAX_LAYERS];
-    for (int l = 0; l < L.NG; ++l) gpv[l] = L.gp(ws, n, s, l);
-    for (int l = 0; l + 1 < NL; ++l) hv[l] = L.hidden(ws, n, s, l);
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.combine = 3;
-    a.bwd = last;
-    return enqueue_dgrad_chain(f, f_dgrad, batch, gpv, hv, a, stream);
-  };
-  auto tgt = [](float* out, const float* sa, float a_c, const float* sb, float b_c, float g_h) {
-    BwdTarget t;
-    t.out = out; t.srcA = sa; t.srcB = sb;
-    t.a_c = a_c; t.a_h = 0.f; t.b_c = b_c; t.b_h = 0.f; t.g_c = 0.f; t.g_h = g_h;
-    return t;
-  };
-
+  const FixedTableau& tab = fixed_tableau(method);
+  FixedCombine fwd[kFixedMaxStages];
+  FixedTargets plan[kFixedMaxStages];
+  for (int s = 0; s < S; ++s) {
+    fwd[s] = fixed_combine(tab, s, /*with_result=*/false);
+    plan[s] = adjoint_targets(tab, s);
+  }
   // seed: a_y = grad_out[T-1] is the stage-1 adjoint of the last interval
-  ODEHIP_CHECK_HIP(hipMemcpyAsync(L.gp(ws, n_times - 2, 0, NH), L.go(ws, n_times - 1), st_b, hipMemcpyDeviceToDevice, stream));
-  float scales[4096];
-  ODEHIP_REQUIRE((n_times - 1) * S <= 4096, "odeint_adjoint_backward: too many evaluations");
+  ODEHIP_CHECK_HIP(hipMemcpyAsync(L.gp(ws, n_times - 2, 0, NH), L.go(ws, n_times - 1), (size_t)batch * L.C * kPix * 4,
+                                  hipMemcpyDeviceToDevice, stream));
+  float scales[kMaxWgradEvals];
   float* a_final = L.p(ws, L.off_xs);
+  float* hidv[ODEHIP_MAX_LAYERS];
   // every interval is conv launches only (recomputed stages + input-gradient chains, all bookkeeping in their epilogues)
   PersistScope persist;
   if ((rc = persist.begin(f, f_dgrad, (n_times - 1) * S * NL * 2)) != ODEHIP_OK) return rc;
   auto sweep = [&]() -> int {
-  for (int n = n_times - 2; n >= 0; --n) {
-    const float* y = L.y(ws, n + 1);                       // integrate from t[n+1] back to t[n]
-    const float* a = L.gp(ws, n, 0, NH);                   // a_y at t[n+1]
-    float* a_next = n > 0 ? L.gp(ws, n - 1, 0, NH) : a_final;  // a_y at t[n] (+ grad_out[n]) seeds the next interval
-    CombineArgs c;
-    memset(&c, 0, sizeof(c));
-    c.y = y;
-    c.h_ptr = hdev + n;
-    c.k_scale = -1.0f;                                     // negated dynamics
-    BwdArgs w;
-    memset(&w, 0, sizeof(w));
-    w.h_ptr = hdev + n;
-    const float dt = hbuf[n];
-    if (method == ODEHIP_EULER) {
-      scales[n * S + 0] = dt;
-      if ((rc = run_f(n, 0, y, c)) != ODEHIP_OK) return rc;
-      w.n_targets = 1;
-      w.tgt[0] = tgt(a_next, a, 1.f, L.go(ws, n), 1.f, 1.f);            // a + dt K1 + grad_out[n]
-      if ((rc = chain(n, 0, w)) != ODEHIP_OK) return rc;
-    } else if (method == ODEHIP_MIDPOINT) {
-      scales[n * S + 0] = 0.0f;                                         // b = (0, 1)
-      scales[n * S + 1] = dt;
-      c.c1[0] = 0.5f;
-      c.out1 = L.xin(ws, n, 1);                                         // Y2 = y + dt/2 k1'
-      if ((rc = run_f(n, 0, y, c)) != ODEHIP_OK) return rc;
-      w.n_targets = 1;
-      w.tgt[0] = tgt(L.gp(ws, n, 1, NH), a, 1.f, nullptr, 0.f, 0.5f);   // A2 = a + dt/2 K1
-      if ((rc = chain(n, 0, w)) != ODEHIP_OK) return rc;
-      c.c1[0] = 0.f;
-      c.out1 = nullptr;
-      if ((rc = run_f(n, 1, L.xin(ws, n, 1), c)) != ODEHIP_OK) return rc;
-      w.tgt[0] = tgt(a_next, a, 1.f, L.go(ws, n), 1.f, 1.f);            // a + dt K2 + grad_out[n]
-      if ((rc = chain(n, 1, w)) != ODEHIP_OK) return rc;
-    } else {
-      const float third = 1.0f / 3.0f;
-      scales[n * S + 0] = dt * 0.125f;
-      scales[n * S + 1] = dt * 0.375f;
-      scales[n * S + 2] = dt * 0.375f;
-      scales[n * S + 3] = dt * 0.125f;
-      // stage 1: k1' = -f(y); Y2 = y + dt k1'/3.   K1: A2 = a + dt/3 K1; Q3 = a - dt/3 K1; Q4 = a + dt K1; R = a + dt/8 K1
-      c.k_out = k[0];
-      c.c1[0] = third;
-      c.out1 = L.xin(ws, n, 1);
-      if ((rc = run_f(n, 0, y, c)) != ODEHIP_OK) return rc;
-      w.n_targets = 4;
-      w.tgt[0] = tgt(L.gp(ws, n, 1, NH), a, 1.f, nullptr, 0.f, third);
-      w.tgt[1] = tgt(q3, a, 1.f, nullptr, 0.f, -third);
-      w.tgt[2] = tgt(q4, a, 1.f, nullptr, 0.f, 1.f);
-      w.tgt[3] = tgt(rr, a, 1.f, nullptr, 0.f, 0.125f);
-      if ((rc = chain(n, 0, w)) != ODEHIP_OK) return rc;
-      // stage 2: Y3 = y + dt (k2' - k1'/3).   K2: A3 = Q3 + dt K2; Q4 -= dt K2; R += 3dt/8 K2
-      c.n_prev = 1;
-      c.k_prev[0] = k[0];
-      c.k_out = k[1];
-      c.c1[0] = -third;
-      c.c1[1] = 1.f;
-      c.out1 = L.xin(ws, n, 2);
-      if ((rc = run_f(n, 1, L.xin(ws, n, 1), c)) != ODEHIP_OK) return rc;
-      w.n_targets = 3;
-      w.tgt[0] = tgt(L.gp(ws, n, 2, NH), q3, 1.f, nullptr, 0.f, 1.f);
-      w.tgt[1] = tgt(q4, q4, 1.f, nullptr, 0.f, -1.f);
-      w.tgt[2] = tgt(rr, rr, 1.f, nullptr, 0.f, 0.375f);
-      if ((rc = chain(n, 1, w)) != ODEHIP_OK) return rc;
-      // stage 3: Y4 = y + dt (k1' - k2' + k3').   K3: A4 = Q4 + dt K3; R += 3dt/8 K3
-      c.n_prev = 2;
-      c.k_prev[1] = k[1];
-      c.k_out = nullptr;
-      c.c1[0] = 1.f;
-      c.c1[1] = -1.f;
-      c.c1[2] = 1.f;
-      c.out1 = L.xin(ws, n, 3);
-      if ((rc = run_f(n, 2, L.xin(ws, n, 2), c)) != ODEHIP_OK) return rc;
-      w.n_targets = 2;
-      w.tgt[0] = tgt(L.gp(ws, n, 3, NH), q4, 1.f, nullptr, 0.f, 1.f);
-      w.tgt[1] = tgt(rr, rr, 1.f, nullptr, 0.f, 0.375f);
-      if ((rc = chain(n, 2, w)) != ODEHIP_OK) return rc;
-      // stage 4: only the activations at Y4 are needed (y is reset to the stored y[n]).   K4: a_next = R + dt/8 K4 + grad_out[n]
-      memset(&c, 0, sizeof(c));
-      c.k_scale = -1.0f;
-      c.k_out = k[2];  // k4' itself is unused; the epilogue needs some destination
-      if ((rc = run_f(n, 3, L.xin(ws, n, 3), c)) != ODEHIP_OK) return rc;
-      w.n_targets = 1;
-      w.tgt[0] = tgt(a_next, rr, 1.f, L.go(ws, n), 1.f, 0.125f);
-      if ((rc = chain(n, 3, w)) != ODEHIP_OK) return rc;
+    for (int n = n_times - 2; n >= 0; --n) {
+      const float* y = L.y(ws, n + 1);                       // integrate from t[n+1] back to t[n]
+      float* a_next = n > 0 ? L.gp(ws, n - 1, 0, NH) : a_final;  // a_y at t[n] (+ grad_out[n]) seeds the next interval
+      auto slot = [&](int sl) -> float* {                    // stage 0's tensor is a_y at t[n+1]
+        return sl >= kSlotQ ? sums[sl - kSlotQ - 2] : sl >= 0 ? L.gp(ws, n, sl, NH) : sl == kSlotState ? L.gp(ws, n, 0, NH)
+                                                               : sl == kSlotR ? sums[2] : sl == kSlotOut ? a_next : nullptr;
+      };
+      CombineArgs last, base;
+      memset(&last, 0, sizeof(last));
+      last.k_scale = -1.0f;                                  // negated dynamics
+      base = last;
+      base.y = y;
+      base.h_ptr = hdev + n;
+      for (int s = 0; s < S; ++s) {
+        scales[n * S + s] = bp.hbuf[n] * tab.b[s];
+        // Y_{s+1} = y + dt sum_j a[s+1][j] k_j'.  The last stage only leaves its activations (y is reset to the stored y[n]): its
+        // epilogue stores nothing, and with neither y nor a destination set it reads nothing either
+        CombineArgs c = last;
+        if (s + 1 < S) c = stage_combine(fwd[s], s, base, k, L.xin(ws, n, s + 1), nullptr, nullptr);
+        for (int l = 0; l < NH; ++l) hidv[l] = L.hidden(ws, n, s, l);
+        if ((rc = enqueue_f_saving(f, s == 0 ? y : L.xin(ws, n, s), batch, hidv, ping, pong, &c, nullptr, nullptr, stream)) != ODEHIP_OK)
+          return rc;
+        // K_s = J_f(Y_s)^T A_s, A_s = GP[n][s][NH]
+        if ((rc = bp.dgrad_chain(n, s, resolve_targets(plan[s], hdev + n, L.go(ws, n), slot))) != ODEHIP_OK) return rc;
+      }
     }
-  }
-  return ODEHIP_OK;
+    return ODEHIP_OK;
   };
   rc = sweep();
-  const int rc2 = persist.finish(hbuf, hdev, nullptr, batch, (unsigned*)L.p(ws, L.off_psync), f->ks, stream);
-  if (rc != ODEHIP_OK || rc2 != ODEHIP_OK) return rc != ODEHIP_OK ? rc : rc2;
-  rc = odehip_q4_to_nchw(a_final, grad_z0_nchw, batch, L.C, stream);
-  if (rc != ODEHIP_OK) return rc;
-  rc = wgrad_all_layers(f, L, ws, n_times, batch, /*adjoint=*/true, scales, grad_w, grad_b, stream);
-  if (rc != ODEHIP_OK) return rc;
-  return guard_gradients(persist, f, batch, grad_z0_nchw, grad_w, grad_b, stream);
+  return bp.finish(persist, rc, a_final, /*adjoint=*/true, scales);
 }

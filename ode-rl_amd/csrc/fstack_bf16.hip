@@ -19,6 +19,7 @@
 // CUs idle -- at B = 64 one f evaluation still takes ~1/3 of five bf16 launches.
 #include <string.h>
 
+#include "fixed_tableau.h"
 #include "fused_bf16.h"
 
 namespace odehip {
@@ -212,30 +213,22 @@ struct TrajArgs {
   unsigned long long stride_x, stride_h_eval, stride_h_layer;
 };
 
-// the stage programs of fixed_grid.hip (torchdiffeq _impl/fixed_grid.py; rk4 = the 3/8 rule), compile-time constants here: per
-// stage, how many earlier k enter its combine (n_prev) and the weights of k_1 .. k_{n_prev} and (last) of the stage's own k
-template <int METHOD> struct StageProgram;
-template <> struct StageProgram<ODEHIP_EULER> {
-  static constexpr int S = 1;
-  static constexpr int n_prev[4] = {0, 0, 0, 0};
-  static constexpr float c[4][4] = {{1.0f, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-};
-template <> struct StageProgram<ODEHIP_MIDPOINT> {
-  static constexpr int S = 2;
-  static constexpr int n_prev[4] = {0, 0, 0, 0};   // the midpoint rule's result does not use k1
-  static constexpr float c[4][4] = {{0.5f, 0, 0, 0}, {1.0f, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-};
-template <> struct StageProgram<ODEHIP_RK4> {
-  static constexpr int S = 4;
-  static constexpr int n_prev[4] = {0, 1, 2, 3};
-  static constexpr float c[4][4] = {{1.0f / 3.0f, 0, 0, 0}, {-(1.0f / 3.0f), 1.0f, 0, 0}, {1.0f, -1.0f, 1.0f, 0}, {0.125f, 0.375f, 0.375f, 0.125f}};
+// the forward plan of fixed_tableau.h as compile-time constants: per stage, how many earlier k enter its combine (n_prev) and the
+// weights of the kept k_j and (last) of the stage's own k
+template <int METHOD> struct StageProgram {
+  static constexpr int S = kFixedTableau[METHOD].S;
+  static constexpr FixedCombine st[kFixedMaxStages] = {fixed_combine(kFixedTableau[METHOD], 0), fixed_combine(kFixedTableau[METHOD], 1),
+                                                       fixed_combine(kFixedTableau[METHOD], 2), fixed_combine(kFixedTableau[METHOD], 3)};
+  // the kernel keeps k_j in register slot j: the kept stages must be 0 .. n_prev-1
+  static constexpr bool in_order(int s) { return st[s].n_prev == 0 || (st[s].prev[st[s].n_prev - 1] == st[s].n_prev - 1 && st[s].n_prev <= 3); }
 };
 
 template <int METHOD, bool SAVE>
 __global__ __launch_bounds__(512, 1) void ftraj_bf16_kernel(const TrajArgs ta) {
   typedef StageProgram<METHOD> Prog;
   constexpr int S = Prog::S;
-  constexpr int NK = Prog::n_prev[S - 1];   // stage derivatives that must be kept (rk4: 3, midpoint / euler: 0)
+  constexpr int NK = Prog::st[S - 1].n_prev;   // stage derivatives that must be kept (rk4: 3, midpoint / euler: 0)
+  static_assert(Prog::in_order(0) && Prog::in_order(1) && Prog::in_order(2) && Prog::in_order(3), "kept stages are not a prefix");
   // TWO activation tiles (round 3): a layer reads one and writes its output into the other, so no wave has to wait for the slowest
   // reader before it rewrites -- the in-place rewrite of the single-tile kernels needs a barrier of its own per layer and
   // serialises the epilogue behind it.  Both fit next to the weight ring because a tile here has NO column borders: the dx = -1 /
@@ -393,12 +386,12 @@ __global__ __launch_bounds__(512, 1) void ftraj_bf16_kernel(const TrajArgs ta) {
         for (int g = 0; g < 4; ++g) {
           f32x4 kc = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
           kc *= ta.k_scale;
-          f32x4 sa = kc * Prog::c[s][Prog::n_prev[s]];
+          f32x4 sa = kc * Prog::st[s].c[Prog::st[s].n_prev];
 #pragma unroll
           for (int j = 0; j < NK; ++j)
-            if (j < Prog::n_prev[s]) {
+            if (j < Prog::st[s].n_prev) {
               const f32x4 kp = {k[j][nb][4 * g], k[j][nb][4 * g + 1], k[j][nb][4 * g + 2], k[j][nb][4 * g + 3]};
-              sa += kp * Prog::c[s][j];
+              sa += kp * Prog::st[s].c[j];
             }
           const f32x4 yv = {y[nb][4 * g], y[nb][4 * g + 1], y[nb][4 * g + 2], y[nb][4 * g + 3]};
           const f32x4 ov = yv + sa * h;
