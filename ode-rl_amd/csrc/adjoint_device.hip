@@ -19,7 +19,6 @@
 // A training step at B=64, T=10 is 27 ticks instead of ~720 per-layer launches and 27 stream synchronisations.
 #include <math.h>
 #include <string.h>
-#include <time.h>
 
 #include <vector>
 
@@ -93,13 +92,7 @@ __device__ void adj_sums4(const float* base, int stride, const int* which, int c
   __syncthreads();
 }
 
-__device__ double adj_dense_weight(const AdjCtl* st, int s, double x) {  // dp5::dense_weight
-  const double d1 = s == 0 ? 1.0 : 0.0, d7 = s == 6 ? 1.0 : 0.0, b = st->csol[s], m = st->cmid[s];
-  const double A4 = 2.0 * (d7 - d1) - 8.0 * b + 16.0 * m;
-  const double B3 = 5.0 * d1 - 3.0 * d7 + 14.0 * b - 32.0 * m;
-  const double C2 = d7 - 4.0 * d1 - 5.0 * b + 16.0 * m;
-  return x * d1 + x * x * C2 + x * x * x * B3 + x * x * x * x * A4;
-}
+__device__ double adj_dense_weight(const AdjCtl* st, int s, double x) { return dp5::dense_weight(s, x, st->csol[s], st->cmid[s]); }
 
 __device__ void adj_decide(AdjCtl* st, float s0, float s1, float s2, float s3, AdjMailbox* mb);
 
@@ -180,7 +173,7 @@ __device__ void adj_decide(AdjCtl* st, float s0, float s1, float s2, float s3, A
     else start_interval(st->n_times - 2, st->goq_base + (unsigned long long)(st->n_times - 1) * ST, false);
   } else if (phase == PH_P0) {  // _select_initial_step, first half
     const float d0 = fmaxf(rms(s0), rms(s1)), d1 = fmaxf(rms(s2), rms(s3));
-    st->h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+    st->h0 = dp5::initial_step_h0(d0, d1);
     st->d1 = d1;
     st->nfe += 1;
     st->phase = PH_P1;
@@ -189,11 +182,8 @@ __device__ void adj_decide(AdjCtl* st, float s0, float s1, float s2, float s3, A
   } else if (phase == PH_P1) {  // second half: d2 -> dt; first attempt
     const float h0 = st->h0, d1 = st->d1;
     const float d2 = fmaxf(rms(s0), rms(s1)) / h0;
-    float h1;
-    if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
-    else h1 = powf(0.01f / fmaxf(d1, d2), 1.0f / 5.0f);
     st->nfe += 1;
-    st->dt = (double)fminf(100.0f * h0, h1);
+    st->dt = (double)dp5::initial_step_dt(h0, d1, d2);
     st->t_cur = -st->t[st->n + 1];
     st->t_end = -st->t[st->n];
     ok = start_attempt();
@@ -206,13 +196,7 @@ __device__ void adj_decide(AdjCtl* st, float s0, float s1, float s2, float s3, A
     } else {
       const bool accept = ratio <= 1.0f;
       const double dt = st->dt;
-      double dtn;
-      if (ratio == 0.0f) {
-        dtn = dt * 10.0;
-      } else {
-        const double dfactor = ratio < 1.0f ? 1.0 : 0.2;
-        dtn = dt * fmin(10.0, fmax(0.9 / pow((double)ratio, 0.2), dfactor));
-      }
+      const double dtn = dp5::next_step_size(dt, ratio);
       if (!accept) {
         st->n_reject += 1;
         st->dt = dtn;
@@ -302,12 +286,6 @@ __device__ void adj_decide(AdjCtl* st, float s0, float s1, float s2, float s3, A
 __global__ void adj_init_kernel(AdjCtl* st, AdjCtl init) { *st = init; }
 
 static AdjMailbox* g_adj_mailbox = nullptr;
-
-static double adj_now_s() {
-  timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return ts.tv_sec + 1e-9 * ts.tv_nsec;
-}
 
 int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host, int n_times, int batch, float rtol,
                           float atol, const float* y_traj_nchw, const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w,
@@ -506,35 +484,15 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
     if ((rc = ew(s_xin(1), Ycur, 1, k0y, &b21, hp, nullptr)) != ODEHIP_OK) return rc;
     if ((rc = ew(s_gp(1, NH), Acur, 1, k0a, &b21, hp, nullptr)) != ODEHIP_OK) return rc;
     std::vector<ConvArgs> F[7], D[7];   // rows of evaluation e = s - 1 (stage s lives at index s-1 of the slot)
-    for (int s = 2; s <= 7; ++s) {
-      memset(&cy, 0, sizeof(cy));
-      memset(&ca, 0, sizeof(ca));
+    float* const kyR[7] = {kyA, ky[1], ky[2], ky[3], ky[4], ky[5], kyB};   // k1 / k7: whichever of buffers 0 and 6 holds the role
+    float* const kaR[7] = {kaA, ka[1], ka[2], ka[3], ka[4], ka[5], kaB};
+    for (int s = 2; s <= 7; ++s) {   // Y_{s+1}, A_{s+1} (s = 6: y1, a1; s = 7: error norms)
+      const int nx = s < 7 ? s : 6;
+      dopri5_stage_combine(cy, s, Ycur, hp, kyR, s_xin(nx), L.part(ws, 4), rtol, atol);
+      dopri5_stage_combine(ca, s, Acur, hp, kaR, s_gp(nx, NH), L.part(ws, 5), rtol, atol);
       cy.order = ca.order = 1;
       cy.k_scale = -1.0f;
       ca.k_scale = 1.0f;
-      cy.y = Ycur;
-      ca.y = Acur;
-      cy.h_ptr = ca.h_ptr = hp;
-      cy.n_prev = ca.n_prev = s - 1;
-      for (int j = 0; j < s - 1; ++j) {
-        cy.k_prev[j] = j == 0 ? kyA : ky[j];
-        ca.k_prev[j] = j == 0 ? kaA : ka[j];
-      }
-      cy.k_out = s == 7 ? kyB : ky[s - 1];
-      ca.k_out = s == 7 ? kaB : ka[s - 1];
-      if (s <= 6) {
-        for (int j = 0; j < s; ++j) cy.c1[j] = ca.c1[j] = (float)dp5::kBeta[s - 1][j];
-        cy.out1 = s_xin(s);       // Y_{s+1}  (s = 6: y1)
-        ca.out1 = s_gp(s, NH);    // A_{s+1}  (s = 6: a1)
-      } else {
-        for (int j = 0; j < 7; ++j) cy.ce[j] = ca.ce[j] = (float)dp5::kCErr[j];
-        cy.err_y1 = s_xin(6);
-        ca.err_y1 = s_gp(6, NH);
-        cy.err_partials = L.part(ws, 4);
-        ca.err_partials = L.part(ws, 5);
-        cy.rtol = ca.rtol = rtol;
-        cy.atol = ca.atol = atol;
-      }
       if ((rc = rows_f(s - 1, s_xin(s - 1), cy, F[s - 1])) != ODEHIP_OK) return rc;
       if ((rc = rows_d(s - 1, ca, D[s - 1])) != ODEHIP_OK) return rc;
       ODEHIP_REQUIRE((int)F[s - 1].size() == NL && (int)D[s - 1].size() == NL, "adjoint: unexpected row count of an evaluation");
@@ -587,8 +545,8 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
   const int psync_words = (int)(persist_sync_bytes(batch) / 4);
 
   // ---- ticks: the host stays at most one tick ahead of the device ------------------------------------------------------------
-  int enq = 0, seen = 0;
-  double t_progress = adj_now_s();
+  int enq = 0;
+  MailboxWatch watch(&g_adj_mailbox->ticks);
   for (;;) {
     hipLaunchKernelGGL(adj_control_kernel, dim3(1), dim3(256), 0, stream, state, L.part(ws, 0), part_stride, psync, psync_words, g_adj_mailbox);
     ODEHIP_CHECK_HIP(hipGetLastError());
@@ -597,11 +555,7 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
     if (rc != ODEHIP_OK) return rc;
     ++enq;
     while (g_adj_mailbox->ticks + 1 < enq) {
-      if (g_adj_mailbox->ticks != seen) {
-        seen = g_adj_mailbox->ticks;
-        t_progress = adj_now_s();
-      }
-      if (adj_now_s() - t_progress > 120.0) {
+      if (watch.stalled()) {
         set_error("odeint_adjoint_dopri5_backward: no progress from the device for 120 s (%d of %d ticks)", g_adj_mailbox->ticks, enq);
         return ODEHIP_EHIP;
       }
@@ -611,10 +565,7 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
   if (g_adj_mailbox->status != 0) {
     const int s = g_adj_mailbox->status;
     ODEHIP_CHECK_HIP(hipStreamSynchronize(stream));   // (error path: nothing of this call may still write the mailbox afterwards)
-    if (s == ODEHIP_ENAN) set_error("odeint_adjoint_dopri5_backward: non-finite error ratio");
-    else if (s == ODEHIP_ENOTCONV) set_error("odeint_adjoint_dopri5_backward: underflow in dt");
-    else set_error("odeint_adjoint_dopri5_backward: more than max_accept = %d accepted steps", max_accept);
-    return s;
+    return controller_error(true, s, max_accept);
   }
   // a(t[0]) is the result of the last P3 program: a2[0]
   rc = odehip_q4_to_nchw(L.p(ws, L.off_a2), grad_z0_nchw, batch, L.C, stream);
@@ -629,11 +580,7 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
                       f->w_bf16[l] != nullptr);
     if (rc != ODEHIP_OK) return rc;
   }
-  if (stats_host) {
-    stats_host[0] = g_adj_mailbox->nfe;
-    stats_host[1] = g_adj_mailbox->n_accept;
-    stats_host[2] = g_adj_mailbox->n_reject;
-  }
+  write_stats(stats_host, g_adj_mailbox->nfe, g_adj_mailbox->n_accept, g_adj_mailbox->n_reject);
   float* regions[2 * ODEHIP_MAX_LAYERS + 1];
   size_t floats[2 * ODEHIP_MAX_LAYERS + 1];
   int nr = 0;
@@ -646,9 +593,9 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
   // A tick may still be queued behind `done` (the host runs one ahead): its controller writes the mailbox once more.  Wait for it
   // (the work enqueued above keeps the device busy meanwhile) so that the next call's freshly cleared mailbox cannot be overwritten
   // by this call's last controller.
-  t_progress = adj_now_s();
+  watch = MailboxWatch(&g_adj_mailbox->ticks);
   while (g_adj_mailbox->ticks < enq) {
-    if (adj_now_s() - t_progress > 120.0) {
+    if (watch.stalled()) {
       set_error("odeint_adjoint_dopri5_backward: the device did not drain (%d of %d ticks)", g_adj_mailbox->ticks, enq);
       return ODEHIP_EHIP;
     }

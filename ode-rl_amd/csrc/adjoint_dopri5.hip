@@ -25,59 +25,12 @@
 
 #include "odehip_internal.h"
 #include "adjoint_layout.h"
+#include "dopri5_reduce.h"
 
 namespace odehip {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-
-
-// sum over elements of ((a - b) / (atol + |y|*rtol))^2, one partial per workgroup (b may be null)
-__global__ __launch_bounds__(256) void adj_sumsq_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                        const float* __restrict__ y, float atol, float rtol, long long n4,
-                                                        float* __restrict__ partials) {
-  __shared__ float sh[256];
-  float s = 0.0f;
-  for (long long i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    f32x4 d = ((const f32x4*)a)[i];
-    const f32x4 yv = ((const f32x4*)y)[i];
-    if (b) d -= ((const f32x4*)b)[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float r = d[k] / (atol + fabsf(yv[k]) * rtol);
-      s += r * r;
-    }
-  }
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partials[blockIdx.x] = sh[0];
-}
-
-// out[j] = sum of partials_j (fixed order), j < n_arrays; one workgroup
-struct PartialSet {
-  const float* p[8];
-  int n[8];
-  int count;
-};
-__global__ __launch_bounds__(256) void adj_reduce_kernel(PartialSet ps, float* __restrict__ out) {
-  __shared__ float sh[256];
-  for (int j = 0; j < ps.count; ++j) {
-    float s = 0.0f;
-    for (int i = threadIdx.x; i < ps.n[j]; i += 256) s += ps.p[j][i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) out[j] = sh[0];
-    __syncthreads();
-  }
-}
 
 // out = y + sum_j c[j]*k[j] (+ add)      (coefficients already include the step size)
 struct AdjLin {
@@ -117,12 +70,8 @@ __global__ __launch_bounds__(256) void theta_sumsq_kernel(const float* __restric
     s += v * v;
   }
   sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[j] = sh[0];
+  const float sum = block_tree_sum(sh);
+  if (threadIdx.x == 0) out[j] = sum;
 }
 // a += d
 __global__ __launch_bounds__(256) void theta_add_kernel(float* __restrict__ a, const float* __restrict__ d, int n) {
@@ -198,7 +147,7 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
       ODEHIP_CHECK_HIP(hipMemsetAsync(grad_w[l], 0, (size_t)f->channels[l + 1] * f->channels[l] * 9 * 4, stream));
       ODEHIP_CHECK_HIP(hipMemsetAsync(grad_b[l], 0, (size_t)f->channels[l + 1] * 4, stream));
     }
-    if (stats_host) stats_host[0] = stats_host[1] = stats_host[2] = 0;
+    write_stats(stats_host, 0, 0, 0);
     return ODEHIP_OK;
   }
 
@@ -218,18 +167,18 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
     return enqueue_dgrad_chain(f, f_dgrad, batch, gpv, hidv, a, stream);
   };
   auto sumsq = [&](int j, const float* a, const float* b, const float* y) {
-    hipLaunchKernelGGL(adj_sumsq_kernel, dim3(256), dim3(256), 0, stream, a, b, y, atol, rtol, n4, L.part(ws, j));
+    hipLaunchKernelGGL(scaled_sumsq_kernel, dim3(256), dim3(256), 0, stream, a, b, y, atol, rtol, n4, L.part(ws, j));
   };
   // reduce `count` partial arrays and bring the sums to the host (one synchronisation)
   auto fetch = [&](int count, const int* which, const int* lens, float* out) -> int {
-    PartialSet ps;
-    memset(&ps, 0, sizeof(ps));
-    ps.count = count;
+    SumSet ss;
+    memset(&ss, 0, sizeof(ss));
+    ss.count = count;
     for (int j = 0; j < count; ++j) {
-      ps.p[j] = L.part(ws, which[j]);
-      ps.n[j] = lens[j];
+      ss.p[j] = L.part(ws, which[j]);
+      ss.n[j] = lens[j];
     }
-    hipLaunchKernelGGL(adj_reduce_kernel, dim3(1), dim3(256), 0, stream, ps, sums);
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, stream, ss, sums, (const int*)nullptr);
     ODEHIP_CHECK_HIP(hipMemcpyAsync(g_adj_host, sums, (size_t)(mixed_norm ? 8 + 4 * NL : count) * 4, hipMemcpyDeviceToHost, stream));
     ODEHIP_CHECK_HIP(hipStreamSynchronize(stream));
     for (int j = 0; j < count; ++j) out[j] = g_adj_host[j];
@@ -354,7 +303,7 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
         d0 = fmaxf(d0, theta_rms_max(g_adj_host + 8));
         d1 = fmaxf(d1, theta_rms_max(g_adj_host + 8 + NT));
       }
-      const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+      const float h0 = dp5::initial_step_h0(d0, d1);
       float* k0y[1] = {ky[0]};
       float* k0a[1] = {ka[0]};
       lincomb(L.xin(ws, slot, 1), y_cur, 1, k0y, &h0, nullptr);
@@ -375,10 +324,7 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
       float d2 = fmaxf(rms(s2[0]), rms(s2[1]));
       if (mixed_norm) d2 = fmaxf(d2, theta_rms_max(g_adj_host + 8));
       d2 /= h0;
-      float h1;
-      if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
-      else h1 = powf(0.01f / fmaxf(d1, d2), 1.0f / 5.0f);
-      g_adj_host[32] = fminf(100.0f * h0, h1);
+      g_adj_host[32] = dp5::initial_step_dt(h0, d1, d2);
     }
     double dt = (double)g_adj_host[32];
     double t_cur = t_begin;
@@ -395,34 +341,12 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
         lincomb(L.xin(ws, slot, 1), y_cur, 1, k0y, &c, nullptr);
         lincomb(L.gp(ws, slot, 1, NH), a_cur, 1, k0a, &c, nullptr);
       }
-      for (int s = 2; s <= 7; ++s) {  // stage s lives at index s-1 of the slot
-        memset(&cy, 0, sizeof(cy));
-        memset(&ca, 0, sizeof(ca));
+      for (int s = 2; s <= 7; ++s) {  // stage s lives at index s-1 of the slot; Y_{s+1}, A_{s+1} (s = 6: y1, a1; s = 7: error norms)
+        const int nx = s < 7 ? s : 6;
+        dopri5_stage_combine(cy, s, y_cur, hdev, ky, L.xin(ws, slot, nx), L.part(ws, 4), rtol, atol);
+        dopri5_stage_combine(ca, s, a_cur, hdev, ka, L.gp(ws, slot, nx, NH), L.part(ws, 5), rtol, atol);
         cy.k_scale = -1.0f;
         ca.k_scale = 1.0f;
-        cy.y = y_cur;
-        ca.y = a_cur;
-        cy.h_ptr = ca.h_ptr = hdev;
-        cy.n_prev = ca.n_prev = s - 1;
-        for (int j = 0; j < s - 1; ++j) {
-          cy.k_prev[j] = ky[j];
-          ca.k_prev[j] = ka[j];
-        }
-        cy.k_out = ky[s - 1];
-        ca.k_out = ka[s - 1];
-        if (s <= 6) {
-          for (int j = 0; j < s; ++j) cy.c1[j] = ca.c1[j] = (float)dp5::kBeta[s - 1][j];
-          cy.out1 = L.xin(ws, slot, s);       // Y_{s+1}  (s = 6: y1)
-          ca.out1 = L.gp(ws, slot, s, NH);    // A_{s+1}  (s = 6: a1)
-        } else {
-          for (int j = 0; j < 7; ++j) cy.ce[j] = ca.ce[j] = (float)dp5::kCErr[j];
-          cy.err_y1 = L.xin(ws, slot, 6);
-          ca.err_y1 = L.gp(ws, slot, 6, NH);
-          cy.err_partials = L.part(ws, 4);
-          ca.err_partials = L.part(ws, 5);
-          cy.rtol = ca.rtol = rtol;
-          cy.atol = ca.atol = atol;
-        }
         if ((rc = eval_aug(slot, s - 1, L.xin(ws, slot, s - 1), cy, ca)) != ODEHIP_OK) return rc;
       }
       nfe += 6;
@@ -445,13 +369,7 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
       if (mixed_norm) ratio = fmaxf(ratio, theta_rms_max(g_adj_host + 8));
       ODEHIP_REQUIRE(ratio == ratio, "odeint_adjoint_dopri5_backward: non-finite error ratio");
       const bool accept = ratio <= 1.0f;
-      double dtn;
-      if (ratio == 0.0f) {
-        dtn = dt * 10.0;
-      } else {
-        const double dfactor = ratio < 1.0f ? 1.0 : 0.2;
-        dtn = dt * fmin(10.0, fmax(0.9 / pow((double)ratio, 0.2), dfactor));
-      }
+      const double dtn = dp5::next_step_size(dt, ratio);
       if (!accept) {
         ++n_reject;
         dt = dtn;
@@ -514,11 +432,7 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
       ODEHIP_CHECK_HIP(hipMemcpyAsync(grad_b[l], th_run + spans.off[2 * l + 1], (size_t)(spans.off[2 * l + 2] - spans.off[2 * l + 1]) * 4,
                                       hipMemcpyDeviceToDevice, stream));
     }
-    if (stats_host) {
-      stats_host[0] = nfe;
-      stats_host[1] = n_accept;
-      stats_host[2] = n_reject;
-    }
+    write_stats(stats_host, nfe, n_accept, n_reject);
     return ODEHIP_OK;
   }
   // ---- seminorm: a_theta does not steer the steps, so ONE wgrad launch per layer over every recorded stage evaluation
@@ -538,10 +452,6 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
     rc = launch_wgrad(table, n_eval, batch, 4, slabs, grad_w[l], grad_b[l], f->channels[l + 1], f->channels[l], stream, f->w_bf16[l] != nullptr);
     if (rc != ODEHIP_OK) return rc;
   }
-  if (stats_host) {
-    stats_host[0] = nfe;
-    stats_host[1] = n_accept;
-    stats_host[2] = n_reject;
-  }
+  write_stats(stats_host, nfe, n_accept, n_reject);
   return ODEHIP_OK;
 }

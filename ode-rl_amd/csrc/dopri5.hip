@@ -13,17 +13,17 @@
 // FSAL hand-over y <- y1, k1 <- k7, and the first stage input of the next attempt).
 #include <math.h>
 #include <string.h>
-#include <time.h>
 
 #include "odehip_internal.h"
 #include "persist.h"
 #include "dopri5_layout.h"
+#include "dopri5_reduce.h"
 
 namespace odehip {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Dormand-Prince-Shampine tableau (torchdiffeq/_impl/dopri5.py)
+// (the tableau and the scalar step-size decisions: dopri5_control.h)
 
 struct DopriState {
   double t0, t1, dt;   // accepted interval [t0, t1]; size of the attempt in flight
@@ -72,7 +72,6 @@ __device__ float block_sum(const float* v, int n, float* sh) {
   return sh[0];
 }
 
-// partial sums of ((a - b) / (atol + |y|*rtol))^2 per workgroup (b may be null)
 __global__ __launch_bounds__(256) void scaled_sumsq_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                            const float* __restrict__ y, float atol, float rtol,
                                                            long long n4, float* __restrict__ partials) {
@@ -89,12 +88,8 @@ __global__ __launch_bounds__(256) void scaled_sumsq_kernel(const float* __restri
     }
   }
   sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partials[blockIdx.x] = sh[0];
+  const float sum = block_tree_sum(sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 
 // out = y + h * sum_j c[j] * k[j]   (h from device memory)
@@ -126,7 +121,7 @@ __global__ __launch_bounds__(256) void init1_kernel(DopriState* st, const float*
   if (threadIdx.x == 0) {
     const float n = (float)st->n_elems;
     const float d0 = sqrtf(s0 / n), d1 = sqrtf(s1 / n);
-    st->h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+    st->h0 = dp5::initial_step_h0(d0, d1);
     st->ratio = d1;  // parked for init2
   }
 }
@@ -139,10 +134,7 @@ __global__ __launch_bounds__(256) void init2_kernel(DopriState* st, const float*
     const float n = (float)st->n_elems;
     const float h0 = st->h0, d1 = st->ratio;
     const float d2 = sqrtf(s2 / n) / h0;
-    float h1;
-    if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
-    else h1 = powf(0.01f / fmaxf(d1, d2), 1.0f / 5.0f);
-    const double dt = (double)fminf(100.0f * h0, h1);
+    const double dt = (double)dp5::initial_step_dt(h0, d1, d2);
     st->t0 = st->t1 = t_out[0];
     st->dt = dt;
     st->h = (float)dt;
@@ -201,15 +193,7 @@ __global__ __launch_bounds__(256) void controller_kernel(DopriState* st, const f
     st->n_reject += 1;
     st->j_lo = st->j_hi = st->j_next;
   }
-  // dt_next (float64, order 5, safety 0.9, ifactor 10, dfactor 0.2 -- 1 after an accepted step)
-  double dtn;
-  if (ratio == 0.0f) {
-    dtn = dt * 10.0;
-  } else {
-    const double dfactor = ratio < 1.0f ? 1.0 : 0.2;
-    const double fac = fmin(10.0, fmax(0.9 / pow((double)ratio, 0.2), dfactor));
-    dtn = dt * fac;
-  }
+  const double dtn = dp5::next_step_size(dt, ratio);
   st->dt = dtn;
   st->h = (float)dtn;
   const bool done = st->j_next >= st->n_times;
@@ -360,12 +344,6 @@ __global__ void init_state_kernel(DopriState* st, float rtol, float atol, int n_
 }
 
 
-// out[j] = fixed-order sum of partial array j (one workgroup)
-struct SumSet {
-  const float* p[4];
-  int n[4];
-  int count;
-};
 __global__ __launch_bounds__(256) void sum_partials_kernel(SumSet ss, float* __restrict__ out, const int* skip) {
   __shared__ float sh[256];
   if (skip && *skip) return;
@@ -374,12 +352,6 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(SumSet ss, float* __r
     if (threadIdx.x == 0) out[j] = s;
     __syncthreads();
   }
-}
-
-static double now_s() {
-  timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return ts.tv_sec + 1e-9 * ts.tv_nsec;
 }
 
 // ---- one dopri5 solve in flight.  The synchronous entry points build it on their stack and run it to completion; the asynchronous
@@ -402,8 +374,7 @@ struct D5Ctx {
   FinishArgs fa;
   long long n4 = 0;
   Mailbox* mb = nullptr;
-  int enq = 0, seen = 0;
-  double t_progress = 0;
+  int enq = 0;
 };
 constexpr int kD5Slots = 4;
 static D5Ctx g_d5[kD5Slots];
@@ -451,25 +422,11 @@ static int d5_attempt(D5Ctx& x) {
   PersistScope persist;
   if ((rc = persist.begin(f, nullptr, 6 * f->n_convs)) != ODEHIP_OK) return rc;
   CombineArgs c;
-  for (int s = 2; s <= 7; ++s) {  // k_s = f(x_s); fused: x_{s+1} = y + h*sum beta_{s+1,j} k_j   (s = 7: error norm)
-    memset(&c, 0, sizeof(c));
+  for (int s = 2; s <= 7; ++s) {  // k_s = f(x_s); fused: x_{s+1} = y + h*sum beta_{s+1,j} k_j   (s = 7: error norm against y1 = x7)
+    float* const out_next = x.saving ? s_xin(s < 7 ? s : 6) : (s < 6 ? x.xs : x.y1);
+    dopri5_stage_combine(c, s, x.y, &x.state->h, x.k, out_next, x.part0, x.rtol, x.atol);
     c.k_scale = x.ksc;
     c.order = all_64(f);   // 64-channel stacks: the adaptive walk (stage sums formed ahead of the matrix work), same bits per layer
-    c.y = x.y;
-    c.h_ptr = &x.state->h;
-    c.n_prev = s - 1;
-    for (int j = 0; j < s - 1; ++j) c.k_prev[j] = x.k[j];
-    c.k_out = x.k[s - 1];
-    if (s <= 6) {
-      for (int j = 0; j < s; ++j) c.c1[j] = (float)dp5::kBeta[s - 1][j];
-      c.out1 = x.saving ? s_xin(s) : (s < 6 ? x.xs : x.y1);  // x7 = y1 (c_sol equals the last beta row)
-    } else {
-      for (int j = 0; j < 7; ++j) c.ce[j] = (float)dp5::kCErr[j];
-      c.err_y1 = x.saving ? s_xin(6) : x.y1;
-      c.err_partials = x.part0;
-      c.rtol = x.rtol;
-      c.atol = x.atol;
-    }
     if (x.saving) {   // evaluation (slot, s - 1): input and hidden activations live in the slot the device picks
       ODEHIP_REQUIRE(persist.recording(), "odeint_dopri5: the persistent walk became unavailable during a saving forward");
       float* hid_s[ODEHIP_MAX_LAYERS];
@@ -508,17 +465,11 @@ static int d5_attempt(D5Ctx& x) {
 static int d5_run_to_done(D5Ctx& x) {
   const int RUN_AHEAD = x.global_norm ? 0 : 1;
   int rc;
-  x.t_progress = now_s();
+  MailboxWatch watch(&x.mb->steps_done);
   auto stalled = [&](const char* what) {
-    if (x.mb->steps_done != x.seen) {   // the limit is on time WITHOUT progress, not on the whole integration
-      x.seen = x.mb->steps_done;
-      x.t_progress = now_s();
-    }
-    if (now_s() - x.t_progress > 120.0) {
-      set_error("odeint_dopri5: %s (steps done %d of %d enqueued)", what, x.mb->steps_done, x.enq);
-      return true;
-    }
-    return false;
+    if (!watch.stalled()) return false;
+    set_error("odeint_dopri5: %s (steps done %d of %d enqueued)", what, x.mb->steps_done, x.enq);
+    return true;
   };
   for (;;) {
     while (!x.mb->done && x.mb->steps_done + RUN_AHEAD < x.enq)
@@ -541,12 +492,8 @@ static int d5_collect(D5Ctx& x, int* stats_host, double* accepted_host, int acce
   }
   Mailbox* mb = x.mb;
   if (saved_out) *saved_out = x.saving && mb->save_ok && mb->status == 0;
-  if (stats_host) {
-    stats_host[0] = mb->nfe;
-    stats_host[1] = mb->n_accept;
-    stats_host[2] = mb->n_reject;
-    stats_host[3] = x.enq;
-  }
+  write_stats(stats_host, mb->nfe, mb->n_accept, mb->n_reject);
+  if (stats_host) stats_host[3] = x.enq;
   if (accepted_host) {  // (t0, dt) pairs; the caller sees from stats_host[1] > accepted_cap that the log is incomplete
     int n = mb->n_accept < kLogCap ? mb->n_accept : kLogCap;
     if (n > accepted_cap) n = accepted_cap;
@@ -555,15 +502,7 @@ static int d5_collect(D5Ctx& x, int* stats_host, double* accepted_host, int acce
       accepted_host[2 * i + 1] = mb->log[i][1];
     }
   }
-  if (mb->status == ODEHIP_ENAN) {
-    set_error("odeint_dopri5: non-finite error ratio (non-finite values in state `y`)");
-    return ODEHIP_ENAN;
-  }
-  if (mb->status == ODEHIP_ENOTCONV) {
-    set_error("odeint_dopri5: underflow in dt or max_num_steps exceeded");
-    return ODEHIP_ENOTCONV;
-  }
-  return ODEHIP_OK;
+  return controller_error(false, mb->status);
 }
 
 
@@ -860,13 +799,9 @@ extern "C" int odehip_odeint_dopri5_collect(int token, int* stats_host, double* 
     return ODEHIP_OK;
   }
   // the attempts start() enqueued and the seal behind them are all this solve ever gets: wait for them, enqueue nothing
-  cx.t_progress = now_s();
+  MailboxWatch watch(&cx.mb->steps_done);
   while (cx.mb->steps_done < cx.enq) {
-    if (cx.mb->steps_done != cx.seen) {
-      cx.seen = cx.mb->steps_done;
-      cx.t_progress = now_s();
-    }
-    if (now_s() - cx.t_progress > 120.0) {
+    if (watch.stalled()) {
       set_error("odeint_dopri5_collect: no progress from the device for 120 s (steps done %d of %d enqueued)", cx.mb->steps_done, cx.enq);
       return ODEHIP_EHIP;
     }
@@ -874,12 +809,8 @@ extern "C" int odehip_odeint_dopri5_collect(int token, int* stats_host, double* 
   if (!cx.mb->done) {
     // the seal runs right behind the last controller: its verdict is at most a kernel away
     ODEHIP_CHECK_HIP(hipStreamSynchronize(cx.stream));
-    if (stats_host) {
-      stats_host[0] = cx.mb->nfe;
-      stats_host[1] = cx.mb->n_accept;
-      stats_host[2] = cx.mb->n_reject;
-      stats_host[3] = cx.enq;
-    }
+    write_stats(stats_host, cx.mb->nfe, cx.mb->n_accept, cx.mb->n_reject);
+    if (stats_host) stats_host[3] = cx.enq;
     set_error("odeint_dopri5_collect: the solve was not finished by the %d attempted steps start() enqueued (%d accepted, %d rejected "
               "so far); the frames it had not reached were NaN-filled, because the work enqueued behind start() has already consumed "
               "`out`.  Start again with more attempts, or use the synchronous call", cx.enq, cx.mb->n_accept, cx.mb->n_reject);

@@ -200,23 +200,20 @@ static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_
   for (int n = 0; n < N && !saved; ++n) {
     const float* y0 = n == 0 ? L.xin(ws, 0, 0) : L.xin(ws, n - 1, 6);
     for (int s = 2; s <= 7; ++s) {
-      memset(&c, 0, sizeof(c));
+      if (s <= 6) {
+        dopri5_stage_combine(c, s, y0, hdev + n, k, L.xin(ws, n, s), nullptr, 0.0f, 0.0f);  // Y_{s+1}; s = 6: y1
+      } else {   // no error norm here: k7 = k1 of the next step, and its Y_2 = y1 + h_{n+1}*beta21*k7 rides along
+        memset(&c, 0, sizeof(c));
+        c.k_out = k[6];
+        if (n + 1 < N) {
+          c.y = L.xin(ws, n, 6);
+          c.h_ptr = hdev + n + 1;
+          c.c1[0] = (float)dp5::kBeta[0][0];
+          c.out1 = L.xin(ws, n + 1, 1);
+        }
+      }
       c.k_scale = 1.0f;
       c.order = order1;
-      c.k_out = k[s - 1];
-      if (s <= 6) {
-        c.y = y0;
-        c.h_ptr = hdev + n;
-        c.n_prev = s - 1;
-        for (int j = 0; j < s - 1; ++j) c.k_prev[j] = k[j];
-        for (int j = 0; j < s; ++j) c.c1[j] = (float)dp5::kBeta[s - 1][j];
-        c.out1 = L.xin(ws, n, s);  // Y_{s+1}; s = 6: y1
-      } else if (n + 1 < N) {      // k7 = k1 of the next step: its Y_2 = y1 + h_{n+1}*beta21*k7
-        c.y = L.xin(ws, n, 6);
-        c.h_ptr = hdev + n + 1;
-        c.c1[0] = (float)dp5::kBeta[0][0];
-        c.out1 = L.xin(ws, n + 1, 1);
-      }
       if ((rc = run_f(n, s - 1, L.xin(ws, n, s - 1), c)) != ODEHIP_OK) return rc;
     }
     float* t = k[0]; k[0] = k[6]; k[6] = t;  // FSAL

@@ -3,8 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
+#include <time.h>
 
 #include "../../include/odecgru_hip.h"
+#include "dopri5_control.h"
 
 namespace odehip {
 
@@ -277,31 +280,72 @@ int launch_btraj_bf16_rk4(const odehip_convstack* f_dgrad, const float* grad_out
 // grad_b[l][ch] = sum over segments and samples of bias_part[seg][b][l][ch], in order
 int launch_bias_reduce(const float* bias_part, int n_parts, int n_layers, float* const* grad_b, hipStream_t stream);
 
-// Dormand-Prince 5(4) tableau as torchdiffeq 0.2.1 holds it (_impl/dopri5.py): beta rows, c_sol (= last beta row, padded),
-// c_error = c_sol - 4th-order weights, c_mid (dense-output midpoint weights)
-namespace dp5 {
-inline constexpr double kBeta[6][6] = {
-    {1.0 / 5, 0, 0, 0, 0, 0},
-    {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
-    {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
-    {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
-    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0},
-    {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84},
-};
-inline constexpr double kCSol[7] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0};
-inline constexpr double kCErr[7] = {35.0 / 384 - 1951.0 / 21600, 0, 500.0 / 1113 - 22642.0 / 50085, 125.0 / 192 - 451.0 / 720,
-                                    -2187.0 / 6784 + 12231.0 / 42400, 11.0 / 84 - 649.0 / 6300, -1.0 / 60};
-inline constexpr double kCMid[7] = {6025192743.0 / 30085553152.0 / 2, 0, 51252292925.0 / 65400821598.0 / 2,
-                                    -2691868925.0 / 45128329728.0 / 2, 187940372067.0 / 1594534317056.0 / 2,
-                                    -1776094331.0 / 19743644256.0 / 2, 11237099.0 / 235043384.0 / 2};
-// weight of stage s in the dense output at x: value(x) = y0 + h * sum_s dense_weight(s, x) * k_s   (the quartic of _interp_fit)
-inline double dense_weight(int s, double x) {
-  const double d1 = s == 0 ? 1.0 : 0.0, d7 = s == 6 ? 1.0 : 0.0, b = kCSol[s], m = kCMid[s];
-  const double A4 = 2.0 * (d7 - d1) - 8.0 * b + 16.0 * m;
-  const double B3 = 5.0 * d1 - 3.0 * d7 + 14.0 * b - 32.0 * m;
-  const double C2 = d7 - 4.0 * d1 - 5.0 * b + 16.0 * m;
-  return x * d1 + x * x * C2 + x * x * x * B3 + x * x * x * x * A4;
+// ---- the adaptive solver's drivers (dopri5.hip, dopri5_backward.hip, adjoint_dopri5.hip, adjoint_device.hip) ------------------
+// The stage combine behind k_s = f(x_s) of a Dormand-Prince attempt, s = 2 .. 7 (stage s lives at index s - 1 of k): stages 2 .. 6
+// form the next stage input x_{s+1} = y + h * sum beta_{s+1,j} k_j in out_next (s = 6: y1 -- c_sol equals the last beta row), stage 7
+// the error norm against out_next = y1.  The caller sets k_scale and order afterwards.
+inline void dopri5_stage_combine(CombineArgs& c, int s, const float* y, const float* h_ptr, float* const* k, float* out_next,
+                                 float* err_partials, float rtol, float atol) {
+  memset(&c, 0, sizeof(c));
+  c.y = y;
+  c.h_ptr = h_ptr;
+  c.n_prev = s - 1;
+  for (int j = 0; j < s - 1; ++j) c.k_prev[j] = k[j];
+  c.k_out = k[s - 1];
+  if (s <= 6) {
+    for (int j = 0; j < s; ++j) c.c1[j] = (float)dp5::kBeta[s - 1][j];
+    c.out1 = out_next;
+  } else {
+    for (int j = 0; j < 7; ++j) c.ce[j] = (float)dp5::kCErr[j];
+    c.err_y1 = out_next;
+    c.err_partials = err_partials;
+    c.rtol = rtol;
+    c.atol = atol;
+  }
 }
-}  // namespace dp5
+
+// The host's watch on the progress word of a pinned mailbox a device-side controller writes: the limit is on time WITHOUT
+// progress, not on the whole integration.
+struct MailboxWatch {
+  const volatile int* word;
+  int seen;
+  double t_progress;
+  explicit MailboxWatch(const volatile int* w) : word(w), seen(*w), t_progress(now_s()) {}
+  static double now_s() {
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec + 1e-9 * ts.tv_nsec;
+  }
+  bool stalled() {   // true once 120 s have passed without the word changing
+    if (*word != seen) {
+      seen = *word;
+      t_progress = now_s();
+    }
+    return now_s() - t_progress > 120.0;
+  }
+};
+
+inline void write_stats(int* stats_host, int nfe, int n_accept, int n_reject) {
+  if (!stats_host) return;
+  stats_host[0] = nfe;
+  stats_host[1] = n_accept;
+  stats_host[2] = n_reject;
+}
+
+// the status a device-side controller ended on as the error of its entry point (0: none); returns the status
+inline int controller_error(bool adjoint, int status, int max_accept = 0) {
+  if (!adjoint) {
+    if (status == ODEHIP_ENAN) set_error("odeint_dopri5: non-finite error ratio (non-finite values in state `y`)");
+    else if (status == ODEHIP_ENOTCONV) set_error("odeint_dopri5: underflow in dt or max_num_steps exceeded");
+    else return ODEHIP_OK;
+  } else if (status == ODEHIP_ENAN) {
+    set_error("odeint_adjoint_dopri5_backward: non-finite error ratio");
+  } else if (status == ODEHIP_ENOTCONV) {
+    set_error("odeint_adjoint_dopri5_backward: underflow in dt");
+  } else if (status != 0) {
+    set_error("odeint_adjoint_dopri5_backward: more than max_accept = %d accepted steps", max_accept);
+  }
+  return status;
+}
 
 }  // namespace odehip

@@ -1,0 +1,162 @@
+"""The adaptive step controller proves itself without a device.
+
+tests/dopri5_control_check.cpp includes ode-rl_amd/csrc/dopri5_control.h -- the one place the Dormand-Prince tableau, the scalar part
+of _select_initial_step, _optimal_step_size and the dense-output weights live; the forward solve's controller kernels, the host-driven
+adjoint and the device-controlled adjoint all call it -- and evaluates it under the host compiler.  The results are compared with
+oracle/torchdiffeq_ref.py:
+  next_step_size     against _optimal_step_size: exactly where no pow decides (ratio == 0, the clamps at 10, 1 and 0.2), else to 1e-15
+                     relative (a pow at <= 1 ulp on each side, a division and a product at 0.5 ulp each)
+  initial_step_*     against _select_initial_step on an 8-element fp32 state, every branch taken: 2 fp32 ulp (one powf on each side)
+  dense_weight       y0 + h sum_s W_s(x) k_s against _interp_evaluate(_interp_fit(...)) in float64: 1e-12 x the largest term (the
+                     quartic's coefficients reach 32: there is cancellation); W_s(1) = c_sol[s] to 1e-14"""
+import os
+import shutil
+import struct
+import subprocess
+
+import pytest
+import torch
+
+from oracle import torchdiffeq_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def check(tmp_path_factory):
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.fail("no host C++ compiler found")
+    exe = str(tmp_path_factory.mktemp("dopri5_control") / "dopri5_control_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", os.path.join(ROOT, "tests", "dopri5_control_check.cpp"), "-o", exe], check=True)
+
+    def run(cases):
+        """cases: (op, number, ...) tuples -> one float per case"""
+        text = "".join(op + " " + " ".join(float(v).hex() for v in args) + "\n" for op, *args in cases)
+        res = subprocess.run([exe], input=text, capture_output=True, text=True)
+        assert res.returncode == 0, res.stdout + res.stderr
+        out = [float.fromhex(x) for x in res.stdout.split()]
+        assert len(out) == len(cases), res.stdout
+        return out
+    return run
+
+
+def f32(x):
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+def f32_ulps(a, b):
+    ia, ib = (struct.unpack("i", struct.pack("f", v))[0] for v in (a, b))
+    return abs(ia - ib)
+
+
+# ratio -> the branch of _optimal_step_size that decides: "zero", a clamp (the factor it pins), or None (0.9 / ratio^0.2 itself)
+RATIOS = [(0.0, "zero"), (1e-12, 10.0), (0.3, None), (1.0 - 2.0 ** -24, 1.0), (1.0, None), (1.0 + 2.0 ** -23, None), (7.5, None),
+          (1e6, 0.2), (1e30, 0.2)]
+
+
+def test_next_step_size_is_optimal_step_size(check):
+    cases = [(dt, f32(r), which) for dt in (1e-6, 0.05, 3.0) for r, which in RATIOS]
+    got = check([("next", dt, r) for dt, r, _ in cases])
+    for (dt, r, which), g in zip(cases, got):
+        want = float(ref._optimal_step_size(torch.tensor(dt, dtype=torch.float64), torch.tensor(r, dtype=torch.float32)))
+        unclamped = 0.9 / float(torch.tensor(r, dtype=torch.float64) ** 0.2) if r > 0 else float("inf")
+        print(f"dt {dt!r} ratio {r!r}: got {g!r} want {want!r} decided by {which}")
+        if which == "zero":
+            assert r == 0.0 and g == want == dt * 10.0
+        elif which is not None:
+            # the oracle took this clamp, and not by a hair: one ulp of pow could not have changed the side
+            assert want == dt * which and (unclamped > 10.0 * (1 + 1e-12) if which == 10.0 else unclamped < which * (1 - 1e-12))
+            assert (r < 1.0) == (which != 0.2)   # dfactor is 1 after an accepted step, 0.2 after a rejected one
+            assert g == want
+        else:
+            assert 0.2 < unclamped < 10.0 and not (r < 1.0 and unclamped <= 1.0) and want == dt * unclamped
+            assert abs(g - want) <= 1e-15 * abs(want)
+
+
+def _linear(lam):
+    return lambda t, y: lam * y
+
+
+def _constant(c):
+    return lambda t, y: torch.full_like(y, c)
+
+
+Y0 = torch.tensor([0.7, -1.3, 0.02, 2.5, -0.4, 1.1, -0.9, 0.3], dtype=torch.float32)
+# (name, y0, f, the branch of the first half, the branch of the second half)
+INITIAL_STEP_CASES = [
+    ("y0 = 0", torch.zeros(8), _constant(0.5), "d0 tiny", "100 h0"),
+    ("tiny slope", Y0, _constant(1e-12), "d1 tiny", "100 h0"),
+    ("f = 0", Y0, _constant(0.0), "d1 tiny", "flat"),
+    ("stiff linear", Y0, _linear(-1000.0), "ratio", "100 h0"),
+    ("mild linear", Y0, _linear(-2.0), "ratio", "h1"),
+]
+
+
+def test_initial_step_is_select_initial_step(check):
+    rtol, atol = 1e-3, 1e-4
+    taken = set()
+    for name, y0, func, first, second in INITIAL_STEP_CASES:
+        t0 = torch.tensor(0.25, dtype=torch.float64)
+        f0 = func(t0, y0)
+        norms = []
+
+        def norm(x):
+            norms.append(ref.rms_norm(x))
+            return norms[-1]
+        want = ref._select_initial_step(func, t0, y0, 4, rtol, atol, f0, norm)
+        assert want.dtype == torch.float64 and len(norms) == 3
+        # the branches the ORACLE took, from the norms it formed
+        o_d0, o_d1 = float(norms[0]), float(norms[1])
+        o_first = "d0 tiny" if o_d0 < 1e-5 else "d1 tiny" if o_d1 < 1e-5 else "ratio"
+        # d0, d1, d2 in torch float32 exactly as the oracle forms them; the Euler point from the h0 the program returned
+        scale = atol + torch.abs(y0) * rtol
+        d0, d1 = ref.rms_norm(y0 / scale), ref.rms_norm(f0 / scale)
+        assert float(d0) == o_d0 and float(d1) == o_d1
+        h0 = check([("h0", float(d0), float(d1))])[0]
+        assert h0 == f32(h0)
+        h0_t = torch.tensor(h0, dtype=torch.float32)
+        f1 = func(t0.to(torch.float32) + h0_t, y0 + h0_t * f0)
+        d2 = ref.rms_norm((f1 - f0) / scale) / h0_t
+        assert float(norms[2]) == float(ref.rms_norm((f1 - f0) / scale)), "the program's h0 is not the oracle's"
+        o_d2 = float(d2)
+        flat = o_d1 <= 1e-15 and o_d2 <= 1e-15
+        h1 = torch.max(torch.tensor(1e-6, dtype=torch.float32), h0_t * 1e-3) if flat else (0.01 / max(d1, d2)) ** 0.2
+        assert h1.dtype == torch.float32 and float(100 * h0_t) != float(h1)
+        o_second = "flat" if flat else "100 h0" if float(100 * h0_t) < float(h1) else "h1"
+        taken.add("100 h0 < h1" if float(100 * h0_t) < float(h1) else "h1 < 100 h0")
+        assert float(want) == float(torch.min(100 * h0_t, h1))
+        dt = check([("dt", h0, float(d1), o_d2)])[0]
+        print(f"{name}: d0 {o_d0!r} d1 {o_d1!r} d2 {o_d2!r} h0 {h0!r} dt {dt!r} oracle {float(want)!r} ({o_first}; {o_second})")
+        assert o_first == first and o_second == second, (name, o_first, o_second)
+        taken.update({o_first, o_second})
+        assert dt == f32(dt) and f32_ulps(dt, float(want)) <= 2, (name, dt, float(want))
+    assert taken == {"d0 tiny", "d1 tiny", "ratio", "flat", "100 h0", "h1", "100 h0 < h1", "h1 < 100 h0"}, taken
+
+
+def test_dense_weights_are_the_quartic_of_interp_fit(check):
+    g = torch.Generator().manual_seed(5)
+    y0 = torch.randn(8, generator=g, dtype=torch.float64)
+    k = [torch.randn(8, generator=g, dtype=torch.float64) for _ in range(7)]
+    h = torch.tensor(0.37, dtype=torch.float64)
+    y1 = y0 + h * sum(c * ks for c, ks in zip(ref.DP_C_SOL, k))
+    y_mid = y0 + h * sum(c * ks for c, ks in zip(ref.DP_C_MID, k))
+    coeffs = ref._interp_fit(y0, y1, k, h)
+    # the largest term the two sides add up: the quartic's coefficients weigh y_mid with 32, y0 with 18
+    largest = max(float((32 * y_mid).abs().max()), float((18 * y0).abs().max()), float((14 * y1).abs().max()),
+                  max(float((5 * h * ks).abs().max()) for ks in k))
+    zero, one = torch.tensor(0.0, dtype=torch.float64), torch.tensor(1.0, dtype=torch.float64)
+    for x in (0.0, 0.25, 0.5, 1.0):
+        w = check([("dense", s, x) for s in range(7)])
+        w4 = check([("dense4", s, x, ref.DP_C_SOL[s], ref.DP_C_MID[s]) for s in range(7)])
+        assert w == w4   # the wrapper passes the tableau's own rows
+        got = y0 + h * sum(ws * ks for ws, ks in zip(w, k))
+        want = ref._interp_evaluate(coeffs, zero, one, torch.tensor(x, dtype=torch.float64))
+        err = float((got - want).abs().max())
+        print(f"x {x}: weights {w}, max |difference| {err:.3e}, bound {1e-12 * largest:.3e}")
+        assert err <= 1e-12 * largest
+    w1 = check([("dense", s, 1.0) for s in range(7)])
+    csol = check([("csol", s) for s in range(7)])
+    for s in range(7):
+        assert csol[s] == ref.DP_C_SOL[s]
+        assert abs(w1[s] - ref.DP_C_SOL[s]) <= 1e-14, (s, w1[s])

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Mutation check of the parity suite ("a deliberately wrong tableau coefficient turns the suite red").
 # Builds mutated copies of the library under gpurun_ab/mut/ (git-ignored scratch that travels to the GPU box) -- run with
-# `tools/mutation_check.sh build` HERE (hipcc cross-compiles), then `tools/mutation_check.sh run` on the GPU box: every mutant
+# `tools/mutation_check.sh build` HERE (hipcc cross-compiles; `patterns` only checks that every pattern still changes one file), then `tools/mutation_check.sh run` on the GPU box: every mutant
 # must FAIL the forward parity tests, the unmutated library must pass them.  Summary -> gpurun_out/mutation_check.txt.
 set -u
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -28,7 +28,7 @@ SED[wgrad_wino_at]='s/\*(f32x4\*)(wr + (4 \* i + 2) \* kW2Plane) = t\[i\]\[0\] -
 SED[adapt_combine_ccur]='s/      d_cA = m.c1\[np\];/      d_cA = m.c1[np] * 1.01f;/'                                  # adaptive walk: weight of the stage's own k in an order-1 combine
 SED[adapt_ew_coef]='s/    const float c1 = (m.c_dev ? ((ConstF\*)m.c_dev)\[j\] : m.c1\[j\]) \* hs;/    const float c1 = (m.c_dev ? ((ConstF*)m.c_dev)[j] : m.c1[j]) * hs * 1.01f;/'   # elementwise rows of the walk
 SED[walk16_ew_coef]='s/      s1 = fma4(kv, (m.c_dev ? ((ConstF\*)m.c_dev)\[j\] : m.c1\[j\]) \* hs, s1);/      s1 = fma4(kv, (m.c_dev ? ((ConstF*)m.c_dev)[j] : m.c1[j]) * hs * 1.01f, s1);/'   # ... and their sixteen-workgroup copy (ew_row16)
-SED[adjoint_dense_weight]='s/  const double C2 = d7 - 4.0 \* d1 - 5.0 \* b + 16.0 \* m;\n  return x \* d1/XX/;s/^__device__ double adj_dense_weight(const AdjCtl\* st, int s, double x) {  \/\/ dp5::dense_weight/__device__ double adj_dense_weight(const AdjCtl* st, int s, double x) { x *= 0.97;/'   # device controller: dense-output weights evaluated at the wrong point
+SED[dopri5_dense_weight]='s/^ODEHIP_HD inline double dense_weight(int s, double x, double b, double m) {$/ODEHIP_HD inline double dense_weight(int s, double x, double b, double m) { x *= 0.97;/'   # dopri5_control.h: dense-output weights evaluated at the wrong point (one function behind the device controller, the host-driven adjoint and the backward sweep)
 SED[walk16_out_transform]='s/      val = pk_sub(pk_sub(\*(const f32x4\*)(x + 1024) + bias4, \*(const f32x4\*)(x + 2048)), \*(const f32x4\*)(x + 3072));/      val = pk_sub(pk_sub(*(const f32x4*)(x + 1024) + bias4, *(const f32x4*)(x + 3072)), *(const f32x4*)(x + 2048)) * 1.001f;/'   # 16-workgroup walk: second half of the output transform
 SED[saving_slot_offset]='s/  fa.off_y1 = (long long)(6 \* BL.st);/  fa.off_y1 = (long long)(5 * BL.st);/'                # saving forward: y1 read from the wrong stage input of the slot
 SED[wgrad_wino5_bt]='s/  out\[0\] = w5_fma2(4.0f, in\[0\], w5_fma2(-5.0f, in\[2\], in\[4\]));/  out[0] = w5_fma2(4.0f, in[0], w5_fma2(-4.0f, in[2], in[4]));/'   # Winograd F(2x2,5x5) weight gradient: B^T row 0
@@ -43,7 +43,7 @@ SED[bn_bwd_mean_term]='s/  m2\[c\] = (float)(b \/ count);/  m2[c] = (float)(a \/
 SED[bn_running_var_biased]='s/    const double unbiased = count > 1.0 ? var \* count \/ (count - 1.0) : var;/    const double unbiased = var;/'   # running_var updated with the biased variance
 SED[relu_launders_nan]='s/__device__ __forceinline__ float relu_f(float v) { return v < 0.0f ? 0.0f : v; }/__device__ __forceinline__ float relu_f(float v) { return fmaxf(v, 0.0f); }/'   # the ReLU of every epilogue back to v_max_f32: NaN -> 0
 SED[evalwalk_no_nan_fill]='s/      nan_fill_row16(\*(const ConvArgs\*)((ConstArgs\*)table + l), b, cq, rq, pa.reloc, pa.out_nchw);/      (void)0;/'   # sixteen-workgroup walk: a launch whose wait gave up leaves its outputs as they are
-SED[dopri5_beta32]='s|{44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0}|{44.0 / 45, -56.0 / 15, 31.0 / 9, 0, 0, 0}|'
+SED[dopri5_beta32]='s|{44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0}|{44.0 / 45, -56.0 / 15, 31.0 / 9, 0, 0, 0}|'   # dopri5_control.h: one beta of the Dormand-Prince tableau
 # ---- NaN semantics: a failed asynchronous solve, the ReLU-backward masks
 SED[seal_skips_failed_solve]='s|  if (st->done \&\& st->status == 0) return;   // finished: every frame is written|  if (st->done) return;|'   # seal: a solve the controller failed keeps stale frames
 SED[act_bwd_launders_nan]='s/    g.x = y.x <= 0.0f ? 0.0f : g.x; g.y = y.y <= 0.0f ? 0.0f : g.y;/    g.x = y.x > 0.0f ? g.x : 0.0f; g.y = y.y > 0.0f ? g.y : 0.0f;/;s/    g.z = y.z <= 0.0f ? 0.0f : g.z; g.w = y.w <= 0.0f ? 0.0f : g.w;/    g.z = y.z > 0.0f ? g.z : 0.0f; g.w = y.w > 0.0f ? g.w : 0.0f;/'   # fp32 ReLU backward: NaN -> 0
@@ -86,22 +86,33 @@ PYSED[vidode_inter_detached]='ode-rl_amd/models/VidODE.py|s/self\.extra_info\["p
 PYSED[bn_conv_bias_eval_grad]='ode-rl_amd/autograd.py|s/else stats\[2\] \* gb$/else gb/'   # eval(): the folded convolution bias gets d beta instead of scale * d beta
 TESTS="tests/test_hip_grid_options.py::test_backward_matches_autograd_through_the_restated_loop tests/test_hip_bf16.py::test_whole_trajectory_training_matches_per_evaluation_launches tests/test_hip_tanh_dynamics.py::test_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_backward_random_dynamics tests/test_hip_frame_loss.py tests/test_hip_latent_sample.py tests/test_hip_convgru_sequence.py::test_rollout_forward_against_the_float64_restatement[False-True-10-4-64] tests/test_hip_convgru_sequence.py::test_bptt_against_float64_autograd[False-True-10-4] tests/test_hip_convgru_sequence.py::test_bptt_against_float64_autograd[True-False-10-4] tests/test_hip_convgru_sequence.py::test_a_zero_state_reads_nothing_of_the_state_buffers tests/test_hip_convgru_sequence.py::test_rollout_agrees_with_the_step_by_step_forward[False-True-10-4] tests/test_hip_backward.py::test_backward_strict_on_kink_free_dynamics tests/test_hip_frame_codec.py::test_encoder_matches_reference_fixture tests/test_hip_frame_codec.py::test_decoder_matches_reference_fixture tests/test_hip_conv.py::test_winograd5_conv_matches_torch tests/test_hip_full_size.py::test_cell_and_encoder_full_channels tests/test_hip_odeint.py::test_fixed_grid_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_dopri5_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_fixed_grid_matches_golden_and_oracle tests/test_hip_odeint.py::test_full_size_against_oracle tests/test_hip_backward.py::test_dopri5_backward_matches_autograd_through_oracle tests/test_hip_backward.py::test_dopri5_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_dopri5_saving_forward_equals_reintegration tests/test_hip_reference_configs.py::test_config0_as_stated_b4 tests/test_hip_encoder_backward.py::test_convgru_cell_backward_matches_autograd_through_oracle tests/test_hip_frame_codec.py::test_backward_matches_fp64_autograd tests/test_hip_vidode.py::test_upsample2x_matches_torch tests/test_hip_vidode.py::test_bn_relu_up_matches_torch tests/test_hip_backward.py::test_async_dopri5_forward_matches_the_synchronous_one tests/test_hip_errors.py::test_a_non_finite_state_is_not_laundered tests/test_hip_errors.py::test_a_lost_partner_in_a_single_evaluation_walk_is_loud tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[max_num_steps-no_grad] tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[overflow-saving] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[euler-3-per_layer] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[rk4-20-persistent] tests/test_hip_relu_nan_backward.py::test_bf16_backward_passes_the_gradient_of_a_nan_channel tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-True-True-x] tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-False-False-gamma] tests/test_hip_frame_metrics.py::test_matches_the_fp64_restatement[3-5-3] tests/test_hip_frame_metrics.py::test_matches_the_fp64_restatement[64-10-1] tests/test_hip_frame_metrics.py::test_evaluate_end_to_end tests/test_hip_conv_shapes.py tests/test_hip_vidode_grads.py"
 [ -n "${MUT_TESTS:-}" ] && TESTS=$MUT_TESTS   # a subset of the tests (a GPU lease is short): e.g. the files that cover the mutants of MUT_ONLY
+# a mutated copy of the sources under $MUT/<mutant>; names the file that differs from the tree's (diff -q) and fails unless exactly one does
+mutate() {
+  local m=$1 d=$MUT/$1 f changed=0
+  rm -rf "$d"; mkdir -p "$d/ode-rl_amd/csrc" "$d/include"
+  # sources AND the unmutated build's objects with their timestamps: make then recompiles only what the mutation touches
+  cp -p "$ROOT"/ode-rl_amd/csrc/*.hip "$ROOT"/ode-rl_amd/csrc/*.h "$ROOT"/ode-rl_amd/csrc/Makefile "$d/ode-rl_amd/csrc/"
+  cp -p "$ROOT"/include/*.h "$d/include/"
+  if [ -d "$ROOT/ode-rl_amd/csrc/build" ]; then mkdir -p "$d/ode-rl_amd/csrc/build"; cp -p "$ROOT"/ode-rl_amd/csrc/build/*.o "$d/ode-rl_amd/csrc/build/"; fi
+  sed -i "${SED[$m]}" "$d"/ode-rl_amd/csrc/*.hip "$d"/ode-rl_amd/csrc/*.h
+  for f in "$d"/ode-rl_amd/csrc/*.hip "$d"/ode-rl_amd/csrc/*.h; do
+    diff -q "$f" "$ROOT/ode-rl_amd/csrc/$(basename "$f")" >/dev/null || { echo "mutant $m: ode-rl_amd/csrc/$(basename "$f") differs from the tree's"; changed=$((changed + 1)); }
+  done
+  if [ $changed -ne 1 ]; then echo "mutant $m: the pattern changed $changed files (expected exactly 1)" >&2; return 1; fi
+}
 case "${1:-}" in
+patterns)   # every pattern still finds its line: the mutated sources only, nothing is built
+  bad=0
+  for m in "${!SED[@]}"; do
+    mutate "$m" || bad=1
+    rm -rf "$MUT/$m"
+  done
+  exit $bad ;;
 build)
   for m in "${!SED[@]}"; do
     if [ -n "${MUT_ONLY:-}" ] && [[ ! " $MUT_ONLY " =~ " $m " ]]; then continue; fi
     d=$MUT/$m
-    rm -rf "$d"; mkdir -p "$d/ode-rl_amd/csrc" "$d/include"
-    # sources AND the unmutated build's objects with their timestamps: make then recompiles only what the mutation touches
-    cp -p "$ROOT"/ode-rl_amd/csrc/*.hip "$ROOT"/ode-rl_amd/csrc/*.h "$ROOT"/ode-rl_amd/csrc/Makefile "$d/ode-rl_amd/csrc/"
-    cp -p "$ROOT"/include/*.h "$d/include/"
-    if [ -d "$ROOT/ode-rl_amd/csrc/build" ]; then mkdir -p "$d/ode-rl_amd/csrc/build"; cp -p "$ROOT"/ode-rl_amd/csrc/build/*.o "$d/ode-rl_amd/csrc/build/"; fi
-    sed -i "${SED[$m]}" "$d"/ode-rl_amd/csrc/*.hip "$d"/ode-rl_amd/csrc/*.h
-    changed=0
-    for f in "$d"/ode-rl_amd/csrc/*.hip "$d"/ode-rl_amd/csrc/*.h; do
-      diff -q "$f" "$ROOT/ode-rl_amd/csrc/$(basename "$f")" >/dev/null || changed=$((changed + 1))
-    done
-    if [ $changed -ne 1 ]; then echo "mutant $m: the pattern changed $changed files (expected exactly 1)" >&2; exit 1; fi
+    mutate "$m" || exit 1
     make -s -C "$d/ode-rl_amd/csrc" -j8 OUT_DIR="$d/lib" >/dev/null 2>&1 || { echo "mutant $m failed to build" >&2; exit 1; }
     rm -rf "$d/ode-rl_amd/csrc/build"
     echo "built $m"
@@ -149,5 +160,5 @@ baseline)   # the unmutated library alone (starts a fresh summary; the mutants t
   python -m pytest $TESTS -q > gpurun_out/mut_baseline.log 2>&1; rc=$?
   echo "unmutated library: pytest rc=$rc ($(tail -1 gpurun_out/mut_baseline.log))" | tee "$out"
   exit $rc ;;
-*) echo "usage: $0 build|baseline|run" >&2; exit 2 ;;
+*) echo "usage: $0 patterns|build|baseline|run" >&2; exit 2 ;;
 esac
