@@ -720,6 +720,46 @@ int odehip_loss_vidode_l1_backward(const float* grad_out, const float* pred, con
                                    const void* mask, int mask_is_byte, int batch, int n_frames, int n_sel, int frame_elems, float* grad_pred,
                                    float* grad_inter, void* stream);
 
+/* The adversarial step of Vid-ODE (instnorm_act.hip, gan.hip): what runs around the 4x4 convolutions of its two LSGAN discriminators
+ * (models/gan.py).  Enqueue-only on `stream`, caller-provided memory only, no atomics, arguments checked before any HIP call
+ * (ODEHIP_EINVAL).  Every sum has a fixed order: two calls are bitwise equal.  Pure additions: ODEHIP_ABI_VERSION stays.
+ *
+ * odehip_instnorm_lrelu_forward: InstanceNorm2d (no affine, biased variance) + LeakyReLU(slope) over contiguous planes x (planes, hw),
+ * hw >= 2 (a single element has no variance; torch refuses it too), eps >= 0; slope 0 is ReLU.  One launch.
+ *   mean[p] = fl32(sum_64 x / hw),  d = fl32(x - mean_64),  rstd[p] = fl32(1 / sqrt(sum_64 d^2 / hw + eps))       (_64: in float64)
+ *   y = xhat > 0 ? xhat : slope * xhat,  xhat = d * rstd           (a constant plane gives exactly 0; never E[x^2] - mean^2)
+ * A plane of hw <= 1024 is held in the registers of one wavefront (one read, one write); a larger one is walked three times by one
+ * workgroup.  Nothing crosses planes: a NaN or Inf stays in its plane.
+ * odehip_instnorm_lrelu_backward: from grad_y and the forward's x, mean, rstd, one launch:
+ *   xhat = (x - mean) * rstd,  g' = xhat > 0 ? grad_y : slope * grad_y,  grad_x = rstd * (g' - mean(g') - xhat * mean(g' * xhat))
+ * (the two plane means from float64 sums; the comparison is false for NaN, as torch's leaky_relu_backward has it). */
+int odehip_instnorm_lrelu_forward(const float* x, int planes, int hw, float eps, float slope, float* y, float* mean, float* rstd,
+                                  void* stream);
+int odehip_instnorm_lrelu_backward(const float* grad_y, const float* x, const float* mean, const float* rstd, int planes, int hw,
+                                   float slope, float* grad_x, void* stream);
+
+/* odehip_gan_seq_assemble: the sequences the sequence discriminator judges.  input_real (batch, t_in, P), frames (batch, t, P), P =
+ * frame_elems -> out (t * batch, L, P), all contiguous; row i * batch + n:
+ *   interp 0 (extrapolation)  L = max(t, t_in + 1):  [zeros x (L - l_i)] ++ input_real[n, i:] ++ frames[n, :i+1],  l_i = max(0, t_in - i) + i + 1
+ *   interp 1 (interpolation)  t_in == t, L = t:      input_real[n] with frame i replaced by frames[n, i]
+ * One launch, a gather over `out` (16-byte copies when P % 4 == 0 and the pointers are 16-byte aligned).
+ * odehip_gan_seq_assemble_backward: grad_out (t * batch, L, P) -> grad_frames (batch, t, P), one launch, a gather over grad_frames:
+ * grad_frames[n, j] = the sum of its copies in the rows i = j .. t-1, added in ascending i in fp32 (interpolation: row j alone).
+ * input_real is a constant. */
+int odehip_gan_seq_assemble(const float* input_real, const float* frames, int batch, int t_in, int t, long long frame_elems, int interp,
+                            float* out, void* stream);
+int odehip_gan_seq_assemble_backward(const float* grad_out, int batch, int t_in, int t, long long frame_elems, int interp, float* grad_frames,
+                                     void* stream);
+
+/* odehip_loss_lsgan: out[0] = fl32(sum_64 (pred[i] - target)^2 / n), n >= 1 floats, any alignment of 4 bytes.  Two launches
+ * (workgroup partials in float64 into `workspace`, odehip_loss_lsgan_workspace_bytes(n) bytes, 8-byte aligned; a one-workgroup
+ * final); the order of the sum is a function of n alone.
+ * odehip_loss_lsgan_backward: grad[i] = fl32(grad_out * 2 * (pred[i] - target) / n) in float64 until the one rounding; grad_out is
+ * one float ON THE DEVICE.  One launch. */
+size_t odehip_loss_lsgan_workspace_bytes(long long n);
+int odehip_loss_lsgan(const float* pred, long long n, float target, float* out, void* workspace, void* stream);
+int odehip_loss_lsgan_backward(const float* grad_out, const float* pred, long long n, float target, float* grad, void* stream);
+
 /* Fixed-grid solvers on an internal grid (grid_interp.hip): torchdiffeq 0.2.1's options={"grid_constructor": fn} / "step_size".  The
  * solver runs on a grid of n_grid points chosen by the caller (odehip_odeint_fixed with the grid as its time array) and the n_times
  * requested times are filled by linear interpolation, as FixedGridODESolver.integrate does:

@@ -5,6 +5,7 @@ Public surface = the reference's: `odeint`, `DiffEqSolver`, `ODEFunc`, `create_c
 from . import _lib  # noqa: F401
 from .odeint import odeint, last_stats, step_size_grid  # noqa: F401
 from .autograd import odeint_adjoint, last_adjoint_stats, sample_z0, last_z0_noise, mse_kl_loss, vidode_l1_loss  # noqa: F401
+from .autograd import instnorm_lrelu, gan_sequences, lsgan_loss  # noqa: F401
 from .hip_ops import set_compute_dtype, current_compute_dtype, set_async_dopri5, collect_pending_solves  # noqa: F401
 from .helpers.utils import create_convnet  # noqa: F401
 from .modules.DiffEqSolver import DiffEqSolver, ODEFunc  # noqa: F401
@@ -12,7 +13,10 @@ from .modules.ConvGRUCell import ConvGRUCell  # noqa: F401
 from .modules.ODEConvGRUCell import ODEConvGRUCell  # noqa: F401
 from .metrics import frame_metrics, FrameMetrics  # noqa: F401
 from .optim import FusedAdam, FusedAdamax, decay_learning_rate  # noqa: F401
+from .models.gan import ConvNormAct, Discriminator, create_netD  # noqa: F401
+from .train import train_batch_gan  # noqa: F401
 
 __all__ = ["odeint", "odeint_adjoint", "DiffEqSolver", "ODEFunc", "create_convnet", "ConvGRUCell", "ODEConvGRUCell", "frame_metrics",
            "FrameMetrics", "sample_z0", "last_z0_noise", "mse_kl_loss", "vidode_l1_loss", "step_size_grid", "FusedAdam", "FusedAdamax",
-           "decay_learning_rate"]
+           "decay_learning_rate", "instnorm_lrelu", "gan_sequences", "lsgan_loss", "ConvNormAct", "Discriminator", "create_netD",
+           "train_batch_gan"]

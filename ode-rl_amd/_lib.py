@@ -187,7 +187,16 @@ SIGNATURES = {
                                              ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [ctypes.c_size_t, ctypes.c_void_p]),
     "odehip_loss_vidode_l1_backward": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_longlong] * 2 + [ctypes.c_void_p] * 2 +
                                        [ctypes.c_longlong, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3),
-    "odehip_grid_table_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "odehip_instnorm_lrelu_forward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float] +
+                                      [ctypes.c_void_p] * 4),
+    "odehip_instnorm_lrelu_backward": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_float] + [ctypes.c_void_p] * 2),
+    "odehip_gan_seq_assemble": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_longlong, ctypes.c_int] + [ctypes.c_void_p] * 2),
+    "odehip_gan_seq_assemble_backward": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_longlong, ctypes.c_int] +
+                                         [ctypes.c_void_p] * 2),
+    "odehip_loss_lsgan_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "odehip_loss_lsgan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_float] + [ctypes.c_void_p] * 3),
+    "odehip_loss_lsgan_backward": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_longlong, ctypes.c_float] + [ctypes.c_void_p] * 2),
+    "odehip_grid_table_bytes":(ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "odehip_grid_emit_table": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
                                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]),
     "odehip_grid_emit": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float),

@@ -108,8 +108,11 @@ def host_times(t):
     hit = _t_cache.get(key)
     if hit is not None and hit[0]() is base:
         return hit[1]
-    if len(_t_cache) > 64:
-        _t_cache.clear()
+    if len(_t_cache) > 64:   # forget the tensors that are gone, then the oldest entries -- never the whole cache: clearing it between
+        for k in [k for k, v in _t_cache.items() if v[0]() is None]:   # the two time grids of one model call made every later call
+            del _t_cache[k]                                             # miss on the first of them
+        for k in list(_t_cache)[:max(len(_t_cache) - 32, 0)]:
+            del _t_cache[k]
     host = t.detach().to("cpu", torch.float64)
     _t_cache[key] = (weakref.ref(base), host)
     return host
@@ -1803,3 +1806,112 @@ def loss_vidode_l1_backward(grad_out, pred, inter, truth, init, mask):
     grad_pred, grad_inter = torch.empty_like(args[0]), torch.empty_like(args[0])
     _lib.check(_lib.load().odehip_loss_vidode_l1_backward(_ptr(grad_out), *_l1_call_args(*args), _ptr(grad_pred), _ptr(grad_inter), _stream()))
     return grad_pred, grad_inter
+
+
+def _check_planes(x, who):
+    """x (N, C, ...) float32 on the device -> (contiguous x, planes = N * C, hw = elements per plane)."""
+    require_device_tensor(x, "x")
+    if x.dim() < 3 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{who}: x must be (N, C, ...) with at least one spatial dimension, got {tuple(x.shape)}")
+    hw = x[0, 0].numel()
+    if hw < 2:
+        raise ValueError(f"{who}: expected more than 1 spatial element per plane, got input size {tuple(x.shape)}")
+    return x.detach().contiguous(), x.shape[0] * x.shape[1], hw
+
+
+def instnorm_lrelu(x, eps=1e-5, slope=0.2):
+    """(y, mean, rstd) of InstanceNorm (no affine, biased variance) + LeakyReLU(slope) over the planes of x (N, C, ...): ONE launch
+    (csrc/instnorm_act.hip).  mean, rstd (N * C,) are what instnorm_lrelu_backward needs besides x."""
+    x, planes, hw = _check_planes(x, "instnorm_lrelu")
+    y = torch.empty_like(x)
+    mean = torch.empty(planes, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    _lib.check(_lib.load().odehip_instnorm_lrelu_forward(_ptr(x), planes, hw, float(eps), float(slope), _ptr(y), _ptr(mean), _ptr(rstd), _stream()))
+    return y, mean, rstd
+
+
+def instnorm_lrelu_backward(grad_y, x, mean, rstd, slope=0.2):
+    """grad_x of instnorm_lrelu from grad_y and the forward's x, mean, rstd: ONE launch."""
+    x, planes, hw = _check_planes(x, "instnorm_lrelu_backward")
+    require_device_tensor(grad_y, "grad_y")
+    if grad_y.shape != x.shape or grad_y.device != x.device:
+        raise ValueError(f"instnorm_lrelu_backward: grad_y must be {tuple(x.shape)} on {x.device}, got {tuple(grad_y.shape)} on {grad_y.device}")
+    for name, s in (("mean", mean), ("rstd", rstd)):
+        require_device_tensor(s, name)
+        if tuple(s.shape) != (planes,) or s.device != x.device or not s.is_contiguous():
+            raise ValueError(f"instnorm_lrelu_backward: {name} must be a contiguous ({planes},) on {x.device}, got {tuple(s.shape)} on {s.device}")
+    grad_y = grad_y.detach().contiguous()
+    grad_x = torch.empty_like(x)
+    _lib.check(_lib.load().odehip_instnorm_lrelu_backward(_ptr(grad_y), _ptr(x), _ptr(mean), _ptr(rstd), planes, hw, float(slope), _ptr(grad_x),
+                                                          _stream()))
+    return grad_x
+
+
+def gan_seq_len(t_in, t, interp=False):
+    """L, the frames per row of gan_seq_assemble: t for the interpolation form (which needs t_in == t), else max(t, t_in + 1)."""
+    if interp:
+        if t_in != t:
+            raise ValueError(f"gan_seq_assemble: the interpolation form needs as many observed frames as predictions, got {t_in} and {t}")
+        return t
+    return max(t, t_in + 1)
+
+
+def _check_seq_pair(input_real, frames, who):
+    require_device_tensor(input_real, "input_real")
+    require_device_tensor(frames, "frames")
+    if frames.dim() != 5 or input_real.dim() != 5 or input_real.shape[0] != frames.shape[0] or input_real.shape[2:] != frames.shape[2:] or \
+            min(frames.shape) < 1 or input_real.shape[1] < 1 or input_real.device != frames.device:
+        raise ValueError(f"{who}: input_real must be (b, t_in, c, h, w) and frames (b, t, c, h, w) on one device, got {tuple(input_real.shape)} on "
+                         f"{input_real.device} and {tuple(frames.shape)} on {frames.device}")
+
+
+def gan_seq_assemble(input_real, frames, interp=False):
+    """The rows the sequence discriminator judges, (t * b, L * c, h, w), from input_real (b, t_in, c, h, w) and frames (b, t, c, h, w) in ONE
+    launch (csrc/gan.hip).  Row i * b + n: [zeros] ++ input_real[n, i:] ++ frames[n, :i+1] right-aligned in L = max(t, t_in + 1) frames, or
+    with interp=True input_real[n] with frame i replaced by frames[n, i]."""
+    _check_seq_pair(input_real, frames, "gan_seq_assemble")
+    b, t, c, h, w = frames.shape
+    t_in = input_real.shape[1]
+    seq = gan_seq_len(t_in, t, interp)
+    input_real, frames = input_real.detach().contiguous(), frames.detach().contiguous()
+    out = torch.empty((t * b, seq * c, h, w), dtype=torch.float32, device=frames.device)
+    _lib.check(_lib.load().odehip_gan_seq_assemble(_ptr(input_real), _ptr(frames), b, t_in, t, c * h * w, int(bool(interp)), _ptr(out), _stream()))
+    return out
+
+
+def gan_seq_assemble_backward(grad_out, shape, t_in, interp=False):
+    """grad_frames (b, t, c, h, w) = `shape` of gan_seq_assemble from grad_out (t * b, L * c, h, w): ONE launch, a gather."""
+    b, t, c, h, w = shape
+    seq = gan_seq_len(t_in, t, interp)
+    require_device_tensor(grad_out, "grad_out")
+    if tuple(grad_out.shape) != (t * b, seq * c, h, w):
+        raise ValueError(f"gan_seq_assemble_backward: grad_out must be {(t * b, seq * c, h, w)}, got {tuple(grad_out.shape)}")
+    grad_out = grad_out.detach().contiguous()
+    grad_frames = torch.empty(tuple(shape), dtype=torch.float32, device=grad_out.device)
+    _lib.check(_lib.load().odehip_gan_seq_assemble_backward(_ptr(grad_out), b, t_in, t, c * h * w, int(bool(interp)), _ptr(grad_frames), _stream()))
+    return grad_frames
+
+
+def loss_lsgan(pred, target):
+    """mean (pred - target)^2 as a () device tensor, two launches, float64 sums in a fixed order (csrc/gan.hip)."""
+    require_device_tensor(pred, "pred")
+    if pred.numel() < 1:
+        raise ValueError("loss_lsgan: pred is empty")
+    pred = pred.detach().contiguous()
+    lib = _lib.load()
+    ws = workspace("loss_lsgan", lib.odehip_loss_lsgan_workspace_bytes(pred.numel()), pred.device)
+    out = torch.empty((), dtype=torch.float32, device=pred.device)
+    _lib.check(lib.odehip_loss_lsgan(_ptr(pred), pred.numel(), float(target), _ptr(out), _ptr(ws), _stream()))
+    return out
+
+
+def loss_lsgan_backward(grad_out, pred, target):
+    """grad_pred = grad_out * 2 (pred - target) / n from grad_out, one float on the device, in ONE launch."""
+    require_device_tensor(pred, "pred")
+    if pred.numel() < 1:
+        raise ValueError("loss_lsgan_backward: pred is empty")
+    pred = pred.detach().contiguous()
+    grad_out = _check_device_scalar(grad_out, "grad_out", pred, "loss_lsgan_backward")
+    grad = torch.empty_like(pred)
+    _lib.check(_lib.load().odehip_loss_lsgan_backward(_ptr(grad_out), _ptr(pred), pred.numel(), float(target), _ptr(grad), _stream()))
+    return grad

@@ -83,6 +83,71 @@ def train_batch(model, batch_dict, optimizer, async_solver=False, clip=None):
     return pred.detach() * 255.0, out * 255.0, loss.detach(), loss_dict
 
 
+def train_batch_gan(model, netD_img, netD_seq, batch_dict, optimizer_netG, optimizer_netD, lamb_adv=0.003, clip=None):
+    """One adversarial step in Vid-ODE's order (Vid-ODE/main.py:221-254) around the `get_prediction` / `get_loss` pair of `train_batch`,
+    with the frames in the [0, 1] space `train_batch` works in:
+      1. reconstruction loss of the generator `model`;
+      2. loss_D = lamb_adv * (netD_seq.netD_adv_loss + netD_img.netD_adv_loss) on the detached prediction;
+      3. optimizer_netD.zero_grad(); loss_D.backward(); optimizer_netD.step();
+      4. adv = lamb_adv * (netD_seq.netG_adv_loss + netD_img.netG_adv_loss) against the UPDATED discriminators;
+      5. optimizer_netG.zero_grad(); (loss + adv).backward(); optimizer_netG.step(), `clip` as in `train_batch`.
+    During 4 and 5 the discriminators' parameters have requires_grad switched off (restored afterwards, also when the pass raises): the
+    reference computes those gradients and throws them away at its next zero_grad, here their `.grad` stays as step 3 left it.
+
+    Returns (pred * 255, truth * 255, loss, loss_dict); loss is the reconstruction loss, loss_dict carries 'Per Step Loss (netD)' =
+    loss_D, 'Per Step Loss (netG)' = adv and 'Per Step Loss' = their sum, as the reference logs them (main.py:265-267) -- device scalars,
+    no .item() -- plus 'Gradient Norm' with a clip.
+
+    An irregular batch ('observed_mask' and 'mask_predicted_data' present and not None) gets the reference's frame selection
+    (main.py:230-237) by torch indexing before the discriminators see the frames; `int(observed_mask[0].sum())` is one host read, as
+    there.  The asynchronous dopri5 option of `train_batch` is not available here."""
+    dev = next(model.parameters()).device
+    inp = batch_dict["observed_data"].to(dev) + 0.5
+    out = batch_dict["data_to_predict"].to(dev) + 0.5
+    fake = model.get_prediction(inp, batch_dict=batch_dict)
+    loss = model.get_loss(fake, out)
+    real, input_real = out, inp
+    observed_mask, mask_predicted = batch_dict.get("observed_mask"), batch_dict.get("mask_predicted_data")
+    if observed_mask is not None and mask_predicted is not None:
+        b, _, c, h, w = real.size()
+        n_sel = int(observed_mask[0].sum())
+        input_real = input_real[observed_mask.to(dev).squeeze(-1).bool(), ...].view(b, n_sel, c, h, w)
+        real = real[mask_predicted.to(dev).squeeze(-1).bool(), ...].view(b, n_sel, c, h, w)
+
+    loss_netD = lamb_adv * netD_seq.netD_adv_loss(real, fake, input_real)
+    loss_netD = loss_netD + lamb_adv * netD_img.netD_adv_loss(real, fake, None)
+    optimizer_netD.zero_grad()
+    loss_netD.backward()
+    optimizer_netD.step()
+
+    d_params = [p for net in (netD_img, netD_seq) for p in net.parameters()]
+    flags = [p.requires_grad for p in d_params]
+    try:
+        for p in d_params:
+            p.requires_grad_(False)
+        loss_adv = lamb_adv * netD_seq.netG_adv_loss(real, fake, input_real)
+        loss_adv = loss_adv + lamb_adv * netD_img.netG_adv_loss(None, fake, None)
+        optimizer_netG.zero_grad()
+        (loss + loss_adv).backward()
+    finally:
+        for p, flag in zip(d_params, flags):
+            p.requires_grad_(flag)
+    loss_netD, loss_adv = loss_netD.detach(), loss_adv.detach()
+    loss_dict = {"Per Step Loss (netD)": loss_netD, "Per Step Loss (netG)": loss_adv, "Per Step Loss": loss_netD + loss_adv}
+    if clip is None or clip == -1:
+        optimizer_netG.step()
+    else:
+        from .optim import _FusedOptimizer
+        if isinstance(optimizer_netG, _FusedOptimizer):
+            optimizer_netG.step(max_grad_norm=float(clip))
+            loss_dict["Gradient Norm"] = optimizer_netG.last_clipped_norm
+        else:
+            total = torch.nn.utils.clip_grad_norm_(model.parameters(), float(clip))
+            optimizer_netG.step()
+            loss_dict["Gradient Norm"] = total * torch.clamp(float(clip) / (total + 1e-6), max=1.0)
+    return fake.detach() * 255.0, out * 255.0, loss.detach(), loss_dict
+
+
 def _set_async_quietly(hip_ops, on):
     """set_async_dopri5(on) while another exception is in flight: switching off collects the pending solves, and an error of theirs
     is dropped so that it cannot replace the one being raised (the switch is set before the collection, so it holds either way)."""
