@@ -227,6 +227,17 @@ typedef struct odehip_convgru_cell {
   const float* w_gates_wino;   /* optional: odehip_pack_conv_weight_winograd5 forms of the two 5x5 weights; non-NULL = Winograd       */
   const float* w_can_wino;     /*           F(2x2,5x5) in fp32 (36 instead of 100 multiplies per 2x2 outputs; ignored in bf16 mode)  */
 } odehip_convgru_cell;
+/* The plain cell.  A descriptor whose four gn_* pointers are ALL NULL is the norm-free cell of upstream Vid-ODE
+ * (models/base_conv_gru.py:47-72), with upstream's gate order -- the first `hidden` channels of conv_gates are the RESET gate, the
+ * second the UPDATE gate (the GroupNorm cell above has the update gate first):
+ *   (r, u) = sigmoid(conv_gates(cat(x, h)));  c = tanh(conv_can(cat(x, r h)));  h' = (1 - u) h + u c.
+ * Some but not all of the four NULL stays ODEHIP_EINVAL.  Plain cells are taken by odehip_convgru_cell_forward / _backward and their
+ * workspace queries, by odehip_odeconvgru_encode, _encode_train, _encode_backward, their _masked forms (same three guarantees for
+ * m == 1, m == 0 and fractional m, same exact zeros for an unobserved (frame, sample) in the backward) and the encoder workspace
+ * queries.  The gn_* members of odehip_convgru_cell_grads / odehip_encoder_grads are then not written and may be NULL.  Size limits
+ * are unchanged (hidden % 32 == 0; multiples of 64 on the training path).  Any ks the convolutions take (upstream: 3).  In bf16
+ * compute mode a 3x3 cell runs fp32 in both directions: the bf16 cell kernels are 5x5 only (w_gates_bf16 / w_can_bf16 are ignored
+ * for ks != 5).  odehip_convgru_sequence_* refuses plain cells (ODEHIP_EINVAL).  Pure additions: ODEHIP_ABI_VERSION stays. */
 
 size_t odehip_convgru_cell_workspace_bytes(const odehip_convgru_cell* c, int batch);
 /* one step: x (B,input,16,16), h (B,hidden,16,16) -> h_next, all NCHW          (ConvGRUCell.forward, seq_len = 1) */

@@ -18,6 +18,8 @@
 // per workgroup.  The convolutions above run for every sample either way; without a mask the launches are gn_update_kernel<false>.
 // In the Q4 layout a 32-channel group of one sample is 32 KiB contiguous, so a workgroup holds its whole group in
 // registers (32 floats per thread): statistics are exact two-pass fp32, one HBM read, one write.
+// A cell without GroupNorm (all four gn_* pointers NULL: upstream Vid-ODE's cell, reset gate first) runs the same convolutions with
+// the pointwise kernels of convgru_plain.hip in place of gn_gates_kernel / gn_update_kernel.
 #include <string.h>
 
 #include "convgru_gn.h"
@@ -149,7 +151,9 @@ static int check_cell(const odehip_convgru_cell* c) {
   ODEHIP_REQUIRE(c->hidden > 0 && c->hidden % 32 == 0, "convgru: hidden_dim must be a multiple of 32 (GroupNorm groups of 32; got %d)", c->hidden);
   ODEHIP_REQUIRE(c->input > 0 && c->input % 8 == 0, "convgru: input_dim must be a multiple of 8 (got %d)", c->input);
   ODEHIP_REQUIRE(c->ks == 5 || c->ks == 3 || c->ks == 1, "convgru: kernel size %d unsupported", c->ks);
-  ODEHIP_REQUIRE(c->w_gates && c->b_gates && c->gn_gates_w && c->gn_gates_b && c->w_can && c->b_can && c->gn_can_w && c->gn_can_b,
+  // the four GroupNorm pointers: all given (the reference's cell) or all NULL (upstream Vid-ODE's norm-free cell, convgru_plain.hip)
+  ODEHIP_REQUIRE(c->w_gates && c->b_gates && c->w_can && c->b_can &&
+                     (cell_is_plain(c) || (c->gn_gates_w && c->gn_gates_b && c->gn_can_w && c->gn_can_b)),
                  "convgru: null parameter pointer");
   return ODEHIP_OK;
 }
@@ -162,11 +166,16 @@ static int cell_step(const odehip_convgru_cell* c, const float* x, const float* 
   const int H = c->hidden, I = c->input;
   int rc = conv_layer(x, h, I, I + H, 2 * H, c->ks, c->w_gates, c->b_gates, gates_raw, 0, batch, stream, c->w_gates_bf16, c->w_gates_wino);
   if (rc != ODEHIP_OK) return rc;
-  hipLaunchKernelGGL(gn_gates_kernel, dim3(2 * H / 32, batch), dim3(256), 0, stream, gates_raw, c->gn_gates_w, c->gn_gates_b, h, z,
-                     rh, H / 32);
+  const bool plain = cell_is_plain(c);  // z then holds the update gate u
+  if (plain) launch_plain_gates(gates_raw, h, z, rh, H, batch, stream);
+  else
+    hipLaunchKernelGGL(gn_gates_kernel, dim3(2 * H / 32, batch), dim3(256), 0, stream, gates_raw, c->gn_gates_w, c->gn_gates_b, h, z,
+                       rh, H / 32);
   rc = conv_layer(x, rh, I, I + H, H, c->ks, c->w_can, c->b_can, cand_raw, 0, batch, stream, c->w_can_bf16, c->w_can_wino);
   if (rc != ODEHIP_OK) return rc;
-  if (mask_b)
+  if (plain)
+    launch_plain_update(cand_raw, h, z, h_out, h_out_nchw, nchw_batch_stride, H, batch, mask_b, stream);
+  else if (mask_b)
     hipLaunchKernelGGL(gn_update_kernel<true>, dim3(H / 32, batch), dim3(256), 0, stream, cand_raw, c->gn_can_w, c->gn_can_b, h, z, h_out,
                        h_out_nchw, nchw_batch_stride, H / 32, mask_b);
   else

@@ -20,6 +20,9 @@
 // kernel stores exact zeros, so every later product of an unobserved (frame, sample) is 0 * (what the forward kept): exactly zero
 // for finite frames.  Containment of a NON-FINITE unobserved frame is promised for the forward only -- here the input-gradient and
 // weight-gradient products would multiply it by those zeros.
+// The norm-free cell (all four gn_* pointers NULL; upstream Vid-ODE's, reset gate first): forward and sweep are the same launches with
+// plain_update_bwd_kernel / plain_gates_bwd_kernel (convgru_plain.hip) in place of the two GroupNorm kernels; no affine partials are
+// written or reduced and the gn_* members of the gradient structs are not touched.
 #include <string.h>
 
 #include <vector>
@@ -495,6 +498,9 @@ extern "C" int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e,
   void* ws = workspace;
   const int C = L.C, NH = L.NH, NL = e->f_enc.n_convs, T = n_frames, HH = e->head_hidden, OUT2 = 2 * e->out_ch, ks = e->cell.ks;
   const int HG = C / 32;
+  const bool plain = cell_is_plain(&e->cell);  // no GroupNorm: the pointwise kernels of convgru_plain.hip, no affine gradients
+  ODEHIP_REQUIRE(plain || (gr->gn_gates_w && gr->gn_gates_b && gr->gn_can_w && gr->gn_can_b),
+                 "odeconvgru_encode_backward: null GroupNorm gradient output");
   float* dts = L.p(ws, L.off_dts);
   float* gh = L.p(ws, L.off_gh);
   float* gh_next = L.p(ws, L.off_gh + L.hs);
@@ -547,7 +553,11 @@ extern "C" int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e,
     float* g_cand = L.per(ws, L.off_gcand, idx, L.hs);
     float* g_gates = L.per(ws, L.off_ggates, idx, 2 * L.hs);
     const float* h_ode = L.per(ws, L.off_hode, idx, L.hs);
-    if (mask_tb)
+    const float* mask_b = mask_tb ? mask_tb + (size_t)i * batch : nullptr;
+    if (plain)  // writes the update half of g_gates as well: gz_pre stays unused
+      launch_plain_update_bwd(L.per(ws, L.off_cand, idx, L.hs), gh, L.per(ws, L.off_z, idx, L.hs), h_ode, g_cand, g_gates, gh_ode, C, batch,
+                              mask_b, stream);
+    else if (mask_tb)
       hipLaunchKernelGGL(gn_update_bwd_kernel<true>, dim3(HG, batch), dim3(256), 0, stream, L.per(ws, L.off_cand, idx, L.hs), e->cell.gn_can_w,
                          e->cell.gn_can_b, gh, L.per(ws, L.off_z, idx, L.hs), h_ode, g_cand, gz_pre, gh_ode,
                          pgc + (size_t)idx * batch * C, pgc + pgc_half + (size_t)idx * batch * C, HG, mask_tb + (size_t)i * batch);
@@ -557,9 +567,12 @@ extern "C" int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e,
                          pgc + (size_t)idx * batch * C, pgc + pgc_half + (size_t)idx * batch * C, HG, nullptr);
     if ((rc = conv_bwd(g_cand, C, C, ks, eb->w_can_dx, 0, nullptr, gx_c, eb->bf16[2], eb->wino[2])) != ODEHIP_OK) return rc;
     if ((rc = conv_bwd(g_cand, C, C, ks, eb->w_can_dh, 0, nullptr, g_rh, eb->bf16[3], eb->wino[3])) != ODEHIP_OK) return rc;
-    hipLaunchKernelGGL(gn_gates_bwd_kernel, dim3(2 * HG, batch), dim3(256), 0, stream, L.per(ws, L.off_gates, idx, 2 * L.hs),
-                       e->cell.gn_gates_w, e->cell.gn_gates_b, gz_pre, g_rh, h_ode, gh_ode, g_gates,
-                       pgg + (size_t)idx * batch * 2 * C, pgg + pgg_half + (size_t)idx * batch * 2 * C, HG);
+    if (plain)
+      launch_plain_gates_bwd(L.per(ws, L.off_gates, idx, 2 * L.hs), g_rh, h_ode, gh_ode, g_gates, C, batch, mask_b, stream);
+    else
+      hipLaunchKernelGGL(gn_gates_bwd_kernel, dim3(2 * HG, batch), dim3(256), 0, stream, L.per(ws, L.off_gates, idx, 2 * L.hs),
+                         e->cell.gn_gates_w, e->cell.gn_gates_b, gz_pre, g_rh, h_ode, gh_ode, g_gates,
+                         pgg + (size_t)idx * batch * 2 * C, pgg + pgg_half + (size_t)idx * batch * 2 * C, HG);
     BwdArgs w;
     memset(&w, 0, sizeof(w));
     w.n_targets = 1;
@@ -653,10 +666,12 @@ extern "C" int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e,
   rc = launch_wgrad_layer(table0 + (size_t)(NL + 5) * T, 1, batch, 4, slabs, gr->w_head0, gr->b_head0, 1, HH, C, C, 0, false, true, stream);
   if (rc != ODEHIP_OK) return rc;
   // GroupNorm affine parameters
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(2 * C), dim3(256), 0, stream, pgg, T * batch, 2 * C, gr->gn_gates_w);
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(2 * C), dim3(256), 0, stream, pgg + pgg_half, T * batch, 2 * C, gr->gn_gates_b);
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(C), dim3(256), 0, stream, pgc, T * batch, C, gr->gn_can_w);
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(C), dim3(256), 0, stream, pgc + pgc_half, T * batch, C, gr->gn_can_b);
+  if (!plain) {
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(2 * C), dim3(256), 0, stream, pgg, T * batch, 2 * C, gr->gn_gates_w);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(2 * C), dim3(256), 0, stream, pgg + pgg_half, T * batch, 2 * C, gr->gn_gates_b);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(C), dim3(256), 0, stream, pgc, T * batch, C, gr->gn_can_w);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(C), dim3(256), 0, stream, pgc + pgc_half, T * batch, C, gr->gn_can_b);
+  }
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
 }
@@ -700,6 +715,9 @@ extern "C" int odehip_convgru_cell_backward(const odehip_convgru_cell* c, const 
   ODEHIP_REQUIRE(workspace_bytes >= odehip_convgru_cell_backward_workspace_bytes(c, batch), "convgru_cell_backward: workspace too small");
   hipStream_t stream = (hipStream_t)stream_;
   const int H = c->hidden, I = c->input, ks = c->ks, HG = H / 32;
+  const bool plain = cell_is_plain(c);
+  ODEHIP_REQUIRE(plain || (gr->gn_gates_w && gr->gn_gates_b && gr->gn_can_w && gr->gn_can_b),
+                 "convgru_cell_backward: null GroupNorm gradient output");
   const CellBwdLayout L(c, batch);
   auto at = [&](size_t off) { return (float*)((char*)workspace + off); };
   float *x = at(L.x), *gx_c = at(L.gx_c), *gx_out = at(L.gx_out), *h = at(L.h), *gates = at(L.gates), *z = at(L.z), *rh = at(L.rh),
@@ -730,12 +748,18 @@ extern "C" int odehip_convgru_cell_backward(const odehip_convgru_cell* c, const 
     a.dst = dst;
     return launch_conv(a, ks, stream);
   };
-  hipLaunchKernelGGL(gn_update_bwd_kernel<false>, dim3(HG, batch), dim3(256), 0, stream, cand, c->gn_can_w, c->gn_can_b, ghn, z, h, g_cand,
-                     gz_pre, gh_ode, pgc, pgc + (size_t)batch * H, HG, nullptr);
+  if (plain)
+    launch_plain_update_bwd(cand, ghn, z, h, g_cand, g_gates, gh_ode, H, batch, nullptr, stream);
+  else
+    hipLaunchKernelGGL(gn_update_bwd_kernel<false>, dim3(HG, batch), dim3(256), 0, stream, cand, c->gn_can_w, c->gn_can_b, ghn, z, h, g_cand,
+                       gz_pre, gh_ode, pgc, pgc + (size_t)batch * H, HG, nullptr);
   if ((rc = conv_bwd(g_cand, H, I, cb->w_can_dx, nullptr, gx_c, cb->bf16[2], cb->wino[2])) != ODEHIP_OK) return rc;
   if ((rc = conv_bwd(g_cand, H, H, cb->w_can_dh, nullptr, g_rh, cb->bf16[3], cb->wino[3])) != ODEHIP_OK) return rc;
-  hipLaunchKernelGGL(gn_gates_bwd_kernel, dim3(2 * HG, batch), dim3(256), 0, stream, gates, c->gn_gates_w, c->gn_gates_b, gz_pre, g_rh, h,
-                     gh_ode, g_gates, pgg, pgg + (size_t)batch * 2 * H, HG);
+  if (plain)
+    launch_plain_gates_bwd(gates, g_rh, h, gh_ode, g_gates, H, batch, nullptr, stream);
+  else
+    hipLaunchKernelGGL(gn_gates_bwd_kernel, dim3(2 * HG, batch), dim3(256), 0, stream, gates, c->gn_gates_w, c->gn_gates_b, gz_pre, g_rh, h,
+                       gh_ode, g_gates, pgg, pgg + (size_t)batch * 2 * H, HG);
   BwdArgs w;
   memset(&w, 0, sizeof(w));
   w.n_targets = 1;
@@ -765,11 +789,13 @@ extern "C" int odehip_convgru_cell_backward(const odehip_convgru_cell* c, const 
                               ks == 5 && c->w_gates_bf16, half == 0, stream);
       if (rc != ODEHIP_OK) return rc;
     }
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(2 * H), dim3(256), 0, stream, pgg, batch, 2 * H, gr->gn_gates_w);
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(2 * H), dim3(256), 0, stream, pgg + (size_t)batch * 2 * H, batch, 2 * H,
-                     gr->gn_gates_b);
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(H), dim3(256), 0, stream, pgc, batch, H, gr->gn_can_w);
-  hipLaunchKernelGGL(reduce_rows_kernel, dim3(H), dim3(256), 0, stream, pgc + (size_t)batch * H, batch, H, gr->gn_can_b);
+  if (!plain) {
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(2 * H), dim3(256), 0, stream, pgg, batch, 2 * H, gr->gn_gates_w);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(2 * H), dim3(256), 0, stream, pgg + (size_t)batch * 2 * H, batch, 2 * H,
+                       gr->gn_gates_b);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(H), dim3(256), 0, stream, pgc, batch, H, gr->gn_can_w);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(H), dim3(256), 0, stream, pgc + (size_t)batch * H, batch, H, gr->gn_can_b);
+  }
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
 }

@@ -193,6 +193,15 @@ inline bool all_64(const odehip_convstack* f) {
 int traj_prologue(const float* src, float* dst_q4, float* copy_nchw, int batch, int channels, const float* h_host, int n_h, float* hdev,
                   unsigned* zero_words, int n_zero, hipStream_t stream);
 int max_hidden(const odehip_convstack* f);
+// ---- the norm-free ConvGRU cell (convgru_plain.hip): a descriptor whose four gn_* pointers are all NULL; reset gate first
+inline bool cell_is_plain(const odehip_convgru_cell* c) { return !c->gn_gates_w && !c->gn_gates_b && !c->gn_can_w && !c->gn_can_b; }
+void launch_plain_gates(const float* gates_raw, const float* h, float* u, float* rh, int hidden, int batch, hipStream_t stream);
+void launch_plain_update(const float* cand_raw, const float* h, const float* u, float* h_out, float* h_out_nchw, long long nchw_batch_stride,
+                         int hidden, int batch, const float* mask_b, hipStream_t stream);
+void launch_plain_update_bwd(const float* cand_raw, const float* gh, const float* u, const float* h, float* g_cand_raw, float* g_gates_raw,
+                             float* gh_out, int hidden, int batch, const float* mask_b, hipStream_t stream);
+void launch_plain_gates_bwd(const float* gates_raw, const float* g_rh, const float* h, float* gh_io, float* g_gates_raw, int hidden,
+                            int batch, const float* mask_b, hipStream_t stream);
 int upload_floats(float* dst, const float* src, int n, hipStream_t stream);  // scalars travel as kernel arguments (async)
 // f(x) with the stage combine fused into the last conv; `hidden` (n_convs-1 buffers) keeps the ReLU outputs for a backward pass
 int enqueue_f(const odehip_convstack* f, const float* x_q4, int batch, float* ping, float* pong, const CombineArgs* cmb,

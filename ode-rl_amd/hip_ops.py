@@ -887,13 +887,38 @@ class PackedCell:
         self._stamp = None     # identity of the entry returned last (keys the derived caches)
         self.desc = None
 
+    @property
+    def plain(self):
+        """The norm-free cell of upstream Vid-ODE (models.conv_odegru.ConvGRUCell): conv_gates / conv_can are plain nn.Conv2d, reset gate
+        first.  Its descriptor carries four NULL gn_* pointers and it has four parameters where the GroupNorm cell has eight."""
+        return isinstance(self.cell.conv_gates, torch.nn.Conv2d)
+
+    def _convs(self):
+        c = self.cell
+        return (c.conv_gates, c.conv_can) if self.plain else (c.conv_gates[0], c.conv_can[0])
+
+    def _input_channels(self):
+        return self._convs()[0].in_channels - self.cell.hidden_dim
+
     def _params(self):
         c = self.cell
+        if self.plain:
+            return [c.conv_gates.weight, c.conv_gates.bias, c.conv_can.weight, c.conv_can.bias]
         return [c.conv_gates[0].weight, c.conv_gates[0].bias, c.conv_gates[1].weight, c.conv_gates[1].bias,
                 c.conv_can[0].weight, c.conv_can[0].bias, c.conv_can[1].weight, c.conv_can[1].bias]
 
+    def grad_slots(self, grads):
+        """The eight pointers of ConvGRUCellGrads / the cell part of EncoderGrads for `grads` (one tensor per _params() entry): a plain
+        cell has no GroupNorm slots (NULL, never written)."""
+        if self.plain:
+            return [grads[0].data_ptr(), grads[1].data_ptr(), None, None, grads[2].data_ptr(), grads[3].data_ptr(), None, None]
+        return [g.data_ptr() for g in grads]
+
     def refresh(self, mode=None):
         mode = mode or current_compute_dtype()
+        plain = self.plain
+        if plain and any(cv.bias is None for cv in self._convs()):
+            raise ValueError("the HIP ConvGRU needs both convolutions to carry a bias (bias=True)")
         ps = self._params()
         stamp = (mode, winograd5_enabled()) + tuple((p.data_ptr(), p._version) for p in ps)
         ent = self._cache.get(mode)
@@ -903,26 +928,32 @@ class PackedCell:
         for p in ps:
             require_device_tensor(p, "ConvGRUCell parameter")
         c = self.cell
-        ks = c.conv_gates[0].kernel_size[0]
-        if c.conv_gates[0].padding != (ks // 2, ks // 2):
+        conv_g, conv_c = self._convs()
+        ks = conv_g.kernel_size[0]
+        if any(tuple(cv.kernel_size) != (ks, ks) or tuple(cv.padding) != (ks // 2, ks // 2) or tuple(cv.stride) != (1, 1) for cv in (conv_g, conv_c)):
             raise ValueError("the HIP ConvGRU supports 'same' padding only")
-        if c.conv_gates[1].num_groups * 32 != 2 * c.hidden_dim or c.conv_can[1].num_groups * 32 != c.hidden_dim:
+        if plain:
+            if c.hidden_dim % 32:
+                raise ValueError(f"the HIP ConvGRU needs hidden_dim to be a multiple of 32 (got {c.hidden_dim})")
+        elif c.conv_gates[1].num_groups * 32 != 2 * c.hidden_dim or c.conv_can[1].num_groups * 32 != c.hidden_dim:
             raise ValueError("the HIP ConvGRU needs GroupNorm groups of 32 channels (hidden_dim multiple of 32)")
-        want_wino = mode == "f32" and ks == 5 and winograd5_enabled() and c.input_channels % 8 == 0 and c.hidden_dim % 32 == 0
-        packs = pack_conv_weights_many([(ps[0], 0, False), (ps[4], 0, False)] + ([(ps[0], 2, False), (ps[4], 2, False)] if want_wino else []))
-        keep = [packs[0], ps[1].detach().contiguous(), ps[2].detach().contiguous(), ps[3].detach().contiguous(),
-                packs[1], ps[5].detach().contiguous(), ps[6].detach().contiguous(), ps[7].detach().contiguous()]
+        cin = self._input_channels()
+        w_g, w_c = conv_g.weight, conv_c.weight
+        want_wino = mode == "f32" and ks == 5 and winograd5_enabled() and cin % 8 == 0 and c.hidden_dim % 32 == 0
+        packs = pack_conv_weights_many([(w_g, 0, False), (w_c, 0, False)] + ([(w_g, 2, False), (w_c, 2, False)] if want_wino else []))
+        gn = [None] * 4 if plain else [ps[2].detach().contiguous(), ps[3].detach().contiguous(), ps[6].detach().contiguous(),
+                                       ps[7].detach().contiguous()]
+        keep = [packs[0], conv_g.bias.detach().contiguous(), gn[0], gn[1], packs[1], conv_c.bias.detach().contiguous(), gn[2], gn[3]]
         bf = [None, None]
-        if mode == "bf16" and _bf16_cell_ok(c.input_channels, c.hidden_dim, ks):
-            bf = [pack_conv_weight_bf16_ks(ps[0]), pack_conv_weight_bf16_ks(ps[4])]
+        if mode == "bf16" and _bf16_cell_ok(cin, c.hidden_dim, ks):   # (5x5 only: a 3x3 cell runs fp32 in bf16 mode)
+            bf = [pack_conv_weight_bf16_ks(w_g), pack_conv_weight_bf16_ks(w_c)]
         wino = packs[2:4] if want_wino else [None, None]
         keep = keep + wino
-        d = _lib.ConvGRUCellDesc(input=c.input_channels, hidden=c.hidden_dim, ks=ks,
-                                 w_gates_wino=wino[0].data_ptr() if wino[0] is not None else None,
-                                 w_can_wino=wino[1].data_ptr() if wino[1] is not None else None,
-                                 w_gates=keep[0].data_ptr(), b_gates=keep[1].data_ptr(), gn_gates_w=keep[2].data_ptr(),
-                                 gn_gates_b=keep[3].data_ptr(), w_can=keep[4].data_ptr(), b_can=keep[5].data_ptr(),
-                                 gn_can_w=keep[6].data_ptr(), gn_can_b=keep[7].data_ptr(),
+        ptr = [k.data_ptr() if k is not None else None for k in keep]
+        d = _lib.ConvGRUCellDesc(input=cin, hidden=c.hidden_dim, ks=ks,
+                                 w_gates_wino=ptr[8], w_can_wino=ptr[9],
+                                 w_gates=ptr[0], b_gates=ptr[1], gn_gates_w=ptr[2], gn_gates_b=ptr[3], w_can=ptr[4], b_can=ptr[5],
+                                 gn_can_w=ptr[6], gn_can_b=ptr[7],
                                  w_gates_bf16=bf[0].data_ptr() if bf[0] is not None else None,
                                  w_can_bf16=bf[1].data_ptr() if bf[1] is not None else None)
         self._cache[mode] = (stamp, d, keep, bf)
@@ -930,9 +961,9 @@ class PackedCell:
         return d
 
     def _half_slices(self):
-        """The two 5x5 weights cut into frame half and state half: gates-frame, gates-state, candidate-frame, candidate-state."""
-        i = self.cell.input_channels
-        wg, wc = self.cell.conv_gates[0].weight.detach(), self.cell.conv_can[0].weight.detach()
+        """The two conv weights cut into frame half and state half: gates-frame, gates-state, candidate-frame, candidate-state."""
+        i = self._input_channels()
+        wg, wc = (cv.weight.detach() for cv in self._convs())
         return [w.contiguous() for w in (wg[:, :i], wg[:, i:], wc[:, :i], wc[:, i:])]
 
     def bwd_desc(self):
@@ -994,7 +1025,7 @@ def convgru_cell_backward(packed_cell, x, h, grad_h_next):
     b = x.shape[0]
     params = packed_cell._params()
     grads = [torch.empty_like(p) for p in params]
-    g = _lib.ConvGRUCellGrads(*[t_.data_ptr() for t_ in grads])
+    g = _lib.ConvGRUCellGrads(*packed_cell.grad_slots(grads))
     gx, gh = torch.empty_like(x), torch.empty_like(h)
     lib = _lib.load()
     nbytes = lib.odehip_convgru_cell_backward_workspace_bytes(ctypes.byref(d), b)
@@ -1234,8 +1265,8 @@ def odeconvgru_encode_backward(enc, saved, grad_mean, grad_std, grad_latent=None
     for l in range(nl):
         g.f_w[l] = grads[2 * l].data_ptr()
         g.f_b[l] = grads[2 * l + 1].data_ptr()
-    (g.w_gates, g.b_gates, g.gn_gates_w, g.gn_gates_b, g.w_can, g.b_can, g.gn_can_w, g.gn_can_b, g.w_head0, g.b_head0, g.w_head1,
-     g.b_head1) = (x.data_ptr() for x in grads[2 * nl:])
+    (g.w_gates, g.b_gates, g.gn_gates_w, g.gn_gates_b, g.w_can, g.b_can, g.gn_can_w, g.gn_can_b) = enc.packed_cell.grad_slots(grads[2 * nl:-4])
+    g.w_head0, g.b_head0, g.w_head1, g.b_head1 = (x.data_ptr() for x in grads[-4:])
     gin = torch.empty((t, b, c, 16, 16), dtype=torch.float32, device=dev)
     _lib.check(_lib.load().odehip_odeconvgru_encode_backward_masked(ctypes.byref(d), ctypes.byref(bw), tarr, t, b, run_backwards,
                                                                     _ptr(grad_mean), _ptr(grad_std), _ptr(grad_latent), _ptr(gin),
