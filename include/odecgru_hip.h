@@ -629,6 +629,28 @@ int odehip_mmnist_render(const double* init, const int* digit_ids, const unsigne
                          const float* lut256, int batch, int n_digits, int t_in, int t_out, float* out_in, float* out_pred,
                          void* stream);
 
+/* The training batches of upstream Vid-ODE assembled from a clip store that stays on the device (vidode_batch.hip; DESIGN.md section
+ * 4.18): the frame gather of VideoDataset.__getitem__ (Vid-ODE/dataloader.py), RandomHorizontalFlip, ToTensor(scale=True), Normalize(0.5,
+ * 0.5) (video_transforms.py:32-70), the stacking of video_collate_fn, the split of utils.split_and_subsample_batch and the mask
+ * multiplies of utils.get_next_batch, as ONE launch.  Enqueue-only on `stream`, caller-provided memory only, no LDS, no atomics,
+ * arguments checked before any HIP call (ODEHIP_EINVAL).  Pure addition: ODEHIP_ABI_VERSION stays.
+ *   store      uint8 on the device, store_frames frames of (height, width, channels), channel-last and back to back (the clips of a
+ *              dataset one after the other); channels 1 or 3
+ *   lut256     256 floats on the device: the value of a pixel byte after ToTensor / Normalize, computed by the caller in float32
+ *   outs       HOST array of n_outputs (1..3) device pointers, output k = (batch, n_frames[k], channels, height, width) float32,
+ *              16-byte aligned; n_frames: HOST array
+ *   table      int32 words on the device, table_words of them (checked against the shapes):
+ *                [batch]                    flip flag per sample (non-zero: every frame of the sample is mirrored left-right)
+ *                per output k, in order:    [batch * n_frames[k]] absolute frame index in the store of slot (b, t), then
+ *                                           [batch * n_frames[k]] float32 bit patterns: the factor (mask value) of slot (b, t)
+ *   out_k[b][t][c][y][x] = lut256[store[frame][y][flip ? width-1-x : x][c]] * factor      (one fp32 multiply: a masked frame gets the
+ *              signed zeros of upstream's `filter_mask * data`)
+ * A frame index outside [0, store_frames) is not read; its slot is filled with NaN.  width % 4 == 0 takes the 16-byte path (the
+ * store must then be 4-byte aligned); any other width takes guarded per-pixel loads and stores. */
+int odehip_vidode_batch(const unsigned char* store, long long store_frames, int height, int width, int channels,
+                        const float* lut256, const int* table, long long table_words, int batch, int n_outputs, float* const* outs,
+                        const int* n_frames, void* stream);
+
 /* Evaluation metrics of predicted frames against the ground truth (frame_metrics.hip) -- what the reference's test() computes per
  * predicted frame on the host (train_test.py:104-117: F.mse_loss(...).item(), math.log10, utils.get_normalized_ssim), in two launches
  * on `stream` with no host synchronisation.  pred, truth: (batch, n_frames, channels, 64, 64) fp32, contiguous; channels 1 or 3 (any

@@ -15,6 +15,8 @@ from .metrics import frame_metrics, FrameMetrics  # noqa: F401
 from .optim import FusedAdam, FusedAdamax, decay_learning_rate  # noqa: F401
 from .models.gan import ConvNormAct, Discriminator, create_netD  # noqa: F401
 from .train import train_batch_gan  # noqa: F401
+from . import vidode_data  # noqa: F401
+from .vidode_data import ClipStore, VidODEBatches  # noqa: F401
 # upstream Vid-ODE's own model; its ConvGRUCell, ODEFunc, create_convnet and VidODE share names with the classes above and live in the module
 from .models import conv_odegru  # noqa: F401
 from .models.conv_odegru import Encoder_z0_ODE_ConvGRU, DiffeqSolver  # noqa: F401
@@ -22,4 +24,4 @@ from .models.conv_odegru import Encoder_z0_ODE_ConvGRU, DiffeqSolver  # noqa: F4
 __all__ = ["odeint", "odeint_adjoint", "DiffEqSolver", "ODEFunc", "create_convnet", "ConvGRUCell", "ODEConvGRUCell", "frame_metrics",
            "FrameMetrics", "sample_z0", "last_z0_noise", "mse_kl_loss", "vidode_l1_loss", "step_size_grid", "FusedAdam", "FusedAdamax",
            "decay_learning_rate", "instnorm_lrelu", "gan_sequences", "lsgan_loss", "ConvNormAct", "Discriminator", "create_netD",
-           "train_batch_gan", "conv_odegru", "Encoder_z0_ODE_ConvGRU", "DiffeqSolver"]
+           "train_batch_gan", "conv_odegru", "Encoder_z0_ODE_ConvGRU", "DiffeqSolver", "vidode_data", "ClipStore", "VidODEBatches"]
