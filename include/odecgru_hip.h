@@ -666,6 +666,29 @@ int odehip_vidode_batch(const unsigned char* store, long long store_frames, int 
 int odehip_frame_metrics(const float* pred, const float* truth, int batch, int n_frames, int channels, int height, int width,
                          float data_range, float* sse, float* ssim, float* mse, float* psnr, float* ssim_t, void* stream);
 
+/* Upstream Vid-ODE's evaluation protocol on the device (png_metrics.hip) -- what Vid-ODE/tester.py:49-78,
+ * visualize.save_test_images and evaluate.Evaluation compute through 8-bit PNG files, PIL and scikit-image: per image the squared error
+ * of the 8-bit RGB bytes, its MSE on the [0, 1] scale and the Gaussian SSIM (data_range 255) of the 8-bit luma.  One launch (two with
+ * `accum`), enqueue-only on `stream`, caller-provided memory only, no atomics (two calls are bitwise equal), arguments checked before
+ * any HIP call (ODEHIP_EINVAL).  Pure addition: ODEHIP_ABI_VERSION stays.
+ *   pred, truth   (batch, n_frames, channels, size, size) fp32, contiguous, 16-byte aligned; channels 1 or 3; size 32, 64 or 128
+ *   denorm        non-zero: upstream's opt.input_norm, v = min(max((x + 1) / 2, 0), 1) first (utils.denorm)
+ *   byte          trunc(min(max(v * 255 + 0.5, 0), 255)), every step one fp32 operation (torchvision's save_image); one channel is
+ *                 replicated into R, G and B;  luma L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 (PIL's convert('L'))
+ *   sse[b][t]     int64: sum over the 3 * size^2 RGB bytes of (byte_pred - byte_truth)^2, exact
+ *   mse[b][t]     float64: sse / (255^2 * 3 * size^2)
+ *   ssim[b][t]    float64: scikit-image's structural_similarity(gaussian_weights=True, use_sample_covariance=False, data_range=255)
+ *                 of the two luma planes (sigma 1.5, 11 taps, mean over rows / columns 5 .. size-6), moments in float64
+ *   pred_bytes, truth_bytes   both NULL, or (batch, n_frames, size, size, 3) uint8, 4-byte aligned: the RGB bytes in PNG pixel order
+ *   accum         NULL, or 24 bytes on the device, 8-byte aligned: {float64 sum of ssim, float64 sum of mse, int64 image count}.  A
+ *                 second launch adds this call's batch * n_frames values to the running sums one by one in ascending order (so the sums
+ *                 do not depend on how a set was split into calls) and the number of images to the count.
+ * A NaN in either frame of an image (found by comparing the float with itself) makes that image's ssim and mse NaN, leaves its sse
+ * at -1 and writes the NaN pixel's byte as 0; no other image is affected. */
+int odehip_png_metrics(const float* pred, const float* truth, int batch, int n_frames, int channels, int size, int denorm,
+                       long long* sse, double* mse, double* ssim, unsigned char* pred_bytes, unsigned char* truth_bytes, void* accum,
+                       void* stream);
+
 /* z0 ~ N(mean_z0, std_z0) by the reparameterisation trick and its KL term against N(0, 1) (latent_sample.hip): the `opt.z_sample`
  * mode the reference declares in configs.yaml and leaves at a TODO (models/ODEConvGRU.py:72-77; the objective is named in
  * models/ConvGRU.py:285-290).  ONE launch each, enqueue-only on `stream`, caller-provided memory only, arguments checked before any

@@ -11,7 +11,7 @@ from .helpers.utils import create_convnet  # noqa: F401
 from .modules.DiffEqSolver import DiffEqSolver, ODEFunc  # noqa: F401
 from .modules.ConvGRUCell import ConvGRUCell  # noqa: F401
 from .modules.ODEConvGRUCell import ODEConvGRUCell  # noqa: F401
-from .metrics import frame_metrics, FrameMetrics  # noqa: F401
+from .metrics import frame_metrics, FrameMetrics, png_metrics, PngMetrics, PngEvaluation  # noqa: F401
 from .optim import FusedAdam, FusedAdamax, decay_learning_rate  # noqa: F401
 from .models.gan import ConvNormAct, Discriminator, create_netD  # noqa: F401
 from .train import train_batch_gan  # noqa: F401
@@ -24,4 +24,5 @@ from .models.conv_odegru import Encoder_z0_ODE_ConvGRU, DiffeqSolver  # noqa: F4
 __all__ = ["odeint", "odeint_adjoint", "DiffEqSolver", "ODEFunc", "create_convnet", "ConvGRUCell", "ODEConvGRUCell", "frame_metrics",
            "FrameMetrics", "sample_z0", "last_z0_noise", "mse_kl_loss", "vidode_l1_loss", "step_size_grid", "FusedAdam", "FusedAdamax",
            "decay_learning_rate", "instnorm_lrelu", "gan_sequences", "lsgan_loss", "ConvNormAct", "Discriminator", "create_netD",
-           "train_batch_gan", "conv_odegru", "Encoder_z0_ODE_ConvGRU", "DiffeqSolver", "vidode_data", "ClipStore", "VidODEBatches"]
+           "train_batch_gan", "conv_odegru", "Encoder_z0_ODE_ConvGRU", "DiffeqSolver", "vidode_data", "ClipStore", "VidODEBatches",
+           "png_metrics", "PngMetrics", "PngEvaluation"]

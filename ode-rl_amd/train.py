@@ -204,6 +204,70 @@ def evaluate(model, batches):
             "avg_mse": float(mse[-1]), "avg_psnr": float(psnr[-1]), "avg_ssim": float(ssim[-1])}
 
 
+def _select_frames(frames, mask):
+    """Upstream's `data[mask.squeeze(-1).byte()].view(b, int(mask[0].sum()), c, h, w)` (Vid-ODE/tester.py:65-67) without a device
+    read: the mask is looked at where the loader left it (the host), a mask that keeps every frame selects nothing, and the others
+    index with positions uploaded through pinned memory.  mask: None, (B, T, 1) or (B, T)."""
+    import numpy as np
+    from . import vidode_data
+    if mask is None:
+        return frames
+    b, t = frames.shape[:2]
+    keep = mask.detach().cpu().reshape(b, -1).numpy() != 0
+    if keep.shape[1] != t:
+        raise ValueError(f"evaluate_vidode: mask_predicted_data {tuple(mask.shape)} does not match the {t} frames of data_to_predict")
+    if keep.all():
+        return frames
+    n = int(keep[0].sum())
+    if not (keep.sum(axis=1) == n).all():
+        raise ValueError(f"evaluate_vidode: mask_predicted_data keeps {keep.sum(axis=1).tolist()} frames per sample; upstream's view needs "
+                         "the same number in every sample")
+    cols = torch.from_numpy(np.stack([np.nonzero(row)[0] for row in keep]).reshape(b, n))
+    rows = torch.arange(b).unsqueeze(-1).expand_as(cols).contiguous()
+    return frames[vidode_data._upload(rows, frames.device), vidode_data._upload(cols, frames.device)]
+
+
+def evaluate_vidode(model, loader, opt, n_batches=None):
+    """Upstream Vid-ODE's `Tester.infer_and_metrics` (Vid-ODE/tester.py:49-78) with `visualize.save_test_images` and
+    `evaluate.Evaluation` behind it, without the PNG files: model.eval() under no_grad, and per batch of `loader` (the dictionaries a
+    `vidode_data.VidODEBatches` yields) `vidode_data.get_next_batch(..., test_interp=not opt.extrap)`, `model.get_reconstruction` with
+    upstream's five arguments, `data_to_predict` selected by `mask_predicted_data`, then `PngEvaluation.update(preds, truth,
+    input_norm=opt.input_norm)`: 8-bit RGB bytes, luma SSIM and byte MSE accumulated on the device.  `n_batches` ends an endless loader
+    (upstream's `n_test_batches`); a finite iterable needs none.
+
+    Returns {'ssim', 'mse', 'psnr', 'n_images'}: upstream's avg_ssim, avg_mse and avg_psnr = 10 log10(1 / avg_mse) over all images, from
+    the one host transfer at the end.  Left out: writing the PNG files, `os.listdir`, and upstream's `rm -rf` of the result directory.
+    The model's training mode is restored on the way out, also when a batch raises."""
+    from . import metrics, vidode_data
+    if getattr(opt, "dataset", None) == "hurricane":
+        raise NotImplementedError("evaluate_vidode: the Hurricane set is not implemented (its loader needs Pad and ToTensor(scale=False), "
+                                  "and upstream scores its 'orignal_data_to_predict')")
+    test_interp = not opt.extrap
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            ev, seen = None, 0
+            for data_dict in loader:
+                if n_batches is not None and seen >= n_batches:
+                    break
+                batch_dict = vidode_data.get_next_batch(data_dict, test_interp=test_interp)
+                preds, _ = model.get_reconstruction(time_steps_to_predict=batch_dict["tp_to_predict"], truth=batch_dict["observed_data"],
+                                                    truth_time_steps=batch_dict["observed_tp"], mask=batch_dict["observed_mask"],
+                                                    out_mask=batch_dict["mask_predicted_data"])
+                truth = _select_frames(batch_dict["data_to_predict"].to(preds.device), batch_dict["mask_predicted_data"])
+                if ev is None:
+                    ev = metrics.PngEvaluation(preds.device)
+                ev.update(preds, truth, input_norm=bool(getattr(opt, "input_norm", False)))
+                seen += 1
+            if ev is None:
+                raise ValueError("evaluate_vidode: no batches")
+            avg_ssim, avg_mse, avg_psnr, n_images = ev.summary()
+    finally:
+        model.train(was_training)
+    return {"ssim": avg_ssim, "mse": avg_mse, "psnr": avg_psnr, "n_images": n_images}
+
+
 def checkpoint_name(ckpt_id, step):
     return f"{ckpt_id}_{step:010d}.pickle"                    # helpers/utils.py:215-217
 

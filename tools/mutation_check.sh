@@ -79,6 +79,9 @@ SED[gn_gates_odd_boundary]='s/    if (!is_z) s \*= hp\[q \* kPix\];/    if (!is_
 # ---- the norm-free ConvGRU cell of upstream Vid-ODE (convgru_plain.hip; tests/test_hip_vidode_upstream.py)
 SED[plain_gates_swapped]='s/  const bool is_reset = q < hq;/  const bool is_reset = q >= hq;/;s/  const size_t o = ((size_t)b \* hq + (is_reset ? q : q - hq)) \* kPix + threadIdx.x;/  const size_t o = ((size_t)b * hq + (q < hq ? q : q - hq)) * kPix + threadIdx.x;/'   # the first half of conv_gates taken as the update gate (same addresses)
 SED[plain_bwd_drops_bypass]='s/  if (blend) d += (1.0f - m) \* g;  \/\/ the part of the blend that bypasses the cell/  (void)blend;/'   # fractional mask: the (1-m) g term of the state gradient dropped
+# ---- upstream Vid-ODE's evaluation protocol (png_metrics.hip; tests/test_hip_png_metrics.py)
+SED[png_luma_no_rounding]='s/  return (19595u \* r + 38470u \* g + 7471u \* b + 0x8000u) >> 16;/  return (19595u * r + 38470u * g + 7471u * b) >> 16;/'   # PIL'"'"'s luma truncated instead of rounded
+SED[png_crop_from_row_4]='s/^constexpr int kPngCropRow = kPngRadius; /constexpr int kPngCropRow = kPngRadius - 1; /'   # S averaged over rows 4 .. S-7 (row -1 of the first plane = the reduction scratch in front of it: still inside the allocation)
 # mutants of the Python binding, "file|sed script": applied to the tree's own file for the run and restored afterwards (run only)
 declare -A PYSED
 PYSED[z0_offset_stuck]='ode-rl_amd/autograd.py|s/gen.set_offset(at + 4)/gen.set_offset(at)/;s/_explicit_seed\[1\] = offset + 1/_explicit_seed[1] = offset/'   # consecutive sample_z0 calls draw the same noise
@@ -87,7 +90,7 @@ PYSED[vidode_prev_detached]='ode-rl_amd/models/VidODE.py|s/^            prev = s
 PYSED[vidode_skip_detached]='ode-rl_amd/models/VidODE.py|s/^        skip = self\.conv_encoder(inputs\[:, -1, \.\.\.\])$/        skip = self.conv_encoder(inputs[:, -1, ...]).detach()/'   # the second encoder pass contributes nothing to the encoder'"'"'s gradients
 PYSED[vidode_inter_detached]='ode-rl_amd/models/VidODE.py|s/self\.extra_info\["pred_intermediates"\], self\.batch_dict/self.extra_info["pred_intermediates"].detach(), self.batch_dict/'   # the frame-difference term of the loss reaches nothing
 PYSED[bn_conv_bias_eval_grad]='ode-rl_amd/autograd.py|s/else stats\[2\] \* gb$/else gb/'   # eval(): the folded convolution bias gets d beta instead of scale * d beta
-TESTS="tests/test_hip_grid_options.py::test_backward_matches_autograd_through_the_restated_loop tests/test_hip_bf16.py::test_whole_trajectory_training_matches_per_evaluation_launches tests/test_hip_tanh_dynamics.py::test_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_backward_random_dynamics tests/test_hip_frame_loss.py tests/test_hip_latent_sample.py tests/test_hip_convgru_sequence.py::test_rollout_forward_against_the_float64_restatement[False-True-10-4-64] tests/test_hip_convgru_sequence.py::test_bptt_against_float64_autograd[False-True-10-4] tests/test_hip_convgru_sequence.py::test_bptt_against_float64_autograd[True-False-10-4] tests/test_hip_convgru_sequence.py::test_a_zero_state_reads_nothing_of_the_state_buffers tests/test_hip_convgru_sequence.py::test_rollout_agrees_with_the_step_by_step_forward[False-True-10-4] tests/test_hip_backward.py::test_backward_strict_on_kink_free_dynamics tests/test_hip_frame_codec.py::test_encoder_matches_reference_fixture tests/test_hip_frame_codec.py::test_decoder_matches_reference_fixture tests/test_hip_conv.py::test_winograd5_conv_matches_torch tests/test_hip_full_size.py::test_cell_and_encoder_full_channels tests/test_hip_odeint.py::test_fixed_grid_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_dopri5_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_fixed_grid_matches_golden_and_oracle tests/test_hip_odeint.py::test_full_size_against_oracle tests/test_hip_backward.py::test_dopri5_backward_matches_autograd_through_oracle tests/test_hip_backward.py::test_dopri5_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_dopri5_saving_forward_equals_reintegration tests/test_hip_reference_configs.py::test_config0_as_stated_b4 tests/test_hip_encoder_backward.py::test_convgru_cell_backward_matches_autograd_through_oracle tests/test_hip_frame_codec.py::test_backward_matches_fp64_autograd tests/test_hip_vidode.py::test_upsample2x_matches_torch tests/test_hip_vidode.py::test_bn_relu_up_matches_torch tests/test_hip_backward.py::test_async_dopri5_forward_matches_the_synchronous_one tests/test_hip_errors.py::test_a_non_finite_state_is_not_laundered tests/test_hip_errors.py::test_a_lost_partner_in_a_single_evaluation_walk_is_loud tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[max_num_steps-no_grad] tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[overflow-saving] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[euler-3-per_layer] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[rk4-20-persistent] tests/test_hip_relu_nan_backward.py::test_bf16_backward_passes_the_gradient_of_a_nan_channel tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-True-True-x] tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-False-False-gamma] tests/test_hip_frame_metrics.py::test_matches_the_fp64_restatement[3-5-3] tests/test_hip_frame_metrics.py::test_matches_the_fp64_restatement[64-10-1] tests/test_hip_frame_metrics.py::test_evaluate_end_to_end tests/test_hip_conv_shapes.py tests/test_hip_vidode_grads.py tests/test_hip_vidode_upstream.py"
+TESTS="tests/test_hip_grid_options.py::test_backward_matches_autograd_through_the_restated_loop tests/test_hip_bf16.py::test_whole_trajectory_training_matches_per_evaluation_launches tests/test_hip_tanh_dynamics.py::test_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_backward_random_dynamics tests/test_hip_frame_loss.py tests/test_hip_latent_sample.py tests/test_hip_convgru_sequence.py::test_rollout_forward_against_the_float64_restatement[False-True-10-4-64] tests/test_hip_convgru_sequence.py::test_bptt_against_float64_autograd[False-True-10-4] tests/test_hip_convgru_sequence.py::test_bptt_against_float64_autograd[True-False-10-4] tests/test_hip_convgru_sequence.py::test_a_zero_state_reads_nothing_of_the_state_buffers tests/test_hip_convgru_sequence.py::test_rollout_agrees_with_the_step_by_step_forward[False-True-10-4] tests/test_hip_backward.py::test_backward_strict_on_kink_free_dynamics tests/test_hip_frame_codec.py::test_encoder_matches_reference_fixture tests/test_hip_frame_codec.py::test_decoder_matches_reference_fixture tests/test_hip_conv.py::test_winograd5_conv_matches_torch tests/test_hip_full_size.py::test_cell_and_encoder_full_channels tests/test_hip_odeint.py::test_fixed_grid_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_dopri5_on_vigorous_dynamics_matches_reference_fixture tests/test_hip_odeint.py::test_fixed_grid_matches_golden_and_oracle tests/test_hip_odeint.py::test_full_size_against_oracle tests/test_hip_backward.py::test_dopri5_backward_matches_autograd_through_oracle tests/test_hip_backward.py::test_dopri5_adjoint_matches_oracle_adjoint tests/test_hip_backward.py::test_dopri5_saving_forward_equals_reintegration tests/test_hip_reference_configs.py::test_config0_as_stated_b4 tests/test_hip_encoder_backward.py::test_convgru_cell_backward_matches_autograd_through_oracle tests/test_hip_frame_codec.py::test_backward_matches_fp64_autograd tests/test_hip_vidode.py::test_upsample2x_matches_torch tests/test_hip_vidode.py::test_bn_relu_up_matches_torch tests/test_hip_backward.py::test_async_dopri5_forward_matches_the_synchronous_one tests/test_hip_errors.py::test_a_non_finite_state_is_not_laundered tests/test_hip_errors.py::test_a_lost_partner_in_a_single_evaluation_walk_is_loud tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[max_num_steps-no_grad] tests/test_hip_solver_failures.py::test_a_failed_asynchronous_solve_is_sealed_and_reported[overflow-saving] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[euler-3-per_layer] tests/test_hip_relu_nan_backward.py::test_fixed_grid_backward_passes_the_gradient_of_a_nan_channel[rk4-20-persistent] tests/test_hip_relu_nan_backward.py::test_bf16_backward_passes_the_gradient_of_a_nan_channel tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-True-True-x] tests/test_hip_relu_nan_backward.py::test_bn_relu_up_backward_passes_the_gradient_of_a_nan_activation[shape0-False-False-gamma] tests/test_hip_frame_metrics.py::test_matches_the_fp64_restatement[3-5-3] tests/test_hip_frame_metrics.py::test_matches_the_fp64_restatement[64-10-1] tests/test_hip_frame_metrics.py::test_evaluate_end_to_end tests/test_hip_conv_shapes.py tests/test_hip_vidode_grads.py tests/test_hip_vidode_upstream.py tests/test_hip_png_metrics.py::test_ssim_matches_the_float64_restatement"
 [ -n "${MUT_TESTS:-}" ] && TESTS=$MUT_TESTS   # a subset of the tests (a GPU lease is short): e.g. the files that cover the mutants of MUT_ONLY
 # a mutated copy of the sources under $MUT/<mutant>; names the file that differs from the tree's (diff -q) and fails unless exactly one does
 mutate() {
