@@ -651,6 +651,29 @@ int odehip_vidode_batch(const unsigned char* store, long long store_frames, int 
                         const float* lut256, const int* table, long long table_words, int batch, int n_outputs, float* const* outs,
                         const int* n_frames, void* stream);
 
+/* odehip_vidode_batch with upstream's RandomRotation between the flip and ToTensor (vidode_rotate.hip): one
+ * angle per sample, every frame of the sample rotated by it as skimage.transform.rotate(frame, angle, preserve_range=True) is stated
+ * in DESIGN (bilinear, 0 outside the frame, values clipped from below to the frame's own minimum byte).  A rotated pixel is no byte,
+ * so there is no lut256: `input_norm` selects Normalize(0.5, 0.5) after ToTensor(scale=True).  ONE launch, enqueue-only on `stream`,
+ * caller-provided memory only, no LDS, no atomics, arguments checked before any HIP call (ODEHIP_EINVAL).  Pure addition:
+ * ODEHIP_ABI_VERSION stays.  store, outs, n_frames as for odehip_vidode_batch (no alignment asked of the store: byte loads).
+ *   frame_min  uint8 on the device, store_frames entries: the smallest byte of each frame over all its channels
+ *   table      int32 words on the device, 8-byte aligned, table_words of them (checked against the shapes):
+ *                [4 * batch]                per sample two float64 (bit patterns, 2 words each): cos and sin of the angle
+ *                [batch]                    flip flag per sample
+ *                per output k, in order:    frames and factors as for odehip_vidode_batch
+ *   with cx = width / 2 - 0.5, cy = height / 2 - 0.5, all in float64, one rounding per operation, left to right:
+ *     sx = cos * (x - cx) - sin * (y - cy) + cx,  sy = sin * (x - cx) + cos * (y - cy) + cy
+ *     x0 = floor(sx), x1 = ceil(sx), dx = sx - x0 (y likewise);  p(yy, xx) = store[frame][yy][flip ? width-1-xx : xx][c], 0 outside
+ *     v = (1 - dy) * ((1 - dx) * p(y0, x0) + dx * p(y0, x1)) + dy * ((1 - dx) * p(y1, x0) + dx * p(y1, x1))
+ *     v = max(v, frame_min[frame]) unless v == 0            (a non-finite cos or sin gives v = 0)
+ *   out_k[b][t][c][y][x] = normalise(float32(v) / 255) * factor, normalise(f) = input_norm ? (f - 0.5) / 0.5 : f, in float32
+ * cos = 1, sin = 0 gives what odehip_vidode_batch gives with the lut256 of the same input_norm, bit for bit.  A frame index outside
+ * [0, store_frames) is not read; its slot is filled with NaN.  width % 4 == 0 takes 16-byte stores, any other width guarded ones. */
+int odehip_vidode_batch_rotated(const unsigned char* store, long long store_frames, int height, int width, int channels,
+                                const unsigned char* frame_min, int input_norm, const int* table, long long table_words, int batch,
+                                int n_outputs, float* const* outs, const int* n_frames, void* stream);
+
 /* Evaluation metrics of predicted frames against the ground truth (frame_metrics.hip) -- what the reference's test() computes per
  * predicted frame on the host (train_test.py:104-117: F.mse_loss(...).item(), math.log10, utils.get_normalized_ssim), in two launches
  * on `stream` with no host synchronisation.  pred, truth: (batch, n_frames, channels, 64, 64) fp32, contiguous; channels 1 or 3 (any

@@ -4,20 +4,25 @@ Stands in for upstream's `VideoDataset` + `DataLoader` + `video_collate_fn` + `u
 (Vid-ODE/dataloader.py, Vid-ODE/utils.py:73-209).  Upstream does per item a numpy gather, a flip copy, `ToTensor`, `Normalize` and
 later a mask multiply on the host, then a collate and a host->device copy per step; here the clips are uploaded ONCE as uint8
 (`ClipStore`), the host does only upstream's index arithmetic (`VidODEBatches.draw`: which frames, which mask, flipped or not) and
-`odehip_vidode_batch` writes every float tensor of the batch in one launch.
+`odehip_vidode_batch` writes every float tensor of the batch in one launch.  With `rotate=` upstream's `RandomRotation` joins in:
+the host draws one angle per item where upstream draws it and `odehip_vidode_batch_rotated` rotates inside the same single launch.
 
 The host makes upstream's random calls in upstream's order per item (`random.randint` / `np.random.randint` for the window,
-`np.random.choice` for the irregular picks, `random.random()` for the flip), so a run under seeded `random` / `np.random` selects the
-frames and masks upstream selects for the same clips.  The clip order comes from the iterator's own `torch.Generator`.
+`np.random.choice` for the irregular picks, `random.random()` for the flip, `random.uniform` for the angle), so a run under seeded
+`random` / `np.random` selects the frames, masks, flips and angles upstream selects for the same clips.  The clip order comes from the
+iterator's own `torch.Generator`.
 
 Where the pieces of a batch live: the frame tensors are on the device; the time grids (`observed_tp`, `tp_to_predict`) and the masks
 (`observed_mask`, `mask_predicted_data`) are HOST tensors.  The models read frame counts and times on the host (`VidODE._selected`,
 `hip_ops.host_times`), so a device mask would cost them a synchronisation per step; the only device copy of the mask values is the
 factor column of the kernel's table.  Nothing here synchronises: the table travels in one small non-blocking copy from pinned memory.
 
-Out of scope, refused by name: `Scale`, `CenterCrop`, `Pad`, `RandomRotation`, mp4 decoding, `HurricaneVideoDataset`.
+Out of scope, refused by name: `Scale`, `CenterCrop`, `Pad`, mp4 decoding, `HurricaneVideoDataset`; `RandomRotation` as a transform
+object too (the rotation is the `rotate=` argument of `VidODEBatches`).
 """
 import ctypes
+import math
+import numbers
 import os
 import random
 
@@ -36,7 +41,8 @@ def _refuse(name, why):
 Scale = _refuse("Scale", "clips are stored at the model's resolution, so resize them once before building the ClipStore.")
 CenterCrop = _refuse("CenterCrop", "clips are stored at the model's resolution, so crop them once before building the ClipStore.")
 Pad = _refuse("Pad", "clips are stored at the model's resolution, so pad them once before building the ClipStore.")
-RandomRotation = _refuse("RandomRotation", "upstream rotates through scikit-image on the host, which has no place in a device-resident loader.")
+RandomRotation = _refuse("RandomRotation", "a host transform has no place in a device-resident loader; VidODEBatches(rotate=degrees) draws the "
+                         "angle where upstream does and rotates inside the batch launch.")
 HurricaneVideoDataset = _refuse("HurricaneVideoDataset", "the Hurricane set needs Pad and ToTensor(scale=False), neither of which this loader has.")
 
 
@@ -60,7 +66,8 @@ def _upload(host, device):
 
 class ClipStore:
     """uint8 clips (L_i, H, W, C) -- or (L_i, H, W) for one channel -- back to back in one device buffer, uploaded once.  Offsets
-    and lengths stay on the host.  A store on the CPU serves the host side (`VidODEBatches.draw`) only: rendering needs a GPU."""
+    and lengths stay on the host.  `frame_min` (n_frames,) uint8 on the same device holds each frame's smallest byte, which the rotated
+    launch clips to.  A store on the CPU serves the host side (`VidODEBatches.draw`) only: rendering needs a GPU."""
 
     def __init__(self, clips, device=None, min_frames=None):
         clips = list(clips)
@@ -90,6 +97,7 @@ class ClipStore:
             self.require_min_frames(min_frames)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.data = torch.from_numpy(np.concatenate(shaped, axis=0)).to(self.device)
+        self.frame_min = self.data.reshape(self.n_frames, -1).amin(dim=1)
 
     def __len__(self):
         return len(self.lengths)
@@ -121,10 +129,13 @@ class VidODEBatches:
     opt: `window_size`, `sample_size`, `irregular`, `extrap`, `batch_size`; optional `phase` ('train'), `sample_from_beg` (False),
     `unequal` (False) with `input_sequence`, `input_norm` (False).  `train=False` fixes every window at frame 0, keeps the clips in
     order and names the mode "test".  `hflip` draws upstream's `RandomHorizontalFlip` per item (upstream adds it to training sets).
+    `rotate` draws upstream's `RandomRotation` per item after the flip: a number d for angles in (-d, d) degrees (upstream's is 10) or
+    a pair (lo, hi); None (the default) rotates nothing and makes no random call.
     An epoch ends with a smaller batch when the clips do not divide by the batch size (DataLoader's drop_last=False)."""
 
-    def __init__(self, opt, store, train=True, hflip=False, seed=0):
+    def __init__(self, opt, store, train=True, hflip=False, rotate=None, seed=0):
         self.opt, self.store, self.train, self.hflip = opt, store, bool(train), bool(hflip)
+        self.rotate = _degrees(rotate)
         if getattr(opt, "dataset", None) == "hurricane":
             HurricaneVideoDataset()
         self.window_size, self.sample_size = int(opt.window_size), int(opt.sample_size)
@@ -159,7 +170,8 @@ class VidODEBatches:
         else:
             self.n_observed = self.n_data
         self.mode = "train" if self.train else "test"
-        self._lut_host = pixel_table(bool(getattr(opt, "input_norm", False)))
+        self.input_norm = bool(getattr(opt, "input_norm", False))
+        self._lut_host = pixel_table(self.input_norm)
         self._lut = self._lut_host.to(store.device)
         self._gen = torch.Generator().manual_seed(seed)
         self._order, self._cursor = None, 0
@@ -210,40 +222,53 @@ class VidODEBatches:
 
     def draw(self, clips=None):
         """The random part of one batch, all on the host: {"clips" (B,), "rel" (B, T) frame numbers inside each clip, "frames" (B, T)
-        int32 frame numbers in the store, "mask" (B, T) float32, "flip" (B,) bool}.  `clips` overrides the iterator's clip order."""
+        int32 frame numbers in the store, "mask" (B, T) float32, "flip" (B,) bool, "angle" (B,) float64 degrees (zeros without
+        `rotate`)}.  `clips` overrides the iterator's clip order."""
         clips = self._next_clips() if clips is None else np.asarray(clips, dtype=np.int64)
-        rel, mask, flip = [], [], []
+        rel, mask, flip, angle = [], [], [], []
         for c in clips:
             r, m = self._sample(int(self.store.lengths[c]))
             rel.append(r)
             mask.append(m)
             flip.append(self.hflip and random.random() < 0.5)
+            angle.append(random.uniform(*self.rotate) if self.rotate is not None else 0.0)
         rel = np.stack(rel).astype(np.int64)
         frames = rel + self.store.offsets[clips][:, None]
         return {"clips": np.asarray(clips), "rel": rel, "frames": frames.astype(np.int32), "mask": np.stack(mask),
-                "flip": np.array(flip, dtype=bool)}
+                "flip": np.array(flip, dtype=bool), "angle": np.array(angle, dtype=np.float64)}
 
     # ---- the device side ------------------------------------------------------------------------------------------------------------
 
-    def _launch(self, flip, parts):
-        """One `odehip_vidode_batch` launch: parts = [(frames (B, T_k) int32, factors (B, T_k) float32)] -> the float tensors."""
+    def _launch(self, flip, parts, angle=None):
+        """One `odehip_vidode_batch` launch: parts = [(frames (B, T_k) int32, factors (B, T_k) float32)] -> the float tensors.  With
+        `angle` (B,) degrees it is one `odehip_vidode_batch_rotated` launch, whose table starts with cos and sin per sample."""
         store, dev = self.store, self.store.device
         if dev.type != "cuda":
             raise RuntimeError("VidODEBatches assembles batches with the HIP library: the ClipStore must be on a GPU (no CPU fallback)")
         b = len(flip)
         words = [flip.astype(np.int32)]
+        if angle is not None:
+            rad = [math.radians(float(a)) for a in angle]
+            words.insert(0, np.array([[math.cos(a), math.sin(a)] for a in rad], dtype=np.float64).ravel().view(np.int32))
         for frames, factor in parts:
             if int(frames.min()) < 0 or int(frames.max()) >= store.n_frames:
                 raise ValueError("VidODEBatches: frame index outside the store")
             words += [np.ascontiguousarray(frames, dtype=np.int32).ravel(), np.ascontiguousarray(factor, dtype=np.float32).ravel().view(np.int32)]
         table = _upload(torch.from_numpy(np.concatenate(words)), dev)
         outs = [torch.empty((b, f.shape[1], store.channels, store.height, store.width), device=dev) for f, _ in parts]
+        out_ptrs = (ctypes.c_void_p * len(parts))(*[o.data_ptr() for o in outs])
+        counts = (ctypes.c_int * len(parts))(*[f.shape[1] for f, _ in parts])
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream()
-            _lib.check(_lib.load().odehip_vidode_batch(
-                store.data.data_ptr(), store.n_frames, store.height, store.width, store.channels, self._lut.data_ptr(), table.data_ptr(),
-                table.numel(), b, len(parts), (ctypes.c_void_p * len(parts))(*[o.data_ptr() for o in outs]),
-                (ctypes.c_int * len(parts))(*[f.shape[1] for f, _ in parts]), ctypes.c_void_p(stream.cuda_stream)))
+            if angle is None:
+                _lib.check(_lib.load().odehip_vidode_batch(
+                    store.data.data_ptr(), store.n_frames, store.height, store.width, store.channels, self._lut.data_ptr(),
+                    table.data_ptr(), table.numel(), b, len(parts), out_ptrs, counts, ctypes.c_void_p(stream.cuda_stream)))
+            else:
+                _lib.check(_lib.load().odehip_vidode_batch_rotated(
+                    store.data.data_ptr(), store.n_frames, store.height, store.width, store.channels, store.frame_min.data_ptr(),
+                    int(self.input_norm), table.data_ptr(), table.numel(), b, len(parts), out_ptrs, counts,
+                    ctypes.c_void_p(stream.cuda_stream)))
         table.record_stream(stream)   # the launch is asynchronous: keep the table alive until the stream has consumed it
         return outs
 
@@ -275,7 +300,8 @@ class VidODEBatches:
         """The batch of a `draw()`.  test_interp None: the collated and split dictionary (what `__next__` yields); False / True: the
         dictionary `get_next_batch(that, test_interp)` returns, from the same single launch."""
         names, parts, host = self.layout(plan, test_interp)
-        return {**dict(zip(names, self._launch(plan["flip"], parts))), **host}
+        angle = plan["angle"] if self.rotate is not None else None
+        return {**dict(zip(names, self._launch(plan["flip"], parts, angle))), **host}
 
     def __iter__(self):
         return self
@@ -285,6 +311,19 @@ class VidODEBatches:
 
     def next_batch(self, test_interp=False):
         return self.render(self.draw(), test_interp=bool(test_interp))
+
+
+def _degrees(rotate):
+    """`RandomRotation.__init__` (video_transforms.py): a number d means (-d, d) and must not be negative, anything else is (lo, hi)."""
+    if rotate is None:
+        return None
+    if isinstance(rotate, numbers.Number):
+        if rotate < 0:
+            raise ValueError("VidODEBatches: if rotate is a single number, it must be positive")
+        return (-float(rotate), float(rotate))
+    if len(rotate) != 2:
+        raise ValueError("VidODEBatches: if rotate is a sequence, it must be of len 2 (lo, hi)")
+    return (float(rotate[0]), float(rotate[1]))
 
 
 def _selected_columns(mask):
