@@ -496,7 +496,7 @@ int odehip_adam_step_clipped(float* const* params, float* const* grads, float* c
                              const long long* numel, int n_tensors, float lr, float beta1, float beta2, float eps, float weight_decay,
                              int step, const float* coef_dev, void* stream);
 
-/* Adamax (adamax.hip): Vid-ODE's optimizer (Vid-ODE/main.py:187: optim.Adamax(netG.parameters(), lr)) on the tables, the grid and the
+/* Adamax (optim_step.hip): Vid-ODE's optimizer (Vid-ODE/main.py:187: optim.Adamax(netG.parameters(), lr)) on the tables, the grid and the
  * argument checks of the Adam pair above.  Pure additions: ODEHIP_ABI_VERSION stays.  torch.optim.Adamax arithmetic (single-tensor
  * path, maximize off; weight_decay is the L2 form and is skipped when 0), `step` counts from 1 and lr / (1 - beta1^step) is computed
  * on the host in float64:

@@ -11,10 +11,9 @@
 //              grad_pred = sgn(pred - truth_s) g / N, grad_inter = sgn(inter - d) g / N, sgn(0) = sgn(NaN) = 0 (torch.abs's backward)
 //
 // Arithmetic.  Every difference, square, absolute value and sum is formed in float64 from the fp32 inputs and rounded to fp32 once.
-// Sum order: a thread adds its elements in ascending order (16-byte loads, the four elements of a quad in order), a wave folds its
-// 64 lanes by xor-shuffles, thread 0 adds the wave partials in index order, and the second launch adds the workgroup partials in
-// workgroup order.  Which elements a thread sees is a function of the sizes alone (loss_groups / l1_groups below), never of the
-// machine: two calls are bitwise equal, on any device.
+// Sum order: a thread adds its elements in ascending order (16-byte loads, the four elements of a quad in order), then reduce.h's
+// workgroup sum, and the second launch is reduce.h's ordered sum of the workgroup partials.  Which elements a thread sees is a
+// function of the sizes alone (sum_groups / l1_groups), never of the machine: two calls are bitwise equal, on any device.
 //
 // Launches.  Forward: partials, then a one-workgroup final (as frame_metrics.hip).  The single-launch form with an arrival ticket
 // needs a zeroed word per call -- a memset node, i.e. a second launch all the same -- or a ticket the last workgroup resets, which
@@ -23,45 +22,19 @@
 #include <stdint.h>
 
 #include "odehip_internal.h"
+#include "reduce.h"
 
 namespace odehip {
 
 typedef float f32x4l __attribute__((ext_vector_type(4)));
 
 constexpr int kLossThreads = 256;
-constexpr int kLossMaxGroups = 1024;      // workgroup partials of a forward launch at most (the final launch stages them in LDS)
-constexpr int kLossQuadsPerGroup = 2048;  // below kLossMaxGroups groups a workgroup walks this many quads: 8 per thread
 constexpr int kL1ChunkQuads = 1024;       // L1 pair: a work item is this many quads of one (b, j) frame (one 64 x 64 plane)
 
-// workgroups (= partials) of an MSE forward over `quads` 16-byte quads: a function of the size alone
-static inline int loss_groups(long long quads) {
-  const long long g = (quads + kLossQuadsPerGroup - 1) / kLossQuadsPerGroup;
-  return g < 1 ? 1 : (g > kLossMaxGroups ? kLossMaxGroups : (int)g);
-}
 // N of the MSE: every element of every draw
 static inline double mse_elems(int n_samples, int batch, long long row_elems) { return (double)n_samples * (double)batch * (double)row_elems; }
 static inline int l1_chunks(int frame_elems) { return (frame_elems / 4 + kL1ChunkQuads - 1) / kL1ChunkQuads; }
-static inline int l1_groups(long long items) { return items > kLossMaxGroups ? kLossMaxGroups : (int)items; }
-
-__device__ __forceinline__ double loss_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// wave partials -> the workgroup's partial, in wave order; returned to thread 0 (red: kLossThreads / 64 doubles of LDS)
-__device__ __forceinline__ double loss_group_sum(double v, double* red) {
-  v = loss_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 0; w < kLossThreads / 64; ++w) t += red[w];
-  }
-  __syncthreads();
-  return t;
-}
+static inline int l1_groups(long long items) { return items > kSumMaxGroups ? kSumMaxGroups : (int)items; }
 
 // ---- MSE ------------------------------------------------------------------------------------------------------------------------
 
@@ -89,7 +62,7 @@ __global__ __launch_bounds__(kLossThreads) void loss_mse_partial_kernel(const fl
       acc += d * d;
     }
   }
-  const double g = loss_group_sum(acc, red);
+  const double g = group_sum<kLossThreads>(acc, red);
   if (threadIdx.x == 0) partials[blockIdx.x] = g;
 }
 
@@ -97,16 +70,14 @@ __global__ __launch_bounds__(kLossThreads) void loss_mse_partial_kernel(const fl
 __global__ __launch_bounds__(kLossThreads) void loss_mse_final_kernel(const double* __restrict__ partials, int n_partials, double n_elems,
                                                                       const float* __restrict__ kl, int batch, double kl_scale,
                                                                       float kl_weight, float* __restrict__ out) {
-  __shared__ double stage[kLossMaxGroups];
+  __shared__ double stage[kSumMaxGroups];
   __shared__ double red[kLossThreads / 64];
-  for (int i = threadIdx.x; i < n_partials; i += kLossThreads) stage[i] = partials[i];
   double k = 0.0;
   if (kl)
     for (int b = threadIdx.x; b < batch; b += kLossThreads) k += (double)kl[b];
-  k = loss_group_sum(k, red);   // (its barriers also publish `stage`)
+  k = group_sum<kLossThreads>(k, red);
+  const double s = ordered_sum<kLossThreads>(partials, n_partials, stage);
   if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int i = 0; i < n_partials; ++i) s += stage[i];
     const double mse = s / n_elems, kl_term = kl ? k * kl_scale : 0.0;
     out[0] = (float)(kl ? mse + (double)kl_weight * kl_term : mse);
     out[1] = (float)mse;
@@ -211,7 +182,9 @@ __global__ __launch_bounds__(kLossThreads) void loss_l1_partial_kernel(L1Args a,
       }
     }
   }
-  const double gp = loss_group_sum(acc_p, red), gd = loss_group_sum(acc_d, red);
+  const double gp = group_sum<kLossThreads>(acc_p, red);
+  __syncthreads();   // red is used again
+  const double gd = group_sum<kLossThreads>(acc_d, red);
   if (threadIdx.x == 0) {
     partials[2 * blockIdx.x] = gp;
     partials[2 * blockIdx.x + 1] = gd;
@@ -220,7 +193,9 @@ __global__ __launch_bounds__(kLossThreads) void loss_l1_partial_kernel(L1Args a,
 
 __global__ __launch_bounds__(kLossThreads) void loss_l1_final_kernel(const double* __restrict__ partials, int n_partials, double n_elems,
                                                                      float* __restrict__ out) {
-  __shared__ double stage[2 * kLossMaxGroups];
+  // reduce.h's ordered sum of two interleaved series at once: thread 0's additions are the whole cost of this kernel, and two
+  // ordered_sum calls would run the two dependent chains one after the other instead of side by side
+  __shared__ double stage[2 * kSumMaxGroups];
   for (int i = threadIdx.x; i < 2 * n_partials; i += kLossThreads) stage[i] = partials[i];
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -271,8 +246,6 @@ __global__ __launch_bounds__(kLossThreads) void loss_l1_backward_kernel(L1Args a
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // 0 or ODEHIP_EINVAL (message set); *quads_out = the quads of pred
 static int check_mse_shape(const char* who, int n_samples, int batch, long long row_elems, long long* quads_out) {
   ODEHIP_REQUIRE(n_samples >= 1 && batch >= 1 && row_elems >= 4, "%s: n_samples (%d), batch (%d) and row_elems (%lld) must be at least 1, 1 and 4",
@@ -318,7 +291,7 @@ using namespace odehip;
 
 extern "C" size_t odehip_loss_mse_workspace_bytes(int n_samples, int batch, long long row_elems) {
   if (n_samples < 1 || batch < 1 || row_elems < 4) return 0;
-  return (size_t)loss_groups((row_elems / 4) * batch * n_samples) * sizeof(double);
+  return (size_t)sum_groups((row_elems / 4) * batch * n_samples) * sizeof(double);
 }
 
 extern "C" int odehip_loss_mse(const float* pred, const float* truth, int n_samples, int batch, long long row_elems, const float* kl,
@@ -329,7 +302,7 @@ extern "C" int odehip_loss_mse(const float* pred, const float* truth, int n_samp
   ODEHIP_REQUIRE(aligned16(pred) && aligned16(truth), "loss_mse: pred and truth must be 16-byte aligned");
   ODEHIP_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)kl & 3) == 0,
                  "loss_mse: misaligned workspace (8 bytes), out or kl (4 bytes)");
-  const int groups = loss_groups(quads);
+  const int groups = sum_groups(quads);
   ODEHIP_REQUIRE(workspace_bytes >= (size_t)groups * sizeof(double), "loss_mse: workspace of %zu bytes, %zu needed", workspace_bytes,
                  (size_t)groups * sizeof(double));
   hipLaunchKernelGGL(loss_mse_partial_kernel, dim3((unsigned)groups), dim3(kLossThreads), 0, (hipStream_t)stream, pred, truth, (unsigned)quads,

@@ -4,54 +4,35 @@
 // host per predicted frame).  Here: one launch over all (b, t) frames and a small one for the means over the batch, no host
 // round trip.
 //
-// SSIM is scikit-image's structural_similarity(x, y, data_range=R, gaussian_weights=True, use_sample_covariance=False) of a 2-D
-// float image, averaged over the channels:
-//   window   sigma = 1.5, truncate = 3.5 -> radius int(3.5 * 1.5 + 0.5) = 5: 11 taps w_k ~ exp(-k^2 / (2 sigma^2)), normalised to
-//            sum 1, applied along rows and then along columns;
-//   moments  ux, uy, uxx, uyy, uxy = filtered x, y, x^2, y^2, x y;  vx = uxx - ux^2, vy = uyy - uy^2, vxy = uxy - ux uy;
-//   S        = (2 ux uy + C1) (2 vxy + C2) / ((ux^2 + uy^2 + C1) (vx + vy + C2)),  C1 = (0.01 R)^2, C2 = (0.03 R)^2;
-//   result   mean of S over rows and columns 5 .. 58 (scikit-image crops (win_size - 1) / 2 = 5 pixels).
-// A window centred on 5 .. 58 reads pixels 0 .. 63 only, so the filter's border mode (scipy's 'reflect') never reaches the result
-// and the outer ring of S is not computed at all.
+// SSIM is the quantity defined in ssim_window.h (scikit-image's Gaussian-window structural_similarity) in float32, the mean of S over
+// rows and columns 5 .. 58, averaged over the channels.
 //
 // Layout.  One 256-thread workgroup per frame (b, t); it walks the frame's channels.  Per channel both 64x64 planes go to LDS
 // with 16-byte loads (2 x 16 KiB; the squared error is summed from the registers on the way).  Wave w owns the output rows
 // 5 + {0..13, 14..27, 28..40, 41..53}[w], lane l the output column 5 + l (54 of 64 lanes; the others repeat column 58 and are
 // left out of the sum).  A lane streams down its column: for every input row it forms the five row-filtered moments from 2 x 11 LDS
-// words (consecutive lanes read consecutive words: conflict-free) and folds them into eleven pending column sums held in
-// registers, acc[k] <- w[k] h + acc[k + 1]; acc[0] is then the finished window of the output row ten rows up.  Nothing but the two
-// input planes lives in LDS (33 KiB per workgroup: several workgroups per CU), at the price of row-filtering the ten halo rows of
-// each wave twice (96 instead of 64 row passes per plane).  Every sum runs in a fixed order with explicit fmas: no atomics, two
-// calls are bitwise equal.  NaN is not laundered: every pixel of a plane lies in some interior window, so one NaN reaches the
+// words (consecutive lanes read consecutive words: conflict-free, 11 ordered fmas per moment) and folds them into ssim_window.h's
+// pending column sums.  Nothing but the two input planes lives in LDS (33 KiB per workgroup: several workgroups per CU), at the
+// price of row-filtering the ten halo rows of each wave twice (96 instead of 64 row passes per plane).  Every sum runs in a fixed
+// order with explicit fmas; the frame's two sums are reduce.h's wave sum and then the four waves pairwise, (0 + 1) + (2 + 3): no
+// atomics, two calls are bitwise equal.  NaN is not laundered: every pixel of a plane lies in some interior window, so one NaN reaches the
 // frame's SSIM and squared error through plain arithmetic (the lane mask is a select on the lane index, never on the value).
 #include <math.h>
 
 #include "odehip_internal.h"
+#include "reduce.h"
+#include "ssim_window.h"
 
 namespace odehip {
 
 constexpr int kFrame = 64;                      // frames are 64 x 64 (the reference's `resolution` in every config)
 constexpr int kPlane = kFrame * kFrame;
-constexpr int kWinRadius = 5;
-constexpr int kWinTaps = 2 * kWinRadius + 1;
-constexpr int kInterior = kFrame - 2 * kWinRadius;   // 54 rows and columns of S enter the mean
-constexpr int kFirstRow = kWinRadius;                // ... starting at row 5
-constexpr int kFirstCol = kWinRadius;                // ... and column 5
+constexpr int kInterior = kFrame - 2 * kSsimRadius;   // 54 rows and columns of S enter the mean, from row and column kSsimCrop on
 
 typedef float f32x4m __attribute__((ext_vector_type(4)));
 
-struct MetricTaps {
-  float w[kWinRadius + 1];   // w[|k|], k = -5 .. 5
-};
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void frame_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ truth, int channels,
-                                                            MetricTaps taps, float c1, float c2, float* __restrict__ sse,
+                                                            SsimTaps<float> taps, float c1, float c2, float* __restrict__ sse,
                                                             float* __restrict__ ssim) {
 #pragma clang fp contract(off)
   // x plane, y plane, then one row of reduction scratch
@@ -61,9 +42,9 @@ __global__ __launch_bounds__(256) void frame_metrics_kernel(const float* __restr
   float* const red = lds + 2 * kPlane;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n_rows = wave < 2 ? 14 : 13;
-  const int row0 = kFirstRow + (wave < 2 ? 14 * wave : 28 + 13 * (wave - 2));   // first output row of this wave
+  const int row0 = kSsimCrop + (wave < 2 ? 14 * wave : 28 + 13 * (wave - 2));   // first output row of this wave
   const bool counted = lane < kInterior;
-  const int col = kFirstCol + (counted ? lane : kInterior - 1);
+  const int col = kSsimCrop + (counted ? lane : kInterior - 1);
   const long long frame = blockIdx.x;
   float sq = 0.0f, ss = 0.0f;
   for (int c = 0; c < channels; ++c) {
@@ -83,19 +64,19 @@ __global__ __launch_bounds__(256) void frame_metrics_kernel(const float* __restr
       }
     }
     __syncthreads();
-    float acc[kWinTaps][5];
+    float acc[kSsimTaps][5];
 #pragma unroll
-    for (int k = 0; k < kWinTaps; ++k)
+    for (int k = 0; k < kSsimTaps; ++k)
 #pragma unroll
       for (int m = 0; m < 5; ++m) acc[k][m] = 0.0f;
-    for (int i = 0; i < n_rows + 2 * kWinRadius; ++i) {
-      const int row = row0 - kWinRadius + i;
-      const float* const xr = sx + row * kFrame + col - kWinRadius;
-      const float* const yr = sy + row * kFrame + col - kWinRadius;
+    for (int i = 0; i < n_rows + 2 * kSsimRadius; ++i) {
+      const int row = row0 - kSsimRadius + i;
+      const float* const xr = sx + row * kFrame + col - kSsimRadius;
+      const float* const yr = sy + row * kFrame + col - kSsimRadius;
       float h[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-      for (int d = 0; d < kWinTaps; ++d) {
-        const float w = taps.w[d < kWinRadius ? kWinRadius - d : d - kWinRadius];
+      for (int d = 0; d < kSsimTaps; ++d) {
+        const float w = taps.w[d < kSsimRadius ? kSsimRadius - d : d - kSsimRadius];
         const float xv = xr[d], yv = yr[d];
         h[0] = fmaf(w, xv, h[0]);
         h[1] = fmaf(w, yv, h[1]);
@@ -103,21 +84,9 @@ __global__ __launch_bounds__(256) void frame_metrics_kernel(const float* __restr
         h[3] = fmaf(w, yv * yv, h[3]);
         h[4] = fmaf(w, xv * yv, h[4]);
       }
-      // acc[k]: the column sum of output row (row - 10 + k) so far; this input row is its tap 10 - k
-#pragma unroll
-      for (int k = 0; k < kWinTaps; ++k) {
-        const float w = taps.w[k < kWinRadius ? kWinRadius - k : k - kWinRadius];
-#pragma unroll
-        for (int m = 0; m < 5; ++m) acc[k][m] = fmaf(w, h[m], k + 1 < kWinTaps ? acc[k + 1][m] : 0.0f);
-      }
-      if (i >= 2 * kWinRadius) {   // acc[0] is complete
-        const float ux = acc[0][0], uy = acc[0][1], uxx = acc[0][2], uyy = acc[0][3], uxy = acc[0][4];
-        const float vx = uxx - ux * ux;
-        const float vy = uyy - uy * uy;
-        const float vxy = uxy - ux * uy;
-        const float a1 = 2.0f * ux * uy + c1, a2 = 2.0f * vxy + c2;
-        const float b1 = ux * ux + uy * uy + c1, b2 = vx + vy + c2;
-        const float s = (a1 * a2) / (b1 * b2);
+      ssim_fold_row(acc, h, taps);
+      if (i >= 2 * kSsimRadius) {   // acc[0] is complete
+        const float s = ssim_value(acc[0], c1, c2);
         ss += counted ? s : 0.0f;
       }
     }
@@ -164,20 +133,9 @@ extern "C" int odehip_frame_metrics(const float* pred, const float* truth, int b
   ODEHIP_REQUIRE(data_range > 0.0f && isfinite(data_range), "frame_metrics: data_range must be positive and finite (got %g)", (double)data_range);
   ODEHIP_REQUIRE(height == kFrame && width == kFrame && (channels == 1 || channels == 3),
                  "frame_metrics: unsupported frame shape (channels %d, %d x %d): 1 or 3 channels of 64 x 64 only", channels, height, width);
-  // scipy.ndimage's _gaussian_kernel1d, evaluated in fp64 and rounded once
-  const double sigma = 1.5;
-  double phi[kWinRadius + 1], sum = 0.0;
-  for (int k = 0; k <= kWinRadius; ++k) {
-    phi[k] = exp(-0.5 / (sigma * sigma) * (double)(k * k));
-    sum += k ? 2.0 * phi[k] : phi[k];
-  }
-  MetricTaps taps;
-  for (int k = 0; k <= kWinRadius; ++k) taps.w[k] = (float)(phi[k] / sum);
-  const double k1 = 0.01, k2 = 0.03, range = (double)data_range;
-  const float c1 = (float)((k1 * range) * (k1 * range));
-  const float c2 = (float)((k2 * range) * (k2 * range));
-  hipLaunchKernelGGL(frame_metrics_kernel, dim3((unsigned)(batch * n_frames)), dim3(256), 0, (hipStream_t)stream, pred, truth, channels, taps, c1, c2,
-                     sse, ssim);
+  const double range = (double)data_range;
+  hipLaunchKernelGGL(frame_metrics_kernel, dim3((unsigned)(batch * n_frames)), dim3(256), 0, (hipStream_t)stream, pred, truth, channels,
+                     ssim_taps<float>(), ssim_constant<float>(0.01, range), ssim_constant<float>(0.03, range), sse, ssim);
   ODEHIP_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(frame_metrics_mean_kernel, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)sse,
                      (const float*)ssim, batch, n_frames, (double)batch * channels * kPlane, range * range, mse, psnr, ssim_t);

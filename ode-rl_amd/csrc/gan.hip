@@ -9,22 +9,21 @@
 // i = j .. t-1 (one copy per row; interpolation: row j alone), added in ascending i in fp32.  input_real gets no gradient.
 //
 // LSGAN.  out = mean (pred - target)^2: every difference, square and sum in float64 from the fp32 input, rounded to fp32 once.
-// Sum order: a thread adds its elements in ascending order, a wave folds its 64 lanes by xor-shuffles, thread 0 adds the wave
-// partials in wave order, the second launch adds the workgroup partials in workgroup order -- a function of n alone, so two calls
-// are bitwise equal.  Forward: partials, then a one-workgroup final (as frame_loss.hip); backward: one launch,
+// Sum order: a thread adds its elements in ascending order, then reduce.h's workgroup sum, and the second launch is reduce.h's
+// ordered sum of the workgroup partials -- a function of n alone, so two calls are bitwise equal.  Forward: partials, then a
+// one-workgroup final (as frame_loss.hip); backward: one launch,
 // grad = fl32(grad_out 2 (pred - target) / n) with the quotient taken in float64.
 #include <math.h>
 #include <stdint.h>
 
 #include "odehip_internal.h"
+#include "reduce.h"
 
 namespace odehip {
 
 typedef float f32x4g __attribute__((ext_vector_type(4)));
 
 constexpr int kGanThreads = 256;
-constexpr int kGanMaxGroups = 1024;       // workgroup partials of an LSGAN forward at most (the final launch stages them in LDS)
-constexpr int kGanElemsPerGroup = 2048;   // below kGanMaxGroups groups a workgroup walks this many elements: 8 per thread
 constexpr long long kGanMaxBlocks = 8192;
 
 struct SeqArgs {
@@ -87,17 +86,6 @@ __global__ __launch_bounds__(kGanThreads) void seq_assemble_backward_kernel(cons
 
 // ---- LSGAN ----------------------------------------------------------------------------------------------------------------------
 
-static inline int lsgan_groups(long long n) {
-  const long long g = (n + kGanElemsPerGroup - 1) / kGanElemsPerGroup;
-  return g < 1 ? 1 : (g > kGanMaxGroups ? kGanMaxGroups : (int)g);
-}
-
-__device__ __forceinline__ double gan_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(kGanThreads) void lsgan_partial_kernel(const float* __restrict__ pred, long long n, double target,
                                                                     double* __restrict__ partials) {
   __shared__ double red[kGanThreads / 64];
@@ -107,27 +95,15 @@ __global__ __launch_bounds__(kGanThreads) void lsgan_partial_kernel(const float*
     const double d = (double)pred[i] - target;
     acc += d * d;
   }
-  acc = gan_wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kGanThreads / 64; ++w) t += red[w];
-    partials[blockIdx.x] = t;
-  }
+  const double t = group_sum<kGanThreads>(acc, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 
 __global__ __launch_bounds__(kGanThreads) void lsgan_final_kernel(const double* __restrict__ partials, int n_partials, double n_elems,
                                                                   float* __restrict__ out) {
-  __shared__ double stage[kGanMaxGroups];
-  for (int i = threadIdx.x; i < n_partials; i += kGanThreads) stage[i] = partials[i];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int i = 0; i < n_partials; ++i) s += stage[i];
-    out[0] = (float)(s / n_elems);
-  }
+  __shared__ double stage[kSumMaxGroups];
+  const double s = ordered_sum<kGanThreads>(partials, n_partials, stage);
+  if (threadIdx.x == 0) out[0] = (float)(s / n_elems);
 }
 
 __global__ __launch_bounds__(kGanThreads) void lsgan_backward_kernel(const float* __restrict__ grad_out, const float* __restrict__ pred,
@@ -139,7 +115,6 @@ __global__ __launch_bounds__(kGanThreads) void lsgan_backward_kernel(const float
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 
-static inline bool gan_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static inline unsigned gan_blocks(long long total) {
   const long long g = (total + kGanThreads - 1) / kGanThreads;
   return (unsigned)(g > kGanMaxBlocks ? kGanMaxBlocks : g);
@@ -168,7 +143,7 @@ extern "C" int odehip_gan_seq_assemble(const float* input_real, const float* fra
   if (int rc = fill_seq_args("gan_seq_assemble", &a, batch, t_in, t, frame_elems, interp)) return rc;
   ODEHIP_REQUIRE((((uintptr_t)input_real | (uintptr_t)frames | (uintptr_t)out) & 3) == 0, "gan_seq_assemble: misaligned pointer (4 bytes)");
   const long long items = (long long)t * batch * a.L;
-  if (frame_elems % 4 == 0 && gan_aligned16(input_real) && gan_aligned16(frames) && gan_aligned16(out)) {
+  if (frame_elems % 4 == 0 && aligned16(input_real) && aligned16(frames) && aligned16(out)) {
     a.fe = frame_elems / 4;
     const long long total = items * a.fe;
     hipLaunchKernelGGL(seq_assemble_kernel<f32x4g>, dim3(gan_blocks(total)), dim3(kGanThreads), 0, (hipStream_t)stream,
@@ -189,7 +164,7 @@ extern "C" int odehip_gan_seq_assemble_backward(const float* grad_out, int batch
   if (int rc = fill_seq_args("gan_seq_assemble_backward", &a, batch, t_in, t, frame_elems, interp)) return rc;
   ODEHIP_REQUIRE((((uintptr_t)grad_out | (uintptr_t)grad_frames) & 3) == 0, "gan_seq_assemble_backward: misaligned pointer (4 bytes)");
   const long long items = (long long)batch * t;
-  if (frame_elems % 4 == 0 && gan_aligned16(grad_out) && gan_aligned16(grad_frames)) {
+  if (frame_elems % 4 == 0 && aligned16(grad_out) && aligned16(grad_frames)) {
     a.fe = frame_elems / 4;
     const long long total = items * a.fe;
     hipLaunchKernelGGL(seq_assemble_backward_kernel<f32x4g>, dim3(gan_blocks(total)), dim3(kGanThreads), 0, (hipStream_t)stream,
@@ -205,7 +180,7 @@ extern "C" int odehip_gan_seq_assemble_backward(const float* grad_out, int batch
 
 extern "C" size_t odehip_loss_lsgan_workspace_bytes(long long n) {
   if (n < 1) return 0;
-  return (size_t)lsgan_groups(n) * sizeof(double);
+  return (size_t)sum_groups(n) * sizeof(double);
 }
 
 extern "C" int odehip_loss_lsgan(const float* pred, long long n, float target, float* out, void* workspace, void* stream) {
@@ -213,7 +188,7 @@ extern "C" int odehip_loss_lsgan(const float* pred, long long n, float target, f
   ODEHIP_REQUIRE(n >= 1, "loss_lsgan: n (%lld) must be at least 1", n);
   ODEHIP_REQUIRE((((uintptr_t)pred | (uintptr_t)out) & 3) == 0 && ((uintptr_t)workspace & 7) == 0,
                  "loss_lsgan: misaligned pred or out (4 bytes) or workspace (8 bytes)");
-  const int groups = lsgan_groups(n);
+  const int groups = sum_groups(n);
   hipLaunchKernelGGL(lsgan_partial_kernel, dim3((unsigned)groups), dim3(kGanThreads), 0, (hipStream_t)stream, pred, n, (double)target,
                      (double*)workspace);
   ODEHIP_CHECK_HIP(hipGetLastError());

@@ -11,13 +11,14 @@
 // Arithmetic.  The mean is the float64 sum of the plane divided by hw (a constant plane has exactly that constant as its mean, hence
 // exactly zero output); the values are centred in float64 against it and rounded to fp32 once, so a large common offset costs no
 // accuracy; the variance is the float64 sum of the squared centred values -- never E[x^2] - mean^2.  Sum order: a lane adds its
-// values in slot order, a wave folds its 64 lanes by xor-shuffles, and (large planes) thread 0 adds the wave partials in wave order:
-// a function of hw and of whether the tensors are 16-byte aligned, so two calls are bitwise equal.  The comparisons `xhat > 0` are false for NaN, as in torch's
+// values in slot order, then reduce.h's wave sum or (large planes) reduce.h's workgroup sum: a function of hw and of whether the
+// tensors are 16-byte aligned, so two calls are bitwise equal.  The comparisons `xhat > 0` are false for NaN, as in torch's
 // leaky_relu and leaky_relu_backward.
 #include <math.h>
 #include <stdint.h>
 
 #include "odehip_internal.h"
+#include "reduce.h"
 
 namespace odehip {
 
@@ -26,12 +27,6 @@ typedef float f32x4n __attribute__((ext_vector_type(4)));
 constexpr int kNormThreads = 256;
 constexpr int kNormWaves = kNormThreads / 64;
 constexpr int kNormWaveMax = 1024;   // largest plane one wavefront holds in registers
-
-__device__ __forceinline__ double norm_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.0f ? v : slope * v; }
 
@@ -90,14 +85,14 @@ __global__ __launch_bounds__(kNormThreads) void instnorm_lrelu_fwd_wave_kernel(c
   double s = 0.0;
 #pragma unroll
   for (int k = 0; k < NPL; ++k) s += (double)v[k];
-  const double m = norm_wave_sum(s) / (double)hw;
+  const double m = wave_sum(s) / (double)hw;
   double ss = 0.0;
 #pragma unroll
   for (int k = 0; k < NPL; ++k) {
     v[k] = ok[k] ? (float)((double)v[k] - m) : 0.0f;
     ss += (double)v[k] * (double)v[k];
   }
-  const float r = (float)(1.0 / sqrt(norm_wave_sum(ss) / (double)hw + (double)eps));
+  const float r = (float)(1.0 / sqrt(wave_sum(ss) / (double)hw + (double)eps));
 #pragma unroll
   for (int k = 0; k < NPL; ++k) v[k] = lrelu(v[k] * r, slope);
   plane_store<NPL, VEC>(y + base, hw, lane, v);
@@ -124,30 +119,13 @@ __global__ __launch_bounds__(kNormThreads) void instnorm_lrelu_bwd_wave_kernel(c
     s1 += (double)g[k];
     s2 += (double)g[k] * (double)xh[k];
   }
-  const float m1 = (float)(norm_wave_sum(s1) / (double)hw), m2 = (float)(norm_wave_sum(s2) / (double)hw);
+  const float m1 = (float)(wave_sum(s1) / (double)hw), m2 = (float)(wave_sum(s2) / (double)hw);
 #pragma unroll
   for (int k = 0; k < NPL; ++k) g[k] = r * (g[k] - m1 - xh[k] * m2);
   plane_store<NPL, VEC>(gx + base, hw, lane, g);
 }
 
 // ---- one workgroup per plane (hw > 1024) ----------------------------------------------------------------------------------------
-
-// the workgroup's sum, in wave order, to every thread (red: kNormWaves + 1 doubles of LDS)
-__device__ __forceinline__ double norm_group_sum(double v, double* red) {
-  v = norm_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kNormWaves; ++w) t += red[w];
-    red[kNormWaves] = t;
-  }
-  __syncthreads();
-  const double t = red[kNormWaves];
-  __syncthreads();
-  return t;
-}
 
 __global__ __launch_bounds__(kNormThreads) void instnorm_lrelu_fwd_group_kernel(const float* __restrict__ x, int hw, float eps, float slope,
                                                                                 float* __restrict__ y, float* __restrict__ mean,
@@ -157,13 +135,13 @@ __global__ __launch_bounds__(kNormThreads) void instnorm_lrelu_fwd_group_kernel(
   const float* const p = x + base;
   double s = 0.0;
   for (int e = threadIdx.x; e < hw; e += kNormThreads) s += (double)p[e];
-  const double m = norm_group_sum(s, red) / (double)hw;
+  const double m = group_sum_all<kNormThreads>(s, red) / (double)hw;
   double ss = 0.0;
   for (int e = threadIdx.x; e < hw; e += kNormThreads) {
     const float d = (float)((double)p[e] - m);
     ss += (double)d * (double)d;
   }
-  const float r = (float)(1.0 / sqrt(norm_group_sum(ss, red) / (double)hw + (double)eps));
+  const float r = (float)(1.0 / sqrt(group_sum_all<kNormThreads>(ss, red) / (double)hw + (double)eps));
   for (int e = threadIdx.x; e < hw; e += kNormThreads) y[base + e] = lrelu((float)((double)p[e] - m) * r, slope);
   if (threadIdx.x == 0) mean[blockIdx.x] = (float)m, rstd[blockIdx.x] = r;
 }
@@ -181,7 +159,7 @@ __global__ __launch_bounds__(kNormThreads) void instnorm_lrelu_bwd_group_kernel(
     s1 += (double)gp;
     s2 += (double)gp * (double)xh;
   }
-  const float m1 = (float)(norm_group_sum(s1, red) / (double)hw), m2 = (float)(norm_group_sum(s2, red) / (double)hw);
+  const float m1 = (float)(group_sum_all<kNormThreads>(s1, red) / (double)hw), m2 = (float)(group_sum_all<kNormThreads>(s2, red) / (double)hw);
   for (int e = threadIdx.x; e < hw; e += kNormThreads) {
     const float xh = (x[base + e] - m) * r, g = gy[base + e];
     gx[base + e] = r * ((xh > 0.0f ? g : slope * g) - m1 - xh * m2);
@@ -189,8 +167,6 @@ __global__ __launch_bounds__(kNormThreads) void instnorm_lrelu_bwd_group_kernel(
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-
-static inline bool norm_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // values per lane of the one-wave kernels for a plane of hw <= kNormWaveMax elements
 static inline int norm_slots(int hw, bool vec) {
@@ -238,7 +214,7 @@ extern "C" int odehip_instnorm_lrelu_forward(const float* x, int planes, int hw,
     hipLaunchKernelGGL(instnorm_lrelu_fwd_group_kernel, dim3((unsigned)planes), dim3(kNormThreads), 0, (hipStream_t)stream, x, hw, eps, slope, y,
                        mean, rstd);
   } else {
-    const bool vec = hw % 4 == 0 && hw > 64 && norm_aligned16(x) && norm_aligned16(y);
+    const bool vec = hw % 4 == 0 && hw > 64 && aligned16(x) && aligned16(y);
     const int npl = norm_slots(hw, vec);
     const dim3 grid((unsigned)((planes + kNormWaves - 1) / kNormWaves));
     NORM_DISPATCH(instnorm_lrelu_fwd_wave_kernel, vec, npl, x, planes, hw, eps, slope, y, mean, rstd)
@@ -257,7 +233,7 @@ extern "C" int odehip_instnorm_lrelu_backward(const float* grad_y, const float* 
     hipLaunchKernelGGL(instnorm_lrelu_bwd_group_kernel, dim3((unsigned)planes), dim3(kNormThreads), 0, (hipStream_t)stream, grad_y, x, mean, rstd,
                        hw, slope, grad_x);
   } else {
-    const bool vec = hw % 4 == 0 && hw > 64 && norm_aligned16(grad_y) && norm_aligned16(x) && norm_aligned16(grad_x);
+    const bool vec = hw % 4 == 0 && hw > 64 && aligned16(grad_y) && aligned16(x) && aligned16(grad_x);
     const int npl = norm_slots(hw, vec);
     const dim3 grid((unsigned)((planes + kNormWaves - 1) / kNormWaves));
     NORM_DISPATCH(instnorm_lrelu_bwd_wave_kernel, vec, npl, grad_y, x, mean, rstd, planes, hw, slope, grad_x)

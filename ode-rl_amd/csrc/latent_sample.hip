@@ -15,8 +15,8 @@
 //
 // Layout.  Forward: grid (B, K), 1024 threads; workgroup (b, k) walks the C * 64 quads of sample b with 16-byte loads and stores.
 // The k = 0 workgroup of every b also forms kl[b]: per element in float64 (the whole term, log included -- 16 elements per thread at
-// C = 64, nothing next to the Philox rounds), summed per thread in quad order, across the wave by xor-shuffles and across the 16
-// waves in index order; rounded to fp32 once.  No atomics: two calls are bitwise equal, and kl[b] depends on nothing but sample b.
+// C = 64, nothing next to the Philox rounds), summed per thread in quad order, then reduce.h's workgroup sum (16 waves); rounded
+// to fp32 once.  No atomics: two calls are bitwise equal, and kl[b] depends on nothing but sample b.
 // Backward: one thread per quad of (B, C, 16, 16); it walks k = 0 .. K-1 in order with explicit fmas (contraction off), so the
 // regenerated-noise call and the eps_in call run the same arithmetic.  No clamp anywhere: std = 0 gives kl = +inf and z0 = mean, a
 // NaN stays a NaN in its own sample.
@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "odehip_internal.h"
+#include "reduce.h"
 
 namespace odehip {
 
@@ -72,12 +73,6 @@ __device__ __forceinline__ f32x4s noise_quad(unsigned long long q, NoiseKey key)
   return e;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // grid (batch, n_samples); eps_in / eps_out / kl may be NULL
 __global__ __launch_bounds__(kSampleThreads) void latent_sample_kernel(const float* __restrict__ mean, const float* __restrict__ std_, int batch,
                                                                        int channels, NoiseKey key, int batch_offset, int global_batch,
@@ -110,15 +105,8 @@ __global__ __launch_bounds__(kSampleThreads) void latent_sample_kernel(const flo
     }
   }
   if (!with_kl) return;   // uniform over the workgroup
-  acc = wave_sum_f64(acc);
-  if ((tid & 63) == 0) red[tid >> 6] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kSampleThreads / 64; ++w) t += red[w];
-    kl[b] = (float)t;
-  }
+  const double t = group_sum<kSampleThreads>(acc, red);
+  if (tid == 0) kl[b] = (float)t;
 }
 
 // one thread per quad of (batch, channels, 16, 16); grad_kl / eps_in may be NULL

@@ -12,8 +12,8 @@
 // A PNG round trip is lossless, so these bytes are the file contents.
 //   sse   = sum over the 3 S S RGB bytes of (byte_pred - byte_truth)^2: an exact integer (at most 3 * 128 * 128 * 255^2 = 3.2e9:
 //           32-bit partials per wave, summed in 64 bits);  mse = sse / (255^2 * 3 S S) in float64.
-//   ssim  = the quantity defined in the header of frame_metrics.hip (sigma 1.5, 11 taps, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, mean
-//           over rows and columns 5 .. S-6) on the two luma planes, every moment in float64: the bytes, their squares and products are
+//   ssim  = the quantity defined in ssim_window.h (sigma 1.5, 11 taps, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, mean over rows and
+//           columns 5 .. S-6) on the two luma planes, every moment in float64: the bytes, their squares and products are
 //           exact integers, so only the weighted sums round.  (float32 moments at data_range 255 lose the variance uxx - ux^2 to
 //           cancellation.)
 //
@@ -23,29 +23,23 @@
 // read.  Pass 2: the interior columns go to lanes (S = 128: two groups of 64 lanes, 118 columns), the interior rows to the remaining
 // waves in strips (S = 32, 64: four strips; S = 128: two).  A lane streams down its column: per input row the five row-filtered
 // moments -- mirrored taps are paired in integers first (x[-k] + x[k], x[-k]^2 + x[k]^2, ...: exact), so a row costs 6 instead of 11
-// fmas per moment -- folded into eleven pending column sums in registers, acc[k] <- w[k] h + acc[k + 1]; acc[0] is then the finished
-// window of the output row ten rows up.  A strip row-filters its ten halo rows again.  Four consecutive lanes read the four bytes
-// of one LDS word (a broadcast, no bank conflict).  Every sum runs in a fixed order: no atomics, two calls are bitwise equal.
+// fmas per moment -- folded into ssim_window.h's pending column sums.  A strip row-filters its ten halo rows again.  Four
+// consecutive lanes read the four bytes of one LDS word (a broadcast, no bank conflict).  Every sum runs in a fixed order; the
+// image's sums are reduce.h's wave sum and then the four waves pairwise, (0 + 1) + (2 + 3): no atomics, two calls are bitwise equal.
 //
 // NaN is not laundered: a conversion to a byte would hide it, so it is detected by a comparison on the float (x != x) in either
 // frame; the image's ssim and mse are then NaN, its sse -1, the NaN pixel's byte 0; no other image is touched.
 #include <math.h>
 
 #include "odehip_internal.h"
+#include "reduce.h"
+#include "ssim_window.h"
 
 namespace odehip {
 
-constexpr int kPngRadius = 5;
-constexpr int kPngTaps = 2 * kPngRadius + 1;
-constexpr int kPngCropRow = kPngRadius;    // S enters the mean from this row on ... (scikit-image crops (win_size - 1) / 2 = 5)
-constexpr int kPngCropCol = kPngRadius;    // ... and from this column on
 constexpr int kPngScratch = 256;           // bytes of reduction scratch in FRONT of the planes (the row above the first plane stays inside the allocation)
 
 typedef float png_f32x4 __attribute__((ext_vector_type(4)));
-
-struct PngTaps {
-  double w[kPngRadius + 1];   // w[|k|], k = -5 .. 5
-};
 
 // utils.denorm and torchvision's save_image on one value; a NaN gives byte 0 (the caller flags it)
 __device__ __forceinline__ unsigned png_quantise(float x, bool denorm) {
@@ -64,18 +58,6 @@ __device__ __forceinline__ unsigned png_quantise(float x, bool denorm) {
 // PIL's convert('L') (ImagingConvert rgb2l): ITU-R 601-2 in 16-bit fixed point, rounded
 __device__ __forceinline__ unsigned png_luma(unsigned r, unsigned g, unsigned b) {
   return (19595u * r + 38470u * g + 7471u * b + 0x8000u) >> 16;
-}
-
-__device__ __forceinline__ double png_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ unsigned png_wave_sum(unsigned v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += (unsigned)__shfl_xor((int)v, off, 64);
-  return v;
 }
 
 // four pixels of one frame: C planes -> RGB bytes rgb[c][e]; returns whether one of the values was NaN
@@ -120,12 +102,12 @@ __device__ __forceinline__ unsigned png_emit(const unsigned (&rgb)[3][4], unsign
 
 template <int S, int C>
 __global__ __launch_bounds__(256) void png_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ truth, int denorm,
-                                                          PngTaps taps, double c1, double c2, long long* __restrict__ sse,
+                                                          SsimTaps<double> taps, double c1, double c2, long long* __restrict__ sse,
                                                           double* __restrict__ mse, double* __restrict__ ssim,
                                                           unsigned char* __restrict__ pred_bytes, unsigned char* __restrict__ truth_bytes) {
 #pragma clang fp contract(off)
   constexpr int kPix = S * S;
-  constexpr int kInterior = S - 2 * kPngRadius;             // rows and columns of S that enter the mean
+  constexpr int kInterior = S - 2 * kSsimRadius;            // rows and columns of S that enter the mean
   constexpr int kColGroups = (kInterior + 63) / 64;         // 64 interior columns per wave
   constexpr int kStrips = 4 / kColGroups;                   // the other waves split the interior rows
   static_assert(kColGroups * kStrips == 4 && kPix % 1024 == 0, "four waves, whole quads per thread");
@@ -162,7 +144,7 @@ __global__ __launch_bounds__(256) void png_metrics_kernel(const float* __restric
     ((unsigned*)sx)[q] = png_emit(a, bx ? bx + 3 * q : nullptr);
     ((unsigned*)sy)[q] = png_emit(b, by ? by + 3 * q : nullptr);
   }
-  sq = png_wave_sum(sq);                                     // at most 3 * 128 * 128 * 255^2 / 4 per wave: fits 32 bits
+  sq = wave_sum(sq);                                         // at most 3 * 128 * 128 * 255^2 / 4 per wave: fits 32 bits
   const bool wave_bad = __any(bad);
   if (lane == 0) {
     red_sq[wave] = sq;
@@ -182,57 +164,52 @@ __global__ __launch_bounds__(256) void png_metrics_kernel(const float* __restric
   const int group = wave % kColGroups, strip = wave / kColGroups;
   const int n_rows = kInterior / kStrips + (strip < kInterior % kStrips ? 1 : 0);
   const int first = strip * (kInterior / kStrips) + (strip < kInterior % kStrips ? strip : kInterior % kStrips);
-  const int row0 = kPngCropRow + first;                      // first output row of this wave
+  const int row0 = kSsimCrop + first;                        // first output row of this wave
   const int j = 64 * group + lane;
   const bool counted = j < kInterior;
-  const int col = kPngCropCol + (counted ? j : kInterior - 1);
-  double acc[kPngTaps][5];
+  const int col = kSsimCrop + (counted ? j : kInterior - 1);
+  double acc[kSsimTaps][5];
 #pragma unroll
-  for (int k = 0; k < kPngTaps; ++k)
+  for (int k = 0; k < kSsimTaps; ++k)
 #pragma unroll
     for (int m = 0; m < 5; ++m) acc[k][m] = 0.0;
   double ss = 0.0;
-  for (int i = 0; i < n_rows + 2 * kPngRadius; ++i) {
-    const int row = row0 - kPngRadius + i;
-    const unsigned char* const xr = sx + row * S + col - kPngRadius;
-    const unsigned char* const yr = sy + row * S + col - kPngRadius;
-    unsigned xv[kPngTaps], yv[kPngTaps];
+  for (int i = 0; i < n_rows + 2 * kSsimRadius; ++i) {
+    const int row = row0 - kSsimRadius + i;
+    const unsigned char* const xr = sx + row * S + col - kSsimRadius;
+    const unsigned char* const yr = sy + row * S + col - kSsimRadius;
+    unsigned xv[kSsimTaps], yv[kSsimTaps];
 #pragma unroll
-    for (int d = 0; d < kPngTaps; ++d) {
+    for (int d = 0; d < kSsimTaps; ++d) {
       xv[d] = xr[d];
       yv[d] = yr[d];
     }
-    const unsigned xc = xv[kPngRadius], yc = yv[kPngRadius];
+    const unsigned xc = xv[kSsimRadius], yc = yv[kSsimRadius];
     double h[5] = {taps.w[0] * (double)xc, taps.w[0] * (double)yc, taps.w[0] * (double)(xc * xc), taps.w[0] * (double)(yc * yc),
                    taps.w[0] * (double)(xc * yc)};
 #pragma unroll
-    for (int k = kPngRadius; k >= 1; --k) {                  // the two taps at distance k share a weight: paired in integers, exactly
-      const unsigned xa = xv[kPngRadius - k], xb = xv[kPngRadius + k], ya = yv[kPngRadius - k], yb = yv[kPngRadius + k];
+    for (int k = kSsimRadius; k >= 1; --k) {                 // the two taps at distance k share a weight: paired in integers, exactly
+      const unsigned xa = xv[kSsimRadius - k], xb = xv[kSsimRadius + k], ya = yv[kSsimRadius - k], yb = yv[kSsimRadius + k];
       h[0] = fma(taps.w[k], (double)(xa + xb), h[0]);
       h[1] = fma(taps.w[k], (double)(ya + yb), h[1]);
       h[2] = fma(taps.w[k], (double)(xa * xa + xb * xb), h[2]);
       h[3] = fma(taps.w[k], (double)(ya * ya + yb * yb), h[3]);
       h[4] = fma(taps.w[k], (double)(xa * ya + xb * yb), h[4]);
     }
-    // acc[k]: the column sum of output row (row - 10 + k) so far; this input row is its tap 10 - k
+    // ssim_window.h's ssim_fold_row, written out: through the helper the compiler lays this float64 loop out differently, which
+    // costs 1 - 2 % at 64 images of 3 channels.  acc[k]: the column sum of output row (row - 10 + k) so far; this input row is its tap 10 - k
 #pragma unroll
-    for (int k = 0; k < kPngTaps; ++k) {
-      const double w = taps.w[k < kPngRadius ? kPngRadius - k : k - kPngRadius];
+    for (int k = 0; k < kSsimTaps; ++k) {
+      const double w = taps.w[k < kSsimRadius ? kSsimRadius - k : k - kSsimRadius];
 #pragma unroll
-      for (int m = 0; m < 5; ++m) acc[k][m] = fma(w, h[m], k + 1 < kPngTaps ? acc[k + 1][m] : 0.0);
+      for (int m = 0; m < 5; ++m) acc[k][m] = fma(w, h[m], k + 1 < kSsimTaps ? acc[k + 1][m] : 0.0);
     }
-    if (i >= 2 * kPngRadius) {   // acc[0] is complete
-      const double ux = acc[0][0], uy = acc[0][1], uxx = acc[0][2], uyy = acc[0][3], uxy = acc[0][4];
-      const double vx = uxx - ux * ux;
-      const double vy = uyy - uy * uy;
-      const double vxy = uxy - ux * uy;
-      const double a1 = 2.0 * ux * uy + c1, a2 = 2.0 * vxy + c2;
-      const double b1 = ux * ux + uy * uy + c1, b2 = vx + vy + c2;
-      const double s = (a1 * a2) / (b1 * b2);
+    if (i >= 2 * kSsimRadius) {   // acc[0] is complete
+      const double s = ssim_value(acc[0], c1, c2);
       ss += counted ? s : 0.0;
     }
   }
-  ss = png_wave_sum(ss);
+  ss = wave_sum(ss);
   if (lane == 0) red_ss[wave] = ss;
   __syncthreads();
   if (tid == 0) {
@@ -268,7 +245,7 @@ __global__ __launch_bounds__(64) void png_metrics_accumulate_kernel(const double
 }
 
 template <int S>
-static int png_launch(const float* pred, const float* truth, int images, int channels, int denorm, const PngTaps& taps, double c1, double c2,
+static int png_launch(const float* pred, const float* truth, int images, int channels, int denorm, const SsimTaps<double>& taps, double c1, double c2,
                       long long* sse, double* mse, double* ssim, unsigned char* pred_bytes, unsigned char* truth_bytes, hipStream_t stream) {
   if (channels == 1)
     hipLaunchKernelGGL((png_metrics_kernel<S, 1>), dim3((unsigned)images), dim3(256), 0, stream, pred, truth, denorm, taps, c1, c2, sse, mse, ssim,
@@ -297,16 +274,8 @@ extern "C" int odehip_png_metrics(const float* pred, const float* truth, int bat
   ODEHIP_REQUIRE(((uintptr_t)pred | (uintptr_t)truth) % 16 == 0, "png_metrics: pred and truth must be 16-byte aligned");
   ODEHIP_REQUIRE(((uintptr_t)sse | (uintptr_t)mse | (uintptr_t)ssim | (uintptr_t)accum) % 8 == 0 && ((uintptr_t)pred_bytes | (uintptr_t)truth_bytes) % 4 == 0,
                  "png_metrics: sse, mse, ssim and accum must be 8-byte aligned, the byte outputs 4-byte aligned");
-  // scipy.ndimage's _gaussian_kernel1d in float64
-  const double window_sigma = 1.5;
-  double phi[kPngRadius + 1], sum = 0.0;
-  for (int k = 0; k <= kPngRadius; ++k) {
-    phi[k] = exp(-0.5 / (window_sigma * window_sigma) * (double)(k * k));
-    sum += k ? 2.0 * phi[k] : phi[k];
-  }
-  PngTaps taps;
-  for (int k = 0; k <= kPngRadius; ++k) taps.w[k] = phi[k] / sum;
-  const double c1 = (0.01 * 255.0) * (0.01 * 255.0), c2 = (0.03 * 255.0) * (0.03 * 255.0);
+  const SsimTaps<double> taps = ssim_taps<double>();
+  const double c1 = ssim_constant<double>(0.01, 255.0), c2 = ssim_constant<double>(0.03, 255.0);
   const int images = batch * n_frames;
   int rc;
   if (size == 32)

@@ -1,5 +1,5 @@
 """`FusedAdam`: torch.optim.Adam semantics (the reference's optimizer, train_test.py:24) with ONE HIP launch per step for all
-parameter tensors (csrc/adam.hip) instead of torch's per-op foreach launches.  State layout and `state_dict()` are those of
+parameter tensors (csrc/optim_step.hip) instead of torch's per-op foreach launches.  State layout and `state_dict()` are those of
 torch.optim.Adam (`step`, `exp_avg`, `exp_avg_sq`), so the reference's pickled optimizer state (helpers/utils.py:218-222)
 loads into it and vice versa.
 
@@ -7,7 +7,7 @@ Gradient clipping by global norm (the reference's `opt.clip`, train_test.py:187-
 torch.nn.utils.clip_grad_norm_, and `FusedAdam(max_grad_norm=...)` folds the scaling into the optimizer launch.  Neither reads
 anything back to the host.
 
-`FusedAdamax` is the same for torch.optim.Adamax (csrc/adamax.hip), the optimizer of Vid-ODE's recipe (Vid-ODE/main.py:187), and
+`FusedAdamax` is the same for torch.optim.Adamax (csrc/optim_step.hip), the optimizer of Vid-ODE's recipe (Vid-ODE/main.py:187), and
 `decay_learning_rate` that recipe's per-epoch decay (main.py:214)."""
 import ctypes
 
@@ -37,7 +37,7 @@ def _tables(*lists):
 
 
 def _grad_norm(grads, max_norm):
-    """(total_norm, coef, clipped_norm) as one fresh (3,) device tensor -- csrc/adam.hip's two-stage sum of squares over `grads` -- and
+    """(total_norm, coef, clipped_norm) as one fresh (3,) device tensor -- csrc/optim_step.hip's two-stage sum of squares over `grads` -- and
     the host tables (pointers, element counts, n) it was called with."""
     lib = _lib.load()
     (g,), numel, n = _tables(grads)
@@ -171,7 +171,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
 
 class FusedAdam(_FusedOptimizer):
-    """torch.optim.Adam (amsgrad off) in one launch per 24 tensors (csrc/adam.hip); clipping, state and step: `_FusedOptimizer`."""
+    """torch.optim.Adam (amsgrad off) in one launch per 24 tensors (csrc/optim_step.hip); clipping, state and step: `_FusedOptimizer`."""
 
     _kind, _second, _step_fn, _clipped_fn = "Adam", "exp_avg_sq", "odehip_adam_step", "odehip_adam_step_clipped"
 
@@ -180,7 +180,7 @@ class FusedAdam(_FusedOptimizer):
 
 
 class FusedAdamax(_FusedOptimizer):
-    """torch.optim.Adamax in one launch per 24 tensors (csrc/adamax.hip), with torch's defaults: Vid-ODE's optimizer
+    """torch.optim.Adamax in one launch per 24 tensors (csrc/optim_step.hip), with torch's defaults: Vid-ODE's optimizer
     (Vid-ODE/main.py:187).  State per parameter is torch's (`step`, `exp_avg`, `exp_inf`), so state dicts go both ways; `exp_inf` is
     torch's bit for bit, and a NaN gradient gives NaN there and in the parameter, never a finite update.  Clipping, `step(closure,
     max_grad_norm=)`, `last_grad_norm` / `last_clipped_norm`: `_FusedOptimizer`.  torch's `maximize`, `foreach`, `differentiable`

@@ -1,4 +1,4 @@
-"""FusedAdamax (csrc/adamax.hip) against torch.optim.Adamax(foreach=False) on the same device, fed bit-identical parameters and
+"""FusedAdamax (csrc/optim_step.hip) against torch.optim.Adamax(foreach=False) on the same device, fed bit-identical parameters and
 gradients for 3 consecutive steps, and train_batch / decay_learning_rate around it (Vid-ODE's recipe, Vid-ODE/main.py:187,214).
 
 Tensor sets: n tensors that reach the kernel, n = 23, 24, 25, 49 (the launches take 24 tensors each: one launch, one full, two, three),

@@ -1,4 +1,4 @@
-"""Gradient clipping by global norm on the device (csrc/adam.hip: grad_sqsum -> grad_norm_finish -> adam_clip / grad_scale) against
+"""Gradient clipping by global norm on the device (csrc/optim_step.hip: grad_sqsum -> grad_norm_finish -> the clipping update / grad_scale) against
 the float64 restatement of tests/_clip_ref.py and against torch.nn.utils.clip_grad_norm_ + torch.optim.Adam on the same inputs.
 
 Tensor set: 40 parameters, so two 24-tensor launch chunks: (1,), (7,3), (64,), (64,64,3,3) repeated, one tensor of 0 elements, one

@@ -1,5 +1,5 @@
 """The Adamax step on the parameter lists of ODEConvGRU (40 tensors, 1.04 M parameters) and VidODE (3.49 M parameters), on the same GPU:
-  * fused           FusedAdamax.step()                      (csrc/adamax.hip: one launch per 24 tensors)
+  * fused           FusedAdamax.step()                      (csrc/optim_step.hip: one launch per 24 tensors)
   * fused_clip      FusedAdamax(max_grad_norm=c).step()     (sum of squares -> coefficient -> the update reading the coefficient)
   * foreach         torch.optim.Adamax(foreach=True).step()
   * foreach_clip    torch.nn.utils.clip_grad_norm_(params, c), then that step

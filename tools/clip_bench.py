@@ -1,5 +1,5 @@
 """Clipped optimizer step on the ODEConvGRU model's parameter set (40 tensors, 1.04 M parameters), on the same GPU:
-  * fused       FusedAdam(max_grad_norm=c).step(): sum of squares -> coefficient -> Adam reading the coefficient (csrc/adam.hip)
+  * fused       FusedAdam(max_grad_norm=c).step(): sum of squares -> coefficient -> Adam reading the coefficient (csrc/optim_step.hip)
   * torch_clip  torch.nn.utils.clip_grad_norm_(params, c) followed by the unclipped FusedAdam.step()
   * hip_clip    ode_rl_amd.optim.clip_grad_norm_(params, c) followed by the unclipped FusedAdam.step()
   * unclipped   FusedAdam.step() alone (what clipping adds is the difference)
