@@ -558,6 +558,31 @@ int odehip_bn_relu_up2x_backward(const float* grad_out, const float* x, int batc
                                  const float* invstd, const float* scale, const float* shift, int training, int upsample, float* grad_x,
                                  float* grad_weight, float* grad_bias, float* g_pre, void* workspace, size_t workspace_bytes, void* stream);
 
+/* BatchNorm statistics over the ranks of a batch-sharded job: the train-mode pass above cut in two at its per-channel float64 sums, so
+ * that the caller can sum them over the ranks in between (ONE collective per pass, on `stream`).  A rank's shard holds at least one
+ * sample; shards may be uneven, the element count travels with the sums.
+ *   odehip_bn_sync_stats              sums [2 channels + 1] (device) = [sum x | sum x^2 | batch * height * width] of this shard
+ *   odehip_bn_sync_relu_up2x_forward  the rest of the forward from the REDUCED sums: mean, biased variance, running statistics with the
+ *                                     global count, scale / shift, out.  Keep sums[2 channels] (the global count) for the backward.
+ *   odehip_bn_sync_backward_sums      g_pre written once; sums [2 channels] = [sum g_pre | sum g_pre * xhat] of this shard, xhat from the
+ *                                     global mean / invstd of the forward; grad_weight, grad_bias = these LOCAL sums (as nn.SyncBatchNorm
+ *                                     returns them: the gradient all-reduce adds them up)
+ *   odehip_bn_sync_backward_apply     grad_x = scale * (g_pre - m1 - xhat * m2), (m1, m2) = the REDUCED sums / *count (device)
+ * workspace: odehip_bn_workspace_bytes(channels) (stats, backward_sums), 2 * channels floats (backward_apply).  With one rank the four
+ * calls compute bit for bit what the two calls above do.  Arguments are checked before any HIP call (ODEHIP_EINVAL).  Pure additions:
+ * ODEHIP_ABI_VERSION stays. */
+int odehip_bn_sync_stats(const float* x, int batch, int channels, int height, int width, double* sums, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int odehip_bn_sync_relu_up2x_forward(const float* x, int batch, int channels, int height, int width, const double* sums, const float* weight,
+                                     const float* bias, float* running_mean, float* running_var, float momentum, float eps, int upsample,
+                                     float* out, float* mean_out, float* invstd_out, float* scale_out, float* shift_out, void* stream);
+int odehip_bn_sync_backward_sums(const float* grad_out, const float* x, int batch, int channels, int height, int width, const float* mean,
+                                 const float* invstd, const float* scale, const float* shift, int upsample, float* g_pre, float* grad_weight,
+                                 float* grad_bias, double* sums, void* workspace, size_t workspace_bytes, void* stream);
+int odehip_bn_sync_backward_apply(const float* g_pre, const float* x, int batch, int channels, int height, int width, const float* mean,
+                                  const float* invstd, const float* scale, const double* sums, const double* count, float* grad_x,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the conv encoder / decoder either side of the path (models/ODEConvGRU.py:101-118 Encoder, :121-140 Decoder; n_downs = 2) --
  * Each is ONE fused launch: the 32x32 intermediate stays in LDS, the 16 -> out_ch and in_ch -> 32 layers run on the fp32 MFMA.
  * Frames are 64x64, latents 16x16 (the path's fixed map size).  LeakyReLU slope: the reference's 0.2.

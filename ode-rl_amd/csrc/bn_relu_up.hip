@@ -12,6 +12,9 @@
 //   backward  bn_bwd_reduce_kernel: g_pre = [upsampling transposed as a gather](grad_out) * (pre-activation > 0), written once, with the
 //             per-channel sums of g_pre and g_pre * xhat -> finalize -> bn_bwd_apply_kernel: dx = scale * (g_pre - mean(g_pre) - xhat *
 //             mean(g_pre * xhat)) (train) or scale * g_pre (eval).
+//   cross-rank (batch sharding, opt-in: ode_rl_amd.dist.sync_batchnorm) the same kernels, each pass cut in two at its per-channel float64
+//             sums -- forward [sum x | sum x^2 | count], backward [sum g_pre | sum g_pre * xhat] -- which the host all-reduces in between;
+//             d gamma, d beta stay the rank's own sums.  Plain launches in stream order: no atomics, no grid barrier, no host read.
 // All HBM-bound; every reduction has a fixed order (bitwise reproducible).  NCHW fp32 as torch holds the tensors.
 #include "odehip_internal.h"
 
@@ -68,17 +71,22 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
   }
 }
 
-// one thread per channel: statistics of the call, the affine map of the normalisation, nn.BatchNorm2d's running statistics
-__global__ void bn_finalize_kernel(const double* __restrict__ part, int C, double count, float eps, float momentum, const float* __restrict__ weight,
-                                   const float* __restrict__ bias, float* __restrict__ running_mean, float* __restrict__ running_var,
-                                   float* __restrict__ mean_out, float* __restrict__ invstd_out, float* __restrict__ scale, float* __restrict__ shift) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  double a = 0.0, b = 0.0;
+// the kBnSplit partial pairs of channel c, added in index order
+__device__ __forceinline__ void bn_fold(const double* __restrict__ part, int c, double& a, double& b) {
+  a = 0.0;
+  b = 0.0;
   for (int s = 0; s < kBnSplit; ++s) {
     a += part[((size_t)c * kBnSplit + s) * 2];
     b += part[((size_t)c * kBnSplit + s) * 2 + 1];
   }
+}
+
+// channel c from its sum a, sum of squares b and element count: statistics of the call, the affine map of the normalisation,
+// nn.BatchNorm2d's running statistics
+__device__ __forceinline__ void bn_channel_affine(int c, double a, double b, double count, float eps, float momentum,
+                                                  const float* __restrict__ weight, const float* __restrict__ bias,
+                                                  float* __restrict__ running_mean, float* __restrict__ running_var, float* __restrict__ mean_out,
+                                                  float* __restrict__ invstd_out, float* __restrict__ scale, float* __restrict__ shift) {
   const double mean = a / count;
   double var = b / count - mean * mean;
   var = var < 0.0 ? 0.0 : var;
@@ -89,10 +97,45 @@ __global__ void bn_finalize_kernel(const double* __restrict__ part, int C, doubl
   scale[c] = g * invstd;
   shift[c] = be - (float)mean * g * invstd;
   if (running_mean) {
+#pragma clang fp contract(off)   // a * b + c * d: which product is fused is the compiler's choice per kernel; both kernels round both
     const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
     running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * (float)mean;
     running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (float)unbiased;
   }
+}
+
+// one thread per channel
+__global__ void bn_finalize_kernel(const double* __restrict__ part, int C, double count, float eps, float momentum, const float* __restrict__ weight,
+                                   const float* __restrict__ bias, float* __restrict__ running_mean, float* __restrict__ running_var,
+                                   float* __restrict__ mean_out, float* __restrict__ invstd_out, float* __restrict__ scale, float* __restrict__ shift) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double a, b;
+  bn_fold(part, c, a, b);
+  bn_channel_affine(c, a, b, count, eps, momentum, weight, bias, running_mean, running_var, mean_out, invstd_out, scale, shift);
+}
+
+// ---- cross-rank statistics: the same pass cut at the per-channel sums, which the host reduces over the ranks in between ----------
+// sums = [sum x (C) | sum x^2 (C) | count] of this rank's shard
+__global__ void bn_sync_fold_kernel(const double* __restrict__ part, int C, double count, double* __restrict__ sums) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double a, b;
+  bn_fold(part, c, a, b);
+  sums[c] = a;
+  sums[C + c] = b;
+  if (c == 0) sums[2 * C] = count;
+}
+
+// ... and bn_finalize_kernel from the reduced sums: the count is the global one
+__global__ void bn_sync_finalize_kernel(const double* __restrict__ sums, int C, float eps, float momentum, const float* __restrict__ weight,
+                                        const float* __restrict__ bias, float* __restrict__ running_mean, float* __restrict__ running_var,
+                                        float* __restrict__ mean_out, float* __restrict__ invstd_out, float* __restrict__ scale,
+                                        float* __restrict__ shift) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  bn_channel_affine(c, sums[c], sums[C + c], sums[2 * C], eps, momentum, weight, bias, running_mean, running_var, mean_out, invstd_out, scale,
+                    shift);
 }
 
 // eval mode: the affine map from the running statistics
@@ -219,15 +262,35 @@ __global__ void bn_bwd_finalize_kernel(const double* __restrict__ part, int C, d
                                        float* __restrict__ m1, float* __restrict__ m2) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  double a = 0.0, b = 0.0;
-  for (int s = 0; s < kBnSplit; ++s) {
-    a += part[((size_t)c * kBnSplit + s) * 2];
-    b += part[((size_t)c * kBnSplit + s) * 2 + 1];
-  }
+  double a, b;
+  bn_fold(part, c, a, b);
   dbeta[c] = (float)a;
   dgamma[c] = (float)b;
   m1[c] = (float)(a / count);
   m2[c] = (float)(b / count);
+}
+
+// cross-rank: d beta, d gamma stay this rank's sums (the gradient all-reduce adds them up, as for nn.SyncBatchNorm); the means wait
+// for the reduction of sums = [sum g_pre (C) | sum g_pre * xhat (C)]
+__global__ void bn_sync_bwd_fold_kernel(const double* __restrict__ part, int C, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                        double* __restrict__ sums) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double a, b;
+  bn_fold(part, c, a, b);
+  dbeta[c] = (float)a;
+  dgamma[c] = (float)b;
+  sums[c] = a;
+  sums[C + c] = b;
+}
+
+// count: the global element count on the device, as the forward's reduction left it
+__global__ void bn_sync_bwd_means_kernel(const double* __restrict__ sums, const double* __restrict__ count, int C, float* __restrict__ m1,
+                                         float* __restrict__ m2) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  m1[c] = (float)(sums[c] / *count);
+  m2[c] = (float)(sums[C + c] / *count);
 }
 
 // dx = scale * (g_pre - m1 - xhat * m2) (train) | scale * g_pre (eval: m1 = m2 = null)
@@ -260,6 +323,28 @@ static unsigned grid_for(long long work) {
   return (unsigned)(blocks < 65536 ? (blocks < 1 ? 1 : blocks) : 65536);
 }
 
+static void launch_relu_up(const float* x, const float* scale, const float* shift, float* out, int batch, int channels, int height, int width,
+                           int upsample, hipStream_t stream) {
+  const long long planes = (long long)batch * channels;
+  if (upsample) {
+    hipLaunchKernelGGL((bn_relu_up_kernel<true>), dim3(grid_for(planes * 2LL * height * (width / 2))), dim3(256), 0, stream, x, scale, shift, out, planes,
+                       channels, height, width);
+  } else {
+    hipLaunchKernelGGL((bn_relu_up_kernel<false>), dim3(grid_for(planes * (long long)height * width / 4)), dim3(256), 0, stream, x, scale, shift, out,
+                       planes, channels, height, width);
+  }
+}
+
+static void launch_bwd_reduce(const float* grad_out, const float* x, const float* scale, const float* shift, const float* mean, const float* invstd,
+                              float* g_pre, int batch, int channels, int height, int width, int upsample, double* part, hipStream_t stream) {
+  if (upsample)
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<true>), dim3(channels, kBnSplit), dim3(256), 0, stream, grad_out, x, scale, shift, mean, invstd, g_pre, batch,
+                       channels, height, width, part);
+  else
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<false>), dim3(channels, kBnSplit), dim3(256), 0, stream, grad_out, x, scale, shift, mean, invstd, g_pre, batch,
+                       channels, height, width, part);
+}
+
 }  // namespace odehip
 
 using namespace odehip;
@@ -285,14 +370,7 @@ extern "C" int odehip_bn_relu_up2x_forward(const float* x, int batch, int channe
     hipLaunchKernelGGL(bn_eval_affine_kernel, dim3((channels + 63) / 64), dim3(64), 0, stream, channels, eps, weight, bias, running_mean, running_var,
                        mean_out, invstd_out, scale_out, shift_out);
   }
-  const long long planes = (long long)batch * channels;
-  if (upsample) {
-    hipLaunchKernelGGL((bn_relu_up_kernel<true>), dim3(grid_for(planes * 2LL * height * (width / 2))), dim3(256), 0, stream, x, scale_out, shift_out, out,
-                       planes, channels, height, width);
-  } else {
-    hipLaunchKernelGGL((bn_relu_up_kernel<false>), dim3(grid_for(planes * (long long)HW / 4)), dim3(256), 0, stream, x, scale_out, shift_out, out, planes,
-                       channels, height, width);
-  }
+  launch_relu_up(x, scale_out, shift_out, out, batch, channels, height, width, upsample, stream);
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
 }
@@ -311,17 +389,79 @@ extern "C" int odehip_bn_relu_up2x_backward(const float* grad_out, const float* 
   double* part = (double*)workspace;
   float* m1 = (float*)((char*)workspace + odehip_bn_workspace_bytes(channels));
   float* m2 = m1 + channels;
-  if (upsample)
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<true>), dim3(channels, kBnSplit), dim3(256), 0, stream, grad_out, x, scale, shift, mean, invstd, g_pre, batch,
-                       channels, height, width, part);
-  else
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<false>), dim3(channels, kBnSplit), dim3(256), 0, stream, grad_out, x, scale, shift, mean, invstd, g_pre, batch,
-                       channels, height, width, part);
+  launch_bwd_reduce(grad_out, x, scale, shift, mean, invstd, g_pre, batch, channels, height, width, upsample, part, stream);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((channels + 63) / 64), dim3(64), 0, stream, (const double*)part, channels, (double)batch * HW, grad_weight,
                      grad_bias, m1, m2);
   const long long planes = (long long)batch * channels;
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(planes * (long long)HW / 4)), dim3(256), 0, stream, g_pre, x, scale, mean, invstd,
                      training ? m1 : (const float*)nullptr, training ? m2 : (const float*)nullptr, grad_x, planes, channels, HW);
+  ODEHIP_CHECK_HIP(hipGetLastError());
+  return ODEHIP_OK;
+}
+
+// ---- cross-rank statistics (header: "BatchNorm statistics over the ranks of a batch-sharded job") ------------------------------------
+#define ODEHIP_BN_SHAPE(fn)                                                                                                            \
+  ODEHIP_REQUIRE(batch > 0 && channels > 0 && height > 0 && width > 0 && width % 4 == 0,                                                \
+                 fn ": bad shape (%d, %d, %d, %d); the width must be a multiple of 4 and a rank's shard holds at least one sample", batch, \
+                 channels, height, width)
+
+extern "C" int odehip_bn_sync_stats(const float* x, int batch, int channels, int height, int width, double* sums, void* workspace,
+                                    size_t workspace_bytes, void* stream_) {
+  ODEHIP_REQUIRE(x && sums, "bn_sync_stats: null pointer");
+  ODEHIP_BN_SHAPE("bn_sync_stats");
+  ODEHIP_REQUIRE(workspace && workspace_bytes >= odehip_bn_workspace_bytes(channels), "bn_sync_stats: workspace too small");
+  hipStream_t stream = (hipStream_t)stream_;
+  const int HW = height * width;
+  hipLaunchKernelGGL(bn_stats_kernel, dim3(channels, kBnSplit), dim3(256), 0, stream, x, batch, channels, HW, (double*)workspace);
+  hipLaunchKernelGGL(bn_sync_fold_kernel, dim3((channels + 63) / 64), dim3(64), 0, stream, (const double*)workspace, channels, (double)batch * HW,
+                     sums);
+  ODEHIP_CHECK_HIP(hipGetLastError());
+  return ODEHIP_OK;
+}
+
+extern "C" int odehip_bn_sync_relu_up2x_forward(const float* x, int batch, int channels, int height, int width, const double* sums,
+                                                const float* weight, const float* bias, float* running_mean, float* running_var, float momentum,
+                                                float eps, int upsample, float* out, float* mean_out, float* invstd_out, float* scale_out,
+                                                float* shift_out, void* stream_) {
+  ODEHIP_REQUIRE(x && sums && out && mean_out && invstd_out && scale_out && shift_out, "bn_sync_relu_up2x_forward: null pointer");
+  ODEHIP_BN_SHAPE("bn_sync_relu_up2x_forward");
+  hipStream_t stream = (hipStream_t)stream_;
+  hipLaunchKernelGGL(bn_sync_finalize_kernel, dim3((channels + 63) / 64), dim3(64), 0, stream, sums, channels, eps, momentum, weight, bias,
+                     running_mean, running_var, mean_out, invstd_out, scale_out, shift_out);
+  launch_relu_up(x, scale_out, shift_out, out, batch, channels, height, width, upsample, stream);
+  ODEHIP_CHECK_HIP(hipGetLastError());
+  return ODEHIP_OK;
+}
+
+extern "C" int odehip_bn_sync_backward_sums(const float* grad_out, const float* x, int batch, int channels, int height, int width, const float* mean,
+                                            const float* invstd, const float* scale, const float* shift, int upsample, float* g_pre,
+                                            float* grad_weight, float* grad_bias, double* sums, void* workspace, size_t workspace_bytes,
+                                            void* stream_) {
+  ODEHIP_REQUIRE(grad_out && x && mean && invstd && scale && shift && g_pre && grad_weight && grad_bias && sums, "bn_sync_backward_sums: null pointer");
+  ODEHIP_BN_SHAPE("bn_sync_backward_sums");
+  ODEHIP_REQUIRE(workspace && workspace_bytes >= odehip_bn_workspace_bytes(channels), "bn_sync_backward_sums: workspace too small");
+  hipStream_t stream = (hipStream_t)stream_;
+  launch_bwd_reduce(grad_out, x, scale, shift, mean, invstd, g_pre, batch, channels, height, width, upsample, (double*)workspace, stream);
+  hipLaunchKernelGGL(bn_sync_bwd_fold_kernel, dim3((channels + 63) / 64), dim3(64), 0, stream, (const double*)workspace, channels, grad_weight, grad_bias,
+                     sums);
+  ODEHIP_CHECK_HIP(hipGetLastError());
+  return ODEHIP_OK;
+}
+
+extern "C" int odehip_bn_sync_backward_apply(const float* g_pre, const float* x, int batch, int channels, int height, int width, const float* mean,
+                                             const float* invstd, const float* scale, const double* sums, const double* count, float* grad_x,
+                                             void* workspace, size_t workspace_bytes, void* stream_) {
+  ODEHIP_REQUIRE(g_pre && x && mean && invstd && scale && sums && count && grad_x, "bn_sync_backward_apply: null pointer");
+  ODEHIP_BN_SHAPE("bn_sync_backward_apply");
+  ODEHIP_REQUIRE(workspace && workspace_bytes >= 2 * (size_t)channels * sizeof(float), "bn_sync_backward_apply: workspace too small");
+  hipStream_t stream = (hipStream_t)stream_;
+  float* m1 = (float*)workspace;
+  float* m2 = m1 + channels;
+  hipLaunchKernelGGL(bn_sync_bwd_means_kernel, dim3((channels + 63) / 64), dim3(64), 0, stream, sums, count, channels, m1, m2);
+  const long long planes = (long long)batch * channels;
+  const int HW = height * width;
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(planes * (long long)HW / 4)), dim3(256), 0, stream, g_pre, x, scale, mean, invstd,
+                     (const float*)m1, (const float*)m2, grad_x, planes, channels, HW);
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
 }

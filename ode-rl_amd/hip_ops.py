@@ -1350,9 +1350,13 @@ def upsample2x_backward(g):
     return gin
 
 
-def bn_relu_up_forward(x, bn, upsample, conv_bias=None):
+def bn_relu_up_forward(x, bn, upsample, conv_bias=None, group=None):
     """relu(bn(x)) [upsampled x2] in one pass (csrc/bn_relu_up.hip); bn: an nn.BatchNorm2d (its running statistics are updated in
     train() mode exactly as the module would).  Returns (out, saved) with saved = (mean, invstd, scale, shift) for the backward.
+    group: a torch.distributed process group over which the batch is sharded (ode_rl_amd.dist.sync_batchnorm).  In train() mode the
+    statistics are then those of the GLOBAL batch: the pass stops at its per-channel float64 sums [sum x | sum x^2 | count], ONE
+    all-reduce on the current stream adds them over the ranks, and the pass resumes (shards may be uneven, not empty).  eval() mode
+    needs no collective.  saved gains the reduced buffer's count for the backward.
     conv_bias: the bias of the convolution that produced x, NOT added to x (the caller ran the convolution without it).  A
     per-channel constant in front of BatchNorm cancels in train() mode -- only running_mean sees it -- and shifts the running mean in
     eval() mode: folding it here saves the bias-add pass over x and, in the backward, the reduction of a bias gradient that is exactly
@@ -1360,6 +1364,8 @@ def bn_relu_up_forward(x, bn, upsample, conv_bias=None):
     require_device_tensor(x, "input")
     if x.dim() != 4 or x.shape[3] % 4:
         raise ValueError(f"bn_relu_up: needs (N, C, H, W) with W % 4 == 0, got {tuple(x.shape)}")
+    if group is not None and x.shape[0] == 0:
+        raise ValueError("bn_relu_up: this rank's shard of the batch is empty; cross-rank statistics need at least one sample per rank")
     x = x.contiguous()
     n, c, h, w = x.shape
     dev = x.device
@@ -1388,17 +1394,32 @@ def bn_relu_up_forward(x, bn, upsample, conv_bias=None):
     ws = workspace(("bn", c), nws + 8 * c, dev)
     if training and bn.track_running_stats and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
-    _lib.check(lib.odehip_bn_relu_up2x_forward(_ptr(x), n, c, h, w, _ptr(bn.weight), _ptr(bn.bias), _ptr(run_mean),
-                                               _ptr(bn.running_var) if tracked else None,
-                                               int(training), float(bn.momentum), float(bn.eps), int(bool(upsample)), _ptr(out),
-                                               _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]), _ptr(stats[3]), _ptr(ws), ws.numel(), _stream()))
+    saved = (stats, training)
+    if group is not None and training:
+        sums = torch.empty(2 * c + 1, dtype=torch.float64, device=dev)
+        _lib.check(lib.odehip_bn_sync_stats(_ptr(x), n, c, h, w, _ptr(sums), _ptr(ws), ws.numel(), _stream()))
+        torch.distributed.all_reduce(sums, op=torch.distributed.ReduceOp.SUM, group=group)
+        _lib.check(lib.odehip_bn_sync_relu_up2x_forward(_ptr(x), n, c, h, w, _ptr(sums), _ptr(bn.weight), _ptr(bn.bias), _ptr(run_mean),
+                                                        _ptr(bn.running_var) if tracked else None, float(bn.momentum), float(bn.eps),
+                                                        int(bool(upsample)), _ptr(out), _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]),
+                                                        _ptr(stats[3]), _stream()))
+        saved = (stats, training, sums[2 * c:])
+    else:
+        _lib.check(lib.odehip_bn_relu_up2x_forward(_ptr(x), n, c, h, w, _ptr(bn.weight), _ptr(bn.bias), _ptr(run_mean),
+                                                   _ptr(bn.running_var) if tracked else None,
+                                                   int(training), float(bn.momentum), float(bn.eps), int(bool(upsample)), _ptr(out),
+                                                   _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]), _ptr(stats[3]), _ptr(ws), ws.numel(),
+                                                   _stream()))
     if conv_bias is not None and training and tracked:
         bn.running_mean.add_(conv_bias, alpha=bn.momentum)   # the mean of (x + b) is mean(x) + b
-    return out, (stats, training)
+    return out, saved
 
 
-def bn_relu_up_backward(grad_out, x, saved, upsample):
-    stats, training = saved
+def bn_relu_up_backward(grad_out, x, saved, upsample, group=None):
+    """(grad_x, grad_weight, grad_bias).  group: the forward's.  In train() mode the two per-channel sums of the backward are then
+    all-reduced (ONE collective) before dx; grad_weight / grad_bias stay this rank's sums, as nn.SyncBatchNorm returns them -- the
+    gradient all-reduce of the step adds them up."""
+    stats, training = saved[:2]
     require_device_tensor(grad_out, "gradient")
     grad_out, x = grad_out.contiguous(), x.contiguous()
     n, c, h, w = x.shape
@@ -1411,6 +1432,19 @@ def bn_relu_up_backward(grad_out, x, saved, upsample):
     gw = torch.empty(c, dtype=torch.float32, device=dev)
     gb = torch.empty(c, dtype=torch.float32, device=dev)
     ws = workspace(("bn", c), lib.odehip_bn_workspace_bytes(c) + 8 * c, dev)
+    if group is not None and training:
+        if len(saved) != 3:
+            raise ValueError("bn_relu_up backward: `group` given, but the forward ran without one")
+        sums = torch.empty(2 * c, dtype=torch.float64, device=dev)
+        _lib.check(lib.odehip_bn_sync_backward_sums(_ptr(grad_out), _ptr(x), n, c, h, w, _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]),
+                                                    _ptr(stats[3]), int(bool(upsample)), _ptr(g_pre), _ptr(gw), _ptr(gb), _ptr(sums), _ptr(ws),
+                                                    ws.numel(), _stream()))
+        torch.distributed.all_reduce(sums, op=torch.distributed.ReduceOp.SUM, group=group)
+        _lib.check(lib.odehip_bn_sync_backward_apply(_ptr(g_pre), _ptr(x), n, c, h, w, _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]), _ptr(sums),
+                                                     _ptr(saved[2]), _ptr(gx), _ptr(ws), ws.numel(), _stream()))
+        return gx, gw, gb
+    if len(saved) == 3:
+        raise ValueError("bn_relu_up backward: the forward reduced its statistics over a process group; pass the same `group`")
     _lib.check(lib.odehip_bn_relu_up2x_backward(_ptr(grad_out), _ptr(x), n, c, h, w, _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]), _ptr(stats[3]),
                                                 int(training), int(bool(upsample)), _ptr(gx), _ptr(gw), _ptr(gb), _ptr(g_pre), _ptr(ws), ws.numel(),
                                                 _stream()))

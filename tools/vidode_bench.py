@@ -2,7 +2,10 @@
 step, and the forward's parts: BatchNorm conv encoder (library), ODEConvGRUCell on 128-channel latents (HIP), DiffEqSolver (HIP),
 the upsample / conv / BatchNorm flow decoder (library, one call per predicted frame: models/VidODE.py:143-158), the warp chain +
 compositing (HIP).  Answers VERDICT r03 #7: which share of a VidODE step is still MIOpen.
-  python tools/vidode_bench.py [--batch 64] [--frames 10] [--method rk4|dopri5] [--steps 10]"""
+  python tools/vidode_bench.py [--batch 64] [--frames 10] [--method rk4|dopri5] [--steps 10]
+Batch-sharded (one process per rank, RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in the environment as torchrun sets them; --batch is
+the GLOBAL batch): --sharded adds the gradient all-reduce, --sync-batchnorm also the cross-rank BatchNorm statistics
+(ode_rl_amd.dist.sync_batchnorm); --backend gloo lets the ranks share one card (a functional rehearsal, not scaling)."""
 import argparse
 import json
 import os
@@ -22,17 +25,33 @@ def main():
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--only", default="all", choices=["all", "train"])
     p.add_argument("--miopen-find", action="store_true", help="torch.backends.cudnn.benchmark: let MIOpen search solvers for the library convolutions")
+    p.add_argument("--sharded", action="store_true", help="shard the batch over the ranks of the job; one gradient all-reduce per step")
+    p.add_argument("--sync-batchnorm", action="store_true", help="--sharded with BatchNorm statistics over all ranks")
+    p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: every rank on cuda:0")
     a = p.parse_args()
+    rank = world = None
+    if a.sharded or a.sync_batchnorm:
+        import torch.distributed as dist
+        dist.init_process_group(a.backend)
+        rank, world = dist.get_rank(), dist.get_world_size()
     torch.backends.cudnn.benchmark = a.miopen_find
     import ode_rl_amd  # noqa: F401
     from ode_rl_amd.data import MovingMNISTSynthetic
     from ode_rl_amd.models.VidODE import VidODE
-    dev = torch.device("cuda", 0)
+    dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)) if world and a.backend == "nccl" else 0)
+    torch.cuda.set_device(dev)
     torch.manual_seed(0)
     opt = argparse.Namespace(n_downs=2, resolution=64, in_channels=1, n_layers=2, decode_diff_method=a.method)
     m = VidODE(opt, torch.device("cpu")).to(dev)
     T = a.frames
-    batch = next(MovingMNISTSynthetic(T, T, num_objects=[2], batch_size=a.batch, device=dev, seed=0))
+    if world:
+        from ode_rl_amd import dist as odist
+        lo, hi = odist.shard_bounds(a.batch, rank, world)
+        odist.broadcast_parameters(m)
+        if a.sync_batchnorm:
+            odist.sync_batchnorm(m)
+        a.batch = hi - lo
+    batch = next(MovingMNISTSynthetic(T, T, num_objects=[2], batch_size=a.batch, device=dev, seed=rank or 0))
     frames = batch["observed_data"] + 0.5
     ts = torch.arange(2 * T, dtype=torch.float64, device=dev) / (2 * T)
     ones = torch.ones(a.batch, T, 1, device=dev)
@@ -57,9 +76,13 @@ def main():
         optim.zero_grad()
         loss = m.get_loss(m.get_prediction(frames, bd), bd["data_to_predict"])
         loss.backward()
+        if world:
+            odist.allreduce_gradients(m.parameters())
         optim.step()
 
     res = {"model": "VidODE", "batch": a.batch, "frames_in": T, "frames_out": T, "method": a.method}
+    if world:
+        res.update(rank=rank, world=world, backend=a.backend, sync_batchnorm=a.sync_batchnorm)
     if a.only == "train":
         res["train_step_ms"] = timed(train, a.steps)
         print(json.dumps(res), flush=True)
