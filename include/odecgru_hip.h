@@ -274,6 +274,18 @@ int odehip_odeconvgru_encode(const odehip_encoder* e, const float* inputs_nchw, 
 int odehip_odeconvgru_encode_masked(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames, int batch,
                                     int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw, void* workspace,
                                     size_t workspace_bytes, void* stream, const float* mask_tb);
+/* The same with a HOST hint about whole steps.  step_observed_host: n_frames bytes on the HOST, indexed by FRAME like the rows of
+ * mask_tb, or NULL = every step runs = exactly odehip_odeconvgru_encode_masked.  A frame whose byte is 0 is computed exactly as if
+ * its whole mask_tb row were 0 -- whatever that row holds, and also when mask_tb is NULL -- but without the launches: no cell
+ * convolution and no gates / update kernel run for it, the Euler step writes h_ode straight into the next state (the bits the update
+ * kernels copy for m == 0), and a wanted latent slot is filled by one small copy kernel.  Nothing of an all-unobserved frame is
+ * read, so its contents (non-finite included) cannot reach any output.  cell_steps_run: HOST int or NULL, receives the number of
+ * steps for which this call launched the cell.  The hint is read during the call only.  No host synchronisation, no device
+ * read-back.  Pure additions: ODEHIP_ABI_VERSION stays. */
+int odehip_odeconvgru_encode_steps(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames, int batch,
+                                   int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw, void* workspace,
+                                   size_t workspace_bytes, void* stream, const float* mask_tb, const unsigned char* step_observed_host,
+                                   int* cell_steps_run);
 
 /* Backward of one ConvGRU step (ConvGRUCell.forward with seq_len = 1): grad_h_next -> grad_x, grad_h and the gradients of
  * the cell's eight parameters.  Stateless: the step is recomputed from (x, h) inside the call.  input_dim and hidden_dim
@@ -385,6 +397,25 @@ int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e, const odeh
                                              int batch, int run_backwards, const float* grad_mean_nchw, const float* grad_std_nchw,
                                              const float* grad_latent_nchw, float* grad_inputs_nchw, const odehip_encoder_grads* grads,
                                              void* workspace, size_t workspace_bytes, void* stream, const float* mask_tb);
+/* The pair with the host step hint of odehip_odeconvgru_encode_steps (step_observed_host: n_frames bytes on the HOST indexed by
+ * frame, or NULL = the two calls above; both calls of a pair are given the same hint).  For a frame whose byte is 0 the forward keeps
+ * only what the sweep reads for it (the state in front of the Euler step and the dynamics' hidden activations; the next state IS
+ * h_ode), and the sweep launches no gates / update backward kernel and no input-gradient convolution: the state gradient goes
+ * unchanged to the Euler step's adjoint, and the frame's grad_inputs slab is zero-filled in stream order.  The cell's weight-gradient
+ * tables hold the observed frames only (fewer than n_frames entries: the fixed summation order is that of the shorter table); with no
+ * observed frame there is no cell weight-gradient launch and the cell's gradient tensors are exact zeros.  The encoder dynamics,
+ * their weight gradients over all n_frames steps and the head are untouched.  odehip_encoder_train_workspace_bytes as before.
+ * cell_steps_run: HOST int or NULL, the number of steps whose cell kernels this call launched.  Since nothing multiplies an
+ * all-unobserved frame any more, its contents cannot reach any gradient either. */
+int odehip_odeconvgru_encode_train_steps(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames,
+                                         int batch, int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw,
+                                         void* workspace, size_t workspace_bytes, void* stream, const float* mask_tb,
+                                         const unsigned char* step_observed_host, int* cell_steps_run);
+int odehip_odeconvgru_encode_backward_steps(const odehip_encoder* e, const odehip_encoder_bwd* eb, const double* t_host, int n_frames,
+                                            int batch, int run_backwards, const float* grad_mean_nchw, const float* grad_std_nchw,
+                                            const float* grad_latent_nchw, float* grad_inputs_nchw, const odehip_encoder_grads* grads,
+                                            void* workspace, size_t workspace_bytes, void* stream, const float* mask_tb,
+                                            const unsigned char* step_observed_host, int* cell_steps_run);
 
 /* ---- odeint, adaptive dopri5 (torchdiffeq Dopri5Solver; the reference's default method, configs.yaml:79) ------ */
 

@@ -314,6 +314,23 @@ SIGNATURES = {
                                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                                 ctypes.POINTER(EncoderGrads), ctypes.c_void_p, ctypes.c_size_t,
                                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    # the three encoder calls with the host step hint: the _masked signature + step_observed_host (n_frames bytes, host) + cell_steps_run
+    "odehip_odeconvgru_encode_steps": (ctypes.c_int, [ctypes.POINTER(EncoderDesc), ctypes.c_void_p,
+                                                      ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.POINTER(ctypes.c_int)]),
+    "odehip_odeconvgru_encode_train_steps": (ctypes.c_int, [ctypes.POINTER(EncoderDesc), ctypes.c_void_p,
+                                                            ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                            ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                            ctypes.POINTER(ctypes.c_int)]),
+    "odehip_odeconvgru_encode_backward_steps": (ctypes.c_int, [ctypes.POINTER(EncoderDesc), ctypes.POINTER(EncoderBwd),
+                                                               ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                               ctypes.POINTER(EncoderGrads), ctypes.c_void_p, ctypes.c_size_t,
+                                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                               ctypes.POINTER(ctypes.c_int)]),
     "odehip_odeint_dopri5": (ctypes.c_int, [ctypes.POINTER(ConvStack), ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
                                             ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_double, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),

@@ -174,12 +174,13 @@ def sequence_with_grad(packed, x_seq, h0, n_steps):
 class _EncodeFn(torch.autograd.Function):
     """ODEConvGRUCell.forward / run_ode_conv_gru under autograd: csrc/convgru_backward.hip keeps the per-frame conv outputs and
     sweeps back; the gradient may arrive through (mean, std) and, when latent_ys was asked for, through latent_ys.  mask: the
-    observation mask (hip_ops.encoder_mask), a constant; its device image lives in ctx.saved until the backward pass."""
+    observation mask (hip_ops.encoder_mask), a constant; its device image lives in ctx.saved until the backward pass, and so does the
+    host step hint (steps: hip_ops.encoder_steps), so the backward skips the steps the forward skipped."""
 
     @staticmethod
-    def forward(ctx, inputs, timesteps, enc, want_latent, run_backwards, mask, *params):
+    def forward(ctx, inputs, timesteps, enc, want_latent, run_backwards, mask, steps, *params):
         ctx.mode = hip_ops.current_compute_dtype()
-        mean, std, latent, saved = hip_ops.odeconvgru_encode_train(enc, inputs.detach(), timesteps, want_latent, run_backwards, mask)
+        mean, std, latent, saved = hip_ops.odeconvgru_encode_train(enc, inputs.detach(), timesteps, want_latent, run_backwards, mask, steps)
         ctx.enc, ctx.saved, ctx.want_latent = enc, saved, want_latent
         hip_ops.record_versions(ctx, params)
         return (mean, std, latent) if want_latent else (mean, std)
@@ -192,11 +193,11 @@ class _EncodeFn(torch.autograd.Function):
             raise RuntimeError("the encoder's saved activations were already consumed (backward called twice)")
         gin, grads = hip_ops.odeconvgru_encode_backward(ctx.enc, ctx.saved, grad_mean, grad_std, grad_latent if ctx.want_latent else None)
         ctx.saved = None
-        return (gin, None, None, None, None, None) + tuple(grads)
+        return (gin, None, None, None, None, None, None) + tuple(grads)
 
 
-def encode_with_grad(enc, inputs, timesteps, want_latent=False, run_backwards=True, mask=None):
-    return _EncodeFn.apply(inputs, timesteps, enc, bool(want_latent), bool(run_backwards), mask, *hip_ops.encoder_params(enc))
+def encode_with_grad(enc, inputs, timesteps, want_latent=False, run_backwards=True, mask=None, steps=None):
+    return _EncodeFn.apply(inputs, timesteps, enc, bool(want_latent), bool(run_backwards), mask, steps, *hip_ops.encoder_params(enc))
 
 
 class _WarpCompositeFn(torch.autograd.Function):

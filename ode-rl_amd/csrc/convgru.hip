@@ -16,6 +16,9 @@
 // Observation mask (odehip_odeconvgru_encode_masked; upstream Vid-ODE models/base_conv_gru.py:66-70, which the reference's cell takes
 // and forgets): the state a step leaves is m h' + (1-m) h_ode with m = mask[frame, sample], decided inside gn_update_kernel<true>
 // per workgroup.  The convolutions above run for every sample either way; without a mask the launches are gn_update_kernel<false>.
+// Host step hint (odehip_odeconvgru_encode_steps): a step whose frame NO sample observed launches none of the four cell kernels -- the
+// Euler combine writes h_ode straight into the next state buffer (the bits the update kernels copy for m == 0) and a wanted latent
+// slot is filled by state_to_latent_kernel.
 // In the Q4 layout a 32-channel group of one sample is 32 KiB contiguous, so a workgroup holds its whole group in
 // registers (32 floats per thread): statistics are exact two-pass fp32, one HBM read, one write.
 // A cell without GroupNorm (all four gn_* pointers NULL: upstream Vid-ODE's cell, reset gate first) runs the same convolutions with
@@ -95,6 +98,16 @@ __global__ __launch_bounds__(256) void gn_update_kernel(const float* __restrict_
       n[0] = o.x; n[kPix] = o.y; n[2 * kPix] = o.z; n[3 * kPix] = o.w;
     }
   }
+}
+
+// Q4 state (B,hid) -> its NCHW latent slot, for a step whose cell did not run: grid (hid / 4, B), one f32x4 per thread, the indexing of
+// the update kernels' epilogue (quad g * 8 + q of sample b, pixel threadIdx.x).
+__global__ __launch_bounds__(256) void state_to_latent_kernel(const float* __restrict__ h, float* __restrict__ h_out_nchw,
+                                                              long long nchw_batch_stride, int hid_quads) {
+  const int q = blockIdx.x, b = blockIdx.y;
+  const f32x4 o = ((const f32x4*)h)[((size_t)b * hid_quads + q) * kPix + threadIdx.x];
+  float* n = h_out_nchw + (size_t)b * nchw_batch_stride + (size_t)(q * 4) * kPix + threadIdx.x;
+  n[0] = o.x; n[kPix] = o.y; n[2 * kPix] = o.z; n[3 * kPix] = o.w;
 }
 
 // head output (B, 2*out_ch) Q4 -> mean (B,out_ch) NCHW, std = |.| (B,out_ch) NCHW   (ODEConvGRUCell.py:35-36)
@@ -206,6 +219,9 @@ void launch_split_mean_std(const float* head_out, float* mean, float* stdv, int 
   hipLaunchKernelGGL(split_mean_std_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, head_out, mean, stdv, total, out_ch / 4);
 }
 int check_cell_desc(const odehip_convgru_cell* c) { return check_cell(c); }
+void launch_state_to_latent(const float* h, float* h_out_nchw, long long nchw_batch_stride, int hidden, int batch, hipStream_t stream) {
+  hipLaunchKernelGGL(state_to_latent_kernel, dim3(hidden / 4, batch), dim3(256), 0, stream, h, h_out_nchw, nchw_batch_stride, hidden / 4);
+}
 }  // namespace odehip
 
 // x: (B,input,16,16), h: (B,hidden,16,16) NCHW -> h_next NCHW      (ConvGRUCell.forward with seq_len = 1)
@@ -252,10 +268,20 @@ extern "C" int odehip_odeconvgru_encode(const odehip_encoder* e, const float* in
                                          workspace_bytes, stream_, nullptr);
 }
 
-// mask_tb: (T, B) on the device, row i = the observation mask of FRAME i (whenever it is visited), or null = all observed
 extern "C" int odehip_odeconvgru_encode_masked(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames,
                                                int batch, int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw,
                                                void* workspace, size_t workspace_bytes, void* stream_, const float* mask_tb) {
+  return odehip_odeconvgru_encode_steps(e, inputs_nchw, t_host, n_frames, batch, run_backwards, mean_nchw, std_nchw, latent_nchw, workspace,
+                                        workspace_bytes, stream_, mask_tb, nullptr, nullptr);
+}
+
+// mask_tb: (T, B) on the device, row i = the observation mask of FRAME i (whenever it is visited), or null = all observed.
+// step_observed_host: T bytes on the host, byte i == 0 = no sample observed FRAME i (its step runs without the cell), or null = every
+// step runs the cell.  cell_steps_run (host, may be null): the number of steps that did.
+extern "C" int odehip_odeconvgru_encode_steps(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames,
+                                              int batch, int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw,
+                                              void* workspace, size_t workspace_bytes, void* stream_, const float* mask_tb,
+                                              const unsigned char* step_observed_host, int* cell_steps_run) {
   ODEHIP_REQUIRE(e, "odeconvgru_encode: null descriptor");
   int rc = check_stack(&e->f_enc);
   if (rc != ODEHIP_OK) return rc;
@@ -302,9 +328,10 @@ extern "C" int odehip_odeconvgru_encode_masked(const odehip_encoder* e, const fl
   if (rc != ODEHIP_OK) return rc;
   ODEHIP_CHECK_HIP(hipMemsetAsync(hbuf[0], 0, hs, stream));  // prev_input = zeros
 
-  int cur = 0;
+  int cur = 0, n_run = 0;
   for (int idx = 0; idx < n_frames; ++idx) {
     const int i = run_backwards ? n_frames - 1 - idx : idx;
+    const bool observed = step_is_observed(step_observed_host, i);
     // h_ode = h + dt * f_enc(h)
     CombineArgs c;
     memset(&c, 0, sizeof(c));
@@ -313,10 +340,16 @@ extern "C" int odehip_odeconvgru_encode_masked(const odehip_encoder* e, const fl
     c.h_ptr = dts + idx;
     c.n_prev = 0;
     c.c1[0] = 1.0f;
-    c.out1 = h_ode;
+    c.out1 = observed ? h_ode : hbuf[cur ^ 1];  // nobody observed frame i: the Euler-advanced state IS the next state
     rc = enqueue_f(&e->f_enc, hbuf[cur], batch, ping, pong, &c, nullptr, nullptr, stream);
     if (rc != ODEHIP_OK) return rc;
     float* lat = latent_nchw ? latent_nchw + (size_t)idx * C * kPix : nullptr;  // latent_ys (B,T,C,H,W): slot idx of each sample
+    if (!observed) {
+      if (lat) launch_state_to_latent(hbuf[cur ^ 1], lat, (long long)n_frames * C * kPix, C, batch, stream);
+      cur ^= 1;
+      continue;
+    }
+    ++n_run;
     rc = cell_step(&e->cell, frames + (size_t)i * hf, h_ode, hbuf[cur ^ 1], lat, (long long)n_frames * C * kPix, batch, gates, z,
                    rh, cand, stream, mask_tb ? mask_tb + (size_t)i * batch : nullptr);
     if (rc != ODEHIP_OK) return rc;
@@ -332,5 +365,6 @@ extern "C" int odehip_odeconvgru_encode_masked(const odehip_encoder* e, const fl
   hipLaunchKernelGGL(split_mean_std_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, head_out, mean_nchw, std_nchw, total,
                      e->out_ch / 4);
   ODEHIP_CHECK_HIP(hipGetLastError());
+  if (cell_steps_run) *cell_steps_run = n_run;
   return ODEHIP_OK;
 }

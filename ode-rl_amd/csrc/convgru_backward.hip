@@ -20,6 +20,12 @@
 // kernel stores exact zeros, so every later product of an unobserved (frame, sample) is 0 * (what the forward kept): exactly zero
 // for finite frames.  Containment of a NON-FINITE unobserved frame is promised for the forward only -- here the input-gradient and
 // weight-gradient products would multiply it by those zeros.
+// Host step hint (the *_steps entry points): a step whose frame NO sample observed.  Forward: the Euler combine writes h_ode into the
+// next state slot; the per-step h_ode / gates / z / rh / cand slots stay unwritten (the sweep does not read them).  Sweep: no cell
+// kernel and no input-gradient convolution; the gradient at the state behind the step IS the seed of the Euler step's adjoint, so
+// whoever produces it (the head, or the dynamics chain of the step behind) writes it straight into that step's seed slot, where the
+// dynamics' weight-gradient table finds it; the frame's gradient slab is zero-filled.  The cell's weight-gradient tables list the
+// observed steps only, and the GroupNorm partial rows of the others are zero-filled (the reduction keeps its T * B rows and its order).
 // The norm-free cell (all four gn_* pointers NULL; upstream Vid-ODE's, reset gate first): forward and sweep are the same launches with
 // plain_update_bwd_kernel / plain_gates_bwd_kernel (convgru_plain.hip) in place of the two GroupNorm kernels; no affine partials are
 // written or reduced and the gn_* members of the gradient structs are not touched.
@@ -422,6 +428,16 @@ extern "C" int odehip_odeconvgru_encode_train(const odehip_encoder* e, const flo
 extern "C" int odehip_odeconvgru_encode_train_masked(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames,
                                                      int batch, int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw,
                                                      void* workspace, size_t workspace_bytes, void* stream_, const float* mask_tb) {
+  return odehip_odeconvgru_encode_train_steps(e, inputs_nchw, t_host, n_frames, batch, run_backwards, mean_nchw, std_nchw, latent_nchw,
+                                              workspace, workspace_bytes, stream_, mask_tb, nullptr, nullptr);
+}
+
+// step_observed_host: T bytes on the host indexed by frame (0 = no sample observed it: the step keeps the state in front of the Euler
+// step and the dynamics' hidden activations, nothing of the cell), or null; the backward call is given the same bytes.
+extern "C" int odehip_odeconvgru_encode_train_steps(const odehip_encoder* e, const float* inputs_nchw, const double* t_host, int n_frames,
+                                                    int batch, int run_backwards, float* mean_nchw, float* std_nchw, float* latent_nchw,
+                                                    void* workspace, size_t workspace_bytes, void* stream_, const float* mask_tb,
+                                                    const unsigned char* step_observed_host, int* cell_steps_run) {
   int rc = check_encoder(e, "odeconvgru_encode_train");
   if (rc != ODEHIP_OK) return rc;
   ODEHIP_REQUIRE(inputs_nchw && t_host && mean_nchw && std_nchw && workspace, "odeconvgru_encode_train: null pointer");
@@ -439,20 +455,27 @@ extern "C" int odehip_odeconvgru_encode_train_masked(const odehip_encoder* e, co
   if (rc != ODEHIP_OK) return rc;
   ODEHIP_CHECK_HIP(hipMemsetAsync(L.hstate(ws, 0), 0, hs_b, stream));
   float* hidv[ODEHIP_MAX_LAYERS];
+  int n_run = 0;
   for (int idx = 0; idx < n_frames; ++idx) {
     const int i = visited_frame(n_frames, idx, run_backwards);
+    const bool observed = step_is_observed(step_observed_host, i);
     CombineArgs c;
     memset(&c, 0, sizeof(c));
     c.k_scale = 1.0f;
     c.y = L.hstate(ws, idx);
     c.h_ptr = L.p(ws, L.off_dts) + idx;
     c.c1[0] = 1.0f;
-    c.out1 = L.per(ws, L.off_hode, idx, L.hs);
+    c.out1 = observed ? L.per(ws, L.off_hode, idx, L.hs) : L.hstate(ws, idx + 1);  // nobody observed frame i: h_ode IS the next state
     for (int l = 0; l < NH; ++l) hidv[l] = L.hidden(ws, idx, l);
     rc = enqueue_f_saving(&e->f_enc, L.hstate(ws, idx), batch, hidv, L.p(ws, L.off_ping), L.p(ws, L.off_pong), &c, nullptr, nullptr,
                           stream);
     if (rc != ODEHIP_OK) return rc;
     float* lat = latent_nchw ? latent_nchw + (size_t)idx * C * kPix : nullptr;  // latent_ys (B,T,C,H,W): slot idx of each sample
+    if (!observed) {
+      if (lat) launch_state_to_latent(L.hstate(ws, idx + 1), lat, (long long)n_frames * C * kPix, C, batch, stream);
+      continue;
+    }
+    ++n_run;
     rc = cell_step_q4(&e->cell, L.frame(ws, i), L.per(ws, L.off_hode, idx, L.hs), L.hstate(ws, idx + 1), lat, (long long)n_frames * C * kPix, batch,
                       L.per(ws, L.off_gates, idx, 2 * L.hs), L.per(ws, L.off_z, idx, L.hs), L.per(ws, L.off_rh, idx, L.hs),
                       L.per(ws, L.off_cand, idx, L.hs), stream, mask_tb ? mask_tb + (size_t)i * batch : nullptr);
@@ -466,6 +489,7 @@ extern "C" int odehip_odeconvgru_encode_train_masked(const odehip_encoder* e, co
   if (rc != ODEHIP_OK) return rc;
   launch_split_mean_std(L.p(ws, L.off_headout), mean_nchw, std_nchw, batch, e->out_ch, stream);
   ODEHIP_CHECK_HIP(hipGetLastError());
+  if (cell_steps_run) *cell_steps_run = n_run;
   return ODEHIP_OK;
 }
 
@@ -485,6 +509,19 @@ extern "C" int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e,
                                                         const float* grad_std_nchw, const float* grad_latent_nchw,
                                                         float* grad_inputs_nchw, const odehip_encoder_grads* gr, void* workspace,
                                                         size_t workspace_bytes, void* stream_, const float* mask_tb) {
+  return odehip_odeconvgru_encode_backward_steps(e, eb, t_host, n_frames, batch, run_backwards, grad_mean_nchw, grad_std_nchw,
+                                                 grad_latent_nchw, grad_inputs_nchw, gr, workspace, workspace_bytes, stream_, mask_tb, nullptr,
+                                                 nullptr);
+}
+
+// step_observed_host: the bytes the forward call (odehip_odeconvgru_encode_train_steps) was given, or null.  A step whose frame nobody
+// observed contributes nothing to the cell's gradients and reads nothing of its frame: no cell kernel runs for it.
+extern "C" int odehip_odeconvgru_encode_backward_steps(const odehip_encoder* e, const odehip_encoder_bwd* eb, const double* t_host,
+                                                       int n_frames, int batch, int run_backwards, const float* grad_mean_nchw,
+                                                       const float* grad_std_nchw, const float* grad_latent_nchw,
+                                                       float* grad_inputs_nchw, const odehip_encoder_grads* gr, void* workspace,
+                                                       size_t workspace_bytes, void* stream_, const float* mask_tb,
+                                                       const unsigned char* step_observed_host, int* cell_steps_run) {
   int rc = check_encoder(e, "odeconvgru_encode_backward");
   if (rc != ODEHIP_OK) return rc;
   ODEHIP_REQUIRE(eb && t_host && grad_mean_nchw && grad_std_nchw && grad_inputs_nchw && gr && workspace,
@@ -502,8 +539,13 @@ extern "C" int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e,
   ODEHIP_REQUIRE(plain || (gr->gn_gates_w && gr->gn_gates_b && gr->gn_can_w && gr->gn_can_b),
                  "odeconvgru_encode_backward: null GroupNorm gradient output");
   float* dts = L.p(ws, L.off_dts);
-  float* gh = L.p(ws, L.off_gh);
-  float* gh_next = L.p(ws, L.off_gh + L.hs);
+  // steps (in visiting order) whose cell ran; the gradient at the state behind step idx lives in one of two buffers, or, if that
+  // step's cell did not run, in its seed slot (fh >= hs bytes): it is the seed of the Euler step's adjoint as it stands
+  bool ran[64];
+  int n_run = 0;
+  for (int idx = 0; idx < T; ++idx) n_run += (ran[idx] = step_is_observed(step_observed_host, visited_frame(T, idx, run_backwards)));
+  auto gh_home = [&](int idx) { return ran[idx] ? L.p(ws, L.off_gh + (size_t)((T - 1 - idx) & 1) * L.hs) : L.gp(ws, idx, NH); };
+  float* gh = gh_home(T - 1);
   float* gz_pre = L.p(ws, L.off_gzpre);
   float* gh_ode = L.p(ws, L.off_ghode);
   float* gx_c = L.p(ws, L.off_gxc);
@@ -511,6 +553,8 @@ extern "C" int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e,
   float* pgg = L.p(ws, L.off_pgg);  // [2][T*B][2C]: dgamma then dbeta partials of the gates GroupNorm
   float* pgc = L.p(ws, L.off_pgc);  // [2][T*B][C]
   const size_t pgg_half = (size_t)T * batch * 2 * C, pgc_half = (size_t)T * batch * C;
+  if (!plain && n_run < T)  // the partial rows of the steps without a cell: exact zeros, as gn_update_bwd_kernel<true> stores for m == 0
+    ODEHIP_CHECK_HIP(hipMemsetAsync(pgg, 0, L.off_tab - L.off_pgg, stream));
 
   auto conv_bwd = [&](const float* src, int cin, int cout, int k, const float* wt, int combine, const BwdArgs* bw, float* dst,
                       const void* wbf = nullptr, const float* wwino = nullptr) {
@@ -550,40 +594,45 @@ extern "C" int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e,
       hipLaunchKernelGGL(add_nchw_slice_to_q4_kernel, dim3((total + 255) / 256), dim3(256), 0, stream,
                          grad_latent_nchw + (size_t)idx * C * kPix, (long long)T * C * kPix, gh, total, C / 4);
     }
-    float* g_cand = L.per(ws, L.off_gcand, idx, L.hs);
-    float* g_gates = L.per(ws, L.off_ggates, idx, 2 * L.hs);
-    const float* h_ode = L.per(ws, L.off_hode, idx, L.hs);
-    const float* mask_b = mask_tb ? mask_tb + (size_t)i * batch : nullptr;
-    if (plain)  // writes the update half of g_gates as well: gz_pre stays unused
-      launch_plain_update_bwd(L.per(ws, L.off_cand, idx, L.hs), gh, L.per(ws, L.off_z, idx, L.hs), h_ode, g_cand, g_gates, gh_ode, C, batch,
-                              mask_b, stream);
-    else if (mask_tb)
-      hipLaunchKernelGGL(gn_update_bwd_kernel<true>, dim3(HG, batch), dim3(256), 0, stream, L.per(ws, L.off_cand, idx, L.hs), e->cell.gn_can_w,
-                         e->cell.gn_can_b, gh, L.per(ws, L.off_z, idx, L.hs), h_ode, g_cand, gz_pre, gh_ode,
-                         pgc + (size_t)idx * batch * C, pgc + pgc_half + (size_t)idx * batch * C, HG, mask_tb + (size_t)i * batch);
-    else
-      hipLaunchKernelGGL(gn_update_bwd_kernel<false>, dim3(HG, batch), dim3(256), 0, stream, L.per(ws, L.off_cand, idx, L.hs), e->cell.gn_can_w,
-                         e->cell.gn_can_b, gh, L.per(ws, L.off_z, idx, L.hs), h_ode, g_cand, gz_pre, gh_ode,
-                         pgc + (size_t)idx * batch * C, pgc + pgc_half + (size_t)idx * batch * C, HG, nullptr);
-    if ((rc = conv_bwd(g_cand, C, C, ks, eb->w_can_dx, 0, nullptr, gx_c, eb->bf16[2], eb->wino[2])) != ODEHIP_OK) return rc;
-    if ((rc = conv_bwd(g_cand, C, C, ks, eb->w_can_dh, 0, nullptr, g_rh, eb->bf16[3], eb->wino[3])) != ODEHIP_OK) return rc;
-    if (plain)
-      launch_plain_gates_bwd(L.per(ws, L.off_gates, idx, 2 * L.hs), g_rh, h_ode, gh_ode, g_gates, C, batch, mask_b, stream);
-    else
-      hipLaunchKernelGGL(gn_gates_bwd_kernel, dim3(2 * HG, batch), dim3(256), 0, stream, L.per(ws, L.off_gates, idx, 2 * L.hs),
-                         e->cell.gn_gates_w, e->cell.gn_gates_b, gz_pre, g_rh, h_ode, gh_ode, g_gates,
-                         pgg + (size_t)idx * batch * 2 * C, pgg + pgg_half + (size_t)idx * batch * 2 * C, HG);
-    BwdArgs w;
-    memset(&w, 0, sizeof(w));
-    w.n_targets = 1;
-    w.tgt[0].out = L.per(ws, L.off_gx, i, L.hs);  // gradient of observed frame i
-    w.tgt[0].srcA = gx_c;
-    w.tgt[0].a_c = 1.0f;
-    w.tgt[0].g_c = 1.0f;
-    if ((rc = conv_bwd(g_gates, 2 * C, C, ks, eb->w_gates_dx, 3, &w, nullptr, eb->bf16[0], eb->wino[0])) != ODEHIP_OK) return rc;
-    w.tgt[0].out = L.gp(ws, idx, NH);             // seed of the encoder-dynamics chain = total gradient of h_ode
-    w.tgt[0].srcA = gh_ode;
-    if ((rc = conv_bwd(g_gates, 2 * C, C, ks, eb->w_gates_dh, 3, &w, nullptr, eb->bf16[1], eb->wino[1])) != ODEHIP_OK) return rc;
+    float* gh_next = idx > 0 ? gh_home(idx - 1) : L.p(ws, L.off_gh + (size_t)(T & 1) * L.hs);  // idx == 0: nobody reads it
+    if (ran[idx]) {
+      float* g_cand = L.per(ws, L.off_gcand, idx, L.hs);
+      float* g_gates = L.per(ws, L.off_ggates, idx, 2 * L.hs);
+      const float* h_ode = L.per(ws, L.off_hode, idx, L.hs);
+      const float* mask_b = mask_tb ? mask_tb + (size_t)i * batch : nullptr;
+      if (plain)  // writes the update half of g_gates as well: gz_pre stays unused
+        launch_plain_update_bwd(L.per(ws, L.off_cand, idx, L.hs), gh, L.per(ws, L.off_z, idx, L.hs), h_ode, g_cand, g_gates, gh_ode, C, batch,
+                                mask_b, stream);
+      else if (mask_tb)
+        hipLaunchKernelGGL(gn_update_bwd_kernel<true>, dim3(HG, batch), dim3(256), 0, stream, L.per(ws, L.off_cand, idx, L.hs), e->cell.gn_can_w,
+                           e->cell.gn_can_b, gh, L.per(ws, L.off_z, idx, L.hs), h_ode, g_cand, gz_pre, gh_ode,
+                           pgc + (size_t)idx * batch * C, pgc + pgc_half + (size_t)idx * batch * C, HG, mask_tb + (size_t)i * batch);
+      else
+        hipLaunchKernelGGL(gn_update_bwd_kernel<false>, dim3(HG, batch), dim3(256), 0, stream, L.per(ws, L.off_cand, idx, L.hs), e->cell.gn_can_w,
+                           e->cell.gn_can_b, gh, L.per(ws, L.off_z, idx, L.hs), h_ode, g_cand, gz_pre, gh_ode,
+                           pgc + (size_t)idx * batch * C, pgc + pgc_half + (size_t)idx * batch * C, HG, nullptr);
+      if ((rc = conv_bwd(g_cand, C, C, ks, eb->w_can_dx, 0, nullptr, gx_c, eb->bf16[2], eb->wino[2])) != ODEHIP_OK) return rc;
+      if ((rc = conv_bwd(g_cand, C, C, ks, eb->w_can_dh, 0, nullptr, g_rh, eb->bf16[3], eb->wino[3])) != ODEHIP_OK) return rc;
+      if (plain)
+        launch_plain_gates_bwd(L.per(ws, L.off_gates, idx, 2 * L.hs), g_rh, h_ode, gh_ode, g_gates, C, batch, mask_b, stream);
+      else
+        hipLaunchKernelGGL(gn_gates_bwd_kernel, dim3(2 * HG, batch), dim3(256), 0, stream, L.per(ws, L.off_gates, idx, 2 * L.hs),
+                           e->cell.gn_gates_w, e->cell.gn_gates_b, gz_pre, g_rh, h_ode, gh_ode, g_gates,
+                           pgg + (size_t)idx * batch * 2 * C, pgg + pgg_half + (size_t)idx * batch * 2 * C, HG);
+      BwdArgs w;
+      memset(&w, 0, sizeof(w));
+      w.n_targets = 1;
+      w.tgt[0].out = L.per(ws, L.off_gx, i, L.hs);  // gradient of observed frame i
+      w.tgt[0].srcA = gx_c;
+      w.tgt[0].a_c = 1.0f;
+      w.tgt[0].g_c = 1.0f;
+      if ((rc = conv_bwd(g_gates, 2 * C, C, ks, eb->w_gates_dx, 3, &w, nullptr, eb->bf16[0], eb->wino[0])) != ODEHIP_OK) return rc;
+      w.tgt[0].out = L.gp(ws, idx, NH);             // seed of the encoder-dynamics chain = total gradient of h_ode
+      w.tgt[0].srcA = gh_ode;
+      if ((rc = conv_bwd(g_gates, 2 * C, C, ks, eb->w_gates_dh, 3, &w, nullptr, eb->bf16[1], eb->wino[1])) != ODEHIP_OK) return rc;
+    } else {  // gh already sits in the seed slot; the frame's gradient is exactly zero
+      ODEHIP_CHECK_HIP(hipMemsetAsync(L.per(ws, L.off_gx, i, L.hs), 0, (size_t)batch * C * kPix * 4, stream));
+    }
     // h_ode = h + dt f(h):  gh = seed + dt J_f(h)^T seed
     {
       float* gpv[ODEHIP_MAX_LAYERS + 1];
@@ -601,7 +650,7 @@ extern "C" int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e,
       a.bwd.tgt[0].g_h = 1.0f;
       if ((rc = enqueue_dgrad_chain(&e->f_enc, &eb->f_dgrad, batch, gpv, hv, a, stream)) != ODEHIP_OK) return rc;
     }
-    float* t = gh; gh = gh_next; gh_next = t;
+    gh = gh_next;
   }
   rc = odehip_q4_to_nchw(L.p(ws, L.off_gx), grad_inputs_nchw, T * batch, C, stream);
   if (rc != ODEHIP_OK) return rc;
@@ -623,11 +672,12 @@ extern "C" int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e,
       h.a = l == 0 ? L.hstate(ws, idx) : L.hidden(ws, idx, l - 1);
       h.scale = frame_dt(t_host, T, idx, run_backwards);
     }
-  for (int j = 0; j < 2; ++j) {   // ConvGRU convs on cat(x, state): the two halves of the input are separate tensors
+  for (int j = 0; j < 2; ++j) {   // ConvGRU convs on cat(x, state): the two halves of the input are separate tensors; the steps whose cell ran
     const size_t gbytes = (size_t)(jobs[j].g_ch / C) * L.hs;
     for (int half = 0; half < 2; ++half)
-      for (int idx = 0; idx < T; ++idx) {
-        WgradPair& h = host[(size_t)(NL + 2 * j + half) * T + idx];
+      for (int idx = 0, k = 0; idx < T; ++idx) {
+        if (!ran[idx]) continue;
+        WgradPair& h = host[(size_t)(NL + 2 * j + half) * T + k++];
         h.g = L.per(ws, jobs[j].g_off, idx, gbytes);
         h.a = half == 0 ? L.frame(ws, visited_frame(T, idx, run_backwards)) : L.per(ws, jobs[j].a2_off, idx, L.hs);
         h.scale = 1.0f;
@@ -652,10 +702,15 @@ extern "C" int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e,
   }
   for (int j = 0; j < 2; ++j) {
     const CatJob& J = jobs[j];
+    if (n_run == 0) {  // no step ran the cell: no launch, the gradients are exact zeros
+      ODEHIP_CHECK_HIP(hipMemsetAsync(J.dw, 0, (size_t)J.g_ch * 2 * C * ks * ks * 4, stream));
+      ODEHIP_CHECK_HIP(hipMemsetAsync(J.db, 0, (size_t)J.g_ch * 4, stream));
+      continue;
+    }
     for (int half = 0; half < 2; ++half) {
       const WgradPair* const table = table0 + (size_t)(NL + 2 * j + half) * T;
       const bool bf16 = ks == 5 && e->cell.w_gates_bf16;  // bf16 compute mode: operands rounded to bf16, fp32 accumulation
-      rc = launch_wgrad_layer(table, T, batch, bf16 ? 4 : wgrad_esplit(batch, T), slabs, J.dw, J.db, ks, J.g_ch, C, 2 * C, half * C, bf16,
+      rc = launch_wgrad_layer(table, n_run, batch, bf16 ? 4 : wgrad_esplit(batch, n_run), slabs, J.dw, J.db, ks, J.g_ch, C, 2 * C, half * C, bf16,
                               half == 0, stream);
       if (rc != ODEHIP_OK) return rc;
     }
@@ -673,6 +728,7 @@ extern "C" int odehip_odeconvgru_encode_backward_masked(const odehip_encoder* e,
     hipLaunchKernelGGL(reduce_rows_kernel, dim3(C), dim3(256), 0, stream, pgc + pgc_half, T * batch, C, gr->gn_can_b);
   }
   ODEHIP_CHECK_HIP(hipGetLastError());
+  if (cell_steps_run) *cell_steps_run = n_run;
   return ODEHIP_OK;
 }
 

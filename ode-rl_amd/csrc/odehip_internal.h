@@ -202,6 +202,10 @@ void launch_plain_update_bwd(const float* cand_raw, const float* gh, const float
                              float* gh_out, int hidden, int batch, const float* mask_b, hipStream_t stream);
 void launch_plain_gates_bwd(const float* gates_raw, const float* g_rh, const float* h, float* gh_io, float* g_gates_raw, int hidden,
                             int batch, const float* mask_b, hipStream_t stream);
+// the host step hint of the odehip_odeconvgru_encode*_steps entry points: FRAME i runs the cell unless its byte is 0 (null: every frame)
+inline bool step_is_observed(const unsigned char* step_observed_host, int frame) { return !step_observed_host || step_observed_host[frame] != 0; }
+// Q4 state (B,hidden) -> the NCHW latent slot of a step whose cell did not run (convgru.hip)
+void launch_state_to_latent(const float* h, float* h_out_nchw, long long nchw_batch_stride, int hidden, int batch, hipStream_t stream);
 int upload_floats(float* dst, const float* src, int n, hipStream_t stream);  // scalars travel as kernel arguments (async)
 // f(x) with the stage combine fused into the last conv; `hidden` (n_convs-1 buffers) keeps the ReLU outputs for a backward pass
 int enqueue_f(const odehip_convstack* f, const float* x_q4, int batch, float* ping, float* pong, const CombineArgs* cmb,

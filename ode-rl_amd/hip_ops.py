@@ -8,6 +8,7 @@ import os
 import threading
 import weakref
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1139,6 +1140,8 @@ class PackedEncoder:
         self._stamp = None
         self._keep = None
         self.desc = None
+        self.last_cell_steps = None            # steps for which the last forward call launched the cell (cell_steps_run)
+        self.last_cell_steps_backward = None   # the same of the last backward call
 
     def refresh(self):
         fd = self.f_stack.refresh()
@@ -1206,10 +1209,63 @@ def encoder_mask(mask, n_frames, batch, device, who="odeconvgru_encode"):
     return mask.reshape(batch, n_frames).to(device=device, dtype=torch.float32).t().contiguous()
 
 
-def _encode(enc, inputs, timesteps, want_latent, run_backwards, train, mask=None):
+def _check_mask(mask, n_frames, batch, who):
+    if not isinstance(mask, torch.Tensor):
+        raise TypeError(f"{who}: mask must be a torch.Tensor or None (got {type(mask).__name__})")
+    if mask.is_complex():
+        raise TypeError(f"{who}: mask must be a real or boolean tensor (got {mask.dtype})")
+    if tuple(mask.shape) not in ((batch, n_frames), (batch, n_frames, 1)):
+        raise ValueError(f"{who}: mask must be (B, T) = ({batch}, {n_frames}) (or with a trailing 1), batch-first; got {tuple(mask.shape)}")
+
+
+def observed_steps(mask, n_frames, batch, who="odeconvgru_encode"):
+    """Which frames ANY sample observed, as the host step hint of the odehip_odeconvgru_encode*_steps calls: None or a length-T uint8
+    numpy array, byte i = 1 iff mask[b, i] != 0 for some b (after encoder_mask's dtype rule: float32 as it is, so fractional values
+    count and -0.0 does not; any other dtype as mask != 0).  Pure host code: a mask on the HOST is looked at where it is; a mask on the
+    device gives None -- it is never read back -- and so does no mask.  mask: (B, T) or (B, T, 1) as for encoder_mask."""
+    if mask is None:
+        return None
+    _check_mask(mask, n_frames, batch, who)
+    if mask.device.type != "cpu":
+        return None
+    host = mask.detach()
+    try:
+        values = host.numpy()                # a view: a handful of numpy calls on B x T values, a few microseconds on the launch path
+    except (TypeError, RuntimeError):        # a dtype numpy lacks (bfloat16)
+        values = (host != 0).numpy()
+    return np.ascontiguousarray((values.reshape(batch, n_frames) != 0).any(axis=0), dtype=np.uint8)
+
+
+def encoder_steps(steps, mask, n_frames, batch, who="odeconvgru_encode"):
+    """The `steps=` keyword of the encoder calls -> the host step hint (None or a length-T uint8 numpy array).  None (the default):
+    derived from a host mask by observed_steps.  False: no hint, every step launches the cell.  A length-T sequence of booleans (list,
+    numpy array, host tensor): the caller's own hint, with a device mask or with no mask at all -- a frame it switches off is computed
+    as if its whole mask row were 0, whatever the mask says."""
+    if steps is None or steps is True:
+        return observed_steps(mask, n_frames, batch, who)
+    if steps is False:
+        return None
+    if isinstance(steps, torch.Tensor):
+        if steps.device.type != "cpu":
+            raise TypeError(f"{who}: steps must live on the host (a list, a numpy array or a CPU tensor): a tensor on {steps.device} would "
+                            "have to be read back, which costs the host synchronisation the hint exists to avoid")
+        steps = steps.detach().numpy()
+    arr = np.asarray(steps)
+    if arr.ndim != 1 or arr.shape[0] != n_frames:
+        raise ValueError(f"{who}: steps must be a sequence of T = {n_frames} booleans, one per frame; got shape {tuple(arr.shape)}")
+    return np.ascontiguousarray(arr != 0, dtype=np.uint8)
+
+
+def _steps_ptr(steps):
+    return None if steps is None else steps.ctypes.data_as(ctypes.c_void_p)
+
+
+def _encode(enc, inputs, timesteps, want_latent, run_backwards, train, mask=None, steps=None):
     """The encoder forward of both paths: (mean, std, latent_ys or None, what odeconvgru_encode_backward needs).  train: the entry point
-    that keeps the per-frame activations, in a private workspace.  mask: see encoder_mask; None = every frame observed."""
-    if isinstance(inputs, torch.Tensor) and inputs.dim() == 5:   # (the mask is refused before anything is built or launched)
+    that keeps the per-frame activations, in a private workspace.  mask: see encoder_mask; None = every frame observed.  steps: see
+    encoder_steps; the step count of the call goes to enc.last_cell_steps."""
+    if isinstance(inputs, torch.Tensor) and inputs.dim() == 5:   # (mask and steps are refused before anything is built or launched)
+        steps = encoder_steps(steps, mask, inputs.shape[0], inputs.shape[1])
         mask = encoder_mask(mask, inputs.shape[0], inputs.shape[1], inputs.device)
     require_device_tensor(inputs, "inputs")
     d = enc.refresh()
@@ -1222,28 +1278,31 @@ def _encode(enc, inputs, timesteps, want_latent, run_backwards, train, mask=None
     lib = _lib.load()
     if train:
         ws = alloc_workspace(lib.odehip_encoder_train_workspace_bytes(ctypes.byref(d), t, b), inputs.device)   # owned by this call's graph node
-        fn = lib.odehip_odeconvgru_encode_train_masked
+        fn = lib.odehip_odeconvgru_encode_train_steps
     else:
         ws = workspace(("enc", t, b, c), lib.odehip_encoder_workspace_bytes(ctypes.byref(d), t, b), inputs.device)
-        fn = lib.odehip_odeconvgru_encode_masked
+        fn = lib.odehip_odeconvgru_encode_steps
     mean = torch.empty((b, d.out_ch, 16, 16), dtype=torch.float32, device=inputs.device)
     std = torch.empty_like(mean)
     latent = torch.empty((b, t, c, 16, 16), dtype=torch.float32, device=inputs.device) if want_latent else None
+    n_run = ctypes.c_int(-1)
     _lib.check(fn(ctypes.byref(d), _ptr(inputs), tarr, t, b, int(bool(run_backwards)), _ptr(mean), _ptr(std), _ptr(latent), _ptr(ws),
-                  ws.numel(), _stream(), _ptr(mask)))
-    return mean, std, latent, (ws, tarr, t, b, c, int(bool(run_backwards)), mask)
+                  ws.numel(), _stream(), _ptr(mask), _steps_ptr(steps), ctypes.byref(n_run)))
+    enc.last_cell_steps = n_run.value
+    return mean, std, latent, (ws, tarr, t, b, c, int(bool(run_backwards)), mask, steps)
 
 
-def odeconvgru_encode_train(enc, inputs, timesteps, want_latent=False, run_backwards=True, mask=None):
+def odeconvgru_encode_train(enc, inputs, timesteps, want_latent=False, run_backwards=True, mask=None, steps=None):
     """Forward of the training path: returns (mean, std, latent_ys or None, saved) -- `saved` holds the workspace the backward
-    call needs and the (T, B) device image of `mask`."""
-    return _encode(enc, inputs, timesteps, want_latent, run_backwards, True, mask)
+    call needs, the (T, B) device image of `mask` and the host step hint (see encoder_steps), so the backward uses the forward's."""
+    return _encode(enc, inputs, timesteps, want_latent, run_backwards, True, mask, steps)
 
 
 def odeconvgru_encode_backward(enc, saved, grad_mean, grad_std, grad_latent=None, mask=None):
     """(grad_inputs (T,B,C,16,16), [gradient of every tensor of encoder_params(enc)]); grad_latent: what arrives through latent_ys.
-    mask: the forward call's mask; None = the image of it that `saved` holds (none if the forward had none)."""
-    ws, tarr, t, b, c, run_backwards, mask_tb = saved
+    mask: the forward call's mask; None = the image of it that `saved` holds (none if the forward had none).  The step hint is the
+    forward's (in `saved`); the number of steps whose cell kernels ran goes to enc.last_cell_steps_backward."""
+    ws, tarr, t, b, c, run_backwards, mask_tb, steps = saved
     if mask is not None:
         mask_tb = encoder_mask(mask, t, b, ws.device, "odeconvgru_encode_backward")
     d = enc.refresh()
@@ -1268,14 +1327,17 @@ def odeconvgru_encode_backward(enc, saved, grad_mean, grad_std, grad_latent=None
     (g.w_gates, g.b_gates, g.gn_gates_w, g.gn_gates_b, g.w_can, g.b_can, g.gn_can_w, g.gn_can_b) = enc.packed_cell.grad_slots(grads[2 * nl:-4])
     g.w_head0, g.b_head0, g.w_head1, g.b_head1 = (x.data_ptr() for x in grads[-4:])
     gin = torch.empty((t, b, c, 16, 16), dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().odehip_odeconvgru_encode_backward_masked(ctypes.byref(d), ctypes.byref(bw), tarr, t, b, run_backwards,
-                                                                    _ptr(grad_mean), _ptr(grad_std), _ptr(grad_latent), _ptr(gin),
-                                                                    ctypes.byref(g), _ptr(ws), ws.numel(), _stream(), _ptr(mask_tb)))
+    n_run = ctypes.c_int(-1)
+    _lib.check(_lib.load().odehip_odeconvgru_encode_backward_steps(ctypes.byref(d), ctypes.byref(bw), tarr, t, b, run_backwards,
+                                                                   _ptr(grad_mean), _ptr(grad_std), _ptr(grad_latent), _ptr(gin),
+                                                                   ctypes.byref(g), _ptr(ws), ws.numel(), _stream(), _ptr(mask_tb),
+                                                                   _steps_ptr(steps), ctypes.byref(n_run)))
+    enc.last_cell_steps_backward = n_run.value
     return gin, grads
 
 
-def odeconvgru_encode(enc, inputs, timesteps, want_latent=False, run_backwards=True, mask=None):
-    return _encode(enc, inputs, timesteps, want_latent, run_backwards, False, mask)[:3]
+def odeconvgru_encode(enc, inputs, timesteps, want_latent=False, run_backwards=True, mask=None, steps=None):
+    return _encode(enc, inputs, timesteps, want_latent, run_backwards, False, mask, steps)[:3]
 
 
 # ---- VidODE's warp chain + mask compositing (csrc/warp.hip) ---------------------------------------------------------------

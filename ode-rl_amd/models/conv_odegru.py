@@ -169,34 +169,37 @@ class Encoder_z0_ODE_ConvGRU(nn.Module):
     def _wants_grad(self, x):
         return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in hip_ops.encoder_params(self._packed())))
 
-    def _encode(self, input_tensor, time_steps, mask, run_backwards, want_latent):
-        """The fused call on batch-first frames: (mean, std, latent_ys or None)."""
+    def _encode(self, input_tensor, time_steps, mask, run_backwards, want_latent, steps=None):
+        """The fused call on batch-first frames: (mean, std, latent_ys or None).  steps: hip_ops.encoder_steps -- by default a frame no
+        sample of a HOST mask observed launches nothing of the cell."""
         hip_ops.require_device_tensor(input_tensor, "input_tensor")
         frames = input_tensor.permute(1, 0, 2, 3, 4)   # the library reads time-first frames
         if self._wants_grad(input_tensor):
             from ..autograd import encode_with_grad
-            out = encode_with_grad(self._packed(), frames, time_steps, want_latent=want_latent, run_backwards=run_backwards, mask=mask)
+            out = encode_with_grad(self._packed(), frames, time_steps, want_latent=want_latent, run_backwards=run_backwards, mask=mask,
+                                   steps=steps)
             return out if want_latent else out + (None,)
-        return hip_ops.odeconvgru_encode(self._packed(), frames, time_steps, want_latent=want_latent, run_backwards=run_backwards, mask=mask)
+        return hip_ops.odeconvgru_encode(self._packed(), frames, time_steps, want_latent=want_latent, run_backwards=run_backwards, mask=mask,
+                                         steps=steps)
 
-    def forward(self, input_tensor, time_steps, mask=None, tracker=None):
+    def forward(self, input_tensor, time_steps, mask=None, tracker=None, steps=None):
         """-> (mean_z0, |std_z0|), each (b, z0_dim, h, w).  mask (b, t) or (b, t, 1), indexed by frame; None = every frame observed.
-        `tracker` is accepted and ignored."""
+        `tracker` is accepted and ignored.  steps (fused only): see `_encode`."""
         if not self.batch_first:
             input_tensor = input_tensor.permute(1, 0, 2, 3, 4)
         assert input_tensor.size(1) == len(time_steps), "Sequence length should be same as time_steps"
         if self.fused:
-            mean, std, _ = self._encode(input_tensor, time_steps, mask, self.run_backwards, False)
+            mean, std, _ = self._encode(input_tensor, time_steps, mask, self.run_backwards, False, steps)
             return mean, std
         last_yi, _ = self.run_ode_conv_gru(input_tensor=input_tensor, mask=mask, time_steps=time_steps, run_backwards=self.run_backwards)
         mean_z0, std_z0 = torch.split(self.transform_z0(last_yi), self.z0_dim, dim=1)
         return mean_z0, std_z0.abs()
 
-    def run_ode_conv_gru(self, input_tensor, mask, time_steps, run_backwards=True, tracker=None):
+    def run_ode_conv_gru(self, input_tensor, mask, time_steps, run_backwards=True, tracker=None, steps=None):
         """(last yi, latent_ys (b, t, c, h, w)) from batch-first frames (upstream :146-199); slot k of latent_ys is the state after the
         k-th visited frame."""
         if self.fused:
-            _, _, latent = self._encode(input_tensor, time_steps, mask, run_backwards, True)
+            _, _, latent = self._encode(input_tensor, time_steps, mask, run_backwards, True, steps)
             return latent[:, -1], latent
         b, t, c, h, w = input_tensor.size()
         times = [float(v) for v in hip_ops.host_times(time_steps)]
@@ -313,8 +316,7 @@ class VidODE(nn.Module):
         dev = self.device
         truth = truth.to(dev)
         n_pred, out_sel = self._selected(out_mask, len(time_steps_to_predict))
-        mask = None if mask is None else mask.to(dev)
-        b, t, c, h, w = truth.shape
+        b, t, c, h, w = truth.shape   # (the mask stays where the loader left it: on the host it also tells which encoder steps to skip)
         resize = 2 ** self.opt.n_downs
         start = self._init_image(truth)
         skip_conn_embed = self.encoder(start).view(b, -1, h // resize, w // resize)
