@@ -82,6 +82,15 @@ SED[plain_bwd_drops_bypass]='s/  if (blend) d += (1.0f - m) \* g;  \/\/ the part
 # ---- upstream Vid-ODE's evaluation protocol (png_metrics.hip; tests/test_hip_png_metrics.py)
 SED[png_luma_no_rounding]='s/  return (19595u \* r + 38470u \* g + 7471u \* b + 0x8000u) >> 16;/  return (19595u * r + 38470u * g + 7471u * b) >> 16;/'   # PIL'"'"'s luma truncated instead of rounded
 SED[png_crop_from_row_4]='s/^constexpr int kPngCropRow = kPngRadius; /constexpr int kPngCropRow = kPngRadius - 1; /'   # S averaged over rows 4 .. S-7 (row -1 of the first plane = the reduction scratch in front of it: still inside the allocation)
+# ---- the solver arithmetic in epilogue() (conv_common.h; tests/test_hip_solver_stacks.py): every pattern matches the copy behind the
+# 32x32-accumulator kernels only, not emit_quad()'s; each stays inside the buffers of the layer it is given
+SED[epilogue_drops_k_scale]='s/    kc = act_fwd(kc, a.act) \* m.k_scale;   \/\/ (a Tanh head before the sign)/    kc = act_fwd(kc, a.act);/'   # stage combine: the sign of a decreasing t is lost
+# (combine 2 multiplies by sc_c + sc_h * h, but every driver sets sc_c = 1, sc_h = 0: dropping `v *= sc;` changes no result the
+# library can produce, so the combine-2 mutant drops the activation mask instead)
+SED[epilogue_mask_dropped]='s/^        if (w.mask_src) v = act_bwd(v, \*(const f32x4\*)(w.mask_src + off), a.act);$/        (void)0;/'   # combine 2: the gradient passes every hidden unit unmasked
+SED[epilogue_target_drops_h]='s/      f32x4 o = gx \* (T.g_c + T.g_h \* hb);/      f32x4 o = gx * T.g_c;/'   # combine 3: the device-side step size of a reverse-sweep target
+SED[epilogue_partial_slot]='s/m.err_partials\[part_idx >= 0 ? part_idx : (int)(blockIdx.x + blockIdx.y \* gridDim.x) \* 4 + wave\] = esum;/m.err_partials[part_idx >= 0 ? part_idx : (int)(blockIdx.x + blockIdx.y * gridDim.x) + wave] = esum;/'   # error partials of neighbouring workgroups overwrite each other (lower slots: inside the array)
+SED[dopri5_partial_count]='s/  const int n_conv_partials = pps > 16 ? batch \* pps : batch \* (C \/ 32) \* 2 \* 4;/  const int n_conv_partials = pps > 16 ? batch * pps : batch * (C \/ 64) * 2 * 4;/'   # the controller sums half of the partials (none at C = 32); the arrays keep their size of at least 1024 floats
 # mutants of the Python binding, "file|sed script": applied to the tree's own file for the run and restored afterwards (run only)
 declare -A PYSED
 PYSED[z0_offset_stuck]='ode-rl_amd/autograd.py|s/gen.set_offset(at + 4)/gen.set_offset(at)/;s/_explicit_seed\[1\] = offset + 1/_explicit_seed[1] = offset/'   # consecutive sample_z0 calls draw the same noise
