@@ -671,6 +671,12 @@ int odehip_frame_encode_backward(const float* pack, const float* w2, const float
  * setting.  odehip_persistent_trajectory_launches: how many trajectories have taken that path in this process. */
 int odehip_set_persistent_trajectory(int enable);
 long long odehip_persistent_trajectory_launches(void);
+/* Fixed-grid trajectories of a 64-channel stack whose batch gives every group of four workgroups ONE sample (batch <= 64) walk in
+ * row strips: workgroup = (sample, all 64 output channels, 4 rows), one input transform per tile.  Results
+ * are bit-identical to the other walks.  On by default (environment ODEHIP_STRIP_WALK=0 turns it off); the switch is for A/B
+ * measurements and tests and returns the previous setting.  odehip_strip_walk_launches: launches of that kernel in this process. */
+int odehip_set_strip_walk(int enable);
+long long odehip_strip_walk_launches(void);
 /* Sticky error word of the persistent launches: 0 = none, else the code a capped in-kernel wait left when it gave up (2: a
  * partner workgroup never announced itself, 3: a partner's layer never arrived).  Host-side read of mapped memory, no
  * synchronisation.  clear != 0 resets the word and switches the persistent path off for the process. */

@@ -140,6 +140,8 @@ SIGNATURES = {
                                    [ctypes.c_float] * 5 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "odehip_set_persistent_trajectory": (ctypes.c_int, [ctypes.c_int]),
     "odehip_persistent_trajectory_launches": (ctypes.c_longlong, []),
+    "odehip_set_strip_walk": (ctypes.c_int, [ctypes.c_int]),
+    "odehip_strip_walk_launches": (ctypes.c_longlong, []),
     "odehip_persistent_error": (ctypes.c_int, [ctypes.c_int]),
     "odehip_upsample2x_bilinear": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "odehip_upsample2x_bilinear_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,

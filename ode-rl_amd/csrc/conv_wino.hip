@@ -212,6 +212,115 @@ struct RowCursor {
   }
 };
 
+// The epilogue of a fixed-grid walk's layer (PERSIST without ADAPT) on operands fetched at the START of the layer: every scalar the
+// epilogue needs AND this lane's own operands of the stage combine (y, earlier k's: written by this very lane at least one layer ago)
+// are fetched behind the wait for the first chunk -- after the last MFMA there is only arithmetic and stores left.  (Read from the
+// table at that point they cost a scalar-cache miss each, one after the other.)  A lane owns channel quad Q of one 2x2 output tile:
+// quad q of the four is pixel (row0 + (q >> 1), 2 otx + (q & 1)).  Shared by wino_layer and wino_strip_layer, which differ only in which
+// (Q, tile) a lane owns: emit_quad's plain / stage-combine arithmetic, same expressions, same order.
+template <int QOUT>
+struct PreEpilogue {
+  int combine = 0, act = 0, np = 0;
+  float* dst = nullptr;
+  float* kout = nullptr;
+  float* out1 = nullptr;
+  float* out2 = nullptr;
+  float* nchw = nullptr;
+  bool y = false;
+  float h = 1.0f, ks = 1.0f, c1c = 0.0f, c2c = 0.0f, c1[3] = {0.f, 0.f, 0.f}, c2[3] = {0.f, 0.f, 0.f};
+  f32x4 yv[4], kv[3][4];
+
+  __device__ __forceinline__ void fetch(const ConvArgs& a, const PersistHook& hk, int b, int Q, int row0, int otx) {
+    combine = a.combine;
+    act = a.act;
+    dst = a.dst;
+    // a table whose step size only exists on the device (dopri5: h_by_value == 0) takes the shared epilogue for its
+    // stage-combine / reverse layers; ReLU-mask layers of such a table read *h_ptr here
+    if (combine == 1 && !a.h_by_value) combine = 3;
+    if (combine == 2) {  // ReLU-mask backward layer: dst = scale * acc * (mask > 0); the mask values are fetched now
+      const BwdArgs& w = a.bwd;
+      typedef const __attribute__((address_space(4))) float ConstF;
+      const float hb = a.h_by_value ? a.cmb.atol : (w.h_ptr ? *(ConstF*)w.h_ptr : 0.0f);  // constant during the launch
+      ks = w.sc_c + w.sc_h * hb;
+      y = w.mask_src != nullptr;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const size_t off = (((size_t)b * QOUT + Q) * kPix + (row0 + (q >> 1)) * 16 + 2 * otx + (q & 1)) * 4;
+        if (y) yv[q] = *(const f32x4*)(w.mask_src + off);
+      }
+    } else if (combine == 1) {
+      const CombineArgs& m = a.cmb;
+      np = m.n_prev;
+      h = m.atol;  // the step size itself: the host resolves *h_ptr into this (otherwise unused) field of a persistent table
+      ks = m.k_scale;
+      c1c = m.c1[np];
+      c2c = m.c2[np];
+      kout = m.k_out;
+      out1 = m.out1;
+      out2 = m.out2;
+      nchw = a.dbg ? hk.nchw_base + ((size_t)a.dbg - 1) : nullptr;
+      y = m.y != nullptr;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const size_t off = (((size_t)b * QOUT + Q) * kPix + (row0 + (q >> 1)) * 16 + 2 * otx + (q & 1)) * 4;
+        if (y) yv[q] = *(const f32x4*)(m.y + off);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (j < np) kv[j][q] = *(const f32x4*)(m.k_prev[j] + off);
+      }
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        c1[j] = m.c1[j];
+        c2[j] = m.c2[j];
+      }
+    }
+  }
+
+  // quad q of the lane's four, pixel P, conv output v (bias included)
+  __device__ __forceinline__ void emit(const ConvArgs& a, int b, int Q, int q, int P, f32x4 v, float& esum) const {
+    const size_t off = (((size_t)b * QOUT + Q) * kPix + P) * 4;
+    if (!combine) {
+      *(f32x4*)(dst + off) = act_fwd(v, act);
+      return;
+    }
+    if (combine == 2) {
+      v *= ks;
+      if (y) v = act_bwd(v, yv[q], act);
+      *(f32x4*)(dst + off) = v;
+      return;
+    }
+    if (combine == 3) {  // reverse-sweep targets: the shared epilogue, read from the table
+      emit_quad<false>(a, b, Q, P, v, esum);
+      return;
+    }
+    const f32x4 kc = act_fwd(v, act) * ks;   // (a Tanh head before the sign)
+    if (kout) *(f32x4*)(kout + off) = kc;
+    if (y) {
+      // a stage writes EITHER the next stage input (out1) OR the step result (out2, + its NCHW frame): only the sum that is stored is
+      // formed (the same expression as before for each)
+      if (out1) {
+        f32x4 sa = kc * c1c;
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (j < np) sa += kv[j][q] * c1[j];
+        *(f32x4*)(out1 + off) = yv[q] + sa * h;
+      }
+      if (out2 || nchw) {
+        f32x4 sb = kc * c2c;
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (j < np) sb += kv[j][q] * c2[j];
+        const f32x4 o2 = yv[q] + sb * h;
+        if (out2) *(f32x4*)(out2 + off) = o2;
+        if (nchw) {
+          float* o = nchw + ((size_t)b * (QOUT * 4) + Q * 4) * kPix + P;
+          o[0] = o2.x; o[kPix] = o2.y; o[2 * kPix] = o2.z; o[3 * kPix] = o2.w;
+        }
+      }
+    }
+  }
+};
+
 // One 3x3 layer for workgroup (sample b, 32-channel tile ct, image half rh).  PERSIST: called in a loop by
 // wino_persist_kernel -- the input tile is loaded past the per-CU cache (sc0 sc1: it was written by other CUs of this launch),
 // the first weight chunk is requested BEFORE waiting for the partners, and finished output is announced through hk.done.
@@ -384,19 +493,9 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
   const int Q = ct * 8 + ch * 4 + kq;
   f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
   if (a.bias) bias4 = *(const f32x4*)(a.bias + Q * 4);  // loaded now, used after the last MFMA
-  // PERSIST: every scalar the epilogue needs AND this lane's own operands of the stage combine (y, earlier k's: written by this
-  // very lane at least one layer ago) are fetched now, behind the wait for the first chunk -- after the last MFMA there is only
-  // arithmetic and stores left.  (Read from the table at that point they cost a scalar-cache miss each, one after the other.)
+  // PERSIST: the epilogue's scalars and this lane's own operands are fetched now, behind the wait for the first chunk (PreEpilogue)
   const int tile = thh * 16 + i16, oty = tile >> 3, otx = tile & 7;
-  int e_combine = 0, e_act = 0, e_np = 0;
-  float* e_dst = nullptr;
-  float* e_kout = nullptr;
-  float* e_out1 = nullptr;
-  float* e_out2 = nullptr;
-  float* e_nchw = nullptr;
-  bool e_y = false;
-  float e_h = 1.0f, e_ks = 1.0f, e_c1c = 0.0f, e_c2c = 0.0f, e_c1[3] = {0.f, 0.f, 0.f}, e_c2[3] = {0.f, 0.f, 0.f};
-  f32x4 e_yv[4], e_kv[3][4];
+  PreEpilogue<QOUT> ep;
   // ---- ADAPT: the reduced operand set (see the template comment)
   int d_kind = 0;   // 0 plain / ReLU store; 1 stage combine (order 1); 2 ReLU-mask backward; 3 reverse-sweep targets (<= 2, constant
                     // coefficients) held in registers; 5 anything else: the shared epilogue reads the table after the matrix work
@@ -408,8 +507,8 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
     typedef const __attribute__((address_space(4))) float ConstF;
     const unsigned long long* const rl = hk.reloc;   // relocatable pointers (rel()): every pointer of the reduced paths below is
                                                      // resolved here; rows that fall to the shared epilogue (kind 5) must not carry any
-    e_act = a.act;
-    e_dst = rel(rl, a.dst);
+    ep.act = a.act;
+    ep.dst = rel(rl, a.dst);
     d_kind = a.combine == 0 ? 0 : 5;
     if (a.combine == 2) {
       const BwdArgs& w = a.bwd;
@@ -501,49 +600,7 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
       }
     }
   } else if (PERSIST) {
-    e_combine = a.combine;
-    e_act = a.act;
-    e_dst = a.dst;
-    // a table whose step size only exists on the device (dopri5: h_by_value == 0) takes the shared epilogue for its
-    // stage-combine / reverse layers; ReLU-mask layers of such a table read *h_ptr here
-    if (e_combine == 1 && !a.h_by_value) e_combine = 3;
-    if (e_combine == 2) {  // ReLU-mask backward layer: dst = scale * acc * (mask > 0); the mask values are fetched now
-      const BwdArgs& w = a.bwd;
-      typedef const __attribute__((address_space(4))) float ConstF;
-      const float hb = a.h_by_value ? a.cmb.atol : (w.h_ptr ? *(ConstF*)w.h_ptr : 0.0f);  // constant during the launch
-      e_ks = w.sc_c + w.sc_h * hb;
-      e_y = w.mask_src != nullptr;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const size_t off = (((size_t)b * QOUT + Q) * kPix + (r0 + 2 * oty + (q >> 1)) * 16 + 2 * otx + (q & 1)) * 4;
-        if (e_y) e_yv[q] = *(const f32x4*)(w.mask_src + off);
-      }
-    } else if (e_combine == 1) {
-      const CombineArgs& m = a.cmb;
-      e_np = m.n_prev;
-      e_h = m.atol;  // the step size itself: the host resolves *h_ptr into this (otherwise unused) field of a persistent table
-      e_ks = m.k_scale;
-      e_c1c = m.c1[e_np];
-      e_c2c = m.c2[e_np];
-      e_kout = m.k_out;
-      e_out1 = m.out1;
-      e_out2 = m.out2;
-      e_nchw = a.dbg ? hk.nchw_base + ((size_t)a.dbg - 1) : nullptr;
-      e_y = m.y != nullptr;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const size_t off = (((size_t)b * QOUT + Q) * kPix + (r0 + 2 * oty + (q >> 1)) * 16 + 2 * otx + (q & 1)) * 4;
-        if (e_y) e_yv[q] = *(const f32x4*)(m.y + off);
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          if (j < e_np) e_kv[j][q] = *(const f32x4*)(m.k_prev[j] + off);
-      }
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        e_c1[j] = m.c1[j];
-        e_c2[j] = m.c2[j];
-      }
-    }
+    ep.fetch(a, hk, b, Q, r0 + 2 * oty, otx);
   }
   st.take(2);
 #pragma unroll
@@ -600,60 +657,17 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
     S[1][cI] = pk_sub(pk_sub(acc[1 * 4 + cI], acc[2 * 4 + cI]), acc[3 * 4 + cI]);
   }
   float esum = 0.0f;
-  // emit_quad's plain / stage-combine arithmetic on the operands fetched at the start of the layer (same expressions, same order)
-  auto emit_pre = [&](int q, int P, f32x4 v) {
-    const size_t off = (((size_t)b * QOUT + Q) * kPix + P) * 4;
-    if (!e_combine) {
-      *(f32x4*)(e_dst + off) = act_fwd(v, e_act);
-      return;
-    }
-    if (e_combine == 2) {
-      v *= e_ks;
-      if (e_y) v = act_bwd(v, e_yv[q], e_act);
-      *(f32x4*)(e_dst + off) = v;
-      return;
-    }
-    if (e_combine == 3) {  // reverse-sweep targets: the shared epilogue, read from the table
-      emit_quad<false>(a, b, Q, P, v, esum);
-      return;
-    }
-    const f32x4 kc = act_fwd(v, e_act) * e_ks;   // (a Tanh head before the sign)
-    if (e_kout) *(f32x4*)(e_kout + off) = kc;
-    if (e_y) {
-      // a stage writes EITHER the next stage input (out1) OR the step result (out2, + its NCHW frame): only the sum that is stored is
-      // formed (the same expression as before for each)
-      if (e_out1) {
-        f32x4 sa = kc * e_c1c;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          if (j < e_np) sa += e_kv[j][q] * e_c1[j];
-        *(f32x4*)(e_out1 + off) = e_yv[q] + sa * e_h;
-      }
-      if (e_out2 || e_nchw) {
-        f32x4 sb = kc * e_c2c;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          if (j < e_np) sb += e_kv[j][q] * e_c2[j];
-        const f32x4 o2 = e_yv[q] + sb * e_h;
-        if (e_out2) *(f32x4*)(e_out2 + off) = o2;
-        if (e_nchw) {
-          float* o = e_nchw + ((size_t)b * (QOUT * 4) + Q * 4) * kPix + P;
-          o[0] = o2.x; o[kPix] = o2.y; o[2 * kPix] = o2.z; o[3 * kPix] = o2.w;
-        }
-      }
-    }
-  };
   // ADAPT: the same arithmetic as emit_quad's (order 1 for stage combines), on the operands reduced at the start of the layer
   auto emit_adapt = [&](int q, int P, f32x4 v) {
     const size_t off = (((size_t)b * QOUT + Q) * kPix + P) * 4;
     if (d_kind == 0) {
-      *(f32x4*)(e_dst + off) = act_fwd(v, e_act);
+      *(f32x4*)(ep.dst + off) = act_fwd(v, ep.act);
     } else if (d_kind == 2) {
       v *= d_ks;
-      if (d_has_y) v = act_bwd(v, d_y[q], e_act);
-      *(f32x4*)(e_dst + off) = v;
+      if (d_has_y) v = act_bwd(v, d_y[q], ep.act);
+      *(f32x4*)(ep.dst + off) = v;
     } else if (d_kind == 1) {
-      const f32x4 kc = act_fwd(v, e_act) * d_ks;   // (a Tanh head before the sign)
+      const f32x4 kc = act_fwd(v, ep.act) * d_ks;   // (a Tanh head before the sign)
       if (d_o[0]) *(f32x4*)(d_o[0] + off) = kc;
       if (d_has_y) {
         if (d_o[1]) *(f32x4*)(d_o[1] + off) = fma4(fma4(kc, d_cA, d_sa[q]), d_h, d_y[q]);
@@ -694,8 +708,8 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
       emit_adapt(2 * i, P, y0);
       emit_adapt(2 * i + 1, P + 1, y1);
     } else if (PERSIST) {
-      emit_pre(2 * i, P, y0);
-      emit_pre(2 * i + 1, P + 1, y1);
+      ep.emit(a, b, Q, 2 * i, P, y0, esum);
+      ep.emit(a, b, Q, 2 * i + 1, P + 1, y1, esum);
     } else {
       emit_quad(a, b, Q, P, y0, esum);
       emit_quad(a, b, Q, P + 1, y1, esum);
@@ -937,6 +951,9 @@ __device__ __forceinline__ void persist_walk_v(const PersistArgs& pa, const Conv
 
 __global__ __launch_bounds__(512, 1) void wino_persist_v_kernel(const PersistArgs pa) { persist_walk_v(pa, pa.table); }
 
+// one sample per group: the walk in row strips (below, behind the sixteen-workgroup walk whose producers it shares)
+__global__ void wino_persist_strip_kernel(const PersistArgs pa);
+
 template <int NCHUNK, bool DBG>
 static int launch_wino_nd(const ConvArgs& a, hipStream_t stream) {
   static bool attr_set = false;
@@ -955,19 +972,23 @@ static int launch_wino_n(const ConvArgs& a, hipStream_t stream) {
 
 int launch_wino_persist(const ConvArgs* table_dev, int n_layers, int batch, unsigned* done, unsigned* xcc_of, unsigned* host_err_dev,
                         float* out_nchw, int grid, hipStream_t stream, bool wide, bool adaptive, const int* n_layers_ptr,
-                        const unsigned long long* reloc) {
+                        const unsigned long long* reloc, bool strip) {
   static bool attr_set = false;
   ODEHIP_REQUIRE(!(wide && adaptive) && (adaptive || !n_layers_ptr), "wino_persist: no adaptive walk for 128-channel-ended stacks");
+  ODEHIP_REQUIRE(!strip || (!wide && !adaptive && batch <= grid / 4), "wino_persist: the strip walk takes fixed-grid 64-channel tables, one sample per group");
   if (!attr_set) {
     ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)wino_persist_d_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)wino_persist_v_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)wino_persist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)wino_persist_strip_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     // every workgroup must be resident at once: one per CU (96 KiB of LDS each: two do not fit), `grid` <= number of CUs (checked by the caller)
     int per_cu = 0;
     ODEHIP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)wino_persist_kernel, 512, kWinoLds));
     ODEHIP_REQUIRE(per_cu >= 1, "wino_persist: the kernel does not fit a CU");
     ODEHIP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)wino_persist_d_kernel, 512, kWinoLds));
     ODEHIP_REQUIRE(per_cu >= 1, "wino_persist: the adaptive kernel does not fit a CU");
+    ODEHIP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)wino_persist_strip_kernel, 512, kWinoLds));
+    ODEHIP_REQUIRE(per_cu >= 1, "wino_persist: the strip kernel does not fit a CU");
     attr_set = true;
   }
   PersistArgs pa;
@@ -976,14 +997,22 @@ int launch_wino_persist(const ConvArgs* table_dev, int n_layers, int batch, unsi
   pa.stamps = g_debug_buf;
   constexpr int kSleep6 = 5;          // 5 x 0.18 us (sweep in wino_layer's comment)
   constexpr int kSleep6Combine = 4;   // sweep: 0: 1.382, 4: 1.367, 6: 1.370, 8: 1.383, 12: 1.404 ms
-  pa.sleep6 = kSleep6;
-  pa.sleep6_combine = kSleep6Combine;
+  // The strip walk's own pair: its producers finish their last transform earlier, so they have longer to sleep.  Sweep at B = 64
+  // (profiles/strip_walk.json; median of 3 runs, ms): sleep6 / combine 7/4: 1.233 (one run of three at 1.38), 8/4: 1.198 (one at 1.38),
+  // 9/4: 1.213, 10/4: 1.224, 11/4: 1.245, 12/4: 1.274, 14/4: 1.326; 10/0: 1.224, 10/8: 1.240.  Below 9 periods a run can settle in
+  // a slow mode (1.38 - 1.51 ms: the producers poll the flag line while the neighbours' consumers still work); 10 keeps two periods
+  // of margin to that edge for 1 % of the trajectory.
+  constexpr int kStripSleep6 = 10, kStripSleep6Combine = 4;
+  pa.sleep6 = strip ? kStripSleep6 : kSleep6;
+  pa.sleep6_combine = strip ? kStripSleep6Combine : kSleep6Combine;
   pa.n_layers_ptr = n_layers_ptr;
   pa.reloc = reloc;
   pa.fault_inject = 0;
   // An ordinary launch: the co-residency a cooperative launch would verify is checked above, and a cooperative launch runs on a
   // separate hardware queue (extra cross-queue synchronisation per call; it also crashes rocprofv3's teardown on this stack).
-  if (wide)          hipLaunchKernelGGL(wino_persist_v_kernel, dim3(grid), dim3(512), kWinoLds, stream, pa);
+  // (the strip walk needs 48 KiB of LDS and asks for the others' 96: a second workgroup must not share its CU)
+  if (strip)         hipLaunchKernelGGL(wino_persist_strip_kernel, dim3(grid), dim3(512), kWinoLds, stream, pa);
+  else if (wide)     hipLaunchKernelGGL(wino_persist_v_kernel, dim3(grid), dim3(512), kWinoLds, stream, pa);
   else if (adaptive) hipLaunchKernelGGL(wino_persist_d_kernel, dim3(grid), dim3(512), kWinoLds, stream, pa);
   else               hipLaunchKernelGGL(wino_persist_kernel, dim3(grid), dim3(512), kWinoLds, stream, pa);
   ODEHIP_CHECK_HIP(hipGetLastError());
@@ -1504,6 +1533,215 @@ int launch_wino_persist16(const ConvArgs* table_dev, int n_layers, int batch, un
   hipLaunchKernelGGL(wino_persist16_kernel, dim3(256), dim3(512), kWino16Lds, stream, pa);
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
+}
+
+// ================================================================================================================================
+// One sample per group (batch <= number of groups): FOUR ROW STRIPS per sample instead of two co tiles x two image halves.
+// In the walk above the two co-tile workgroups of an image half DMA and transform the same raw tile into the same V: every
+// V = B^T d B of the trajectory is computed twice, on the SIMDs whose fp32 datapath the MFMAs use.  Here workgroup (sample, row
+// quarter rq) owns ALL 64 output channels of 4 output rows (2 x 8 tiles): consumer wave w multiplies the (16 co = quad block w) x
+// (16 tiles) block for all 16 xi -- the same 64 MFMAs per chunk, the same 64 accumulators, the same register-only output transform
+// as wino_layer, so every accumulator element sees the same MFMA sequence and the results are BIT-IDENTICAL to the other walks and
+// to one launch per layer.  All four waves read the same V fragments and four different U blocks (the packed tensor is
+// [ct][chunk][xi][quad][co 32][4 ci]: wave w reads co tile w >> 1, co (w & 1) * 16 + i16).  Producers: the sixteen-workgroup walk's
+// (6 raw rows x 20 slots; one V row per lane: 8 ds_read_b128 + 4 ds_write_b128) -- half of wino_layer's producer work per chunk.
+// Hand-off: flag word rq * 4 + wave; a strip waits for the 8 or 12 words of strips rq - 1 .. rq + 1 (all channels of the input rows
+// it reads).  A strip overwrites rows only its neighbours and itself have read, and has seen all of them finish the layer that read
+// them, so the tables' buffer reuse (never closer than two layers) holds as it does for the sixteen-workgroup walk.
+// LDS: raw[2] 16 KiB + V[2] 32 KiB = 48 KiB.
+constexpr int kStripLds = 2 * k16Raw + 2 * k16V;
+static_assert(kStripLds <= kWinoLds, "the strip walk is launched with the other walks' LDS request");
+
+__device__ __forceinline__ void wino_strip_layer(const float* __restrict__ p_src, const float* __restrict__ p_u, const ConvArgs& a, int b,
+                                                 int rq, char* smem, const PersistHook& hk) {
+  char* const Rb = smem;
+  char* const Vb = smem + 2 * k16Raw;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r0 = rq * 4;
+  constexpr int nchunk = 4;
+
+  if (wave >= 4) {
+    // =========================================== PRODUCERS ===========================================
+    const int pw = wave - 4;
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc((const char*)p_src + (size_t)b * 16 * kQuadBytes, 16u * kQuadBytes);
+    // raw tile: image rows r0 - 1 .. r0 + 4 in wino_layer's 20-slot rows (conflict-free stride-2 reads), zero-padded by the DMA's
+    // range check
+    int vr[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int s = 64 * p + lane;
+      const int row = s / 20, w = s - row * 20;
+      const int pc = w < 9 ? 2 * w : 2 * (w - 9) + 1;
+      const int irow = r0 - 1 + row, col = pc - 1;
+      vr[p] = (s < 120 && w < 18 && irow >= 0 && irow < kHW && col >= 0 && col < kHW) ? irow * 256 + col * 16 : kOobOffset;
+    }
+    auto issue_raw = [&](int c, int buf) {
+#pragma unroll
+      for (int p = 0; p < 2; ++p)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, ODEHIP_LDS_PTR(Rb + buf * k16Raw + pw * 2048 + p * 1024), 16, vr[p],
+                                                 (c * 4 + pw) * kQuadBytes, 0, 16);
+    };
+    // transform: lane = (tile tt, V row vi) of the quad this wave DMA'd itself (tq = pw: its own vmcnt suffices)
+    const int tt = lane & 15, vi = lane >> 4, tq = pw;
+    const int tty = tt >> 3, ttx = tt & 7;
+    // V row vi of B^T d:  0: p0 - p2   1: p1 + p2   2: p2 - p1   3: p3 - p1  (sign of row 3 folded into U): T = a + sg * b
+    const int ra = vi;
+    const int rb = vi < 2 ? 2 : 1;
+    const float sg = vi == 1 ? 1.0f : -1.0f;
+    const int raw_base = tq * 2048 + (2 * tty * 20 + ttx) * 16;
+    const int off_a = raw_base + ra * 320, off_b = raw_base + rb * 320;
+    const int v_off = tq * 256 + tt * 16;
+    auto transform = [&](int rbuf, int vbuf) {
+      const char* r = Rb + rbuf * k16Raw;
+      f32x4 T[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int cj = ((j & 1) * 9 + (j >> 1)) * 16;
+        const f32x4 da = *(const f32x4*)(r + off_a + cj);
+        const f32x4 db = *(const f32x4*)(r + off_b + cj);
+        T[j] = da + db * sg;
+      }
+      char* v = Vb + vbuf * k16V + v_off + vi * 4 * 1024;
+      *(f32x4*)(v + 0 * 1024) = pk_sub(T[0], T[2]);
+      *(f32x4*)(v + 1 * 1024) = T[1] + T[2];
+      *(f32x4*)(v + 2 * 1024) = pk_sub(T[2], T[1]);
+      *(f32x4*)(v + 3 * 1024) = pk_sub(T[1], T[3]);
+    };
+    // DMA order per wave: raw_0 (2) | raw_1 (2) | then per iteration c: raw_{c+2} (2); counted waits leave the younger ones in flight
+    if (pw == 0) pstamp(hk, 0, lane);
+    if (!hk.first) {
+      // the neighbours cannot be done before this workgroup's own consumers are through their last chunk: sleep through most of it
+      // instead of polling (wino_layer)
+      for (int i = 0; i < hk.sleep6; ++i) __builtin_amdgcn_s_sleep(6);
+      wait_done16(hk, rq > 0 ? (rq - 1) * 4 : 0, rq < 3 ? (rq + 2) * 4 : 16);
+    }
+    if (pw == 0) pstamp(hk, 1, lane);
+    issue_raw(0, 0);
+    issue_raw(1, 1);
+    wait_vmcnt<2>();                   // raw_0 landed (raw_1 still in flight)
+    if (pw == 0) pstamp(hk, 2, lane);
+    transform(0, 0);
+    if (pw == 0) pstamp(hk, 3, lane);
+#pragma unroll
+    for (int c = 0; c < nchunk; ++c) {
+      __builtin_amdgcn_s_barrier();  // [c] V_c ready for the consumers; they are done with chunk c-1
+      if (c + 1 < nchunk) {
+        if (c + 2 < nchunk) {
+          issue_raw(c + 2, c & 1);   // raw buffer consumed by this wave's transform of chunk c
+          wait_vmcnt<2>();           // raw_{c+1} landed (raw_{c+2} still in flight)
+        } else {
+          wait_vmcnt<0>();           // raw_{c+1}, the last one
+        }
+        transform((c + 1) & 1, (c + 1) & 1);  // V buffer last read by the MFMAs of chunk c-1
+      }
+    }
+    return;
+  }
+
+  // ============================================= CONSUMERS =============================================
+  const int i16 = lane & 15, kq = lane >> 4;
+  f32x4 acc[16];
+#pragma unroll
+  for (int x = 0; x < 16; ++x) acc[x] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // this lane's 16 bytes of a position's 2 KiB block [quad 4][co 32][4 ci] of co tile wave >> 1
+  const int u_off = (wave >> 1) * (nchunk * kWU) + kq * 512 + ((wave & 1) * 16 + i16) * 16;
+  const int v_off = kq * 256 + i16 * 16;
+  // U ring as in wino_layer: slot g % kUAhead holds position g of the layer (g = 16 c + xi)
+  constexpr int kG = 16 * nchunk;
+  const __amdgpu_buffer_rsrc_t ru = make_rsrc(p_u, 2u * nchunk * kWU);
+  f32x4 uw[kUAhead];
+#pragma unroll
+  for (int g = 0; g < kUAhead; ++g) uw[g] = load_u(ru, u_off, g * 2048);
+  const int Q = wave * 4 + kq;
+  f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
+  if (a.bias) bias4 = *(const f32x4*)(a.bias + Q * 4);  // loaded now, used after the last MFMA
+  const int oty = i16 >> 3, otx = i16 & 7;
+  PreEpilogue<16> ep;
+  ep.fetch(a, hk, b, Q, r0 + 2 * oty, otx);
+#pragma unroll
+  for (int c = 0; c < nchunk; ++c) {
+    __builtin_amdgcn_s_barrier();  // [c]
+    if (c == 0 && wave == 0) pstamp(hk, 4, lane);
+    const char* v = Vb + (c & 1) * k16V + v_off;
+    // wino_layer's loop: two xi at a time, the next pair's V fragments and the U fragments kUAhead positions on under this pair's MFMAs
+    f32x4 x0 = *(const f32x4*)(v), x1 = *(const f32x4*)(v + 1024);
+    f32x4 x0n, x1n;
+#pragma unroll
+    for (int x = 0; x < 16; x += 2) {
+      const int g = c * 16 + x, s0 = g % kUAhead, s1 = (g + 1) % kUAhead;
+      const f32x4 w0 = uw[s0], w1 = uw[s1];
+      if (x + 2 < 16) {
+        x0n = *(const f32x4*)(v + (x + 2) * 1024);
+        x1n = *(const f32x4*)(v + (x + 3) * 1024);
+      }
+      if (g + kUAhead < kG) {
+        uw[s0] = load_u(ru, u_off, (g + kUAhead) * 2048);
+        uw[s1] = load_u(ru, u_off, (g + kUAhead + 1) * 2048);
+      }
+      acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, x0.x, acc[x], 0, 0, 0);
+      acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, x1.x, acc[x + 1], 0, 0, 0);
+      acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, x0.y, acc[x], 0, 0, 0);
+      acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, x1.y, acc[x + 1], 0, 0, 0);
+      acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, x0.z, acc[x], 0, 0, 0);
+      acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, x1.z, acc[x + 1], 0, 0, 0);
+      acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, x0.w, acc[x], 0, 0, 0);
+      acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, x1.w, acc[x + 1], 0, 0, 0);
+      x0 = x0n; x1 = x1n;
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 7, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  if (wave == 0) pstamp(hk, 5, lane);
+
+  // ---- output transform in registers (wino_layer's expressions): lane (tile i16, row group kq) holds M_xi[co quad][tile] for all xi
+  f32x4 S[2][4];
+#pragma unroll
+  for (int cI = 0; cI < 4; ++cI) {
+    S[0][cI] = acc[0 * 4 + cI] + acc[1 * 4 + cI] + acc[2 * 4 + cI];
+    S[1][cI] = pk_sub(pk_sub(acc[1 * 4 + cI], acc[2 * 4 + cI]), acc[3 * 4 + cI]);
+  }
+  float esum = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const f32x4 y0 = S[i][0] + S[i][1] + S[i][2] + bias4;
+    const f32x4 y1 = pk_sub(pk_sub(S[i][1] + bias4, S[i][2]), S[i][3]);
+    const int P = (r0 + 2 * oty + i) * 16 + 2 * otx;
+    ep.emit(a, b, Q, 2 * i, P, y0, esum);
+    ep.emit(a, b, Q, 2 * i + 1, P + 1, y1, esum);
+  }
+  // this wave's share of the layer is in L2 once its stores are acknowledged; then it counts itself in
+  if (wave == 0) pstamp(hk, 6, lane);
+  announce(hk, hk.done + hk.word0 + wave, wave == 0);
+}
+
+__global__ __launch_bounds__(512, 1) void wino_persist_strip_kernel(const PersistArgs pa) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nwg = gridDim.x;  // a multiple of 32: every XCD holds whole groups of 4
+  const int lid = ((int)blockIdx.x & 7) * (nwg >> 3) + ((int)blockIdx.x >> 3);
+  const int rq = lid & 3, group = lid >> 2;
+  const bool fence = xcc_rendezvous<4>(pa.xcc_of, lid, pa.xcc_of + nwg, pa.host_err);
+  const ConvArgs* table = pa.table;
+  int n_layers = pa.n_layers;
+  if (!walk_start(table, n_layers, nullptr)) return;
+  const int n_groups = nwg >> 2;
+  for (int b = group; b < pa.batch; b += n_groups) {   // (the host selects this walk for batch <= n_groups: one sample per group)
+    RowCursor cur(table, n_layers);
+    int prev_combine = 0;  // the layer whose output this one waits for ended in a Runge-Kutta stage combine (a longer epilogue)
+    for (int l = 0; l < n_layers; ++l) {
+      const ConvArgs& a = cur.row(l);
+      const PersistHook hk = {pa.done + (size_t)b * kDoneStride, (unsigned)l, rq * 4, pa.xcc_of + nwg, pa.host_err, fence,
+                              pa.out_nchw, (pa.stamps && lid == 0 && b == group && l < 64) ? pa.stamps + l * 8 : nullptr, pa.batch,
+                              l == 0, true, true, false, pa.sleep6 + (prev_combine == 1 ? pa.sleep6_combine : 0), nullptr, (unsigned)l};
+      wino_strip_layer(uniform_ptr(cur.src), uniform_ptr(cur.u), a, b, rq, smem, hk);
+      prev_combine = a.combine;
+      cur.next();
+    }
+  }
 }
 
 // returns 1 if the shape has no Winograd instantiation (the caller then runs the direct kernel)

@@ -139,8 +139,10 @@ constexpr int kDoneStride = 64;   // words between the per-sample flag lines of 
 int launch_wino_persist(const ConvArgs* table_dev, int n_layers, int batch, unsigned* done, unsigned* xcc_of, unsigned* host_err_dev,
                         float* out_nchw, int grid, hipStream_t stream, bool wide = false,  // wide: the table has 128-channel layers
                         bool adaptive = false, const int* n_layers_ptr = nullptr,           // adaptive: wino_persist_d_kernel (order-1
-                        const unsigned long long* reloc = nullptr);                         // combines, elementwise rows, h on the device;
-                                                                                            // {row0, rows} and relocation bases on the device)
+                        const unsigned long long* reloc = nullptr,                          // combines, elementwise rows, h on the device;
+                        bool strip = false);                                                // {row0, rows} and relocation bases on the device)
+                                                                                            // strip: wino_persist_strip_kernel (row strips,
+                                                                                            // one sample per group, fixed-grid tables)
 int launch_ew_row(const ConvArgs& a, hipStream_t stream);
 // forward tables of a 64-channel stack at batch <= 16: sixteen workgroups per sample (conv_wino.hip, wino_persist16_kernel)
 int launch_wino_persist16(const ConvArgs* table_dev, int n_layers, int batch, unsigned* done, unsigned* xcc_of, unsigned* host_err_dev,

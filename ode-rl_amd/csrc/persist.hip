@@ -24,6 +24,8 @@ struct PersistState {
   unsigned* host_err_dev = nullptr;
   int enabled = -1;                  // -1 unknown, 0 off (env, device, or a failed launch), 1 on
   long long launches = 0;
+  int strip = -1;                    // the row-strip walk: -1 unknown (environment), 0 off, 1 on
+  long long strip_launches = 0;
   // Tables that differ from call to call (the backward passes of the adaptive solver: buffers, step sizes and dense-output weights
   // follow the accepted steps) bypass the content cache: a ring of device slots filled through staged_upload() -- an
   // ASYNCHRONOUS transfer on the caller's stream, no stream synchronisation.  A slot is reused kVolSlots uploads later;
@@ -190,6 +192,16 @@ __global__ void persist_guard_kernel(const GuardArgs a) {
 static bool walk16_on() {
   static const bool on16 = [] { const char* e = getenv("ODEHIP_PERSIST16"); return !(e && e[0] == '0'); }();
   return on16;
+}
+
+// caller holds g_persist.mu
+static bool strip_walk_on() {
+  PersistState& P = g_persist;
+  if (P.strip < 0) {
+    const char* e = getenv("ODEHIP_STRIP_WALK");
+    P.strip = !(e && e[0] == '0');
+  }
+  return P.strip == 1;
 }
 
 // (see odehip_internal.h) -- takes the lock: not to be called inside a PersistScope
@@ -367,16 +379,28 @@ int PersistScope::finish(const float* hbuf, const float* hdev, float* out_nchw, 
         return ODEHIP_EINVAL;
       }
     }
+    // a group that walks ONE sample (batch <= number of groups): fixed-grid tables of a 64-channel stack take the row-strip walk (one
+    // input transform per tile instead of two; bit-identical results).  Batches that give a group two samples keep the interleaved
+    // walk, whose second sample covers the hand-off.
+    bool strip = false;
+    if (table && !wide && !adaptive && !small16 && !eval_walk_ && hbuf && batch <= kPersistGrid / 4 && strip_walk_on()) {
+      strip = true;
+      for (int i = 0; i < rec_.count && strip; ++i) {
+        const ConvArgs& a = rec_.items[i];   // (kind 1: 64 -> 64, combine 0 .. 3, no order-1 combine)
+        strip = !(a.combine == 1 && (a.cmb.err_partials || a.cmb.n_prev > 3));
+      }
+    }
     if (table) {
       if (!sync_is_zero) ODEHIP_CHECK_HIP(hipMemsetAsync(sync, 0, persist_sync_bytes(batch), stream));
       if (small16) rc = launch_wino_persist16(table, rec_.count, batch, sync, sync + (size_t)batch * kDoneStride, g_persist.host_err_dev, out_nchw, stream,
                                               rows_dev_, reloc_dev_);
       else
       rc = launch_wino_persist(table, rec_.count, batch, sync, sync + (size_t)batch * kDoneStride, g_persist.host_err_dev, out_nchw,
-                               kPersistGrid, stream, wide, adaptive, rows_dev_, reloc_dev_);
+                               kPersistGrid, stream, wide, adaptive, rows_dev_, reloc_dev_, strip);
       if (volatile_) persist_table_async_done(stream);
       if (rc == ODEHIP_OK) {
         ++g_persist.launches;
+        if (strip) ++g_persist.strip_launches;
         launched_ = true;
         abort_word_ = sync + (size_t)batch * kDoneStride + kPersistGrid;   // xcc_of[grid]: zeroed above; a wait that gives up stores 1
         table_ = table;
@@ -384,6 +408,7 @@ int PersistScope::finish(const float* hbuf, const float* hdev, float* out_nchw, 
         table_wide_ = wide;
         table_adaptive_ = adaptive;
         table_small16_ = small16;
+        table_strip_ = strip;
         return rc;
       }
       g_persist.enabled = 0;  // the launch was refused: one launch per layer from now on
@@ -411,8 +436,11 @@ int PersistScope::relaunch(int batch, unsigned* sync, hipStream_t stream, bool s
                      ? launch_wino_persist16(table_, table_rows_, batch, sync, sync + (size_t)batch * kDoneStride, g_persist.host_err_dev, nullptr,
                                              stream, rows_dev_, reloc_dev_)
                      : launch_wino_persist(table_, table_rows_, batch, sync, sync + (size_t)batch * kDoneStride, g_persist.host_err_dev, nullptr,
-                                           kPersistGrid, stream, table_wide_, table_adaptive_, rows_dev_, reloc_dev_);
-  if (rc == ODEHIP_OK) ++g_persist.launches;
+                                           kPersistGrid, stream, table_wide_, table_adaptive_, rows_dev_, reloc_dev_, table_strip_);
+  if (rc == ODEHIP_OK) {
+    ++g_persist.launches;
+    if (table_strip_) ++g_persist.strip_launches;
+  }
   return rc;
 }
 
@@ -425,6 +453,18 @@ extern "C" int odehip_set_persistent_trajectory(int enable) {
   const int was = g_persist.enabled != 0;
   g_persist.enabled = enable ? (g_persist.host_err ? 1 : -1) : 0;
   return was;
+}
+
+extern "C" int odehip_set_strip_walk(int enable) {
+  std::lock_guard<std::mutex> g(g_persist.mu);
+  const int was = strip_walk_on();
+  g_persist.strip = enable ? 1 : 0;
+  return was;
+}
+
+extern "C" long long odehip_strip_walk_launches(void) {
+  std::lock_guard<std::mutex> g(g_persist.mu);
+  return g_persist.strip_launches;
 }
 
 extern "C" int odehip_persistent_error(int clear) {
