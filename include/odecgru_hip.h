@@ -59,7 +59,8 @@ enum {
 };
 
 /* fixed-grid methods of torchdiffeq (_impl/fixed_grid.py); rk4 is the 3/8 rule */
-enum { ODEHIP_EULER = 0, ODEHIP_MIDPOINT = 1, ODEHIP_RK4 = 2, ODEHIP_DOPRI5 = 3 };
+enum { ODEHIP_EULER = 0, ODEHIP_MIDPOINT = 1, ODEHIP_RK4 = 2, ODEHIP_DOPRI5 = 3,
+       ODEHIP_BOSH3 = 4 /* adaptive entry points only (odehip_*adaptive*) */ };
 
 const char* odehip_last_error(void);
 int odehip_version(void);
@@ -492,6 +493,44 @@ int odehip_odeint_dopri5_start(const odehip_convstack* f, const float* z0_nchw, 
                                float rtol, float atol, double first_step, int max_steps, float* out_nchw, int max_accept,
                                int attempts, int* token_out, void* workspace, size_t workspace_bytes, void* stream);
 int odehip_odeint_dopri5_collect(int token, int* stats_host, double* accepted_host, int accepted_cap, int* saved_out);
+
+/* ---- odeint, adaptive, by method code: ODEHIP_DOPRI5 or ODEHIP_BOSH3 (torchdiffeq's Bogacki-Shampine 3(2) pair: four stages, FSAL,
+ * three evaluations of f per attempted step, order 3 -- the step-size exponents are 1/3).  One entry point per dopri5 call above, with
+ * the same arguments, semantics, statuses and workspace rules, plus `method`; the odehip_*dopri5* functions above ARE these calls
+ * with ODEHIP_DOPRI5.  Both methods run the same drivers from their tableau (csrc/dopri5_control.h): the persistent adaptive walk,
+ * the device-side controller and the pinned mailbox, the saving slots (method's stage count per slot) and the reverse sweep.  A
+ * workspace is laid out for its method: size it, fill it and read it with one and the same code.  Any other method code:
+ * ODEHIP_EINVAL (the size functions return 0).  ODEHIP_BOSH3 under exact-global step control (odehip_set_norm_allreduce) is
+ * refused with ODEHIP_EINVAL.  The adjoint pair below takes the method code too: ODEHIP_BOSH3 runs the host-driven backward solve
+ * under both norms (the device-steered seminorm path is dopri5's).  Arguments are checked before any HIP call.  Pure additions: ODEHIP_ABI_VERSION stays. */
+size_t odehip_adaptive_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int method);
+size_t odehip_adaptive_saving_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int max_accept, int method);
+size_t odehip_adaptive_backward_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int n_steps, int method);
+int odehip_odeint_adaptive(int method, const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times, int batch,
+                           float rtol, float atol, double first_step, int max_steps, int negate, float* out_nchw, int* stats_host,
+                           double* accepted_host, int accepted_cap, void* workspace, size_t workspace_bytes, void* stream);
+int odehip_odeint_adaptive_saving(int method, const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times,
+                                  int batch, float rtol, float atol, double first_step, int max_steps, float* out_nchw, int* stats_host,
+                                  double* accepted_host, int accepted_cap, int max_accept, int* saved_out, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int odehip_odeint_adaptive_start(int method, const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times,
+                                 int batch, float rtol, float atol, double first_step, int max_steps, float* out_nchw, int max_accept,
+                                 int attempts, int* token_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t odehip_adjoint_adaptive_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int max_accept, int method);
+int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host,
+                                            int n_times, int batch, float rtol, float atol, const float* y_traj_nchw,
+                                            const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w, float* const* grad_b,
+                                            int max_accept, int mixed_norm, int* stats_host, void* workspace, size_t workspace_bytes,
+                                            void* stream);
+int odehip_odeint_adaptive_collect(int token, int* stats_host, double* accepted_host, int accepted_cap, int* saved_out);
+int odehip_odeint_adaptive_backward(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host,
+                                    int n_times, int batch, const double* accepted_host, int n_steps, const float* z0_nchw,
+                                    const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w, float* const* grad_b,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+int odehip_odeint_adaptive_backward_saved(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host,
+                                          int n_times, int batch, const double* accepted_host, int n_steps, const float* grad_out_nchw,
+                                          float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, int max_accept,
+                                          void* saved_workspace, size_t saved_workspace_bytes, void* stream);
 
 /* ---- optimizer step of the training loop (train_test.py:24,205: optim.Adam(model.parameters(), lr)) ------------------------ */
 

@@ -13,8 +13,9 @@ LIB_PATH = os.environ.get("ODEHIP_LIB") or os.path.join(_HERE, "lib", "libodecgr
 ABI_VERSION = 13   # == odehip_version() of the library these ctypes structs were written against (ODEHIP_ABI_VERSION in the header)
 MAX_LAYERS = 8
 MAX_STAGES = 7
-EULER, MIDPOINT, RK4, DOPRI5 = 0, 1, 2, 3
+EULER, MIDPOINT, RK4, DOPRI5, BOSH3 = 0, 1, 2, 3, 4
 METHODS = {"euler": EULER, "midpoint": MIDPOINT, "rk4": RK4, "dopri5": DOPRI5}
+ADAPTIVE_METHODS = {"dopri5": DOPRI5, "bosh3": BOSH3}   # the method codes of the odehip_*adaptive* entry points
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 
@@ -364,6 +365,25 @@ SIGNATURES = {
                                                      ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_size_t,
                                                      ctypes.c_void_p]),
 }
+
+
+def _with_method():
+    """The odehip_*adaptive* entry points: the dopri5 signatures with the method code in front (size functions: at the end)."""
+    S = SIGNATURES
+    for tail in ("", "_saving", "_start", "_backward", "_backward_saved"):
+        res, args = S["odehip_odeint_dopri5" + tail]
+        S["odehip_odeint_adaptive" + tail] = (res, [ctypes.c_int] + list(args))
+    S["odehip_odeint_adaptive_collect"] = S["odehip_odeint_dopri5_collect"]
+    res, args = S["odehip_odeint_adjoint_dopri5_backward"]
+    S["odehip_odeint_adjoint_adaptive_backward"] = (res, [ctypes.c_int] + list(args))
+    res, args = S["odehip_adjoint_dopri5_workspace_bytes"]
+    S["odehip_adjoint_adaptive_workspace_bytes"] = (res, list(args) + [ctypes.c_int])
+    for head in ("", "_saving", "_backward"):
+        res, args = S["odehip_dopri5%s_workspace_bytes" % head]
+        S["odehip_adaptive%s_workspace_bytes" % head] = (res, list(args) + [ctypes.c_int])
+
+
+_with_method()
 
 
 def load():

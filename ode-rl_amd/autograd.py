@@ -81,7 +81,7 @@ class _GriddedOdeint(torch.autograd.Function):
 
 
 class _Dopri5Odeint(torch.autograd.Function):
-    """odeint(method="dopri5") under autograd: the gradient of the accepted steps (csrc/dopri5_backward.hip)."""
+    """odeint(method="dopri5" / "bosh3") under autograd: the gradient of the accepted steps (csrc/dopri5_backward.hip)."""
 
     @staticmethod
     def forward(ctx, y0, t_host, cfg, stack, *params):
@@ -91,7 +91,7 @@ class _Dopri5Odeint(torch.autograd.Function):
         # backward is then the reverse sweep alone; otherwise ctx.saved is None and the backward re-integrates the logged steps
         from .odeint import run_dopri5
         out, ctx.pending, stats, ctx.saved = run_dopri5(stack, y0d, t_host, cfg, save=True)
-        ctx.stack, ctx.t_host = stack, t_host
+        ctx.stack, ctx.t_host, ctx.method = stack, t_host, cfg.get("method", "dopri5")
         hip_ops.record_versions(ctx, params)
         # asynchronous solve (ctx.pending): nothing is known yet -- the backward pass collects it
         ctx.accepted = _accepted_steps(stats) if ctx.pending is None else None
@@ -108,10 +108,10 @@ class _Dopri5Odeint(torch.autograd.Function):
             ctx.pending = None
             ctx.accepted = _accepted_steps(stats)
         if ctx.saved is not None and len(ctx.accepted) >= 1:
-            grads = hip_ops.odeint_dopri5_backward_saved(ctx.stack, ctx.t_host, ctx.accepted, grad_out, ctx.saved)
+            grads = hip_ops.odeint_dopri5_backward_saved(ctx.stack, ctx.t_host, ctx.accepted, grad_out, ctx.saved, method=ctx.method)
             ctx.saved = None
         else:
-            grads = hip_ops.odeint_dopri5_backward(ctx.stack, ctx.t_host, ctx.accepted, y0, grad_out)
+            grads = hip_ops.odeint_dopri5_backward(ctx.stack, ctx.t_host, ctx.accepted, y0, grad_out, method=ctx.method)
         return _solver_backward_result(*grads)
 
 
@@ -305,8 +305,8 @@ class _AdjointOdeint(torch.autograd.Function):
 
 
 class _AdjointDopri5(torch.autograd.Function):
-    """odeint_adjoint with method="dopri5": adaptive forward (csrc/dopri5.hip), adaptive augmented backward
-    (csrc/adjoint_dopri5.hip) under the seminorm."""
+    """odeint_adjoint with method="dopri5" / "bosh3": adaptive forward (csrc/dopri5.hip), adaptive augmented backward
+    (csrc/adjoint_dopri5.hip) under either norm."""
 
     @staticmethod
     def forward(ctx, y0, t_host, cfg, stack, *params):
@@ -329,7 +329,8 @@ class _AdjointDopri5(torch.autograd.Function):
         cfg = ctx.cfg
         stats = {}
         grads = hip_ops.odeint_adjoint_dopri5_backward(ctx.stack, ctx.t_host, y_traj, grad_out, cfg["adjoint_rtol"], cfg["adjoint_atol"],
-                                                       max_accept=cfg["max_accept"], stats=stats, mixed_norm=cfg["mixed_norm"])
+                                                       max_accept=cfg["max_accept"], stats=stats, mixed_norm=cfg["mixed_norm"],
+                                                       method=cfg.get("method", "dopri5"))
         last_adjoint_stats.clear()
         last_adjoint_stats.update(stats)
         return _solver_backward_result(*grads)
@@ -347,11 +348,11 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
     torchdiffeq's default mixed norm (every parameter tensor's error ratio steers the steps too) or, with
     `adjoint_options={"norm": "seminorm"}`, with the cheaper seminorm; `max_accept` in adjoint_options bounds the accepted
     backward steps whose activations are kept."""
-    from .odeint import FIXED_GRID, _check_monotone, _host_times, check_options, conv_stack_of, dopri5_cfg, odeint
+    from .odeint import ADAPTIVE, FIXED_GRID, _check_monotone, _host_times, check_options, conv_stack_of, dopri5_cfg, odeint
     if method is None:
         method = "dopri5"
-    if method not in FIXED_GRID and method != "dopri5":
-        raise ValueError('Invalid method "{}". Must be one of euler, midpoint, rk4, dopri5'.format(method))
+    if method not in FIXED_GRID + ADAPTIVE:
+        raise ValueError('Invalid method "{}". Must be one of euler, midpoint, rk4, dopri5, bosh3'.format(method))
     if adjoint_method is not None and adjoint_method != method:
         raise NotImplementedError("odeint_adjoint(HIP): adjoint_method must equal method")
     check_options(method, options, "odeint_adjoint")
@@ -378,7 +379,7 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
     unknown = set(adjoint_options) - {"norm", "max_accept"}
     if unknown:
         raise ValueError(f"odeint_adjoint(HIP): unsupported adjoint_options {sorted(unknown)}")
-    cfg = dopri5_cfg(rtol, atol, options)
+    cfg = dopri5_cfg(rtol, atol, options, method)
     cfg.update(adjoint_rtol=float(rtol if adjoint_rtol is None else adjoint_rtol),
                adjoint_atol=float(atol if adjoint_atol is None else adjoint_atol), max_accept=adjoint_options.get("max_accept"),
                mixed_norm=norm != "seminorm")
@@ -399,7 +400,7 @@ def odeint_with_grad(func, y0, t, rtol, atol, method, options=None):
         if grid is not None:
             return _GriddedOdeint.apply(y0, th, method, stack, grid, *params)
         return _FixedGridOdeint.apply(y0, th, method, stack, *params)
-    return _Dopri5Odeint.apply(y0, th, dopri5_cfg(rtol, atol, options), stack, *params)
+    return _Dopri5Odeint.apply(y0, th, dopri5_cfg(rtol, atol, options, method), stack, *params)
 
 
 class _SampleZ0Fn(torch.autograd.Function):

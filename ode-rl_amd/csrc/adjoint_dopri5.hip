@@ -84,9 +84,13 @@ static float* g_adj_host = nullptr;  // 256 B of pinned host memory for the per-
 
 using namespace odehip;
 
-extern "C" size_t odehip_adjoint_dopri5_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int max_accept) {
-  if (!f || batch <= 0 || n_times <= 0 || max_accept <= 0 || f->n_convs < 1) return 0;
+// (the slots of AdjLayout keep room for ODEHIP_MAX_STAGES stages whatever the method: a tableau with S stages uses the first S)
+extern "C" size_t odehip_adjoint_adaptive_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int max_accept, int method) {
+  if (!f || batch <= 0 || n_times <= 0 || max_accept <= 0 || f->n_convs < 1 || !adaptive_tableau(method)) return 0;
   return AdjLayout(f, batch, n_times, max_accept).total;
+}
+extern "C" size_t odehip_adjoint_dopri5_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int max_accept) {
+  return odehip_adjoint_adaptive_workspace_bytes(f, batch, n_times, max_accept, ODEHIP_DOPRI5);
 }
 
 extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_dgrad,
@@ -94,6 +98,23 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
                                                      const float* y_traj_nchw, const float* grad_out_nchw, float* grad_z0_nchw,
                                                      float* const* grad_w, float* const* grad_b, int max_accept, int mixed_norm,
                                                      int* stats_host, void* workspace, size_t workspace_bytes, void* stream_) {
+  return odehip_odeint_adjoint_adaptive_backward(ODEHIP_DOPRI5, f, f_dgrad, t_host, n_times, batch, rtol, atol, y_traj_nchw, grad_out_nchw,
+                                                 grad_z0_nchw, grad_w, grad_b, max_accept, mixed_norm, stats_host, workspace,
+                                                 workspace_bytes, stream_);
+}
+
+// The host-driven loop below reads the tableau of the call's method (S stages; the comments count in dopri5's 7).  The device-steered
+// seminorm path (adjoint_device.hip) is written for dopri5's stages: other methods run this loop under both norms.
+extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad,
+                                                       const double* t_host, int n_times, int batch, float rtol, float atol,
+                                                       const float* y_traj_nchw, const float* grad_out_nchw, float* grad_z0_nchw,
+                                                       float* const* grad_w, float* const* grad_b, int max_accept, int mixed_norm,
+                                                       int* stats_host, void* workspace, size_t workspace_bytes, void* stream_) {
+  const ErrorNames names(method);
+  const Tableau* tbp = adaptive_tableau(method);
+  ODEHIP_REQUIRE(tbp, "odeint_adjoint_adaptive_backward: unknown adaptive method code %d (ODEHIP_DOPRI5 or ODEHIP_BOSH3)", method);
+  const Tableau& tb = *tbp;
+  const int S = tb.stages;
   int rc = check_stack(f);
   if (rc != ODEHIP_OK) return rc;
   ODEHIP_REQUIRE(f_dgrad && t_host && y_traj_nchw && grad_out_nchw && grad_z0_nchw && grad_w && grad_b && workspace,
@@ -128,7 +149,7 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
   auto yq = [&](int n) { return L.p(ws, L.off_y + (size_t)n * L.st); };
   auto goq = [&](int n) { return L.p(ws, L.off_go + (size_t)n * L.st); };
 
-  if (!mixed_norm && n_times > 1) {
+  if (!mixed_norm && n_times > 1 && method == ODEHIP_DOPRI5) {
     // seminorm on a 64-channel fp32 stack: step control on the device, evaluations on the adaptive persistent walk
     // (adjoint_device.hip); `ran` = 0 when that path is not available here -- the host loop below then takes the call
     int ran = 0;
@@ -303,7 +324,7 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
         d0 = fmaxf(d0, theta_rms_max(g_adj_host + 8));
         d1 = fmaxf(d1, theta_rms_max(g_adj_host + 8 + NT));
       }
-      const float h0 = dp5::initial_step_h0(d0, d1);
+      const float h0 = initial_step_h0(d0, d1);
       float* k0y[1] = {ky[0]};
       float* k0a[1] = {ka[0]};
       lincomb(L.xin(ws, slot, 1), y_cur, 1, k0y, &h0, nullptr);
@@ -324,7 +345,7 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
       float d2 = fmaxf(rms(s2[0]), rms(s2[1]));
       if (mixed_norm) d2 = fmaxf(d2, theta_rms_max(g_adj_host + 8));
       d2 /= h0;
-      g_adj_host[32] = dp5::initial_step_dt(h0, d1, d2);
+      g_adj_host[32] = initial_step_dt(h0, d1, d2, tb.order);
     }
     double dt = (double)g_adj_host[32];
     double t_cur = t_begin;
@@ -335,29 +356,29 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
       const float h = (float)dt;
       if ((rc = upload_floats(hdev, &h, 1, stream)) != ODEHIP_OK) return rc;
       {  // stage-2 inputs from k1
-        const float c = (float)dp5::kBeta[0][0] * h;
+        const float c = (float)tb.beta[0][0] * h;
         float* k0y[1] = {ky[0]};
         float* k0a[1] = {ka[0]};
         lincomb(L.xin(ws, slot, 1), y_cur, 1, k0y, &c, nullptr);
         lincomb(L.gp(ws, slot, 1, NH), a_cur, 1, k0a, &c, nullptr);
       }
-      for (int s = 2; s <= 7; ++s) {  // stage s lives at index s-1 of the slot; Y_{s+1}, A_{s+1} (s = 6: y1, a1; s = 7: error norms)
-        const int nx = s < 7 ? s : 6;
-        dopri5_stage_combine(cy, s, y_cur, hdev, ky, L.xin(ws, slot, nx), L.part(ws, 4), rtol, atol);
-        dopri5_stage_combine(ca, s, a_cur, hdev, ka, L.gp(ws, slot, nx, NH), L.part(ws, 5), rtol, atol);
+      for (int s = 2; s <= S; ++s) {  // stage s lives at index s-1 of the slot; Y_{s+1}, A_{s+1} (s = 6: y1, a1; s = 7: error norms)
+        const int nx = s < S ? s : S - 1;
+        adaptive_stage_combine(tb, cy, s, y_cur, hdev, ky, L.xin(ws, slot, nx), L.part(ws, 4), rtol, atol);
+        adaptive_stage_combine(tb, ca, s, a_cur, hdev, ka, L.gp(ws, slot, nx, NH), L.part(ws, 5), rtol, atol);
         cy.k_scale = -1.0f;
         ca.k_scale = 1.0f;
         if ((rc = eval_aug(slot, s - 1, L.xin(ws, slot, s - 1), cy, ca)) != ODEHIP_OK) return rc;
       }
-      nfe += 6;
+      nfe += S - 1;
       StageRef ev[7];
       ev[0] = StageRef{k1_slot, k1_stage, k1_x0, 0.0f};
-      for (int s = 1; s < 7; ++s) ev[s] = StageRef{slot, s, L.xin(ws, slot, s), 0.0f};
+      for (int s = 1; s < S; ++s) ev[s] = StageRef{slot, s, L.xin(ws, slot, s), 0.0f};
       if (mixed_norm) {  // parameter block of this attempt: error estimate and increment, both linear in the seven stages
-        for (int s = 0; s < 7; ++s) ev[s].scale = h * (float)dp5::kCErr[s];
-        if ((rc = theta_wgrad(ev, 7, th_err)) != ODEHIP_OK) return rc;
-        for (int s = 0; s < 7; ++s) ev[s].scale = h * (float)dp5::kCSol[s];
-        if ((rc = theta_wgrad(ev, 7, th_inc)) != ODEHIP_OK) return rc;
+        for (int s = 0; s < S; ++s) ev[s].scale = h * (float)tb.c_err[s];
+        if ((rc = theta_wgrad(ev, S, th_err)) != ODEHIP_OK) return rc;
+        for (int s = 0; s < S; ++s) ev[s].scale = h * (float)tb.c_sol[s];
+        if ((rc = theta_wgrad(ev, S, th_inc)) != ODEHIP_OK) return rc;
         theta_sums(th_err, nullptr, th_run, th_inc, 0);
       }
       float e2[2];
@@ -369,7 +390,7 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
       if (mixed_norm) ratio = fmaxf(ratio, theta_rms_max(g_adj_host + 8));
       ODEHIP_REQUIRE(ratio == ratio, "odeint_adjoint_dopri5_backward: non-finite error ratio");
       const bool accept = ratio <= 1.0f;
-      const double dtn = dp5::next_step_size(dt, ratio);
+      const double dtn = next_step_size(dt, ratio, tb.order);
       if (!accept) {
         ++n_reject;
         dt = dtn;
@@ -380,20 +401,20 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
       const bool final_step = t_new >= t_end;
       float w[7];
       if (!final_step) {
-        for (int s = 0; s < 7; ++s) w[s] = (float)dp5::kCSol[s] * h;
+        for (int s = 0; s < S; ++s) w[s] = (float)tb.c_sol[s] * h;
       } else {
         // dense output at x: a(x) - a0 = h * sum_s W_s(x) k_s  (the quartic of _interp_fit/_interp_evaluate, linear in k)
         const float x = (float)((t_end - t_cur) / (t_new - t_cur));
-        for (int s = 0; s < 7; ++s) w[s] = h * (float)dp5::dense_weight(s, (double)x);
+        for (int s = 0; s < S; ++s) w[s] = h * (float)dense_weight(tb, s, (double)x);
       }
       if (mixed_norm) {  // the parameter block is integrated step by step (its running value enters the next tolerance)
         if (final_step) {
-          for (int s = 0; s < 7; ++s) ev[s].scale = w[s];
-          if ((rc = theta_wgrad(ev, 7, th_inc)) != ODEHIP_OK) return rc;
+          for (int s = 0; s < S; ++s) ev[s].scale = w[s];
+          if ((rc = theta_wgrad(ev, S, th_inc)) != ODEHIP_OK) return rc;
         }
         hipLaunchKernelGGL(theta_add_kernel, dim3(64), dim3(256), 0, stream, th_run, th_inc, P);
       }
-      for (int s = 0; s < 7 && !mixed_norm; ++s) {
+      for (int s = 0; s < S && !mixed_norm; ++s) {
         if (w[s] == 0.0f) continue;
         Entry e;
         e.scale = w[s];
@@ -406,17 +427,17 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
       }
       if (final_step) {
         float* a_next = L.p(ws, L.off_a2 + (size_t)(n & 1) * L.st);
-        lincomb(a_next, a_cur, 7, ka, w, goq(n));  // a(t[n]) + grad_out[n]
+        lincomb(a_next, a_cur, S, ka, w, goq(n));  // a(t[n]) + grad_out[n]
         a_cur = a_next;
         ++slot;
         break;
       }
       // FSAL: (y, a, k1) <- (y1, a1, k7)
-      y_cur = L.xin(ws, slot, 6);
-      a_cur = L.gp(ws, slot, 6, NH);
-      float* t1 = ky[0]; ky[0] = ky[6]; ky[6] = t1;
-      float* t2 = ka[0]; ka[0] = ka[6]; ka[6] = t2;
-      k1_slot = slot; k1_stage = 6; k1_x0 = L.xin(ws, slot, 6);
+      y_cur = L.xin(ws, slot, S - 1);
+      a_cur = L.gp(ws, slot, S - 1, NH);
+      float* t1 = ky[0]; ky[0] = ky[S - 1]; ky[S - 1] = t1;
+      float* t2 = ka[0]; ka[0] = ka[S - 1]; ka[S - 1] = t2;
+      k1_slot = slot; k1_stage = S - 1; k1_x0 = L.xin(ws, slot, S - 1);
       t_cur = t_new;
       dt = dtn;
       ++slot;

@@ -1,4 +1,5 @@
-// dopri5.hip -- adaptive Dormand-Prince 5(4) with a DEVICE-SIDE step controller (gfx950).
+// dopri5.hip -- the adaptive solvers (Dormand-Prince 5(4); Bogacki-Shampine 3(2), "bosh3") with a DEVICE-SIDE step controller
+// (gfx950).  Everything below is driven by the Tableau of the call's method (dopri5_control.h); the comments count in dopri5's numbers.
 //
 // Restates torchdiffeq 0.2.1's Dopri5Solver (_impl/rk_common.py: _adaptive_step, _runge_kutta_step,
 // _compute_error_ratio, _optimal_step_size; _impl/misc.py: _select_initial_step; _impl/interp.py) as called by the
@@ -39,6 +40,7 @@ struct DopriState {
   int n_times, n_partials;
   long long n_elems;
   int max_steps;
+  int order, n_stages;   // of the call's tableau: the step-size exponents are 1 / order, an attempt costs n_stages - 1 evaluations
   // SAVING mode (the forward of a training step keeps the stage inputs and hidden activations of every ACCEPTED step for the
   // backward pass: no re-integration).  An attempt writes them into slot `slot_next` of the backward workspace through
   // relocatable pointers (class 1, conv_wino.hip rel()); a rejected attempt's slot is simply reused, an accepted one moves on.
@@ -121,7 +123,7 @@ __global__ __launch_bounds__(256) void init1_kernel(DopriState* st, const float*
   if (threadIdx.x == 0) {
     const float n = (float)st->n_elems;
     const float d0 = sqrtf(s0 / n), d1 = sqrtf(s1 / n);
-    st->h0 = dp5::initial_step_h0(d0, d1);
+    st->h0 = initial_step_h0(d0, d1);
     st->ratio = d1;  // parked for init2
   }
 }
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(256) void init2_kernel(DopriState* st, const float*
     const float n = (float)st->n_elems;
     const float h0 = st->h0, d1 = st->ratio;
     const float d2 = sqrtf(s2 / n) / h0;
-    const double dt = (double)dp5::initial_step_dt(h0, d1, d2);
+    const double dt = (double)initial_step_dt(h0, d1, d2, st->order);
     st->t0 = st->t1 = t_out[0];
     st->dt = dt;
     st->h = (float)dt;
@@ -167,7 +169,7 @@ __global__ __launch_bounds__(256) void controller_kernel(DopriState* st, const f
   st->ratio = ratio;
   st->accept = accept;
   st->h_used = st->h;
-  st->nfe += 6;
+  st->nfe += st->n_stages - 1;
   st->n_steps += 1;
   const double dt = st->dt;
   int status = 0;
@@ -193,7 +195,7 @@ __global__ __launch_bounds__(256) void controller_kernel(DopriState* st, const f
     st->n_reject += 1;
     st->j_lo = st->j_hi = st->j_next;
   }
-  const double dtn = dp5::next_step_size(dt, ratio);
+  const double dtn = next_step_size(dt, ratio, st->order);
   st->dt = dtn;
   st->h = (float)dtn;
   const bool done = st->j_next >= st->n_times;
@@ -226,7 +228,7 @@ __global__ __launch_bounds__(256) void controller_kernel(DopriState* st, const f
 }
 
 // Elementwise tail of an attempt.  On accept: dense output for the output times inside the step (quartic of
-// _interp_fit/_interp_evaluate), then y <- y1, k1 <- k7 (FSAL).  Always: x2 = y + h_next * beta21 * k1.
+// _interp_fit/_interp_evaluate), then y <- y1, k1 <- k7 (FSAL: the last stage, k[last]).  Always: x2 = y + h_next * beta21 * k1.
 struct FinishArgs {
   const DopriState* st;
   const double* t_out;
@@ -237,10 +239,16 @@ struct FinishArgs {
   float* out_nchw;   // (T,B,C,16,16)
   int channels;
   long long state_floats;
-  long long off_y1, off_x2;   // saving mode: byte offsets of y1 (stage input 6) and of the stage-2 input inside a slot
+  long long off_y1, off_x2;   // saving mode: byte offsets of y1 (the last stage input) and of the stage-2 input inside a slot
+  float cm[7];       // c_mid
+  float b21;         // beta21
+  int dp5_sum;       // 1: the tableau is kDopri5 itself, whose c_mid sum is written out in finish_kernel<7, true> (bit stability)
 };
-__global__ __launch_bounds__(256) void finish_kernel(FinishArgs a, long long n4, float cm0, float cm2, float cm3, float cm4,
-                                                     float cm5, float cm6) {
+// S: the tableau's stage count, DP5: the tableau is kDopri5 itself -- compile-time, so that k[] and cm[] of the by-value argument block
+// are only ever indexed by constants (a run-time index would move the whole block to scratch memory)
+template <int S, bool DP5>
+__global__ __launch_bounds__(256) void finish_kernel(FinishArgs a, long long n4) {
+  constexpr int LAST = S - 1;
   const DopriState* st = a.st;
   const int accept = st->accept, j_lo = st->j_lo, j_hi = st->j_hi;
   if (st->done && !(accept && j_hi > j_lo)) return;  // nothing left to write
@@ -256,11 +264,21 @@ __global__ __launch_bounds__(256) void finish_kernel(FinishArgs a, long long n4,
     f32x4 k1 = ((const f32x4*)a.k[0])[i];
     if (accept) {
       const f32x4 y1 = ((const f32x4*)a.y1)[i];
-      const f32x4 k7 = ((const f32x4*)a.k[6])[i];
+      const f32x4 k7 = ((const f32x4*)a.k[LAST])[i];
       if (j_hi > j_lo) {
-        const f32x4 k3 = ((const f32x4*)a.k[2])[i], k4 = ((const f32x4*)a.k[3])[i], k5 = ((const f32x4*)a.k[4])[i],
-                    k6 = ((const f32x4*)a.k[5])[i];
-        const f32x4 ymid = y0 + (k1 * cm0 + k3 * cm2 + k4 * cm3 + k5 * cm4 + k6 * cm5 + k7 * cm6) * hu;
+        f32x4 ymid;
+        if constexpr (DP5) {   // dopri5, written out (c_mid[1] = 0)
+          const f32x4 k3 = ((const f32x4*)a.k[2])[i], k4 = ((const f32x4*)a.k[3])[i], k5 = ((const f32x4*)a.k[4])[i],
+                      k6 = ((const f32x4*)a.k[5])[i];
+          ymid = y0 + (k1 * a.cm[0] + k3 * a.cm[2] + k4 * a.cm[3] + k5 * a.cm[4] + k6 * a.cm[5] + k7 * a.cm[6]) * hu;
+        } else {             // any other tableau: the stages whose c_mid is not zero, in order
+          f32x4 sm = k1 * a.cm[0];
+#pragma unroll
+          for (int s = 1; s < LAST; ++s)
+            if (a.cm[s] != 0.0f) sm += ((const f32x4*)a.k[s])[i] * a.cm[s];
+          sm += k7 * a.cm[LAST];
+          ymid = y0 + sm * hu;
+        }
         const f32x4 ca = (k7 - k1) * (2.0f * hu) - (y1 + y0) * 8.0f + ymid * 16.0f;
         const f32x4 cb = (k1 * 5.0f - k7 * 3.0f) * hu + y0 * 18.0f + y1 * 14.0f - ymid * 32.0f;
         const f32x4 cc = (k7 - k1 * 4.0f) * hu - y0 * 11.0f - y1 * 5.0f + ymid * 16.0f;
@@ -287,7 +305,7 @@ __global__ __launch_bounds__(256) void finish_kernel(FinishArgs a, long long n4,
         ((f32x4*)a.k[0])[i] = k1;
       }
     }
-    if (!done) ((f32x4*)a.x2)[i] = y0 + k1 * (hn * 0.2f);  // beta21 = 1/5
+    if (!done) ((f32x4*)a.x2)[i] = y0 + k1 * (hn * a.b21);
   }
 }
 
@@ -325,7 +343,7 @@ __global__ void arm_first_step_kernel(DopriState* st, const double* t_out, doubl
 }
 __global__ void init_state_kernel(DopriState* st, float rtol, float atol, int n_times, int n_partials, long long n_elems,
                                   int max_steps, int save_max, unsigned long long slot_base, unsigned long long slot_bytes,
-                                  unsigned long long* reloc) {
+                                  unsigned long long* reloc, int order, int n_stages) {
   DopriState z;
   memset(&z, 0, sizeof(z));
   z.save_max = save_max;
@@ -340,6 +358,8 @@ __global__ void init_state_kernel(DopriState* st, float rtol, float atol, int n_
   z.n_partials = n_partials;
   z.n_elems = n_elems;
   z.max_steps = max_steps;
+  z.order = order;
+  z.n_stages = n_stages;
   *st = z;
 }
 
@@ -354,11 +374,12 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(SumSet ss, float* __r
   }
 }
 
-// ---- one dopri5 solve in flight.  The synchronous entry points build it on their stack and run it to completion; the asynchronous
+// ---- one adaptive solve in flight.  The synchronous entry points build it on their stack and run it to completion; the asynchronous
 // pair (odehip_odeint_dopri5_start / _collect) parks it in a slot between the two calls, so that the host can go on enqueueing the
 // work behind the solver (decoder, loss, the whole backward pass) while the device is still integrating.
 struct D5Ctx {
   bool in_use = false;
+  const Tableau* tb = &kDopri5;
   odehip_convstack f;          // by value: the caller's descriptor need not outlive the start call
   int n_times = 0, batch = 0, n_conv_partials = 0;
   float rtol = 0, atol = 0, ksc = 1;
@@ -417,14 +438,15 @@ static int d5_attempt(D5Ctx& x) {
   int rc;
   constexpr unsigned long long kTag1 = 1ull << 56;
   auto s_xin = [&](int e) { return (float*)(kTag1 | (unsigned long long)((size_t)e * x.bl_st)); };
-  auto s_hid = [&](int e, int l) { return (float*)(kTag1 | (unsigned long long)(7 * x.bl_st + ((size_t)e * x.bl_nh + l) * x.bl_hid)); };
+  const int S = x.tb->stages;
+  auto s_hid = [&](int e, int l) { return (float*)(kTag1 | (unsigned long long)((size_t)S * x.bl_st + ((size_t)e * x.bl_nh + l) * x.bl_hid)); };
   const int* skip = &x.state->done;
   PersistScope persist;
-  if ((rc = persist.begin(f, nullptr, 6 * f->n_convs)) != ODEHIP_OK) return rc;
+  if ((rc = persist.begin(f, nullptr, (S - 1) * f->n_convs)) != ODEHIP_OK) return rc;
   CombineArgs c;
-  for (int s = 2; s <= 7; ++s) {  // k_s = f(x_s); fused: x_{s+1} = y + h*sum beta_{s+1,j} k_j   (s = 7: error norm against y1 = x7)
-    float* const out_next = x.saving ? s_xin(s < 7 ? s : 6) : (s < 6 ? x.xs : x.y1);
-    dopri5_stage_combine(c, s, x.y, &x.state->h, x.k, out_next, x.part0, x.rtol, x.atol);
+  for (int s = 2; s <= S; ++s) {  // k_s = f(x_s); fused: x_{s+1} = y + h*sum beta_{s+1,j} k_j   (s = S: error norm against y1 = x_S)
+    float* const out_next = x.saving ? s_xin(s < S ? s : S - 1) : (s < S - 1 ? x.xs : x.y1);
+    adaptive_stage_combine(*x.tb, c, s, x.y, &x.state->h, x.k, out_next, x.part0, x.rtol, x.atol);
     c.k_scale = x.ksc;
     c.order = all_64(f);   // 64-channel stacks: the adaptive walk (stage sums formed ahead of the matrix work), same bits per layer
     if (x.saving) {   // evaluation (slot, s - 1): input and hidden activations live in the slot the device picks
@@ -433,7 +455,7 @@ static int d5_attempt(D5Ctx& x) {
       for (int l = 0; l < x.bl_nh; ++l) hid_s[l] = s_hid(s - 1, l);
       rc = enqueue_f_saving(f, s_xin(s - 1), x.batch, hid_s, x.ping, x.pong, &c, nullptr, skip, x.stream);
     } else {
-      rc = enqueue_f(f, s < 7 ? x.xs : x.y1, x.batch, x.ping, x.pong, &c, nullptr, skip, x.stream);
+      rc = enqueue_f(f, s < S ? x.xs : x.y1, x.batch, x.ping, x.pong, &c, nullptr, skip, x.stream);
     }
     if (rc != ODEHIP_OK) return rc;
   }
@@ -452,8 +474,15 @@ static int d5_attempt(D5Ctx& x) {
   }
   hipLaunchKernelGGL(controller_kernel, dim3(1), dim3(256), 0, x.stream, x.state, x.global_norm ? g_reduce_buf : x.part0, x.t_dev, x.mb, x.psync,
                      (int)(persist_sync_bytes(x.batch) / 4));
-  hipLaunchKernelGGL(finish_kernel, dim3(1024), dim3(256), 0, x.stream, x.fa, x.n4, (float)dp5::kCMid[0], (float)dp5::kCMid[2],
-                     (float)dp5::kCMid[3], (float)dp5::kCMid[4], (float)dp5::kCMid[5], (float)dp5::kCMid[6]);
+  switch (x.fa.dp5_sum ? 0 : x.tb->stages) {   // one instance per stage count: a further tableau needs no kernel of its own
+    case 0: hipLaunchKernelGGL((finish_kernel<7, true>), dim3(1024), dim3(256), 0, x.stream, x.fa, x.n4); break;
+    case 2: hipLaunchKernelGGL((finish_kernel<2, false>), dim3(1024), dim3(256), 0, x.stream, x.fa, x.n4); break;
+    case 3: hipLaunchKernelGGL((finish_kernel<3, false>), dim3(1024), dim3(256), 0, x.stream, x.fa, x.n4); break;
+    case 4: hipLaunchKernelGGL((finish_kernel<4, false>), dim3(1024), dim3(256), 0, x.stream, x.fa, x.n4); break;
+    case 5: hipLaunchKernelGGL((finish_kernel<5, false>), dim3(1024), dim3(256), 0, x.stream, x.fa, x.n4); break;
+    case 6: hipLaunchKernelGGL((finish_kernel<6, false>), dim3(1024), dim3(256), 0, x.stream, x.fa, x.n4); break;
+    default: hipLaunchKernelGGL((finish_kernel<7, false>), dim3(1024), dim3(256), 0, x.stream, x.fa, x.n4); break;
+  }
   ODEHIP_CHECK_HIP(hipGetLastError());
   ++x.enq;
   return ODEHIP_OK;
@@ -528,8 +557,8 @@ extern "C" int odehip_set_norm_allreduce(odehip_allreduce_fn cb, void* user, int
 }
 
 // Workspace: [state | t_out[T] | partials x3 | ping | pong | xs | y | y1 | k1..k7]
-extern "C" size_t odehip_dopri5_workspace_bytes(const odehip_convstack* f, int batch, int n_times) {
-  if (!f || batch <= 0 || n_times <= 0) return 0;
+extern "C" size_t odehip_adaptive_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int method) {
+  if (!f || batch <= 0 || n_times <= 0 || !adaptive_tableau(method)) return 0;
   const size_t st = al256((size_t)batch * f->channels[0] * kPix * 4);
   const size_t hid = al256((size_t)batch * max_hidden(f) * kPix * 4);
   const size_t np = (size_t)batch * (f->channels[0] / 32) * 2 * 4;
@@ -537,41 +566,70 @@ extern "C" size_t odehip_dopri5_workspace_bytes(const odehip_convstack* f, int b
          al256(persist_sync_bytes(batch)) + al256(16 * 8);
 }
 
-// SAVING forward: the plain forward's workspace followed by the backward pass's (dopri5_layout.h) with max_accept slots
-extern "C" size_t odehip_dopri5_saving_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int max_accept) {
-  if (!f || batch <= 0 || n_times <= 0 || max_accept <= 0 || f->n_convs < 1) return 0;
-  return odehip_dopri5_workspace_bytes(f, batch, n_times) + BwdLayout(f, batch, n_times, max_accept).total;
+extern "C" size_t odehip_dopri5_workspace_bytes(const odehip_convstack* f, int batch, int n_times) {
+  return odehip_adaptive_workspace_bytes(f, batch, n_times, ODEHIP_DOPRI5);
 }
 
-static int dopri5_forward(const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times, int batch, float rtol,
+// SAVING forward: the plain forward's workspace followed by the backward pass's (dopri5_layout.h) with max_accept slots
+extern "C" size_t odehip_adaptive_saving_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int max_accept, int method) {
+  const Tableau* tb = adaptive_tableau(method);
+  if (!f || batch <= 0 || n_times <= 0 || max_accept <= 0 || f->n_convs < 1 || !tb) return 0;
+  return odehip_adaptive_workspace_bytes(f, batch, n_times, method) + BwdLayout(f, batch, n_times, max_accept, tb->stages).total;
+}
+extern "C" size_t odehip_dopri5_saving_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int max_accept) {
+  return odehip_adaptive_saving_workspace_bytes(f, batch, n_times, max_accept, ODEHIP_DOPRI5);
+}
+
+static int dopri5_forward(int method, const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times, int batch, float rtol,
                           float atol, double first_step, int max_steps, int negate, float* out_nchw, int* stats_host,
                           double* accepted_host, int accepted_cap, void* workspace, size_t workspace_bytes, void* stream_,
                           int save_max_accept, int* saved_out, int async_attempts = 0, int* token_out = nullptr);
+
+extern "C" int odehip_odeint_adaptive(int method, const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times,
+                                      int batch, float rtol, float atol, double first_step, int max_steps, int negate,
+                                      float* out_nchw, int* stats_host, double* accepted_host, int accepted_cap, void* workspace,
+                                      size_t workspace_bytes, void* stream_) {
+  const ErrorNames names(method);
+  return dopri5_forward(method, f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, negate, out_nchw, stats_host, accepted_host,
+                        accepted_cap, workspace, workspace_bytes, stream_, 0, nullptr);
+}
 
 extern "C" int odehip_odeint_dopri5(const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times,
                                     int batch, float rtol, float atol, double first_step, int max_steps, int negate,
                                     float* out_nchw, int* stats_host, double* accepted_host, int accepted_cap, void* workspace,
                                     size_t workspace_bytes, void* stream_) {
-  return dopri5_forward(f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, negate, out_nchw, stats_host, accepted_host,
-                        accepted_cap, workspace, workspace_bytes, stream_, 0, nullptr);
+  return odehip_odeint_adaptive(ODEHIP_DOPRI5, f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, negate, out_nchw,
+                                stats_host, accepted_host, accepted_cap, workspace, workspace_bytes, stream_);
 }
 
+extern "C" int odehip_odeint_adaptive_saving(int method, const odehip_convstack* f, const float* z0_nchw, const double* t_host,
+                                             int n_times, int batch, float rtol, float atol, double first_step, int max_steps,
+                                             float* out_nchw, int* stats_host, double* accepted_host, int accepted_cap, int max_accept,
+                                             int* saved_out, void* workspace, size_t workspace_bytes, void* stream_) {
+  const ErrorNames names(method);
+  ODEHIP_REQUIRE(saved_out && max_accept > 0, "odeint_dopri5_saving: saved_out is required and max_accept must be positive");
+  *saved_out = 0;
+  ODEHIP_REQUIRE(adaptive_tableau(method), "odeint_adaptive_saving: unknown adaptive method code %d", method);
+  ODEHIP_REQUIRE(f && workspace_bytes >= odehip_adaptive_saving_workspace_bytes(f, batch, n_times, max_accept, method),
+                 "odeint_dopri5_saving: workspace too small");
+  return dopri5_forward(method, f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, 0, out_nchw, stats_host, accepted_host,
+                        accepted_cap, workspace, workspace_bytes, stream_, max_accept, saved_out);
+}
 extern "C" int odehip_odeint_dopri5_saving(const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times,
                                            int batch, float rtol, float atol, double first_step, int max_steps, float* out_nchw,
                                            int* stats_host, double* accepted_host, int accepted_cap, int max_accept, int* saved_out,
                                            void* workspace, size_t workspace_bytes, void* stream_) {
-  ODEHIP_REQUIRE(saved_out && max_accept > 0, "odeint_dopri5_saving: saved_out is required and max_accept must be positive");
-  *saved_out = 0;
-  ODEHIP_REQUIRE(f && workspace_bytes >= odehip_dopri5_saving_workspace_bytes(f, batch, n_times, max_accept),
-                 "odeint_dopri5_saving: workspace too small");
-  return dopri5_forward(f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, 0, out_nchw, stats_host, accepted_host,
-                        accepted_cap, workspace, workspace_bytes, stream_, max_accept, saved_out);
+  return odehip_odeint_adaptive_saving(ODEHIP_DOPRI5, f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, out_nchw,
+                                       stats_host, accepted_host, accepted_cap, max_accept, saved_out, workspace, workspace_bytes, stream_);
 }
 
-static int dopri5_forward(const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times, int batch, float rtol,
+static int dopri5_forward(int method, const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times, int batch, float rtol,
                           float atol, double first_step, int max_steps, int negate, float* out_nchw, int* stats_host,
                           double* accepted_host, int accepted_cap, void* workspace, size_t workspace_bytes, void* stream_,
                           int save_max_accept, int* saved_out, int async_attempts, int* token_out) {
+  const Tableau* tb = adaptive_tableau(method);
+  ODEHIP_REQUIRE(tb, "odeint_adaptive: unknown adaptive method code %d (ODEHIP_DOPRI5 or ODEHIP_BOSH3)", method);
+  ODEHIP_REQUIRE(method == ODEHIP_DOPRI5 || !g_reduce_cb, "odeint_adaptive: exact-global step control (odehip_set_norm_allreduce) is not implemented for bosh3");
   int rc = check_stack(f);
   if (rc != ODEHIP_OK) return rc;
   ODEHIP_REQUIRE(z0_nchw && t_host && out_nchw && workspace, "odeint_dopri5: null pointer");
@@ -581,7 +639,7 @@ static int dopri5_forward(const odehip_convstack* f, const float* z0_nchw, const
   for (int i = 1; i < n_times; ++i)
     ODEHIP_REQUIRE(t_host[i] > t_host[i - 1], "odeint_dopri5: t must be strictly increasing (t[%d]=%g, t[%d]=%g)", i - 1,
                    t_host[i - 1], i, t_host[i]);
-  ODEHIP_REQUIRE(workspace_bytes >= odehip_dopri5_workspace_bytes(f, batch, n_times), "odeint_dopri5: workspace too small");
+  ODEHIP_REQUIRE(workspace_bytes >= odehip_adaptive_workspace_bytes(f, batch, n_times, method), "odeint_dopri5: workspace too small");
   if (max_steps <= 0) max_steps = 1 << 30;
   hipStream_t stream = (hipStream_t)stream_;
   const int C = f->channels[0];
@@ -636,8 +694,8 @@ static int dopri5_forward(const odehip_convstack* f, const float* z0_nchw, const
   // follows this one; the slot is chosen on the device (class-1 relocatable pointers), so the attempt's table is still the same
   // for every attempt.  Needs the adaptive walk: without it (or for other stacks) nothing is saved and the caller re-integrates.
   bool saving = false;
-  char* bws = base + al256(odehip_dopri5_workspace_bytes(f, batch, n_times));
-  const BwdLayout BL(f, batch, n_times, save_max_accept > 0 ? save_max_accept : 1);
+  char* bws = base + al256(odehip_adaptive_workspace_bytes(f, batch, n_times, method));
+  const BwdLayout BL(f, batch, n_times, save_max_accept > 0 ? save_max_accept : 1, tb->stages);
   if (save_max_accept > 0 && all_64(f) && !g_reduce_cb && n_times > 1) saving = walk_ok;
 
   // exact-global mode: the kernels below read ONE already all-reduced scalar instead of the local partial arrays
@@ -648,7 +706,7 @@ static int dopri5_forward(const odehip_convstack* f, const float* z0_nchw, const
   hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(1), 0, stream, state, rtol, atol, n_times,
                      global_norm ? 1 : n_conv_partials, (long long)st_f * (global_norm ? g_reduce_world : 1), max_steps,
                      saving ? save_max_accept : 0, (unsigned long long)(uintptr_t)(bws + BL.off_slots), (unsigned long long)BL.slot_bytes,
-                     saving ? reloc : (unsigned long long*)nullptr);
+                     saving ? reloc : (unsigned long long*)nullptr, tb->order, tb->stages);
   for (int o = 0; o < n_times; o += 32) {
     DoublePack p;
     const int m = n_times - o < 32 ? n_times - o : 32;
@@ -720,7 +778,7 @@ static int dopri5_forward(const odehip_convstack* f, const float* z0_nchw, const
       hipLaunchKernelGGL(init2_kernel, dim3(1), dim3(256), 0, stream, state, part2, red_grid, t_dev);
     }
   }
-  lc.c[0] = (float)dp5::kBeta[0][0];
+  lc.c[0] = (float)tb->beta[0][0];
   lc.h_ptr = &state->h;
   if (saving) lc.out = BL.xin(bws, 0, 1);
   hipLaunchKernelGGL(lincomb_kernel, dim3(1024), dim3(256), 0, stream, lc, n4);  // x2 of the first attempt
@@ -737,12 +795,16 @@ static int dopri5_forward(const odehip_convstack* f, const float* z0_nchw, const
   fa.out_nchw = out_nchw;
   fa.channels = C;
   fa.state_floats = (long long)st_f;
-  fa.off_y1 = (long long)(6 * BL.st);
+  fa.off_y1 = (long long)((tb->stages - 1) * BL.st);
   fa.off_x2 = (long long)(1 * BL.st);
+  for (int i = 0; i < tb->stages; ++i) fa.cm[i] = (float)tb->c_mid[i];
+  fa.b21 = (float)tb->beta[0][0];
+  fa.dp5_sum = tb == &kDopri5;
 
   ODEHIP_CHECK_HIP(hipMemsetAsync(psync, 0, persist_sync_bytes(batch), stream));   // first attempt's flag area; the controller zeroes it for the next
   // ---- attempted steps
   cx.f = *f;
+  cx.tb = tb;
   cx.n_times = n_times; cx.batch = batch; cx.n_conv_partials = n_conv_partials;
   cx.rtol = rtol; cx.atol = atol; cx.ksc = ksc;
   cx.stream = stream;
@@ -776,22 +838,38 @@ static int dopri5_forward(const odehip_convstack* f, const float* z0_nchw, const
 // unreached frames NaN-filled; collect() reports ODEHIP_ETRUNC for the first, the controller's status for the second.  collect(token) waits for the device (normally long done) and returns what the synchronous call
 // returns (status code, stats, accepted-step log, saved flag).  Everything the start call was given (workspace, out, z0) must stay
 // untouched until collect; at most four solves may be pending.
-extern "C" int odehip_odeint_dopri5_start(const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times, int batch,
-                                          float rtol, float atol, double first_step, int max_steps, float* out_nchw, int max_accept,
-                                          int attempts, int* token_out, void* workspace, size_t workspace_bytes, void* stream_) {
+extern "C" int odehip_odeint_adaptive_start(int method, const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times,
+                                            int batch, float rtol, float atol, double first_step, int max_steps, float* out_nchw,
+                                            int max_accept, int attempts, int* token_out, void* workspace, size_t workspace_bytes,
+                                            void* stream_) {
+  const ErrorNames names(method);
   ODEHIP_REQUIRE(token_out && attempts > 0, "odeint_dopri5_start: token_out is required and attempts must be positive");
   *token_out = -1;
-  ODEHIP_REQUIRE(f && workspace_bytes >= (max_accept > 0 ? odehip_dopri5_saving_workspace_bytes(f, batch, n_times, max_accept)
-                                                           : odehip_dopri5_workspace_bytes(f, batch, n_times)),
+  ODEHIP_REQUIRE(adaptive_tableau(method), "odeint_adaptive_start: unknown adaptive method code %d", method);
+  ODEHIP_REQUIRE(f && workspace_bytes >= (max_accept > 0 ? odehip_adaptive_saving_workspace_bytes(f, batch, n_times, max_accept, method)
+                                                           : odehip_adaptive_workspace_bytes(f, batch, n_times, method)),
                  "odeint_dopri5_start: workspace too small");
   int saved_dummy = 0;
-  return dopri5_forward(f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, 0, out_nchw, nullptr, nullptr, 0, workspace,
+  return dopri5_forward(method, f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, 0, out_nchw, nullptr, nullptr, 0, workspace,
                         workspace_bytes, stream_, max_accept, &saved_dummy, attempts, token_out);
 }
 
+extern "C" int odehip_odeint_dopri5_start(const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times, int batch,
+                                          float rtol, float atol, double first_step, int max_steps, float* out_nchw, int max_accept,
+                                          int attempts, int* token_out, void* workspace, size_t workspace_bytes, void* stream_) {
+  return odehip_odeint_adaptive_start(ODEHIP_DOPRI5, f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, out_nchw,
+                                      max_accept, attempts, token_out, workspace, workspace_bytes, stream_);
+}
+
+// (the token names the solve, whatever its method)
 extern "C" int odehip_odeint_dopri5_collect(int token, int* stats_host, double* accepted_host, int accepted_cap, int* saved_out) {
+  return odehip_odeint_adaptive_collect(token, stats_host, accepted_host, accepted_cap, saved_out);
+}
+
+extern "C" int odehip_odeint_adaptive_collect(int token, int* stats_host, double* accepted_host, int accepted_cap, int* saved_out) {
   ODEHIP_REQUIRE(token >= 0 && token < kD5Slots && g_d5[token].in_use, "odeint_dopri5_collect: no pending solve with token %d", token);
   D5Ctx& cx = g_d5[token];
+  const ErrorNames names(cx.tb == &kBosh3 ? ODEHIP_BOSH3 : ODEHIP_DOPRI5);
   cx.in_use = false;   // whatever happens below, the slot is free again
   if (saved_out) *saved_out = 0;
   if (cx.n_times == 1) {

@@ -12,6 +12,7 @@
 //        gY_s   = J_f(Y_s)^T seed_s  (+ gy1 for s = 7)         -- dgrad chain on the MFMA conv kernels, ReLU mask fused
 //        gy0    = sum_i G_i + sum_{s>=2} gY_s ;  gk_1 goes to the previous step's k7 (FSAL) or, at n = 0, through f(z0);
 //   3. one wgrad launch per layer sums the weight gradients of all 6N+1 stage evaluations (wgrad.hip).
+// The sweep reads the tableau of the call's method (S stages; the numbers above are dopri5's: S = 7, S - 1 = 6 new evaluations per step).
 // Not differentiated: the dependence of the FIRST step size on y0/theta through _select_initial_step (a term of the
 // size of the local error; absent altogether with options={'first_step': dt}).
 #include <math.h>
@@ -33,14 +34,18 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 using namespace odehip;
 
+extern "C" size_t odehip_adaptive_backward_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int n_steps, int method) {
+  const Tableau* tb = adaptive_tableau(method);
+  if (!f || batch <= 0 || n_times <= 0 || n_steps < 0 || f->n_convs < 1 || !tb) return 0;
+  return BwdLayout(f, batch, n_times, n_steps, tb->stages).total;
+}
 extern "C" size_t odehip_dopri5_backward_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int n_steps) {
-  if (!f || batch <= 0 || n_times <= 0 || n_steps < 0 || f->n_convs < 1) return 0;
-  return BwdLayout(f, batch, n_times, n_steps).total;
+  return odehip_adaptive_backward_workspace_bytes(f, batch, n_times, n_steps, ODEHIP_DOPRI5);
 }
 
 // layout_steps: the number of slots the workspace was laid out for (n_steps, or the saving forward's max_accept); saved: the
 // slots already hold the stage inputs and hidden activations of the accepted steps (odehip_odeint_dopri5_saving): no re-integration
-static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host, int n_times, int batch,
+static int dopri5_backward(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host, int n_times, int batch,
                            const double* accepted_host, int n_steps, const float* z0_nchw, const float* grad_out_nchw,
                            float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, void* workspace, size_t workspace_bytes,
                            void* stream_, int layout_steps, bool saved);
@@ -50,29 +55,53 @@ extern "C" int odehip_odeint_dopri5_backward(const odehip_convstack* f, const od
                                              const float* z0_nchw, const float* grad_out_nchw, float* grad_z0_nchw,
                                              float* const* grad_w, float* const* grad_b, void* workspace, size_t workspace_bytes,
                                              void* stream_) {
-  ODEHIP_REQUIRE(z0_nchw, "odeint_dopri5_backward: null pointer");
-  return dopri5_backward(f, f_dgrad, t_host, n_times, batch, accepted_host, n_steps, z0_nchw, grad_out_nchw, grad_z0_nchw, grad_w, grad_b,
-                         workspace, workspace_bytes, stream_, n_steps, false);
+  return odehip_odeint_adaptive_backward(ODEHIP_DOPRI5, f, f_dgrad, t_host, n_times, batch, accepted_host, n_steps, z0_nchw, grad_out_nchw,
+                                         grad_z0_nchw, grad_w, grad_b, workspace, workspace_bytes, stream_);
 }
-
 extern "C" int odehip_odeint_dopri5_backward_saved(const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host,
                                                    int n_times, int batch, const double* accepted_host, int n_steps,
                                                    const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w,
                                                    float* const* grad_b, int max_accept, void* saved_workspace,
                                                    size_t saved_workspace_bytes, void* stream_) {
+  return odehip_odeint_adaptive_backward_saved(ODEHIP_DOPRI5, f, f_dgrad, t_host, n_times, batch, accepted_host, n_steps, grad_out_nchw,
+                                               grad_z0_nchw, grad_w, grad_b, max_accept, saved_workspace, saved_workspace_bytes, stream_);
+}
+
+extern "C" int odehip_odeint_adaptive_backward(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad,
+                                               const double* t_host, int n_times, int batch, const double* accepted_host, int n_steps,
+                                               const float* z0_nchw, const float* grad_out_nchw, float* grad_z0_nchw,
+                                               float* const* grad_w, float* const* grad_b, void* workspace, size_t workspace_bytes,
+                                               void* stream_) {
+  const ErrorNames names(method);
+  ODEHIP_REQUIRE(z0_nchw, "odeint_dopri5_backward: null pointer");
+  return dopri5_backward(method, f, f_dgrad, t_host, n_times, batch, accepted_host, n_steps, z0_nchw, grad_out_nchw, grad_z0_nchw, grad_w, grad_b,
+                         workspace, workspace_bytes, stream_, n_steps, false);
+}
+
+extern "C" int odehip_odeint_adaptive_backward_saved(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad,
+                                                     const double* t_host, int n_times, int batch, const double* accepted_host,
+                                                     int n_steps, const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w,
+                                                     float* const* grad_b, int max_accept, void* saved_workspace,
+                                                     size_t saved_workspace_bytes, void* stream_) {
+  const ErrorNames names(method);
+  ODEHIP_REQUIRE(adaptive_tableau(method), "odeint_adaptive_backward_saved: unknown adaptive method code %d", method);
   ODEHIP_REQUIRE(f && saved_workspace && max_accept > 0 && n_steps >= 1 && n_steps <= max_accept,
                  "odeint_dopri5_backward_saved: needs the saving forward's workspace and 1 <= n_steps <= max_accept");
-  ODEHIP_REQUIRE(saved_workspace_bytes >= odehip_dopri5_saving_workspace_bytes(f, batch, n_times, max_accept),
+  ODEHIP_REQUIRE(saved_workspace_bytes >= odehip_adaptive_saving_workspace_bytes(f, batch, n_times, max_accept, method),
                  "odeint_dopri5_backward_saved: workspace smaller than the saving forward's");
-  char* bws = (char*)saved_workspace + al256(odehip_dopri5_workspace_bytes(f, batch, n_times));   // the backward half (dopri5.hip)
-  return dopri5_backward(f, f_dgrad, t_host, n_times, batch, accepted_host, n_steps, nullptr, grad_out_nchw, grad_z0_nchw, grad_w, grad_b,
+  char* bws = (char*)saved_workspace + al256(odehip_adaptive_workspace_bytes(f, batch, n_times, method));   // the backward half (dopri5.hip)
+  return dopri5_backward(method, f, f_dgrad, t_host, n_times, batch, accepted_host, n_steps, nullptr, grad_out_nchw, grad_z0_nchw, grad_w, grad_b,
                          bws, saved_workspace_bytes - (size_t)(bws - (char*)saved_workspace), stream_, max_accept, true);
 }
 
-static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host, int n_times, int batch,
+static int dopri5_backward(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host, int n_times, int batch,
                            const double* accepted_host, int n_steps, const float* z0_nchw, const float* grad_out_nchw,
                            float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, void* workspace, size_t workspace_bytes,
                            void* stream_, int layout_steps, bool saved) {
+  const Tableau* tbp = adaptive_tableau(method);
+  ODEHIP_REQUIRE(tbp, "odeint_adaptive_backward: unknown adaptive method code %d (ODEHIP_DOPRI5 or ODEHIP_BOSH3)", method);
+  const Tableau& tb = *tbp;
+  const int S = tb.stages;   // stage s (1-based) lives at index s - 1; S - 1 new evaluations per accepted step
   int rc = check_stack(f);
   if (rc != ODEHIP_OK) return rc;
   ODEHIP_REQUIRE(f_dgrad && t_host && (z0_nchw || saved) && grad_out_nchw && grad_z0_nchw && grad_w && grad_b && workspace,
@@ -84,8 +113,8 @@ static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_
     ODEHIP_REQUIRE(f->channels[l] % 64 == 0, "odeint_dopri5_backward: channel counts must be multiples of 64");
   for (int i = 1; i < n_times; ++i)
     ODEHIP_REQUIRE(t_host[i] > t_host[i - 1], "odeint_dopri5_backward: t must be strictly increasing");
-  ODEHIP_REQUIRE(6 * n_steps + 1 <= 32 * 64, "odeint_dopri5_backward: too many accepted steps (%d)", n_steps);
-  const BwdLayout L(f, batch, n_times, layout_steps);
+  ODEHIP_REQUIRE((S - 1) * n_steps + 1 <= 32 * 64, "odeint_dopri5_backward: too many accepted steps (%d)", n_steps);
+  const BwdLayout L(f, batch, n_times, layout_steps, S);
   ODEHIP_REQUIRE(workspace_bytes >= L.total, "odeint_dopri5_backward: workspace too small");
   hipStream_t stream = (hipStream_t)stream_;
   void* ws = workspace;
@@ -113,7 +142,7 @@ static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_
   float* pong = L.p(ws, L.off_pong);
   float* k[7];
   float* gY[7];
-  for (int i = 0; i < 7; ++i) {
+  for (int i = 0; i < S; ++i) {
     k[i] = L.p(ws, L.off_k + (size_t)i * L.st);
     gY[i] = L.p(ws, L.off_gY + (size_t)i * L.st);
   }
@@ -147,9 +176,9 @@ static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_
   }
   int n_out_max = 1;
   for (int n = 0; n < N; ++n) n_out_max = j_hi[n] - j_lo[n] > n_out_max ? j_hi[n] - j_lo[n] : n_out_max;
-  const int ew_per_seed = (n_out_max + 6 + ODEHIP_MAX_STAGES) / ODEHIP_MAX_STAGES + 1;
+  const int ew_per_seed = (n_out_max + S - 1 + ODEHIP_MAX_STAGES) / ODEHIP_MAX_STAGES + 1;
   PersistScope persist;
-  if ((rc = persist.begin(f, f_dgrad, 2 * (6 * N + 1) * NL + (8 * N + 2) * ew_per_seed)) != ODEHIP_OK) return rc;
+  if ((rc = persist.begin(f, f_dgrad, 2 * ((S - 1) * N + 1) * NL + ((S + 1) * N + 2) * ew_per_seed)) != ODEHIP_OK) return rc;
   persist.set_volatile_table(true);
 
   float* hidv[ODEHIP_MAX_LAYERS];
@@ -194,21 +223,21 @@ static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_
   c.k_out = k[0];
   c.y = L.xin(ws, 0, 0);
   c.h_ptr = hdev;
-  c.c1[0] = (float)dp5::kBeta[0][0];
+  c.c1[0] = (float)tb.beta[0][0];
   c.out1 = L.xin(ws, 0, 1);
   if (!saved && (rc = run_f(0, 0, L.xin(ws, 0, 0), c)) != ODEHIP_OK) return rc;  // k1 of the first step (+ its Y_2)
   for (int n = 0; n < N && !saved; ++n) {
-    const float* y0 = n == 0 ? L.xin(ws, 0, 0) : L.xin(ws, n - 1, 6);
-    for (int s = 2; s <= 7; ++s) {
-      if (s <= 6) {
-        dopri5_stage_combine(c, s, y0, hdev + n, k, L.xin(ws, n, s), nullptr, 0.0f, 0.0f);  // Y_{s+1}; s = 6: y1
-      } else {   // no error norm here: k7 = k1 of the next step, and its Y_2 = y1 + h_{n+1}*beta21*k7 rides along
+    const float* y0 = n == 0 ? L.xin(ws, 0, 0) : L.xin(ws, n - 1, S - 1);
+    for (int s = 2; s <= S; ++s) {
+      if (s < S) {
+        adaptive_stage_combine(tb, c, s, y0, hdev + n, k, L.xin(ws, n, s), nullptr, 0.0f, 0.0f);  // Y_{s+1}; s = S - 1: y1
+      } else {   // no error norm here: k_S = k1 of the next step, and its Y_2 = y1 + h_{n+1}*beta21*k_S rides along
         memset(&c, 0, sizeof(c));
-        c.k_out = k[6];
+        c.k_out = k[S - 1];
         if (n + 1 < N) {
-          c.y = L.xin(ws, n, 6);
+          c.y = L.xin(ws, n, S - 1);
           c.h_ptr = hdev + n + 1;
-          c.c1[0] = (float)dp5::kBeta[0][0];
+          c.c1[0] = (float)tb.beta[0][0];
           c.out1 = L.xin(ws, n + 1, 1);
         }
       }
@@ -216,7 +245,7 @@ static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_
       c.order = order1;
       if ((rc = run_f(n, s - 1, L.xin(ws, n, s - 1), c)) != ODEHIP_OK) return rc;
     }
-    float* t = k[0]; k[0] = k[6]; k[6] = t;  // FSAL
+    float* t = k[0]; k[0] = k[S - 1]; k[S - 1] = t;  // FSAL
   }
 
   // ---- 2. reverse sweep ------------------------------------------------------------------------------------------------------
@@ -242,29 +271,29 @@ static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_
     const double t0 = accepted_host[2 * n], t1 = t0 + accepted_host[2 * n + 1];
     const float h = (float)accepted_host[2 * n + 1];
     const int nout = j_hi[n] - j_lo[n];
-    std::vector<float> W((size_t)nout * 7);
+    std::vector<float> W((size_t)nout * S);
     for (int i = 0; i < nout; ++i) {
       const float x = (float)((t_host[j_lo[n] + i] - t0) / (t1 - t0));
-      for (int s = 0; s < 7; ++s) {
-        W[(size_t)i * 7 + s] = h * (float)dp5::dense_weight(s, (double)x);
+      for (int s = 0; s < S; ++s) {
+        W[(size_t)i * S + s] = h * (float)dense_weight(tb, s, (double)x);
       }
     }
-    for (int s = 7; s >= 1; --s) {  // stage s lives at index s-1
+    for (int s = S; s >= 1; --s) {  // stage s lives at index s-1
       src.clear();
       cf.clear();
       for (int i = 0; i < nout; ++i)
-        if (W[(size_t)i * 7 + s - 1] != 0.0f) {
+        if (W[(size_t)i * S + s - 1] != 0.0f) {
           src.push_back(goq(j_lo[n] + i));
-          cf.push_back(W[(size_t)i * 7 + s - 1]);
+          cf.push_back(W[(size_t)i * S + s - 1]);
         }
-      for (int sp = s + 1; sp <= 7; ++sp) {  // Y_{sp} = y0 + h*sum_j beta[sp-2][j] k_{j+1}
-        const float b = (float)dp5::kBeta[sp - 2][s - 1];
+      for (int sp = s + 1; sp <= S; ++sp) {  // Y_{sp} = y0 + h*sum_j beta[sp-2][j] k_{j+1}
+        const float b = (float)tb.beta[sp - 2][s - 1];
         if (b != 0.0f) {
           src.push_back(gY[sp - 1]);
           cf.push_back(h * b);
         }
       }
-      if (s == 7 && have_gk1) {
+      if (s == S && have_gk1) {
         src.push_back(gk1);
         cf.push_back(1.0f);
       }
@@ -275,7 +304,7 @@ static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_
         w.n_targets = 1;
         w.tgt[0].out = gY[s - 1];
         w.tgt[0].g_c = 1.0f;
-        if (s == 7) {  // Y_7 is also the step's result y1
+        if (s == S) {  // Y_S is also the step's result y1
           w.tgt[0].srcA = gy;
           w.tgt[0].a_c = 1.0f;
         }
@@ -293,7 +322,7 @@ static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_
       src.push_back(goq(j_lo[n] + i));
       cf.push_back(1.0f);
     }
-    for (int s = 2; s <= 7; ++s) {
+    for (int s = 2; s <= S; ++s) {
       src.push_back(gY[s - 1]);
       cf.push_back(1.0f);
     }
@@ -319,14 +348,14 @@ static int dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_
   if (rc != ODEHIP_OK) return rc;
 
   // ---- 3. weight / bias gradients: one launch per layer over all stage evaluations; the NL tables travel in ONE staged upload
-  const int n_eval = 6 * N + 1;
+  const int n_eval = (S - 1) * N + 1;
   WgradPair* table = (WgradPair*)L.p(ws, L.off_tab);
   float* slabs = L.p(ws, L.off_slab);
   std::vector<WgradPair> host((size_t)n_eval * NL);
   for (int l = 0; l < NL; ++l) {
     int e = 0;
     for (int n = 0; n < N; ++n)
-      for (int s = (n == 0 ? 0 : 1); s < 7; ++s, ++e) {
+      for (int s = (n == 0 ? 0 : 1); s < S; ++s, ++e) {
         WgradPair& hp = host[(size_t)l * n_eval + e];
         hp.g = L.gp(ws, n, s, wgrad_slot(f, l));
         hp.a = l == 0 ? L.xin(ws, n, s) : L.hidden(ws, n, s, l - 1);

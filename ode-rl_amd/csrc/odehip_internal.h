@@ -16,6 +16,15 @@ constexpr int kPix = kHW * kHW;   // 256 pixels
 constexpr int kQuadBytes = kPix * 16;  // one channel-quad plane of the Q4 layout: 256 px * 4 ch * 4 B
 
 void set_error(const char* fmt, ...);
+// While one lives (on the stack of a method-coded adaptive entry point) the errors this thread sets name the call's method: the
+// drivers are shared and their messages say "dopri5"
+extern thread_local const char* g_err_method;
+struct ErrorNames {
+  const char* prev;
+  explicit ErrorNames(int method) : prev(g_err_method) { g_err_method = method == ODEHIP_BOSH3 ? "bosh3" : nullptr; }
+  ~ErrorNames() { g_err_method = prev; }
+  ErrorNames(const ErrorNames&) = delete;
+};
 int hip_fail(hipError_t e, const char* what);
 
 #define ODEHIP_CHECK_HIP(expr)                                   \
@@ -296,27 +305,31 @@ int launch_btraj_bf16_rk4(const odehip_convstack* f_dgrad, const float* grad_out
 int launch_bias_reduce(const float* bias_part, int n_parts, int n_layers, float* const* grad_b, hipStream_t stream);
 
 // ---- the adaptive solver's drivers (dopri5.hip, dopri5_backward.hip, adjoint_dopri5.hip, adjoint_device.hip) ------------------
-// The stage combine behind k_s = f(x_s) of a Dormand-Prince attempt, s = 2 .. 7 (stage s lives at index s - 1 of k): stages 2 .. 6
-// form the next stage input x_{s+1} = y + h * sum beta_{s+1,j} k_j in out_next (s = 6: y1 -- c_sol equals the last beta row), stage 7
-// the error norm against out_next = y1.  The caller sets k_scale and order afterwards.
-inline void dopri5_stage_combine(CombineArgs& c, int s, const float* y, const float* h_ptr, float* const* k, float* out_next,
-                                 float* err_partials, float rtol, float atol) {
+// The stage combine behind k_s = f(x_s) of an attempt with tableau tb (S = tb.stages), s = 2 .. S (stage s lives at index s - 1 of
+// k): stages 2 .. S - 1 form the next stage input x_{s+1} = y + h * sum beta_{s+1,j} k_j in out_next (s = S - 1: y1 -- c_sol equals
+// the last beta row), stage S the error norm against out_next = y1.  The caller sets k_scale and order afterwards.
+inline void adaptive_stage_combine(const Tableau& tb, CombineArgs& c, int s, const float* y, const float* h_ptr, float* const* k,
+                                   float* out_next, float* err_partials, float rtol, float atol) {
   memset(&c, 0, sizeof(c));
   c.y = y;
   c.h_ptr = h_ptr;
   c.n_prev = s - 1;
   for (int j = 0; j < s - 1; ++j) c.k_prev[j] = k[j];
   c.k_out = k[s - 1];
-  if (s <= 6) {
-    for (int j = 0; j < s; ++j) c.c1[j] = (float)dp5::kBeta[s - 1][j];
+  if (s < tb.stages) {
+    for (int j = 0; j < s; ++j) c.c1[j] = (float)tb.beta[s - 1][j];
     c.out1 = out_next;
   } else {
-    for (int j = 0; j < 7; ++j) c.ce[j] = (float)dp5::kCErr[j];
+    for (int j = 0; j < tb.stages; ++j) c.ce[j] = (float)tb.c_err[j];
     c.err_y1 = out_next;
     c.err_partials = err_partials;
     c.rtol = rtol;
     c.atol = atol;
   }
+}
+inline void dopri5_stage_combine(CombineArgs& c, int s, const float* y, const float* h_ptr, float* const* k, float* out_next,
+                                 float* err_partials, float rtol, float atol) {
+  adaptive_stage_combine(kDopri5, c, s, y, h_ptr, k, out_next, err_partials, rtol, atol);
 }
 
 // The host's watch on the progress word of a pinned mailbox a device-side controller writes: the limit is on time WITHOUT

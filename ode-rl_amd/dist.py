@@ -107,7 +107,9 @@ def enable_global_step_control(device, group=None):
     Installs an all-reduce hook in the HIP library (include/odecgru_hip.h: odehip_set_norm_allreduce): every sum of squares
     the step controller uses is summed over the ranks of `group` first (a 4..8-byte RCCL all-reduce per attempted step), so
     all ranks take the accept/reject decisions a single device holding the full batch would take.  Every rank must call
-    odeint the same number of times with the same t.  Without it each rank adapts on its own shard (agrees to O(rtol))."""
+    odeint the same number of times with the same t.  Without it each rank adapts on its own shard (agrees to O(rtol)).
+    dopri5 only: while the hook is installed, odeint(method="bosh3") raises ValueError ("exact-global step control ... is not
+    implemented for bosh3") -- it is refused, not run per shard."""
     global _global_ctl
     import ctypes
     from . import _lib

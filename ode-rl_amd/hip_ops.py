@@ -567,14 +567,24 @@ def odeint_fixed_on_grid_backward(stack, method, t, grid, batch, grad_out, ws):
 LOG_CAP = 2048   # accepted steps the forward reports back (the backward pass re-integrates them)
 
 
-def _dopri5_buffers(desc, z0, b, c, n, slots):
-    """(workspace, output) of a dopri5 forward.  With `slots` the workspace also keeps the activations of that many accepted steps and
-    is private (it must survive untouched until backward); without, it is the shared ("dopri5", ...) one."""
+def _adaptive_code(method):
+    """The C ABI's code of an adaptive method name ("dopri5", "bosh3").  bosh3 has no bf16 form: refused, not run in another mode."""
+    if method not in _lib.ADAPTIVE_METHODS:
+        raise ValueError(f"not an adaptive method of this path: {method!r}")
+    if method == "bosh3" and current_compute_dtype() == "bf16":
+        raise TypeError("odeint(HIP): method bosh3 is not implemented in bf16 compute mode (fp32 only); use dopri5 or "
+                        'set_compute_dtype("f32")')
+    return _lib.ADAPTIVE_METHODS[method]
+
+
+def _dopri5_buffers(desc, z0, b, c, n, slots, m=_lib.DOPRI5):
+    """(workspace, output) of an adaptive forward of method code m.  With `slots` the workspace also keeps the activations of that many
+    accepted steps and is private (it must survive untouched until backward); without, it is the shared ("dopri5", ...) one."""
     lib = _lib.load()
     if slots:
-        ws = alloc_workspace(lib.odehip_dopri5_saving_workspace_bytes(ctypes.byref(desc), b, n, slots), z0.device)
+        ws = alloc_workspace(lib.odehip_adaptive_saving_workspace_bytes(ctypes.byref(desc), b, n, slots, m), z0.device)
     else:
-        ws = workspace(("dopri5", b, n, tuple(desc.channels)), lib.odehip_dopri5_workspace_bytes(ctypes.byref(desc), b, n), z0.device)
+        ws = workspace(("dopri5", b, n, tuple(desc.channels)), lib.odehip_adaptive_workspace_bytes(ctypes.byref(desc), b, n, m), z0.device)
     return ws, torch.empty((n, b, c, 16, 16), dtype=torch.float32, device=z0.device)
 
 
@@ -594,16 +604,17 @@ def _c_step_log(accepted):
     return (ctypes.c_double * max(len(flat), 1))(*flat)
 
 
-def odeint_dopri5(stack, z0, t, rtol, atol, first_step=0.0, max_steps=0, negate=False):
-    """Adaptive dopri5 trajectory; returns ((T,B,C,16,16), stats dict).  stats["accepted"] = [(t0, dt), ...]."""
+def odeint_dopri5(stack, z0, t, rtol, atol, first_step=0.0, max_steps=0, negate=False, method="dopri5"):
+    """Adaptive trajectory (method: "dopri5" or "bosh3"); returns ((T,B,C,16,16), stats dict).  stats["accepted"] = [(t0, dt), ...]."""
+    m = _adaptive_code(method)
     collect_pending_solves()   # an asynchronous solve still in flight owns the shared ("dopri5", ...) workspace
     desc, z0, b, c, n, tarr = _solver_inputs(stack, z0, t)
-    ws, out = _dopri5_buffers(desc, z0, b, c, n, 0)
+    ws, out = _dopri5_buffers(desc, z0, b, c, n, 0, m)
     stats = (ctypes.c_int * 4)()
     log = (ctypes.c_double * (2 * LOG_CAP))()
-    _lib.check(_lib.load().odehip_odeint_dopri5(ctypes.byref(desc), _ptr(z0), tarr, n, b, float(rtol), float(atol), float(first_step or 0.0),
-                                                int(max_steps), int(bool(negate)), _ptr(out), stats, log, LOG_CAP, _ptr(ws), ws.numel(),
-                                                _stream()))
+    _lib.check(_lib.load().odehip_odeint_adaptive(m, ctypes.byref(desc), _ptr(z0), tarr, n, b, float(rtol), float(atol), float(first_step or 0.0),
+                                                  int(max_steps), int(bool(negate)), _ptr(out), stats, log, LOG_CAP, _ptr(ws), ws.numel(),
+                                                  _stream()))
     return out, _dopri5_stats(stats, log)
 
 
@@ -632,7 +643,7 @@ _pending_solves = []     # PendingDopri5 objects not collected yet
 
 
 def set_async_dopri5(on=True):
-    """Switch the asynchronous dopri5 forward on / off (see above); returns the previous setting."""
+    """Switch the asynchronous adaptive forward (dopri5 and bosh3) on / off (see above); returns the previous setting."""
     global _async_dopri5
     was = _async_dopri5
     _async_dopri5 = bool(on)
@@ -755,47 +766,49 @@ class LazyStats(dict):
         return dict.__repr__(self)
 
 
-def odeint_dopri5_start(stack, z0, t, rtol, atol, first_step=0.0, max_steps=0, save=False):
+def odeint_dopri5_start(stack, z0, t, rtol, atol, first_step=0.0, max_steps=0, save=False, method="dopri5"):
     """Asynchronous dopri5 forward: returns (out, PendingDopri5) at once.  save=True keeps the activations of the accepted steps
     (as odeint_dopri5_saving does) in a private workspace held by the pending object."""
+    m = _adaptive_code(method)
     collect_pending_solves()      # one solve in flight per process: the shared workspaces and the library's slots are free again
     desc, z0, b, c, n, tarr = _solver_inputs(stack, z0, t)
     slots = _dopri5_save_slots if save and os.environ.get("ODEHIP_DOPRI5_SAVE") != "0" else 0
-    ws, out = _dopri5_buffers(desc, z0, b, c, n, slots)
+    ws, out = _dopri5_buffers(desc, z0, b, c, n, slots, m)
     token = ctypes.c_int(-1)
-    _lib.check(_lib.load().odehip_odeint_dopri5_start(ctypes.byref(desc), _ptr(z0), tarr, n, b, float(rtol), float(atol),
+    _lib.check(_lib.load().odehip_odeint_adaptive_start(m, ctypes.byref(desc), _ptr(z0), tarr, n, b, float(rtol), float(atol),
                                                       float(first_step or 0.0), int(max_steps), _ptr(out), int(slots), int(_async_attempts),
                                                       ctypes.byref(token), _ptr(ws), ws.numel(), _stream()))
     return out, PendingDopri5(token.value, (z0, out, ws), slots, ws if slots else None)
 
 
-def odeint_dopri5_saving(stack, z0, t, rtol, atol, first_step=0.0, max_steps=0):
+def odeint_dopri5_saving(stack, z0, t, rtol, atol, first_step=0.0, max_steps=0, method="dopri5"):
     """The forward of a dopri5 TRAINING step: odeint_dopri5 that also keeps the stage inputs and hidden activations of every accepted
     step in a private workspace, so that the backward pass needs no re-integration.  Returns (out, stats, saved) with saved =
     (workspace, max_accept), or None when nothing was kept (other stacks than 64-channel fp32, persistent walk off, more accepted
     steps than slots): the caller then takes odeint_dopri5_backward."""
     if _async_dopri5:   # enqueue only: stats and `saved` are read later (LazyStats / PendingDopri5.collect())
-        out, pending = odeint_dopri5_start(stack, z0, t, rtol, atol, first_step=first_step, max_steps=max_steps, save=True)
+        out, pending = odeint_dopri5_start(stack, z0, t, rtol, atol, first_step=first_step, max_steps=max_steps, save=True, method=method)
         return out, pending, pending
     if os.environ.get("ODEHIP_DOPRI5_SAVE") == "0":   # A/B switch: always re-integrate in the backward pass
-        out, st = odeint_dopri5(stack, z0, t, rtol, atol, first_step=first_step, max_steps=max_steps)
+        out, st = odeint_dopri5(stack, z0, t, rtol, atol, first_step=first_step, max_steps=max_steps, method=method)
         st["saved"] = False
         return out, st, None
+    m = _adaptive_code(method)
     collect_pending_solves()
     desc, z0, b, c, n, tarr = _solver_inputs(stack, z0, t)
     slots = _dopri5_save_slots
-    ws, out = _dopri5_buffers(desc, z0, b, c, n, slots)
+    ws, out = _dopri5_buffers(desc, z0, b, c, n, slots, m)
     stats = (ctypes.c_int * 4)()
     log = (ctypes.c_double * (2 * LOG_CAP))()
     saved = ctypes.c_int(0)
-    _lib.check(_lib.load().odehip_odeint_dopri5_saving(ctypes.byref(desc), _ptr(z0), tarr, n, b, float(rtol), float(atol),
+    _lib.check(_lib.load().odehip_odeint_adaptive_saving(m, ctypes.byref(desc), _ptr(z0), tarr, n, b, float(rtol), float(atol),
                                                        float(first_step or 0.0), int(max_steps), _ptr(out), stats, log, LOG_CAP, slots,
                                                        ctypes.byref(saved), _ptr(ws), ws.numel(), _stream()))
     _grow_save_slots(slots, int(stats[1]))
     return out, _dopri5_stats(stats, log, saved), ((ws, slots) if saved.value else None)
 
 
-def odeint_dopri5_backward_saved(stack, t, accepted, grad_out, saved):
+def odeint_dopri5_backward_saved(stack, t, accepted, grad_out, saved, method="dopri5"):
     """Backward of odeint_dopri5_saving: the reverse sweep over the kept activations (no re-integration)."""
     require_device_tensor(grad_out, "grad_out")
     ws, slots = saved
@@ -805,13 +818,13 @@ def odeint_dopri5_backward_saved(stack, t, accepted, grad_out, saved):
     tarr = _c_times(t)
     b = grad_out.shape[1]
     grads, gw_arr, gb_arr = _stack_grads(stack, b, grad_out.device)
-    _lib.check(_lib.load().odehip_odeint_dopri5_backward_saved(ctypes.byref(desc), ctypes.byref(dg), tarr, len(tarr), b,
+    _lib.check(_lib.load().odehip_odeint_adaptive_backward_saved(_adaptive_code(method), ctypes.byref(desc), ctypes.byref(dg), tarr, len(tarr), b,
                                                                _c_step_log(accepted), len(accepted), _ptr(grad_out), _ptr(grads[0]), gw_arr,
                                                                gb_arr, int(slots), _ptr(ws), ws.numel(), _stream()))
     return grads
 
 
-def odeint_dopri5_backward(stack, t, accepted, z0, grad_out):
+def odeint_dopri5_backward(stack, t, accepted, z0, grad_out, method="dopri5"):
     """Gradient of the accepted dopri5 steps (what autograd through torchdiffeq computes): (grad_z0, [grad_w], [grad_b])."""
     require_device_tensor(grad_out, "grad_out")
     require_device_tensor(z0, "y0")
@@ -821,12 +834,13 @@ def odeint_dopri5_backward(stack, t, accepted, z0, grad_out):
     tarr = _c_times(t)
     n, b, ns = len(tarr), z0.shape[0], len(accepted)
     lib = _lib.load()
-    nbytes = lib.odehip_dopri5_backward_workspace_bytes(ctypes.byref(desc), b, n, ns)
+    m = _adaptive_code(method)
+    nbytes = lib.odehip_adaptive_backward_workspace_bytes(ctypes.byref(desc), b, n, ns, m)
     # keyed WITHOUT the accepted-step count: that count drifts as the weights train, and a key per count would leave one
     # multi-GB buffer behind for every count ever seen; workspace() replaces a buffer that has become too small
     ws = workspace(("dopri5_bwd", b, n, tuple(desc.channels)), nbytes, grad_out.device)
     grads, gw_arr, gb_arr = _stack_grads(stack, b, grad_out.device)
-    _lib.check(lib.odehip_odeint_dopri5_backward(ctypes.byref(desc), ctypes.byref(dg), tarr, n, b, _c_step_log(accepted), ns, _ptr(z0),
+    _lib.check(lib.odehip_odeint_adaptive_backward(m, ctypes.byref(desc), ctypes.byref(dg), tarr, n, b, _c_step_log(accepted), ns, _ptr(z0),
                                                  _ptr(grad_out), _ptr(grads[0]), gw_arr, gb_arr, _ptr(ws), ws.numel(), _stream()))
     return grads
 
@@ -850,9 +864,10 @@ def odeint_adjoint_backward(stack, method, t, y_traj, grad_out):
     return grads
 
 
-def odeint_adjoint_dopri5_backward(stack, t, y_traj, grad_out, rtol, atol, max_accept=None, stats=None, mixed_norm=False):
-    """torchdiffeq odeint_adjoint backward with method="dopri5" (seminorm, or the default mixed norm): (grad_z0, [grad_w...], [grad_b...]).
+def odeint_adjoint_dopri5_backward(stack, t, y_traj, grad_out, rtol, atol, max_accept=None, stats=None, mixed_norm=False, method="dopri5"):
+    """torchdiffeq odeint_adjoint backward with method="dopri5" or "bosh3" (seminorm, or the default mixed norm): (grad_z0, [grad_w...], [grad_b...]).
     `stats`, if a dict, receives nfe / n_accept / n_reject of the backward solve."""
+    m = _adaptive_code(method)
     collect_pending_solves()   # in particular the forward solve whose trajectory this integrates from (its error surfaces here)
     require_device_tensor(grad_out, "grad_out")
     require_device_tensor(y_traj, "y_traj")
@@ -863,14 +878,14 @@ def odeint_adjoint_dopri5_backward(stack, t, y_traj, grad_out, rtol, atol, max_a
     n, b = len(tarr), y_traj.shape[1]
     lib = _lib.load()
     if max_accept is None:  # every accepted step keeps its activations: default to what fits in 32 GiB, at most 256 steps
-        per_step = (lib.odehip_adjoint_dopri5_workspace_bytes(ctypes.byref(desc), b, n, 2)
-                    - lib.odehip_adjoint_dopri5_workspace_bytes(ctypes.byref(desc), b, n, 1))
+        per_step = (lib.odehip_adjoint_adaptive_workspace_bytes(ctypes.byref(desc), b, n, 2, m)
+                    - lib.odehip_adjoint_adaptive_workspace_bytes(ctypes.byref(desc), b, n, 1, m))
         max_accept = int(max(4 * n, min(256, (32 << 30) // max(per_step, 1))))
-    nbytes = lib.odehip_adjoint_dopri5_workspace_bytes(ctypes.byref(desc), b, n, int(max_accept))
+    nbytes = lib.odehip_adjoint_adaptive_workspace_bytes(ctypes.byref(desc), b, n, int(max_accept), m)
     ws = workspace(("adjoint_dopri5", b, n, int(max_accept), tuple(desc.channels)), nbytes, grad_out.device)
     grads, gw_arr, gb_arr = _stack_grads(stack, b, grad_out.device)
     st = (ctypes.c_int * 3)()
-    _lib.check(lib.odehip_odeint_adjoint_dopri5_backward(ctypes.byref(desc), ctypes.byref(dg), tarr, n, b, float(rtol),
+    _lib.check(lib.odehip_odeint_adjoint_adaptive_backward(m, ctypes.byref(desc), ctypes.byref(dg), tarr, n, b, float(rtol),
                                                          float(atol), _ptr(y_traj), _ptr(grad_out), _ptr(grads[0]), gw_arr, gb_arr,
                                                          int(max_accept), int(bool(mixed_norm)), st, _ptr(ws), ws.numel(), _stream()))
     if stats is not None:

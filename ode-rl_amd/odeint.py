@@ -16,6 +16,7 @@ import torch.nn as nn
 from . import _lib, hip_ops
 
 FIXED_GRID = ("euler", "midpoint", "rk4")
+ADAPTIVE = ("dopri5", "bosh3")   # embedded FSAL pairs, one driver (csrc/dopri5_control.h holds their tableaus)
 last_stats = hip_ops.LazyStats()  # nfe / n_accept / n_reject of the most recent dopri5 call (instrumentation; fills itself after an asynchronous solve)
 
 
@@ -69,7 +70,7 @@ def check_options(method, options, where="odeint"):
     """torchdiffeq's `options` that this path implements.  Fixed-grid methods, in `odeint` only: `grid_constructor` (an internal grid
     of the caller's; the requested times are filled by linear interpolation) and `interp: "linear"` next to it; `step_size` stays
     refused -- `step_size_grid(step_size)` builds torchdiffeq's grid for it --, as do `perturb` and any other `interp`: they would
-    change the result and are refused rather than ignored.  dopri5: `first_step` and `max_num_steps`.  Looks at no tensor."""
+    change the result and are refused rather than ignored.  dopri5 and bosh3: `first_step` and `max_num_steps`.  Looks at no tensor."""
     options = options or {}
     if method in FIXED_GRID:
         known = {"grid_constructor", "interp"} if where == "odeint" else set()
@@ -125,8 +126,8 @@ def internal_grid(func, y0, th, options):
 def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     if method is None:
         method = "dopri5"
-    if method not in ("euler", "midpoint", "rk4", "dopri5"):
-        raise ValueError('Invalid method "{}". Must be one of euler, midpoint, rk4, dopri5'.format(method))
+    if method not in FIXED_GRID + ADAPTIVE:
+        raise ValueError('Invalid method "{}". Must be one of euler, midpoint, rk4, dopri5, bosh3'.format(method))
     check_options(method, options)
     hip_ops.require_device_tensor(y0, "y0")
     if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in func.parameters())):
@@ -150,22 +151,23 @@ def odeint_forward(func, y0, t, rtol, atol, method, options=None):
             return hip_ops.odeint_fixed_on_grid(stack, method, y0, th, grid, negate=negate)
         return hip_ops.odeint_fixed(stack, method, y0, th, negate=negate)
     check_options(method, options)
-    return run_dopri5(stack, y0, th, dopri5_cfg(rtol, atol, options), negate=negate)[0]
+    return run_dopri5(stack, y0, th, dopri5_cfg(rtol, atol, options, method), negate=negate)[0]
 
 
-def dopri5_cfg(rtol, atol, options):
-    """Tolerances and the dopri5 `options` this path implements, as run_dopri5 and the autograd Functions take them."""
+def dopri5_cfg(rtol, atol, options, method="dopri5"):
+    """Tolerances, the adaptive method and the `options` this path implements for it, as run_dopri5 and the autograd Functions take
+    them."""
     options = options or {}
     return dict(rtol=float(rtol), atol=float(atol), first_step=float(options.get("first_step") or 0.0),
-                max_num_steps=int(options.get("max_num_steps") or 0))
+                max_num_steps=int(options.get("max_num_steps") or 0), method=method)
 
 
 def run_dopri5(stack, y0, th, cfg, save=False, negate=False):
-    """One dopri5 forward -> (out, pending, stats, saved).  With hip_ops.set_async_dopri5 on (and not for the negated dynamics) the
+    """One adaptive forward (cfg["method"]: dopri5 or bosh3) -> (out, pending, stats, saved).  With hip_ops.set_async_dopri5 on (and not for the negated dynamics) the
     solve is only enqueued: `pending` is its PendingDopri5, bound to last_stats -- the stats are read when somebody looks at them --
     and stats / saved are None.  Otherwise pending is None and last_stats holds the stats.  save: keep the activations of the accepted
     steps for the backward pass (hip_ops.odeint_dopri5_saving); `saved` is then what odeint_dopri5_backward_saved takes, or None."""
-    steps = dict(first_step=cfg["first_step"], max_steps=cfg["max_num_steps"])
+    steps = dict(first_step=cfg["first_step"], max_steps=cfg["max_num_steps"], method=cfg.get("method", "dopri5"))
     saved = None
     if save:
         out, stats, saved = hip_ops.odeint_dopri5_saving(stack, y0, th, cfg["rtol"], cfg["atol"], **steps)

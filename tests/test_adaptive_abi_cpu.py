@@ -1,0 +1,90 @@
+"""The method-coded adaptive entry points (include/odecgru_hip.h: odehip_*adaptive*) check their arguments before any HIP call, so their
+refusals are checkable without a device: an unknown method code is ODEHIP_EINVAL (the size functions return 0), the two known codes size
+a workspace, and bosh3 under exact-global step control (odehip_set_norm_allreduce) is refused by name."""
+import ctypes
+
+import pytest
+
+EINVAL = -1
+
+
+def _stack(L):
+    d = L.ConvStack()
+    d.n_convs, d.ks = 3, 3
+    for i in range(4):
+        d.channels[i] = 64
+    return d
+
+
+def test_size_functions_know_the_two_adaptive_methods_only():
+    from ode_rl_amd import _lib as L
+    lib, d = L.load(), _stack(L)
+    for code in (L.DOPRI5, L.BOSH3):
+        assert lib.odehip_adaptive_workspace_bytes(ctypes.byref(d), 2, 3, code) > 0
+        assert lib.odehip_adaptive_saving_workspace_bytes(ctypes.byref(d), 2, 3, 4, code) > lib.odehip_adaptive_workspace_bytes(ctypes.byref(d), 2, 3, code)
+        assert lib.odehip_adaptive_backward_workspace_bytes(ctypes.byref(d), 2, 3, 4, code) > 0
+        assert lib.odehip_adjoint_adaptive_workspace_bytes(ctypes.byref(d), 2, 3, 4, code) > 0
+    for code in (L.EULER, L.RK4, 5, -1):
+        assert lib.odehip_adaptive_workspace_bytes(ctypes.byref(d), 2, 3, code) == 0
+        assert lib.odehip_adaptive_saving_workspace_bytes(ctypes.byref(d), 2, 3, 4, code) == 0
+        assert lib.odehip_adaptive_backward_workspace_bytes(ctypes.byref(d), 2, 3, 4, code) == 0
+        assert lib.odehip_adjoint_adaptive_workspace_bytes(ctypes.byref(d), 2, 3, 4, code) == 0
+    # the dopri5 names are the dopri5 code; a bosh3 slot holds 4 stages against 7
+    assert lib.odehip_dopri5_workspace_bytes(ctypes.byref(d), 2, 3) == lib.odehip_adaptive_workspace_bytes(ctypes.byref(d), 2, 3, L.DOPRI5)
+    assert lib.odehip_dopri5_saving_workspace_bytes(ctypes.byref(d), 2, 3, 4) == lib.odehip_adaptive_saving_workspace_bytes(ctypes.byref(d), 2, 3, 4, L.DOPRI5)
+    assert lib.odehip_adaptive_backward_workspace_bytes(ctypes.byref(d), 2, 3, 4, L.BOSH3) < lib.odehip_adaptive_backward_workspace_bytes(ctypes.byref(d), 2, 3, 4, L.DOPRI5)
+
+
+@pytest.mark.parametrize("code", [2, 5])
+def test_an_unknown_method_code_is_einval_before_anything_else(code):
+    from ode_rl_amd import _lib as L
+    lib, d = L.load(), _stack(L)
+    p = ctypes.c_void_p(256)   # never dereferenced: the method code is looked at first
+    t = (ctypes.c_double * 2)(0.0, 1.0)
+    tok, saved = ctypes.c_int(0), ctypes.c_int(0)
+    calls = [
+        lambda: lib.odehip_odeint_adaptive(code, ctypes.byref(d), p, t, 2, 1, 1e-3, 1e-4, 0.0, 0, 0, p, None, None, 0, p, 1 << 40, None),
+        lambda: lib.odehip_odeint_adaptive_saving(code, ctypes.byref(d), p, t, 2, 1, 1e-3, 1e-4, 0.0, 0, p, None, None, 0, 4,
+                                                  ctypes.byref(saved), p, 1 << 40, None),
+        lambda: lib.odehip_odeint_adaptive_start(code, ctypes.byref(d), p, t, 2, 1, 1e-3, 1e-4, 0.0, 0, p, 0, 4, ctypes.byref(tok), p,
+                                                 1 << 40, None),
+        lambda: lib.odehip_odeint_adaptive_backward(code, ctypes.byref(d), ctypes.byref(d), t, 2, 1, t, 1, p, p, p, None, None, p, 1 << 40,
+                                                    None),
+        lambda: lib.odehip_odeint_adaptive_backward_saved(code, ctypes.byref(d), ctypes.byref(d), t, 2, 1, t, 1, p, p, None, None, 4, p,
+                                                          1 << 40, None),
+        lambda: lib.odehip_odeint_adjoint_adaptive_backward(code, ctypes.byref(d), ctypes.byref(d), t, 2, 1, 1e-3, 1e-4, p, p, p, None,
+                                                            None, 4, 0, None, p, 1 << 40, None),
+    ]
+    for call in calls:
+        assert call() == EINVAL
+        assert b"method code" in lib.odehip_last_error()
+    with pytest.raises(ValueError):
+        L.check(EINVAL)
+
+
+def test_bosh3_under_exact_global_step_control_is_refused_by_name():
+    from ode_rl_amd import _lib as L
+    lib, d = L.load(), _stack(L)
+    cb = L.ALLREDUCE_FN(lambda ptr, n, stream, user: 1)   # never called: the refusal comes first
+    p = ctypes.c_void_p(256)
+    t = (ctypes.c_double * 2)(0.0, 1.0)
+    assert lib.odehip_set_norm_allreduce(ctypes.cast(cb, ctypes.c_void_p), None, 2, p) == 0
+    try:
+        rc = lib.odehip_odeint_adaptive(L.BOSH3, ctypes.byref(d), p, t, 2, 1, 1e-3, 1e-4, 0.0, 0, 0, p, None, None, 0, p, 1 << 40, None)
+        assert rc == EINVAL and b"is not implemented for bosh3" in lib.odehip_last_error()
+    finally:
+        assert lib.odehip_set_norm_allreduce(None, None, 1, None) == 0
+
+
+def test_errors_of_the_shared_drivers_name_the_calls_method():
+    from ode_rl_amd import _lib as L
+    lib, d = L.load(), _stack(L)
+    p = ctypes.c_void_p(256)
+    t = (ctypes.c_double * 2)(0.0, 1.0)
+    for code, name in ((L.BOSH3, b"bosh3"), (L.DOPRI5, b"dopri5")):   # max_accept = 0: refused before anything is looked at
+        rc = lib.odehip_odeint_adaptive_backward_saved(code, ctypes.byref(d), ctypes.byref(d), t, 2, 1, t, 1, p, p, None, None, 0, p, 1 << 40, None)
+        msg = lib.odehip_last_error()
+        assert rc == EINVAL and msg.startswith(b"odeint_" + name + b"_backward_saved:"), msg
+        assert (b"dopri5" in msg) == (name == b"dopri5")
+    rc = lib.odehip_odeint_dopri5_backward_saved(ctypes.byref(d), ctypes.byref(d), t, 2, 1, t, 1, p, p, None, None, 0, p, 1 << 40, None)
+    assert rc == EINVAL and lib.odehip_last_error().startswith(b"odeint_dopri5_backward_saved:")

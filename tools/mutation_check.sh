@@ -28,9 +28,9 @@ SED[wgrad_wino_at]='s/\*(f32x4\*)(wr + (4 \* i + 2) \* kW2Plane) = t\[i\]\[0\] -
 SED[adapt_combine_ccur]='s/      d_cA = m.c1\[np\];/      d_cA = m.c1[np] * 1.01f;/'                                  # adaptive walk: weight of the stage's own k in an order-1 combine
 SED[adapt_ew_coef]='s/    const float c1 = (m.c_dev ? ((ConstF\*)m.c_dev)\[j\] : m.c1\[j\]) \* hs;/    const float c1 = (m.c_dev ? ((ConstF*)m.c_dev)[j] : m.c1[j]) * hs * 1.01f;/'   # elementwise rows of the walk
 SED[walk16_ew_coef]='s/      s1 = fma4(kv, (m.c_dev ? ((ConstF\*)m.c_dev)\[j\] : m.c1\[j\]) \* hs, s1);/      s1 = fma4(kv, (m.c_dev ? ((ConstF*)m.c_dev)[j] : m.c1[j]) * hs * 1.01f, s1);/'   # ... and their sixteen-workgroup copy (ew_row16)
-SED[dopri5_dense_weight]='s/^ODEHIP_HD inline double dense_weight(int s, double x, double b, double m) {$/ODEHIP_HD inline double dense_weight(int s, double x, double b, double m) { x *= 0.97;/'   # dopri5_control.h: dense-output weights evaluated at the wrong point (one function behind the device controller, the host-driven adjoint and the backward sweep)
+SED[dopri5_dense_weight]='s/^ODEHIP_HD inline double dense_weight(int s, double x, double b, double m, int last) {$/ODEHIP_HD inline double dense_weight(int s, double x, double b, double m, int last) { x *= 0.97;/'   # dopri5_control.h: dense-output weights evaluated at the wrong point (one function behind the device controller, the host-driven adjoint and the backward sweep)
 SED[walk16_out_transform]='s/      val = pk_sub(pk_sub(\*(const f32x4\*)(x + 1024) + bias4, \*(const f32x4\*)(x + 2048)), \*(const f32x4\*)(x + 3072));/      val = pk_sub(pk_sub(*(const f32x4*)(x + 1024) + bias4, *(const f32x4*)(x + 3072)), *(const f32x4*)(x + 2048)) * 1.001f;/'   # 16-workgroup walk: second half of the output transform
-SED[saving_slot_offset]='s/  fa.off_y1 = (long long)(6 \* BL.st);/  fa.off_y1 = (long long)(5 * BL.st);/'                # saving forward: y1 read from the wrong stage input of the slot
+SED[saving_slot_offset]='s/  fa.off_y1 = (long long)((tb->stages - 1) \* BL.st);/  fa.off_y1 = (long long)((tb->stages - 2) * BL.st);/'                # saving forward: y1 read from the wrong stage input of the slot
 SED[wgrad_wino5_bt]='s/  out\[0\] = w5_fma2(4.0f, in\[0\], w5_fma2(-5.0f, in\[2\], in\[4\]));/  out[0] = w5_fma2(4.0f, in[0], w5_fma2(-4.0f, in[2], in[4]));/'   # Winograd F(2x2,5x5) weight gradient: B^T row 0
 SED[codec_bwd_dec_tap]='s/          const int pa = (ky \& 1) ^ 1, ta = ky >> 1, pb = (kx \& 1) ^ 1, tb = kx >> 1;/          const int pa = (ky \& 1) ^ 1, ta = ky >> 1, pb = (kx \& 1), tb = kx >> 1;/'   # decoder backward: column parity of the second layer'"'"'s weights
 SED[codec_bwd_enc_dx]='s/        const int dx = kx == 0 ? 1 : 0;/        const int dx = kx == 2 ? 1 : 0;/'   # encoder backward: which odd-column tap reads the next source column
@@ -91,6 +91,12 @@ SED[epilogue_mask_dropped]='s/^        if (w.mask_src) v = act_bwd(v, \*(const f
 SED[epilogue_target_drops_h]='s/      f32x4 o = gx \* (T.g_c + T.g_h \* hb);/      f32x4 o = gx * T.g_c;/'   # combine 3: the device-side step size of a reverse-sweep target
 SED[epilogue_partial_slot]='s/m.err_partials\[part_idx >= 0 ? part_idx : (int)(blockIdx.x + blockIdx.y \* gridDim.x) \* 4 + wave\] = esum;/m.err_partials[part_idx >= 0 ? part_idx : (int)(blockIdx.x + blockIdx.y * gridDim.x) + wave] = esum;/'   # error partials of neighbouring workgroups overwrite each other (lower slots: inside the array)
 SED[dopri5_partial_count]='s/  const int n_conv_partials = pps > 16 ? batch \* pps : batch \* (C \/ 32) \* 2 \* 4;/  const int n_conv_partials = pps > 16 ? batch * pps : batch * (C \/ 64) * 2 * 4;/'   # the controller sums half of the partials (none at C = 32); the arrays keep their size of at least 1024 floats
+# ---- bosh3 (dopri5_control.h, dopri5.hip): each is rejected by the new files alone -- MUT_TESTS="tests/test_hip_bosh3.py"; the three
+# header mutants also by tests/test_adaptive_control_cpu.py, which compiles the header of the tree it runs in
+SED[bosh3_keeps_dopri5_exponent]='s|fmax(0.9 / pow((double)ratio, 1.0 / (double)order), dfactor)|fmax(0.9 / pow((double)ratio, 0.2), dfactor)|'   # _optimal_step_size with 1/5 for every method
+SED[bosh3_cmid_on_stage_1]='s|^    {0, 1.0 / 2, 0, 0},$|    {1.0 / 2, 0, 0, 0},|'   # c_mid applied to k1 instead of k2
+SED[bosh3_fsal_hands_over_k3]='s|      const f32x4 k7 = ((const f32x4\*)a.k\[LAST\])\[i\];|      const f32x4 k7 = ((const f32x4*)a.k[LAST == 3 ? 2 : LAST])[i];|'   # f1 of a bosh3 step = k3 instead of k4
+SED[bosh3_initial_step_fifth_root]='s|  else h1 = powf(0.01f / fmaxf(d1, d2), 1.0f / (float)order);|  else h1 = powf(0.01f / fmaxf(d1, d2), 1.0f / 5.0f);|'   # _select_initial_step with dopri5 exponent
 # mutants of the Python binding, "file|sed script": applied to the tree's own file for the run and restored afterwards (run only)
 declare -A PYSED
 PYSED[z0_offset_stuck]='ode-rl_amd/autograd.py|s/gen.set_offset(at + 4)/gen.set_offset(at)/;s/_explicit_seed\[1\] = offset + 1/_explicit_seed[1] = offset/'   # consecutive sample_z0 calls draw the same noise
