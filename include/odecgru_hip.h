@@ -502,7 +502,7 @@ int odehip_odeint_dopri5_collect(int token, int* stats_host, double* accepted_ho
  * workspace is laid out for its method: size it, fill it and read it with one and the same code.  Any other method code:
  * ODEHIP_EINVAL (the size functions return 0).  ODEHIP_BOSH3 under exact-global step control (odehip_set_norm_allreduce) is
  * refused with ODEHIP_EINVAL.  The adjoint pair below takes the method code too: ODEHIP_BOSH3 runs the host-driven backward solve
- * under both norms (the device-steered seminorm path is dopri5's).  Arguments are checked before any HIP call.  Pure additions: ODEHIP_ABI_VERSION stays. */
+ * under both norms (the device-steered seminorm path reads the call's tableau as well, but is enabled for dopri5 only).  Arguments are checked before any HIP call.  Pure additions: ODEHIP_ABI_VERSION stays. */
 size_t odehip_adaptive_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int method);
 size_t odehip_adaptive_saving_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int max_accept, int method);
 size_t odehip_adaptive_backward_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int n_steps, int method);

@@ -1,15 +1,16 @@
-// adjoint_device.hip -- the adaptive (dopri5) adjoint of adjoint_dopri5.hip with the step control ON THE DEVICE and every
-// evaluation on the adaptive persistent walk (BASELINE.json configs[2]; torchdiffeq `odeint_adjoint(..., method="dopri5",
-// adjoint_options={"norm": "seminorm"})`, _impl/adjoint.py).  Same arithmetic and the same decisions as the host loop there:
+// adjoint_device.hip -- the adaptive adjoint of adjoint_dopri5.hip with the step control ON THE DEVICE and every evaluation on the
+// adaptive persistent walk (BASELINE.json configs[2]; torchdiffeq `odeint_adjoint(..., method="dopri5",
+// adjoint_options={"norm": "seminorm"})`, _impl/adjoint.py).  It reads the Tableau of the call (S stages; dopri5_control.h); the
+// caller's gate admits dopri5 only so far.  Same arithmetic and the same decisions as the host loop there:
 // per interval t[n+1] -> t[n] a fresh solve of the augmented state (y, a) on the flipped time axis -- k1, the initial-step search
 // (_select_initial_step: d0, d1 -> h0; Euler point; d2 -> dt), attempted steps with the error ratio max(rms_y, rms_a), accept /
 // reject and step-size update of _adaptive_step / _optimal_step_size, dense output at t[n] -- but the host never reads a verdict:
 //
 //   * ONE table (cached by content: it is the same for every call on a workspace) holds four row programs -- P3: dense output of an
 //     interval's last step (+ grad_out[n]); P0: k1 of a fresh interval; P1: the Euler point of the initial-step search; P2: an attempted
-//     step (two elementwise rows for the stage-2 inputs + six augmented evaluations = 62 rows) -- written with RELOCATABLE pointers
-//     (class << 56 | offset, conv_wino.hip rel()) wherever a buffer depends on a decision: the slot an accepted step keeps for the
-//     final weight-gradient launch, the state pointers (y, a) that move with FSAL, the k1 / k7 buffers that swap;
+//     step (two elementwise rows for the stage-2 inputs + S - 1 augmented evaluations; dopri5: six, 62 rows) -- written with
+//     RELOCATABLE pointers (class << 56 | offset, conv_wino.hip rel()) wherever a buffer depends on a decision: the slot an accepted step keeps for the
+//     final weight-gradient launch, the state pointers (y, a) that move with FSAL, the k1 / k_S buffers that swap;
 //   * a TICK = adj_control_kernel (one workgroup: digests the sums of the previous tick -- norms or error partials in fixed order --
 //     takes the decision in torchdiffeq's types, appends the accepted step's stage evaluations to the per-layer weight-gradient
 //     tables, writes {first row, rows} of the next program and the relocation bases, zeroes the walk's flag area) -> the walk
@@ -38,11 +39,14 @@ constexpr int kAdjMaxTimes = 256;
 struct AdjCtl {  // device-resident controller state
   // ---- constants of the call
   float rtol, atol;
-  int n_times, n_part, max_slots, n_layers, nh, wtab_cap;
+  int n_times, n_part, max_slots, n_layers, wtab_cap;
+  int stages, order;   // of the call's tableau; csol / cmid are its rows (a constexpr host table cannot be indexed at run time here)
+  int pad0_;
   double n_elems;
-  unsigned long long slots_base, slot_bytes, st_bytes, hid_bytes;
+  AdjSlotGeom geom;    // the slot geometry the host laid the workspace out with
+  unsigned long long slots_base;
   unsigned long long yq_base, goq_base, a2_base, ky_base, ka_base, wtab_base;
-  double csol[7], cmid[7];
+  double csol[kMaxStages], cmid[kMaxStages];
   int rows_p3p0[2], rows_p0[2], rows_p3[2], rows_p1[2], rows_p2[2];
   // ---- solver state
   int phase;   // program of the walk of THIS tick (what the next controller call digests)
@@ -53,7 +57,7 @@ struct AdjCtl {  // device-resident controller state
   int k1_slot, k1_stage;
   unsigned long long k1_x0;
   int nfe, n_accept, n_reject, n_entries, done, status, ticks;
-  float w[8];                    // weights of the stages in the last accepted step's contribution (device coefficients of P3)
+  float w[kMaxStages];           // weights of the stages in the last accepted step's contribution (device coefficients of P3)
   int rows[2];                   // {first row, rows} of this tick's walk
   unsigned long long reloc[16];  // bases of the relocation classes
   double t[kAdjMaxTimes];
@@ -92,7 +96,7 @@ __device__ void adj_sums4(const float* base, int stride, const int* which, int c
   __syncthreads();
 }
 
-__device__ double adj_dense_weight(const AdjCtl* st, int s, double x) { return dp5::dense_weight(s, x, st->csol[s], st->cmid[s]); }
+__device__ double adj_dense_weight(const AdjCtl* st, int s, double x) { return dense_weight(s, x, st->csol[s], st->cmid[s], st->stages - 1); }
 
 __device__ void adj_decide(AdjCtl* st, float s0, float s1, float s2, float s3, AdjMailbox* mb);
 
@@ -130,15 +134,17 @@ __device__ void adj_decide(AdjCtl* st, float s0, float s1, float s2, float s3, A
   const int phase = st->phase;
   const double N = st->n_elems;
   auto rms = [&](float s) { return sqrtf((float)((double)s / N)); };
-  const unsigned long long ST = st->st_bytes;
-  auto set_k = [&]() {  // the k1 / k7 roles of the stage-derivative buffers 0 and 6
-    const int a = st->parity ? 6 : 0, b = st->parity ? 0 : 6;
+  const AdjSlotGeom& G = st->geom;
+  const unsigned long long ST = G.st;
+  const int S = st->stages, LAST = S - 1;
+  auto set_k = [&]() {  // the k1 / k_S roles of the stage-derivative buffers 0 and S - 1
+    const int a = st->parity ? LAST : 0, b = st->parity ? 0 : LAST;
     st->reloc[RC_KYA] = st->ky_base + (unsigned long long)a * ST;
     st->reloc[RC_KYB] = st->ky_base + (unsigned long long)b * ST;
     st->reloc[RC_KAA] = st->ka_base + (unsigned long long)a * ST;
     st->reloc[RC_KAB] = st->ka_base + (unsigned long long)b * ST;
   };
-  auto slot_addr = [&](int slot) { return st->slots_base + (unsigned long long)slot * st->slot_bytes; };
+  auto slot_addr = [&](int slot) { return st->slots_base + (unsigned long long)slot * G.slot_bytes(); };
   auto start_interval = [&](int n, unsigned long long a_cur, bool with_p3) {  // k1 of a fresh solve over t[n+1] -> t[n]
     st->n = n;
     st->reloc[RC_Y] = st->yq_base + (unsigned long long)(n + 1) * ST;
@@ -173,7 +179,7 @@ __device__ void adj_decide(AdjCtl* st, float s0, float s1, float s2, float s3, A
     else start_interval(st->n_times - 2, st->goq_base + (unsigned long long)(st->n_times - 1) * ST, false);
   } else if (phase == PH_P0) {  // _select_initial_step, first half
     const float d0 = fmaxf(rms(s0), rms(s1)), d1 = fmaxf(rms(s2), rms(s3));
-    st->h0 = dp5::initial_step_h0(d0, d1);
+    st->h0 = initial_step_h0(d0, d1);
     st->d1 = d1;
     st->nfe += 1;
     st->phase = PH_P1;
@@ -183,20 +189,20 @@ __device__ void adj_decide(AdjCtl* st, float s0, float s1, float s2, float s3, A
     const float h0 = st->h0, d1 = st->d1;
     const float d2 = fmaxf(rms(s0), rms(s1)) / h0;
     st->nfe += 1;
-    st->dt = (double)dp5::initial_step_dt(h0, d1, d2);
+    st->dt = (double)initial_step_dt(h0, d1, d2, st->order);
     st->t_cur = -st->t[st->n + 1];
     st->t_end = -st->t[st->n];
     ok = start_attempt();
   } else if (phase == PH_P2) {  // _adaptive_step's scalar part
     const float ratio = fmaxf(rms(s0), rms(s1));
-    st->nfe += 6;
+    st->nfe += S - 1;
     if (!(ratio == ratio)) {
       st->status = ODEHIP_ENAN;
       ok = false;
     } else {
       const bool accept = ratio <= 1.0f;
       const double dt = st->dt;
-      const double dtn = dp5::next_step_size(dt, ratio);
+      const double dtn = next_step_size(dt, ratio, st->order);
       if (!accept) {
         st->n_reject += 1;
         st->dt = dtn;
@@ -206,32 +212,28 @@ __device__ void adj_decide(AdjCtl* st, float s0, float s1, float s2, float s3, A
         const float h = st->h;
         const double t_new = st->t_cur + dt;
         const bool final_step = t_new >= st->t_end;
-        float w[7];
+        float w[kMaxStages];
         if (!final_step) {
-          for (int s = 0; s < 7; ++s) w[s] = (float)st->csol[s] * h;
+          for (int s = 0; s < S; ++s) w[s] = (float)st->csol[s] * h;
         } else {
           const float x = (float)((st->t_end - st->t_cur) / (t_new - st->t_cur));
-          for (int s = 0; s < 7; ++s) w[s] = h * (float)adj_dense_weight(st, s, (double)x);
+          for (int s = 0; s < S; ++s) w[s] = h * (float)adj_dense_weight(st, s, (double)x);
         }
         // the accepted step's stage evaluations join the final weight-gradient sum (a_theta is linear in the stages)
         const unsigned long long sb = slot_addr(st->slot);
         WgradPair* wt = (WgradPair*)st->wtab_base;
-        const int NH = st->nh, NL = st->n_layers;
-        for (int s = 0; s < 7; ++s) {
+        const int NL = st->n_layers;
+        for (int s = 0; s < S; ++s) {
           st->w[s] = w[s];
           if (w[s] == 0.0f) continue;
           if (st->n_entries >= st->wtab_cap) { st->status = ODEHIP_EINVAL; ok = false; break; }
           const unsigned long long eb = s == 0 ? slot_addr(st->k1_slot) : sb;
           const int es = s == 0 ? st->k1_stage : s;
-          const unsigned long long x0 = s == 0 ? st->k1_x0 : sb + (unsigned long long)s * ST;
-          for (int l = 0; l < NL; ++l) {
-            WgradPair& p = wt[(size_t)l * st->wtab_cap + st->n_entries];
-            p.g = (const float*)(eb + 7 * ST + 7 * (unsigned long long)NH * st->hid_bytes +
-                                 ((unsigned long long)es * (NH + 1) + l) * st->hid_bytes);
-            p.a = l == 0 ? (const float*)x0 : (const float*)(eb + 7 * ST + ((unsigned long long)es * NH + (l - 1)) * st->hid_bytes);
-            p.scale = w[s];
-            p.pad_[0] = p.pad_[1] = p.pad_[2] = 0.0f;
-          }
+          const unsigned long long x0 = s == 0 ? st->k1_x0 : sb + G.xin(s);
+          // gradient slot l for layer l, i.e. wgrad_slot(f, l) of a stack without a Tanh head: this path never sees a head (a reverse
+          // sweep over one is not recorded, PersistScope::begin, and the caller then runs the host loop)
+          for (int l = 0; l < NL; ++l)
+            G.wgrad_pair(wt[(size_t)l * st->wtab_cap + st->n_entries], (const char*)eb, es, l, l, (const float*)x0, w[s]);
           st->n_entries += 1;
         }
         if (ok && final_step) {  // a(t[n]) = dense output + grad_out[n]: program P3 in front of the next interval's k1
@@ -240,7 +242,7 @@ __device__ void adj_decide(AdjCtl* st, float s0, float s1, float s2, float s3, A
           st->reloc[RC_APREV] = st->reloc[RC_A];
           st->reloc[RC_ANEXT] = a_next;
           st->reloc[RC_GO] = st->goq_base + (unsigned long long)n * ST;
-          set_k();   // (unchanged: P3 reads the seven stage derivatives of the step just accepted)
+          set_k();   // (unchanged: P3 reads the stage derivatives of the step just accepted)
           st->slot += 1;
           if (n == 0) {
             st->phase = PH_FINAL;
@@ -253,14 +255,14 @@ __device__ void adj_decide(AdjCtl* st, float s0, float s1, float s2, float s3, A
           } else {
             start_interval(n - 1, a_next, true);
           }
-        } else if (ok) {  // FSAL: (y, a, k1) <- (y1, a1, k7)
-          st->reloc[RC_Y] = sb + 6 * ST;
-          st->reloc[RC_A] = sb + 7 * ST + 7 * (unsigned long long)NH * st->hid_bytes + ((unsigned long long)6 * (NH + 1) + NH) * st->hid_bytes;
+        } else if (ok) {  // FSAL: (y, a, k1) <- (y1, a1, k_S)
+          st->reloc[RC_Y] = sb + G.xin(LAST);
+          st->reloc[RC_A] = sb + G.gp(LAST, G.NH);
           st->parity ^= 1;
           set_k();
           st->k1_slot = st->slot;
-          st->k1_stage = 6;
-          st->k1_x0 = sb + 6 * ST;
+          st->k1_stage = LAST;
+          st->k1_x0 = sb + G.xin(LAST);
           st->t_cur = t_new;
           st->dt = dtn;
           st->slot += 1;
@@ -287,25 +289,29 @@ __global__ void adj_init_kernel(AdjCtl* st, AdjCtl init) { *st = init; }
 
 static AdjMailbox* g_adj_mailbox = nullptr;
 
-int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host, int n_times, int batch, float rtol,
-                          float atol, const float* y_traj_nchw, const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w,
-                          float* const* grad_b, int max_accept, int* stats_host, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                          int* ran) {
+int adjoint_adaptive_device(const Tableau& tb, const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host, int n_times,
+                            int batch, float rtol, float atol, const float* y_traj_nchw, const float* grad_out_nchw, float* grad_z0_nchw,
+                            float* const* grad_w, float* const* grad_b, int max_accept, int* stats_host, void* workspace,
+                            size_t workspace_bytes, hipStream_t stream, int* ran) {
   *ran = 0;
+  const char* const mname = tb.name;
+  const int S = tb.stages;
   // read per call (not cached): the parity tests run the host-driven loop and this one in ONE process on the same inputs
   const char* const env_e = getenv("ODEHIP_ADJOINT_DEVICE");
   const bool env_off = env_e && env_e[0] == '0';
   if (env_off || !all_64(f) || n_times < 2 || n_times > kAdjMaxTimes || g_debug_flags) return ODEHIP_OK;
   const AdjLayout L(f, batch, n_times, max_accept);
-  ODEHIP_REQUIRE(workspace_bytes >= L.total, "odeint_adjoint_dopri5_backward: workspace too small");
+  ODEHIP_REQUIRE(workspace_bytes >= L.total, "odeint_adjoint_%s_backward: workspace too small", mname);
   void* ws = workspace;
-  const int NH = L.NH, NL = f->n_convs;
+  const int NH = L.g.NH, NL = f->n_convs;
   const size_t st_b = (size_t)batch * L.C * kPix * 4;
   int rc;
 
   const int n_pps = persist_partials_per_sample(batch);   // (before the scope: it takes the library's lock)
   PersistScope persist;
-  if ((rc = persist.begin(f, f_dgrad, 2 + 15 + 14 + 62)) != ODEHIP_OK) return rc;
+  // rows of the table below: P3 (2), P0 (1 + an evaluation's 2 NL + 4 norm rows), P1 (2 + 2 NL + 2), P2 (2 + (S - 1) evaluations)
+  const int row_cap = 2 + (1 + 2 * NL + 4) + (2 + 2 * NL + 2) + (2 + (S - 1) * 2 * NL);
+  if ((rc = persist.begin(f, f_dgrad, row_cap)) != ODEHIP_OK) return rc;
   if (!persist.recording()) return ODEHIP_OK;   // no persistent walk on this device / switched off: the host loop takes the call
 
   if (!g_adj_mailbox) ODEHIP_CHECK_HIP(hipHostMalloc((void**)&g_adj_mailbox, sizeof(AdjMailbox), hipHostMallocCoherent));
@@ -315,11 +321,11 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
   unsigned* psync = (unsigned*)L.p(ws, L.off_psync);
   float* ping = L.p(ws, L.off_ping);
   float* pong = L.p(ws, L.off_pong);
-  float* ky[7];
-  float* ka[7];
-  for (int i = 0; i < 7; ++i) {
-    ky[i] = L.p(ws, L.off_ky + (size_t)i * L.st);
-    ka[i] = L.p(ws, L.off_ka + (size_t)i * L.st);
+  float* ky[kMaxStages];
+  float* ka[kMaxStages];
+  for (int i = 0; i < kMaxStages; ++i) {
+    ky[i] = L.p(ws, L.off_ky + (size_t)i * L.g.st);
+    ka[i] = L.p(ws, L.off_ka + (size_t)i * L.g.st);
   }
   const int part_stride = L.part_stride();
 
@@ -336,9 +342,9 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
   float* const kyB = tag(RC_KYB, 0);
   float* const kaA = tag(RC_KAA, 0);
   float* const kaB = tag(RC_KAB, 0);
-  auto s_xin = [&](int s) { return tag(RC_SLOT, adj_off_xin(L, s)); };
-  auto s_hid = [&](int s, int l) { return tag(RC_SLOT, adj_off_hidden(L, s, l)); };
-  auto s_gp = [&](int s, int l) { return tag(RC_SLOT, adj_off_gp(L, s, l)); };
+  auto s_xin = [&](int s) { return tag(RC_SLOT, L.g.xin(s)); };
+  auto s_hid = [&](int s, int l) { return tag(RC_SLOT, L.g.hidden(s, l)); };
+  auto s_gp = [&](int s, int l) { return tag(RC_SLOT, L.g.gp(s, l)); };
   int n_rows = 0;
   auto ew = [&](float* out, const float* y, int n, const float* const* k, const float* c, const float* h_ptr, const float* c_dev) -> int {
     ConvArgs a;
@@ -435,9 +441,15 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
   const float one = 1.0f;
   // -- P3: a_next = a_prev + sum_s w_s * K^a_s (+ grad_out[n])
   init.rows_p3[0] = init.rows_p3p0[0] = n_rows;
+  // the stage derivatives in stage order: k1 / k_S are whichever of buffers 0 and S - 1 holds the role
+  float* kyR[kMaxStages];
+  float* kaR[kMaxStages];
+  for (int i = 0; i < S; ++i) {
+    kyR[i] = i == 0 ? kyA : (i == S - 1 ? kyB : ky[i]);
+    kaR[i] = i == 0 ? kaA : (i == S - 1 ? kaB : ka[i]);
+  }
   {
-    const float* kk[7] = {kaA, ka[1], ka[2], ka[3], ka[4], ka[5], kaB};
-    if ((rc = ew(tag(RC_ANEXT, 0), tag(RC_APREV, 0), 7, kk, nullptr, nullptr, (const float*)((char*)state + offsetof(AdjCtl, w)))) != ODEHIP_OK) return rc;
+    if ((rc = ew(tag(RC_ANEXT, 0), tag(RC_APREV, 0), S, kaR, nullptr, nullptr, (const float*)((char*)state + offsetof(AdjCtl, w)))) != ODEHIP_OK) return rc;
     const float* gg[1] = {tag(RC_GO, 0)};
     if ((rc = ew(tag(RC_ANEXT, 0), tag(RC_ANEXT, 0), 1, gg, &one, nullptr, nullptr)) != ODEHIP_OK) return rc;
   }
@@ -478,18 +490,16 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
   init.rows_p2[0] = n_rows;
   {
     const float* hp = (const float*)((char*)state + offsetof(AdjCtl, h));
-    const float b21 = (float)dp5::kBeta[0][0];
+    const float b21 = (float)tb.beta[0][0];
     const float* k0y[1] = {kyA};
     const float* k0a[1] = {kaA};
     if ((rc = ew(s_xin(1), Ycur, 1, k0y, &b21, hp, nullptr)) != ODEHIP_OK) return rc;
     if ((rc = ew(s_gp(1, NH), Acur, 1, k0a, &b21, hp, nullptr)) != ODEHIP_OK) return rc;
-    std::vector<ConvArgs> F[7], D[7];   // rows of evaluation e = s - 1 (stage s lives at index s-1 of the slot)
-    float* const kyR[7] = {kyA, ky[1], ky[2], ky[3], ky[4], ky[5], kyB};   // k1 / k7: whichever of buffers 0 and 6 holds the role
-    float* const kaR[7] = {kaA, ka[1], ka[2], ka[3], ka[4], ka[5], kaB};
-    for (int s = 2; s <= 7; ++s) {   // Y_{s+1}, A_{s+1} (s = 6: y1, a1; s = 7: error norms)
-      const int nx = s < 7 ? s : 6;
-      dopri5_stage_combine(cy, s, Ycur, hp, kyR, s_xin(nx), L.part(ws, 4), rtol, atol);
-      dopri5_stage_combine(ca, s, Acur, hp, kaR, s_gp(nx, NH), L.part(ws, 5), rtol, atol);
+    std::vector<ConvArgs> F[kMaxStages], D[kMaxStages];   // rows of evaluation e = s - 1 (stage s lives at index s-1 of the slot)
+    for (int s = 2; s <= S; ++s) {   // Y_{s+1}, A_{s+1} (s = S - 1: y1, a1; s = S: error norms)
+      const int nx = s < S ? s : S - 1;
+      adaptive_stage_combine(tb, cy, s, Ycur, hp, kyR, s_xin(nx), L.part(ws, 4), rtol, atol);
+      adaptive_stage_combine(tb, ca, s, Acur, hp, kaR, s_gp(nx, NH), L.part(ws, 5), rtol, atol);
       cy.order = ca.order = 1;
       cy.k_scale = -1.0f;
       ca.k_scale = 1.0f;
@@ -497,21 +507,22 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
       if ((rc = rows_d(s - 1, ca, D[s - 1])) != ODEHIP_OK) return rc;
       ODEHIP_REQUIRE((int)F[s - 1].size() == NL && (int)D[s - 1].size() == NL, "adjoint: unexpected row count of an evaluation");
     }
-    // Order: F1 | (F2, D1) woven | (F3, D2) | ... | (F6, D5) | D6.  Y_{s+1} needs only the forward chains up to stage s and A_{s+1}
+    // Order (dopri5): F1 | (F2, D1) woven | (F3, D2) | ... | (F6, D5) | D6.  Y_{s+1} needs only the forward chains up to stage s and A_{s+1}
     // only the input-gradient chains, whose masks come from the SAME stage's forward chain: D_e and F_{e+1} are independent, so
     // in a woven pair every row's predecessor in its own chain lies two rows back (dep_back = 1: its input is loaded and transformed
     // while the consumers still multiply the other chain's row).
     for (int j = 0; j < NL; ++j)
       if ((rc = emit(F[1][j], 0)) != ODEHIP_OK) return rc;
-    for (int e = 1; e <= 5; ++e)
+    for (int e = 1; e <= S - 2; ++e)
       for (int j = 0; j < NL; ++j) {
         if ((rc = emit(F[e + 1][j], (e == 1 && j == 0) ? 0 : 1)) != ODEHIP_OK) return rc;   // F2's first row follows F1's last
         if ((rc = emit(D[e][j], 1)) != ODEHIP_OK) return rc;
       }
     for (int j = 0; j < NL; ++j)
-      if ((rc = emit(D[6][j], 0)) != ODEHIP_OK) return rc;
+      if ((rc = emit(D[S - 1][j], 0)) != ODEHIP_OK) return rc;
   }
   init.rows_p2[1] = n_rows - init.rows_p2[0];
+  ODEHIP_REQUIRE(n_rows == row_cap, "odeint_adjoint_%s_backward: the table has %d rows, the recorder was sized for %d", mname, n_rows, row_cap);
 
   // ---- controller state ---------------------------------------------------------------------------------------------------------
   init.rtol = rtol;
@@ -520,22 +531,21 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
   init.n_part = batch * n_pps;   // partials per array: 16 per sample on the 4-workgroup walk, 64 on the sixteen-workgroup one
   init.max_slots = L.max_slots;
   init.n_layers = NL;
-  init.nh = NH;
-  init.wtab_cap = L.max_slots * 7;
+  init.wtab_cap = L.wtab_cap();
+  init.stages = S;
+  init.order = tb.order;
   init.n_elems = (double)(st_b / 4);
   init.slots_base = (unsigned long long)(uintptr_t)L.p(ws, L.off_slots);
-  init.slot_bytes = L.slot_bytes;
-  init.st_bytes = L.st;
-  init.hid_bytes = L.hid;
+  init.geom = L.g;
   init.yq_base = (unsigned long long)(uintptr_t)L.p(ws, L.off_y);
   init.goq_base = (unsigned long long)(uintptr_t)L.p(ws, L.off_go);
   init.a2_base = (unsigned long long)(uintptr_t)L.p(ws, L.off_a2);
   init.ky_base = (unsigned long long)(uintptr_t)ky[0];
   init.ka_base = (unsigned long long)(uintptr_t)ka[0];
   init.wtab_base = (unsigned long long)(uintptr_t)L.p(ws, L.off_wtab);
-  for (int s = 0; s < 7; ++s) {
-    init.csol[s] = dp5::kCSol[s];
-    init.cmid[s] = dp5::kCMid[s];
+  for (int s = 0; s < S; ++s) {
+    init.csol[s] = tb.c_sol[s];
+    init.cmid[s] = tb.c_mid[s];
   }
   for (int i = 0; i < n_times; ++i) init.t[i] = t_host[i];
   init.phase = PH_INIT;
@@ -556,7 +566,7 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
     ++enq;
     while (g_adj_mailbox->ticks + 1 < enq) {
       if (watch.stalled()) {
-        set_error("odeint_adjoint_dopri5_backward: no progress from the device for 120 s (%d of %d ticks)", g_adj_mailbox->ticks, enq);
+        set_error("odeint_adjoint_%s_backward: no progress from the device for 120 s (%d of %d ticks)", mname, g_adj_mailbox->ticks, enq);
         return ODEHIP_EHIP;
       }
     }
@@ -565,14 +575,14 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
   if (g_adj_mailbox->status != 0) {
     const int s = g_adj_mailbox->status;
     ODEHIP_CHECK_HIP(hipStreamSynchronize(stream));   // (error path: nothing of this call may still write the mailbox afterwards)
-    return controller_error(true, s, max_accept);
+    return controller_error(mname, true, s, max_accept);
   }
   // a(t[0]) is the result of the last P3 program: a2[0]
   rc = odehip_q4_to_nchw(L.p(ws, L.off_a2), grad_z0_nchw, batch, L.C, stream);
   if (rc != ODEHIP_OK) return rc;
   // ---- ONE weight-gradient launch per layer over every recorded stage evaluation (tables written by the controller)
   const int n_eval = g_adj_mailbox->n_entries;
-  ODEHIP_REQUIRE(n_eval >= 1, "odeint_adjoint_dopri5_backward: the controller recorded no stage evaluation");
+  ODEHIP_REQUIRE(n_eval >= 1, "odeint_adjoint_%s_backward: the controller recorded no stage evaluation", mname);
   float* slabs = L.p(ws, L.off_slab);
   const WgradPair* wt = (const WgradPair*)L.p(ws, L.off_wtab);
   for (int l = 0; l < NL; ++l) {
@@ -596,7 +606,7 @@ int adjoint_dopri5_device(const odehip_convstack* f, const odehip_convstack* f_d
   watch = MailboxWatch(&g_adj_mailbox->ticks);
   while (g_adj_mailbox->ticks < enq) {
     if (watch.stalled()) {
-      set_error("odeint_adjoint_dopri5_backward: the device did not drain (%d of %d ticks)", g_adj_mailbox->ticks, enq);
+      set_error("odeint_adjoint_%s_backward: the device did not drain (%d of %d ticks)", mname, g_adj_mailbox->ticks, enq);
       return ODEHIP_EHIP;
     }
   }

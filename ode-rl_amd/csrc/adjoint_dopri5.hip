@@ -103,14 +103,14 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
                                                  workspace_bytes, stream_);
 }
 
-// The host-driven loop below reads the tableau of the call's method (S stages; the comments count in dopri5's 7).  The device-steered
-// seminorm path (adjoint_device.hip) is written for dopri5's stages: other methods run this loop under both norms.
+// The host-driven loop below reads the tableau of the call's method (S stages; the comments count in dopri5's 7), and so does the
+// device-steered seminorm path (adjoint_device.hip), which is enabled for dopri5 only: other methods run this loop under both norms.
 extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad,
                                                        const double* t_host, int n_times, int batch, float rtol, float atol,
                                                        const float* y_traj_nchw, const float* grad_out_nchw, float* grad_z0_nchw,
                                                        float* const* grad_w, float* const* grad_b, int max_accept, int mixed_norm,
                                                        int* stats_host, void* workspace, size_t workspace_bytes, void* stream_) {
-  const ErrorNames names(method);
+  const char* const mname = adaptive_name(method);
   const Tableau* tbp = adaptive_tableau(method);
   ODEHIP_REQUIRE(tbp, "odeint_adjoint_adaptive_backward: unknown adaptive method code %d (ODEHIP_DOPRI5 or ODEHIP_BOSH3)", method);
   const Tableau& tb = *tbp;
@@ -118,19 +118,19 @@ extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_
   int rc = check_stack(f);
   if (rc != ODEHIP_OK) return rc;
   ODEHIP_REQUIRE(f_dgrad && t_host && y_traj_nchw && grad_out_nchw && grad_z0_nchw && grad_w && grad_b && workspace,
-                 "odeint_adjoint_dopri5_backward: null pointer");
-  ODEHIP_REQUIRE(n_times >= 1 && batch > 0 && max_accept > 0, "odeint_adjoint_dopri5_backward: bad sizes");
-  ODEHIP_REQUIRE(rtol > 0 && atol >= 0, "odeint_adjoint_dopri5_backward: rtol must be > 0 and atol >= 0");
-  ODEHIP_REQUIRE(f->ks == 3 && f->channels[0] == f->channels[f->n_convs], "odeint_adjoint_dopri5_backward: 3x3 C -> C dynamics only");
+                 "odeint_adjoint_%s_backward: null pointer", mname);
+  ODEHIP_REQUIRE(n_times >= 1 && batch > 0 && max_accept > 0, "odeint_adjoint_%s_backward: bad sizes", mname);
+  ODEHIP_REQUIRE(rtol > 0 && atol >= 0, "odeint_adjoint_%s_backward: rtol must be > 0 and atol >= 0", mname);
+  ODEHIP_REQUIRE(f->ks == 3 && f->channels[0] == f->channels[f->n_convs], "odeint_adjoint_%s_backward: 3x3 C -> C dynamics only", mname);
   for (int l = 0; l <= f->n_convs; ++l)
-    ODEHIP_REQUIRE(f->channels[l] % 64 == 0, "odeint_adjoint_dopri5_backward: channel counts must be multiples of 64");
+    ODEHIP_REQUIRE(f->channels[l] % 64 == 0, "odeint_adjoint_%s_backward: channel counts must be multiples of 64", mname);
   for (int i = 1; i < n_times; ++i)
-    ODEHIP_REQUIRE(t_host[i] > t_host[i - 1], "odeint_adjoint_dopri5_backward: t must be strictly increasing");
+    ODEHIP_REQUIRE(t_host[i] > t_host[i - 1], "odeint_adjoint_%s_backward: t must be strictly increasing", mname);
   const AdjLayout L(f, batch, n_times, max_accept);
-  ODEHIP_REQUIRE(workspace_bytes >= L.total, "odeint_adjoint_dopri5_backward: workspace too small");
+  ODEHIP_REQUIRE(workspace_bytes >= L.total, "odeint_adjoint_%s_backward: workspace too small", mname);
   hipStream_t stream = (hipStream_t)stream_;
   void* ws = workspace;
-  const int NH = L.NH, NL = f->n_convs;
+  const int NH = L.g.NH, NL = f->n_convs;
   const size_t st_b = (size_t)batch * L.C * kPix * 4;
   const long long n4 = (long long)(st_b / 16);
   const double N = (double)(st_b / 4);
@@ -140,20 +140,21 @@ extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_
   float* sums = L.p(ws, L.off_sums);
   float* ping = L.p(ws, L.off_ping);
   float* pong = L.p(ws, L.off_pong);
-  float* ky[7];
-  float* ka[7];
-  for (int i = 0; i < 7; ++i) {
-    ky[i] = L.p(ws, L.off_ky + (size_t)i * L.st);
-    ka[i] = L.p(ws, L.off_ka + (size_t)i * L.st);
+  float* ky[kMaxStages];
+  float* ka[kMaxStages];
+  for (int i = 0; i < kMaxStages; ++i) {
+    ky[i] = L.p(ws, L.off_ky + (size_t)i * L.g.st);
+    ka[i] = L.p(ws, L.off_ka + (size_t)i * L.g.st);
   }
-  auto yq = [&](int n) { return L.p(ws, L.off_y + (size_t)n * L.st); };
-  auto goq = [&](int n) { return L.p(ws, L.off_go + (size_t)n * L.st); };
+  auto yq = [&](int n) { return L.p(ws, L.off_y + (size_t)n * L.g.st); };
+  auto goq = [&](int n) { return L.p(ws, L.off_go + (size_t)n * L.g.st); };
 
   if (!mixed_norm && n_times > 1 && method == ODEHIP_DOPRI5) {
     // seminorm on a 64-channel fp32 stack: step control on the device, evaluations on the adaptive persistent walk
-    // (adjoint_device.hip); `ran` = 0 when that path is not available here -- the host loop below then takes the call
+    // (adjoint_device.hip); `ran` = 0 when that path is not available here -- the host loop below then takes the call.  The path reads
+    // the tableau; the gate is dopri5 because no other method has been run or measured on it yet (parity tests first).
     int ran = 0;
-    rc = adjoint_dopri5_device(f, f_dgrad, t_host, n_times, batch, rtol, atol, y_traj_nchw, grad_out_nchw, grad_z0_nchw, grad_w, grad_b,
+    rc = adjoint_adaptive_device(tb, f, f_dgrad, t_host, n_times, batch, rtol, atol, y_traj_nchw, grad_out_nchw, grad_z0_nchw, grad_w, grad_b,
                                max_accept, stats_host, workspace, workspace_bytes, stream, &ran);
     if (rc != ODEHIP_OK || ran) return rc;
   }
@@ -180,7 +181,7 @@ extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_
     int r = enqueue_f_saving(f, Y, batch, hidv, ping, pong, &cy, nullptr, nullptr, stream);
     if (r != ODEHIP_OK) return r;
     float* gpv[ODEHIP_MAX_LAYERS + 1];
-    for (int l = 0; l < L.NG; ++l) gpv[l] = L.gp(ws, slot, s, l);
+    for (int l = 0; l < L.g.NG; ++l) gpv[l] = L.gp(ws, slot, s, l);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.combine = 1;
@@ -241,25 +242,24 @@ extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_
     spans.off[NT] = o;
   }
   if (mixed_norm) ODEHIP_CHECK_HIP(hipMemsetAsync(th_run, 0, (size_t)P * 4, stream));
-  struct StageRef {
+  struct StageRef {   // one stage evaluation in a weight-gradient sum
     int slot, stage;
-    const float* x0;
+    const float* x0;  // input of conv 0 of that evaluation
     float scale;
+  };
+  // entry i of layer l's table
+  auto wgrad_pair = [&](WgradPair& p, const StageRef& e, int l) {
+    L.g.wgrad_pair(p, L.slot(ws, e.slot), e.stage, l, wgrad_slot(f, l), e.x0, e.scale);
   };
   // out (flattened parameter layout) = sum_i scale_i * wgrad(evaluation i): one batched launch per layer
   auto theta_wgrad = [&](const StageRef* ev, int n_ev, float* out) -> int {
     WgradPair* tab = (WgradPair*)L.p(ws, L.off_tab);
     float* slab = L.p(ws, L.off_slab);
     for (int l = 0; l < NL; ++l) {
-      WgradPair host[8];
-      memset(host, 0, sizeof(host));
-      for (int i = 0; i < n_ev; ++i) {
-        host[i].g = L.gp(ws, ev[i].slot, ev[i].stage, wgrad_slot(f, l));
-        host[i].a = l == 0 ? ev[i].x0 : L.hidden(ws, ev[i].slot, ev[i].stage, l - 1);
-        host[i].scale = ev[i].scale;
-      }
-      float bits[8 * sizeof(WgradPair) / 4];
-      memcpy(bits, host, sizeof(host));
+      WgradPair host[kMaxStages];
+      for (int i = 0; i < n_ev; ++i) wgrad_pair(host[i], ev[i], l);
+      float bits[kMaxStages * sizeof(WgradPair) / 4];
+      memcpy(bits, host, (size_t)n_ev * sizeof(WgradPair));
       int r = upload_floats((float*)tab, bits, n_ev * (int)(sizeof(WgradPair) / 4), stream);
       if (r != ODEHIP_OK) return r;
       r = launch_wgrad(tab, n_ev, batch, 4, slab, out + spans.off[2 * l], out + spans.off[2 * l + 1], f->channels[l + 1],
@@ -278,19 +278,14 @@ extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_
     return m;
   };
 
-  struct Entry {
-    int slot, stage;
-    const float* x0;  // input of conv 0 of that evaluation
-    float scale;
-  };
-  std::vector<Entry> entries;
+  std::vector<StageRef> entries;
 
   const float* a_cur = goq(n_times - 1);
   int slot = 0;
   for (int n = n_times - 2; n >= 0; --n) {
     const float* y_cur = yq(n + 1);
     const double t_begin = -t_host[n + 1], t_end = -t_host[n];
-    ODEHIP_REQUIRE(slot < L.max_slots, "odeint_adjoint_dopri5_backward: more than max_accept = %d accepted steps", max_accept);
+    ODEHIP_REQUIRE(slot < L.max_slots, "odeint_adjoint_%s_backward: more than max_accept = %d accepted steps", mname, max_accept);
     // ---- k1 = aug dynamics at the interval start (fresh odeint in torchdiffeq): stage 0 of `slot`
     ODEHIP_CHECK_HIP(hipMemcpyAsync(L.gp(ws, slot, 0, NH), a_cur, st_b, hipMemcpyDeviceToDevice, stream));
     CombineArgs cy, ca;
@@ -351,8 +346,8 @@ extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_
     double t_cur = t_begin;
     // ---- attempted steps until t_end is covered
     for (;;) {
-      ODEHIP_REQUIRE(slot < L.max_slots, "odeint_adjoint_dopri5_backward: more than max_accept = %d accepted steps", max_accept);
-      ODEHIP_REQUIRE(t_cur + dt > t_cur, "odeint_adjoint_dopri5_backward: underflow in dt %g", dt);
+      ODEHIP_REQUIRE(slot < L.max_slots, "odeint_adjoint_%s_backward: more than max_accept = %d accepted steps", mname, max_accept);
+      ODEHIP_REQUIRE(t_cur + dt > t_cur, "odeint_adjoint_%s_backward: underflow in dt %g", mname, dt);
       const float h = (float)dt;
       if ((rc = upload_floats(hdev, &h, 1, stream)) != ODEHIP_OK) return rc;
       {  // stage-2 inputs from k1
@@ -371,7 +366,7 @@ extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_
         if ((rc = eval_aug(slot, s - 1, L.xin(ws, slot, s - 1), cy, ca)) != ODEHIP_OK) return rc;
       }
       nfe += S - 1;
-      StageRef ev[7];
+      StageRef ev[kMaxStages];
       ev[0] = StageRef{k1_slot, k1_stage, k1_x0, 0.0f};
       for (int s = 1; s < S; ++s) ev[s] = StageRef{slot, s, L.xin(ws, slot, s), 0.0f};
       if (mixed_norm) {  // parameter block of this attempt: error estimate and increment, both linear in the seven stages
@@ -388,7 +383,7 @@ extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_
       }
       float ratio = fmaxf(rms(e2[0]), rms(e2[1]));
       if (mixed_norm) ratio = fmaxf(ratio, theta_rms_max(g_adj_host + 8));
-      ODEHIP_REQUIRE(ratio == ratio, "odeint_adjoint_dopri5_backward: non-finite error ratio");
+      ODEHIP_REQUIRE(ratio == ratio, "odeint_adjoint_%s_backward: non-finite error ratio", mname);
       const bool accept = ratio <= 1.0f;
       const double dtn = next_step_size(dt, ratio, tb.order);
       if (!accept) {
@@ -399,7 +394,7 @@ extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_
       ++n_accept;
       const double t_new = t_cur + dt;
       const bool final_step = t_new >= t_end;
-      float w[7];
+      float w[kMaxStages];
       if (!final_step) {
         for (int s = 0; s < S; ++s) w[s] = (float)tb.c_sol[s] * h;
       } else {
@@ -416,17 +411,11 @@ extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_
       }
       for (int s = 0; s < S && !mixed_norm; ++s) {
         if (w[s] == 0.0f) continue;
-        Entry e;
-        e.scale = w[s];
-        if (s == 0) {
-          e.slot = k1_slot; e.stage = k1_stage; e.x0 = k1_x0;
-        } else {
-          e.slot = slot; e.stage = s; e.x0 = L.xin(ws, slot, s);
-        }
-        entries.push_back(e);
+        entries.push_back(ev[s]);
+        entries.back().scale = w[s];
       }
       if (final_step) {
-        float* a_next = L.p(ws, L.off_a2 + (size_t)(n & 1) * L.st);
+        float* a_next = L.p(ws, L.off_a2 + (size_t)(n & 1) * L.g.st);
         lincomb(a_next, a_cur, S, ka, w, goq(n));  // a(t[n]) + grad_out[n]
         a_cur = a_next;
         ++slot;
@@ -462,12 +451,7 @@ extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_
   float* slabs = L.p(ws, L.off_slab);
   std::vector<WgradPair> host(n_eval);
   for (int l = 0; l < NL; ++l) {
-    for (int e = 0; e < n_eval; ++e) {
-      host[e].g = L.gp(ws, entries[e].slot, entries[e].stage, wgrad_slot(f, l));
-      host[e].a = l == 0 ? entries[e].x0 : L.hidden(ws, entries[e].slot, entries[e].stage, l - 1);
-      host[e].scale = entries[e].scale;
-      host[e].pad_[0] = host[e].pad_[1] = host[e].pad_[2] = 0.0f;
-    }
+    for (int e = 0; e < n_eval; ++e) wgrad_pair(host[e], entries[e], l);
     ODEHIP_CHECK_HIP(hipMemcpyAsync(table, host.data(), (size_t)n_eval * sizeof(WgradPair), hipMemcpyHostToDevice, stream));
     ODEHIP_CHECK_HIP(hipStreamSynchronize(stream));
     rc = launch_wgrad(table, n_eval, batch, 4, slabs, grad_w[l], grad_b[l], f->channels[l + 1], f->channels[l], stream, f->w_bf16[l] != nullptr);

@@ -11,20 +11,11 @@ namespace odehip {
 
 static thread_local char g_err[512] = "";
 
-thread_local const char* g_err_method = nullptr;
-
 void set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
-  if (g_err_method) {   // inside a method-coded adaptive entry point (ErrorNames): the shared drivers' messages say "dopri5"
-    const size_t n = strlen(g_err_method);   // (<= 6: the text only shrinks)
-    for (char* p = strstr(g_err, "dopri5"); p && n <= 6; p = strstr(p + n, "dopri5")) {
-      memcpy(p, g_err_method, n);
-      memmove(p + n, p + 6, strlen(p + 6) + 1);
-    }
-  }
 }
 
 int hip_fail(hipError_t e, const char* what) {

@@ -234,13 +234,13 @@ struct FinishArgs {
   const double* t_out;
   float* y;          // current state (Q4), updated on accept
   const float* y1;   // candidate state
-  float* k[7];       // k[0] = k1 (updated on accept from k[6])
+  float* k[kMaxStages];   // k[0] = k1 (updated on accept from k[last])
   float* x2;         // stage-2 input of the next attempt
   float* out_nchw;   // (T,B,C,16,16)
   int channels;
   long long state_floats;
   long long off_y1, off_x2;   // saving mode: byte offsets of y1 (the last stage input) and of the stage-2 input inside a slot
-  float cm[7];       // c_mid
+  float cm[kMaxStages];   // c_mid
   float b21;         // beta21
   int dp5_sum;       // 1: the tableau is kDopri5 itself, whose c_mid sum is written out in finish_kernel<7, true> (bit stability)
 };
@@ -386,7 +386,7 @@ struct D5Ctx {
   hipStream_t stream = nullptr;
   DopriState* state = nullptr;
   double* t_dev = nullptr;
-  float *part0 = nullptr, *ping = nullptr, *pong = nullptr, *xs = nullptr, *y = nullptr, *y1 = nullptr, *k[7] = {};
+  float *part0 = nullptr, *ping = nullptr, *pong = nullptr, *xs = nullptr, *y = nullptr, *y1 = nullptr, *k[kMaxStages] = {};
   unsigned* psync = nullptr;
   unsigned long long* reloc = nullptr;
   bool saving = false, global_norm = false, partials64 = false;
@@ -427,13 +427,14 @@ static int d5_reduce_sums(hipStream_t stream, int count, const float* const* arr
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, stream, ss, g_reduce_buf, skip_flag);
   ODEHIP_CHECK_HIP(hipGetLastError());
   const int rcb = g_reduce_cb(g_reduce_buf, count, (void*)stream, g_reduce_user);
-  ODEHIP_REQUIRE(rcb == 0, "odeint_dopri5: the all-reduce callback failed (%d)", rcb);
+  ODEHIP_REQUIRE(rcb == 0, "odeint_dopri5: the all-reduce callback failed (%d)", rcb);   // (bosh3 is refused under exact-global step control)
   return ODEHIP_OK;
 }
 
 // enqueue ONE attempted step: the six evaluations (one persistent launch: the same table for every attempt -- the step size is read
 // through h_ptr, the queued-behind-`done` case through the skip word), the controller, the elementwise tail
 static int d5_attempt(D5Ctx& x) {
+  const char* const mname = x.tb->name;
   const odehip_convstack* f = &x.f;
   int rc;
   constexpr unsigned long long kTag1 = 1ull << 56;
@@ -450,7 +451,7 @@ static int d5_attempt(D5Ctx& x) {
     c.k_scale = x.ksc;
     c.order = all_64(f);   // 64-channel stacks: the adaptive walk (stage sums formed ahead of the matrix work), same bits per layer
     if (x.saving) {   // evaluation (slot, s - 1): input and hidden activations live in the slot the device picks
-      ODEHIP_REQUIRE(persist.recording(), "odeint_dopri5: the persistent walk became unavailable during a saving forward");
+      ODEHIP_REQUIRE(persist.recording(), "odeint_%s: the persistent walk became unavailable during a saving forward", mname);
       float* hid_s[ODEHIP_MAX_LAYERS];
       for (int l = 0; l < x.bl_nh; ++l) hid_s[l] = s_hid(s - 1, l);
       rc = enqueue_f_saving(f, s_xin(s - 1), x.batch, hid_s, x.ping, x.pong, &c, nullptr, skip, x.stream);
@@ -464,7 +465,7 @@ static int d5_attempt(D5Ctx& x) {
   if (x.partials64 && !persist.launched()) {
     // the controller sums 64 error-norm partials per sample (the sixteen-workgroup walk's); a refused launch has just been replayed
     // as per-layer launches, which write 16: the norm of this attempt is not the solver's
-    set_error("odeint_dopri5: the persistent walk became unavailable during the solve (its error-norm partials are laid out for it)");
+    set_error("odeint_%s: the persistent walk became unavailable during the solve (its error-norm partials are laid out for it)", mname);
     return ODEHIP_EHIP;
   }
   if (x.global_norm) {
@@ -492,12 +493,13 @@ static int d5_attempt(D5Ctx& x) {
 // running one keeps the GPU busy; exact-global mode enqueues a collective per attempt, so every rank must enqueue the same number:
 // no run-ahead there), then wait for the last enqueued controller so that the mailbox is final
 static int d5_run_to_done(D5Ctx& x) {
+  const char* const mname = x.tb->name;
   const int RUN_AHEAD = x.global_norm ? 0 : 1;
   int rc;
   MailboxWatch watch(&x.mb->steps_done);
   auto stalled = [&](const char* what) {
     if (!watch.stalled()) return false;
-    set_error("odeint_dopri5: %s (steps done %d of %d enqueued)", what, x.mb->steps_done, x.enq);
+    set_error("odeint_%s: %s (steps done %d of %d enqueued)", mname, what, x.mb->steps_done, x.enq);
     return true;
   };
   for (;;) {
@@ -515,8 +517,9 @@ static int d5_run_to_done(D5Ctx& x) {
 static int d5_collect(D5Ctx& x, int* stats_host, double* accepted_host, int accepted_cap, int* saved_out) {
   // the device has finished every attempt of this call: a persistent launch that gave up a wait is known NOW
   if (const unsigned code = persist_error(true)) {
-    set_error("odeint_dopri5: a persistent launch gave up waiting for a partner workgroup (code %u); the trajectory is invalid.  "
-              "Persistent launches are now disabled for this process", code);
+    const char* const mname = x.tb->name;
+    set_error("odeint_%s: a persistent launch gave up waiting for a partner workgroup (code %u); the trajectory is invalid.  "
+              "Persistent launches are now disabled for this process", mname, code);
     return ODEHIP_EHIP;
   }
   Mailbox* mb = x.mb;
@@ -531,7 +534,7 @@ static int d5_collect(D5Ctx& x, int* stats_host, double* accepted_host, int acce
       accepted_host[2 * i + 1] = mb->log[i][1];
     }
   }
-  return controller_error(false, mb->status);
+  return controller_error(x.tb->name, false, mb->status);
 }
 
 
@@ -562,7 +565,7 @@ extern "C" size_t odehip_adaptive_workspace_bytes(const odehip_convstack* f, int
   const size_t st = al256((size_t)batch * f->channels[0] * kPix * 4);
   const size_t hid = al256((size_t)batch * max_hidden(f) * kPix * 4);
   const size_t np = (size_t)batch * (f->channels[0] / 32) * 2 * 4;
-  return al256(sizeof(DopriState)) + al256((size_t)n_times * 8) + 3 * al256((np > 1024 ? np : 1024) * 4) + 2 * hid + 10 * st +
+  return al256(sizeof(DopriState)) + al256((size_t)n_times * 8) + 3 * al256((np > 1024 ? np : 1024) * 4) + 2 * hid + (3 + kMaxStages) * st +
          al256(persist_sync_bytes(batch)) + al256(16 * 8);
 }
 
@@ -589,7 +592,6 @@ extern "C" int odehip_odeint_adaptive(int method, const odehip_convstack* f, con
                                       int batch, float rtol, float atol, double first_step, int max_steps, int negate,
                                       float* out_nchw, int* stats_host, double* accepted_host, int accepted_cap, void* workspace,
                                       size_t workspace_bytes, void* stream_) {
-  const ErrorNames names(method);
   return dopri5_forward(method, f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, negate, out_nchw, stats_host, accepted_host,
                         accepted_cap, workspace, workspace_bytes, stream_, 0, nullptr);
 }
@@ -606,12 +608,12 @@ extern "C" int odehip_odeint_adaptive_saving(int method, const odehip_convstack*
                                              int n_times, int batch, float rtol, float atol, double first_step, int max_steps,
                                              float* out_nchw, int* stats_host, double* accepted_host, int accepted_cap, int max_accept,
                                              int* saved_out, void* workspace, size_t workspace_bytes, void* stream_) {
-  const ErrorNames names(method);
-  ODEHIP_REQUIRE(saved_out && max_accept > 0, "odeint_dopri5_saving: saved_out is required and max_accept must be positive");
+  const char* const mname = adaptive_name(method);
+  ODEHIP_REQUIRE(saved_out && max_accept > 0, "odeint_%s_saving: saved_out is required and max_accept must be positive", mname);
   *saved_out = 0;
   ODEHIP_REQUIRE(adaptive_tableau(method), "odeint_adaptive_saving: unknown adaptive method code %d", method);
   ODEHIP_REQUIRE(f && workspace_bytes >= odehip_adaptive_saving_workspace_bytes(f, batch, n_times, max_accept, method),
-                 "odeint_dopri5_saving: workspace too small");
+                 "odeint_%s_saving: workspace too small", mname);
   return dopri5_forward(method, f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, 0, out_nchw, stats_host, accepted_host,
                         accepted_cap, workspace, workspace_bytes, stream_, max_accept, saved_out);
 }
@@ -629,17 +631,18 @@ static int dopri5_forward(int method, const odehip_convstack* f, const float* z0
                           int save_max_accept, int* saved_out, int async_attempts, int* token_out) {
   const Tableau* tb = adaptive_tableau(method);
   ODEHIP_REQUIRE(tb, "odeint_adaptive: unknown adaptive method code %d (ODEHIP_DOPRI5 or ODEHIP_BOSH3)", method);
+  const char* const mname = tb->name;
   ODEHIP_REQUIRE(method == ODEHIP_DOPRI5 || !g_reduce_cb, "odeint_adaptive: exact-global step control (odehip_set_norm_allreduce) is not implemented for bosh3");
   int rc = check_stack(f);
   if (rc != ODEHIP_OK) return rc;
-  ODEHIP_REQUIRE(z0_nchw && t_host && out_nchw && workspace, "odeint_dopri5: null pointer");
-  ODEHIP_REQUIRE(n_times >= 1 && batch > 0, "odeint_dopri5: bad sizes (n_times %d, batch %d)", n_times, batch);
-  ODEHIP_REQUIRE(f->channels[0] == f->channels[f->n_convs], "odeint_dopri5: f must map C -> C channels");
-  ODEHIP_REQUIRE(rtol > 0 && atol >= 0, "odeint_dopri5: rtol must be > 0 and atol >= 0");
+  ODEHIP_REQUIRE(z0_nchw && t_host && out_nchw && workspace, "odeint_%s: null pointer", mname);
+  ODEHIP_REQUIRE(n_times >= 1 && batch > 0, "odeint_%s: bad sizes (n_times %d, batch %d)", mname, n_times, batch);
+  ODEHIP_REQUIRE(f->channels[0] == f->channels[f->n_convs], "odeint_%s: f must map C -> C channels", mname);
+  ODEHIP_REQUIRE(rtol > 0 && atol >= 0, "odeint_%s: rtol must be > 0 and atol >= 0", mname);
   for (int i = 1; i < n_times; ++i)
-    ODEHIP_REQUIRE(t_host[i] > t_host[i - 1], "odeint_dopri5: t must be strictly increasing (t[%d]=%g, t[%d]=%g)", i - 1,
+    ODEHIP_REQUIRE(t_host[i] > t_host[i - 1], "odeint_%s: t must be strictly increasing (t[%d]=%g, t[%d]=%g)", mname, i - 1,
                    t_host[i - 1], i, t_host[i]);
-  ODEHIP_REQUIRE(workspace_bytes >= odehip_adaptive_workspace_bytes(f, batch, n_times, method), "odeint_dopri5: workspace too small");
+  ODEHIP_REQUIRE(workspace_bytes >= odehip_adaptive_workspace_bytes(f, batch, n_times, method), "odeint_%s: workspace too small", mname);
   if (max_steps <= 0) max_steps = 1 << 30;
   hipStream_t stream = (hipStream_t)stream_;
   const int C = f->channels[0];
@@ -661,11 +664,11 @@ static int dopri5_forward(int method, const odehip_convstack* f, const float* z0
   D5Ctx stack_ctx;
   int slot = kD5Slots;
   if (async_attempts > 0) {
-    ODEHIP_REQUIRE(token_out && !g_reduce_cb, "odeint_dopri5_start: needs token_out; not available under exact-global step control");
+    ODEHIP_REQUIRE(token_out && !g_reduce_cb, "odeint_%s_start: needs token_out; not available under exact-global step control", mname);
     slot = -1;
     for (int i = 0; i < kD5Slots; ++i)
       if (!g_d5[i].in_use) { slot = i; break; }
-    ODEHIP_REQUIRE(slot >= 0, "odeint_dopri5_start: %d solves are already pending (collect one first)", kD5Slots);
+    ODEHIP_REQUIRE(slot >= 0, "odeint_%s_start: %d solves are already pending (collect one first)", mname, kD5Slots);
   }
   D5Ctx& cx = slot < kD5Slots ? g_d5[slot] : stack_ctx;
   cx = D5Ctx();
@@ -685,8 +688,8 @@ static int dopri5_forward(int method, const odehip_convstack* f, const float* z0
   float* xs = (float*)take(st_b);
   float* y = (float*)take(st_b);
   float* y1 = (float*)take(st_b);
-  float* k[7];
-  for (int i = 0; i < 7; ++i) k[i] = (float*)take(st_b);
+  float* k[kMaxStages];
+  for (int i = 0; i < kMaxStages; ++i) k[i] = (float*)take(st_b);
   unsigned* psync = (unsigned*)take(persist_sync_bytes(batch));
   unsigned long long* reloc = (unsigned long long*)take(16 * 8);
 
@@ -790,7 +793,7 @@ static int dopri5_forward(int method, const odehip_convstack* f, const float* z0
   fa.t_out = t_dev;
   fa.y = y;
   fa.y1 = y1;
-  for (int i = 0; i < 7; ++i) fa.k[i] = k[i];
+  for (int i = 0; i < kMaxStages; ++i) fa.k[i] = k[i];
   fa.x2 = xs;
   fa.out_nchw = out_nchw;
   fa.channels = C;
@@ -809,7 +812,7 @@ static int dopri5_forward(int method, const odehip_convstack* f, const float* z0
   cx.rtol = rtol; cx.atol = atol; cx.ksc = ksc;
   cx.stream = stream;
   cx.state = state; cx.t_dev = t_dev; cx.part0 = part0; cx.ping = ping; cx.pong = pong; cx.xs = xs; cx.y = y; cx.y1 = y1;
-  for (int i = 0; i < 7; ++i) cx.k[i] = k[i];
+  for (int i = 0; i < kMaxStages; ++i) cx.k[i] = k[i];
   cx.psync = psync; cx.reloc = reloc;
   cx.saving = saving; cx.global_norm = global_norm;
   cx.partials64 = n_conv_partials != batch * (C / 32) * 2 * 4;   // (the walks' 64 or 32 partials per sample)
@@ -842,13 +845,13 @@ extern "C" int odehip_odeint_adaptive_start(int method, const odehip_convstack* 
                                             int batch, float rtol, float atol, double first_step, int max_steps, float* out_nchw,
                                             int max_accept, int attempts, int* token_out, void* workspace, size_t workspace_bytes,
                                             void* stream_) {
-  const ErrorNames names(method);
-  ODEHIP_REQUIRE(token_out && attempts > 0, "odeint_dopri5_start: token_out is required and attempts must be positive");
+  const char* const mname = adaptive_name(method);
+  ODEHIP_REQUIRE(token_out && attempts > 0, "odeint_%s_start: token_out is required and attempts must be positive", mname);
   *token_out = -1;
   ODEHIP_REQUIRE(adaptive_tableau(method), "odeint_adaptive_start: unknown adaptive method code %d", method);
   ODEHIP_REQUIRE(f && workspace_bytes >= (max_accept > 0 ? odehip_adaptive_saving_workspace_bytes(f, batch, n_times, max_accept, method)
                                                            : odehip_adaptive_workspace_bytes(f, batch, n_times, method)),
-                 "odeint_dopri5_start: workspace too small");
+                 "odeint_%s_start: workspace too small", mname);
   int saved_dummy = 0;
   return dopri5_forward(method, f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, 0, out_nchw, nullptr, nullptr, 0, workspace,
                         workspace_bytes, stream_, max_accept, &saved_dummy, attempts, token_out);
@@ -869,7 +872,7 @@ extern "C" int odehip_odeint_dopri5_collect(int token, int* stats_host, double* 
 extern "C" int odehip_odeint_adaptive_collect(int token, int* stats_host, double* accepted_host, int accepted_cap, int* saved_out) {
   ODEHIP_REQUIRE(token >= 0 && token < kD5Slots && g_d5[token].in_use, "odeint_dopri5_collect: no pending solve with token %d", token);
   D5Ctx& cx = g_d5[token];
-  const ErrorNames names(cx.tb == &kBosh3 ? ODEHIP_BOSH3 : ODEHIP_DOPRI5);
+  const char* const mname = cx.tb->name;
   cx.in_use = false;   // whatever happens below, the slot is free again
   if (saved_out) *saved_out = 0;
   if (cx.n_times == 1) {
@@ -880,7 +883,7 @@ extern "C" int odehip_odeint_adaptive_collect(int token, int* stats_host, double
   MailboxWatch watch(&cx.mb->steps_done);
   while (cx.mb->steps_done < cx.enq) {
     if (watch.stalled()) {
-      set_error("odeint_dopri5_collect: no progress from the device for 120 s (steps done %d of %d enqueued)", cx.mb->steps_done, cx.enq);
+      set_error("odeint_%s_collect: no progress from the device for 120 s (steps done %d of %d enqueued)", mname, cx.mb->steps_done, cx.enq);
       return ODEHIP_EHIP;
     }
   }
@@ -889,9 +892,9 @@ extern "C" int odehip_odeint_adaptive_collect(int token, int* stats_host, double
     ODEHIP_CHECK_HIP(hipStreamSynchronize(cx.stream));
     write_stats(stats_host, cx.mb->nfe, cx.mb->n_accept, cx.mb->n_reject);
     if (stats_host) stats_host[3] = cx.enq;
-    set_error("odeint_dopri5_collect: the solve was not finished by the %d attempted steps start() enqueued (%d accepted, %d rejected "
+    set_error("odeint_%s_collect: the solve was not finished by the %d attempted steps start() enqueued (%d accepted, %d rejected "
               "so far); the frames it had not reached were NaN-filled, because the work enqueued behind start() has already consumed "
-              "`out`.  Start again with more attempts, or use the synchronous call", cx.enq, cx.mb->n_accept, cx.mb->n_reject);
+              "`out`.  Start again with more attempts, or use the synchronous call", mname, cx.enq, cx.mb->n_accept, cx.mb->n_reject);
     return ODEHIP_ETRUNC;
   }
   return d5_collect(cx, stats_host, accepted_host, accepted_cap, saved_out);

@@ -72,8 +72,8 @@ extern "C" int odehip_odeint_adaptive_backward(int method, const odehip_convstac
                                                const float* z0_nchw, const float* grad_out_nchw, float* grad_z0_nchw,
                                                float* const* grad_w, float* const* grad_b, void* workspace, size_t workspace_bytes,
                                                void* stream_) {
-  const ErrorNames names(method);
-  ODEHIP_REQUIRE(z0_nchw, "odeint_dopri5_backward: null pointer");
+  const char* const mname = adaptive_name(method);
+  ODEHIP_REQUIRE(z0_nchw, "odeint_%s_backward: null pointer", mname);
   return dopri5_backward(method, f, f_dgrad, t_host, n_times, batch, accepted_host, n_steps, z0_nchw, grad_out_nchw, grad_z0_nchw, grad_w, grad_b,
                          workspace, workspace_bytes, stream_, n_steps, false);
 }
@@ -83,12 +83,12 @@ extern "C" int odehip_odeint_adaptive_backward_saved(int method, const odehip_co
                                                      int n_steps, const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w,
                                                      float* const* grad_b, int max_accept, void* saved_workspace,
                                                      size_t saved_workspace_bytes, void* stream_) {
-  const ErrorNames names(method);
+  const char* const mname = adaptive_name(method);
   ODEHIP_REQUIRE(adaptive_tableau(method), "odeint_adaptive_backward_saved: unknown adaptive method code %d", method);
   ODEHIP_REQUIRE(f && saved_workspace && max_accept > 0 && n_steps >= 1 && n_steps <= max_accept,
-                 "odeint_dopri5_backward_saved: needs the saving forward's workspace and 1 <= n_steps <= max_accept");
+                 "odeint_%s_backward_saved: needs the saving forward's workspace and 1 <= n_steps <= max_accept", mname);
   ODEHIP_REQUIRE(saved_workspace_bytes >= odehip_adaptive_saving_workspace_bytes(f, batch, n_times, max_accept, method),
-                 "odeint_dopri5_backward_saved: workspace smaller than the saving forward's");
+                 "odeint_%s_backward_saved: workspace smaller than the saving forward's", mname);
   char* bws = (char*)saved_workspace + al256(odehip_adaptive_workspace_bytes(f, batch, n_times, method));   // the backward half (dopri5.hip)
   return dopri5_backward(method, f, f_dgrad, t_host, n_times, batch, accepted_host, n_steps, nullptr, grad_out_nchw, grad_z0_nchw, grad_w, grad_b,
                          bws, saved_workspace_bytes - (size_t)(bws - (char*)saved_workspace), stream_, max_accept, true);
@@ -101,21 +101,22 @@ static int dopri5_backward(int method, const odehip_convstack* f, const odehip_c
   const Tableau* tbp = adaptive_tableau(method);
   ODEHIP_REQUIRE(tbp, "odeint_adaptive_backward: unknown adaptive method code %d (ODEHIP_DOPRI5 or ODEHIP_BOSH3)", method);
   const Tableau& tb = *tbp;
+  const char* const mname = tb.name;
   const int S = tb.stages;   // stage s (1-based) lives at index s - 1; S - 1 new evaluations per accepted step
   int rc = check_stack(f);
   if (rc != ODEHIP_OK) return rc;
   ODEHIP_REQUIRE(f_dgrad && t_host && (z0_nchw || saved) && grad_out_nchw && grad_z0_nchw && grad_w && grad_b && workspace,
-                 "odeint_dopri5_backward: null pointer");
-  ODEHIP_REQUIRE(n_times >= 1 && batch > 0 && n_steps >= 0, "odeint_dopri5_backward: bad sizes");
-  ODEHIP_REQUIRE(n_steps == 0 || accepted_host, "odeint_dopri5_backward: null step log");
-  ODEHIP_REQUIRE(f->ks == 3 && f->channels[0] == f->channels[f->n_convs], "odeint_dopri5_backward: 3x3 C -> C dynamics only");
+                 "odeint_%s_backward: null pointer", mname);
+  ODEHIP_REQUIRE(n_times >= 1 && batch > 0 && n_steps >= 0, "odeint_%s_backward: bad sizes", mname);
+  ODEHIP_REQUIRE(n_steps == 0 || accepted_host, "odeint_%s_backward: null step log", mname);
+  ODEHIP_REQUIRE(f->ks == 3 && f->channels[0] == f->channels[f->n_convs], "odeint_%s_backward: 3x3 C -> C dynamics only", mname);
   for (int l = 0; l <= f->n_convs; ++l)
-    ODEHIP_REQUIRE(f->channels[l] % 64 == 0, "odeint_dopri5_backward: channel counts must be multiples of 64");
+    ODEHIP_REQUIRE(f->channels[l] % 64 == 0, "odeint_%s_backward: channel counts must be multiples of 64", mname);
   for (int i = 1; i < n_times; ++i)
-    ODEHIP_REQUIRE(t_host[i] > t_host[i - 1], "odeint_dopri5_backward: t must be strictly increasing");
-  ODEHIP_REQUIRE((S - 1) * n_steps + 1 <= 32 * 64, "odeint_dopri5_backward: too many accepted steps (%d)", n_steps);
+    ODEHIP_REQUIRE(t_host[i] > t_host[i - 1], "odeint_%s_backward: t must be strictly increasing", mname);
+  ODEHIP_REQUIRE((S - 1) * n_steps + 1 <= 32 * 64, "odeint_%s_backward: too many accepted steps (%d)", mname, n_steps);
   const BwdLayout L(f, batch, n_times, layout_steps, S);
-  ODEHIP_REQUIRE(workspace_bytes >= L.total, "odeint_dopri5_backward: workspace too small");
+  ODEHIP_REQUIRE(workspace_bytes >= L.total, "odeint_%s_backward: workspace too small", mname);
   hipStream_t stream = (hipStream_t)stream_;
   void* ws = workspace;
   const int NH = L.NH, NL = f->n_convs, N = n_steps;
@@ -128,20 +129,20 @@ static int dopri5_backward(int method, const odehip_convstack* f, const odehip_c
     double t1 = t_host[0];
     for (int n = 0; n < N; ++n) {
       const double t0 = accepted_host[2 * n], dt = accepted_host[2 * n + 1];
-      ODEHIP_REQUIRE(t0 == t1 && dt > 0, "odeint_dopri5_backward: step log is not contiguous at step %d", n);
+      ODEHIP_REQUIRE(t0 == t1 && dt > 0, "odeint_%s_backward: step log is not contiguous at step %d", mname, n);
       t1 = t0 + dt;
       j_lo[n] = j;
       while (j < n_times && t_host[j] <= t1) ++j;
       j_hi[n] = j;
     }
-    ODEHIP_REQUIRE(j == n_times, "odeint_dopri5_backward: the step log does not reach t[%d]", n_times - 1);
+    ODEHIP_REQUIRE(j == n_times, "odeint_%s_backward: the step log does not reach t[%d]", mname, n_times - 1);
   }
 
   float* hdev = L.p(ws, L.off_h);
   float* ping = L.p(ws, L.off_ping);
   float* pong = L.p(ws, L.off_pong);
-  float* k[7];
-  float* gY[7];
+  float* k[kMaxStages];
+  float* gY[kMaxStages];
   for (int i = 0; i < S; ++i) {
     k[i] = L.p(ws, L.off_k + (size_t)i * L.st);
     gY[i] = L.p(ws, L.off_gY + (size_t)i * L.st);
@@ -150,7 +151,7 @@ static int dopri5_backward(int method, const odehip_convstack* f, const odehip_c
   rc = odehip_nchw_to_q4(grad_out_nchw, goq(0), n_times * batch, L.C, stream);
   if (rc != ODEHIP_OK) return rc;
   if (N == 0) {  // a single output time: out[0] = z0
-    ODEHIP_REQUIRE(n_times == 1 && !saved, "odeint_dopri5_backward: empty step log");
+    ODEHIP_REQUIRE(n_times == 1 && !saved, "odeint_%s_backward: empty step log", mname);
     ODEHIP_CHECK_HIP(hipMemcpyAsync(grad_z0_nchw, grad_out_nchw, st_b, hipMemcpyDeviceToDevice, stream));
     for (int l = 0; l < NL; ++l) {
       ODEHIP_CHECK_HIP(hipMemsetAsync(grad_w[l], 0, (size_t)f->channels[l + 1] * f->channels[l] * 9 * 4, stream));

@@ -1,7 +1,7 @@
 // dopri5_control.h -- the adaptive solvers' tableaus (dopri5, bosh3) and the scalar decisions made with them, once: torchdiffeq
 // 0.2.1's _select_initial_step (scalar part), _optimal_step_size and the dense-output weights of _interp_fit.  Host code, the forward
 // solve's controller kernels (dopri5.hip), the device-controlled adjoint (adjoint_device.hip) and the stand-alone check of
-// tests/test_dopri5_control_cpu.py all read this one file: it compiles in a .hip file and under a plain host C++17 compiler.
+// tests/adaptive_control_check.cpp all read this one file: it compiles in a .hip file and under a plain host C++17 compiler.
 // What differs between the callers stays with them: the finite test on the error ratio, how max_steps is counted, what nfe starts
 // at, the saving-slot bookkeeping and the mixed norm's extra maximum over the parameter tensors.
 #pragma once
@@ -22,6 +22,7 @@ namespace odehip {
 // k_S is the next step's k_1.  A further FSAL pair is one more table here (up to kMaxStages stages) and a method code.
 constexpr int kMaxStages = ODEHIP_MAX_STAGES;
 struct Tableau {
+  const char* name;   // as torchdiffeq spells the method; the entry points' error messages carry it
   int stages;   // S
   int order;    // of the solution that is carried on: the step-size exponent is 1 / order, the initial step's too
   double beta[kMaxStages - 1][kMaxStages - 1];
@@ -66,7 +67,7 @@ inline double dense_weight(const Tableau& tb, int s, double x) { return dense_we
 // Dormand-Prince 5(4) as torchdiffeq 0.2.1 holds it (_impl/dopri5.py): beta rows, c_sol (= last beta row, padded),
 // c_error = c_sol - 4th-order weights, c_mid (dense-output midpoint weights)
 inline constexpr Tableau kDopri5 = {
-    7, 5,
+    "dopri5", 7, 5,
     {{1.0 / 5, 0, 0, 0, 0, 0},
      {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
      {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
@@ -82,7 +83,7 @@ inline constexpr Tableau kDopri5 = {
 
 // Bogacki-Shampine 3(2) as torchdiffeq 0.2.1 holds it (_impl/bosh3.py)
 inline constexpr Tableau kBosh3 = {
-    4, 3,
+    "bosh3", 4, 3,
     {{1.0 / 2}, {0, 3.0 / 4}, {2.0 / 9, 1.0 / 3, 4.0 / 9}},
     {2.0 / 9, 1.0 / 3, 4.0 / 9, 0},
     {2.0 / 9 - 7.0 / 24, 1.0 / 3 - 1.0 / 4, 4.0 / 9 - 1.0 / 3, -1.0 / 8},
@@ -94,17 +95,10 @@ inline const Tableau* adaptive_tableau(int method) {
   return method == ODEHIP_DOPRI5 ? &kDopri5 : (method == ODEHIP_BOSH3 ? &kBosh3 : nullptr);
 }
 
-// dopri5 under its old names: the same arithmetic (1 / 5 and 0.2 are what 1 / order rounds to in their types)
-namespace dp5 {
-inline constexpr auto& kBeta = kDopri5.beta;
-inline constexpr auto& kCSol = kDopri5.c_sol;
-inline constexpr auto& kCErr = kDopri5.c_err;
-inline constexpr auto& kCMid = kDopri5.c_mid;
-using odehip::initial_step_h0;
-ODEHIP_HD inline float initial_step_dt(float h0, float d1, float d2) { return odehip::initial_step_dt(h0, d1, d2, 5); }
-ODEHIP_HD inline double next_step_size(double dt, float ratio) { return odehip::next_step_size(dt, ratio, 5); }
-ODEHIP_HD inline double dense_weight(int s, double x, double b, double m) { return odehip::dense_weight(s, x, b, m, 6); }
-inline double dense_weight(int s, double x) { return odehip::dense_weight(kDopri5, s, x); }
-}  // namespace dp5
+// the method's name in the error messages of the entry points the two methods share (an unknown code is reported under dopri5's)
+inline const char* adaptive_name(int method) {
+  const Tableau* tb = adaptive_tableau(method);
+  return tb ? tb->name : kDopri5.name;
+}
 
 }  // namespace odehip

@@ -16,15 +16,6 @@ constexpr int kPix = kHW * kHW;   // 256 pixels
 constexpr int kQuadBytes = kPix * 16;  // one channel-quad plane of the Q4 layout: 256 px * 4 ch * 4 B
 
 void set_error(const char* fmt, ...);
-// While one lives (on the stack of a method-coded adaptive entry point) the errors this thread sets name the call's method: the
-// drivers are shared and their messages say "dopri5"
-extern thread_local const char* g_err_method;
-struct ErrorNames {
-  const char* prev;
-  explicit ErrorNames(int method) : prev(g_err_method) { g_err_method = method == ODEHIP_BOSH3 ? "bosh3" : nullptr; }
-  ~ErrorNames() { g_err_method = prev; }
-  ErrorNames(const ErrorNames&) = delete;
-};
 int hip_fail(hipError_t e, const char* what);
 
 #define ODEHIP_CHECK_HIP(expr)                                   \
@@ -327,10 +318,6 @@ inline void adaptive_stage_combine(const Tableau& tb, CombineArgs& c, int s, con
     c.atol = atol;
   }
 }
-inline void dopri5_stage_combine(CombineArgs& c, int s, const float* y, const float* h_ptr, float* const* k, float* out_next,
-                                 float* err_partials, float rtol, float atol) {
-  adaptive_stage_combine(kDopri5, c, s, y, h_ptr, k, out_next, err_partials, rtol, atol);
-}
 
 // The host's watch on the progress word of a pinned mailbox a device-side controller writes: the limit is on time WITHOUT
 // progress, not on the whole integration.
@@ -360,18 +347,18 @@ inline void write_stats(int* stats_host, int nfe, int n_accept, int n_reject) {
   stats_host[2] = n_reject;
 }
 
-// the status a device-side controller ended on as the error of its entry point (0: none); returns the status
-inline int controller_error(bool adjoint, int status, int max_accept = 0) {
+// the status a device-side controller ended on as the error of its entry point (0: none; mname: the tableau's name); returns the status
+inline int controller_error(const char* mname, bool adjoint, int status, int max_accept = 0) {
   if (!adjoint) {
-    if (status == ODEHIP_ENAN) set_error("odeint_dopri5: non-finite error ratio (non-finite values in state `y`)");
-    else if (status == ODEHIP_ENOTCONV) set_error("odeint_dopri5: underflow in dt or max_num_steps exceeded");
+    if (status == ODEHIP_ENAN) set_error("odeint_%s: non-finite error ratio (non-finite values in state `y`)", mname);
+    else if (status == ODEHIP_ENOTCONV) set_error("odeint_%s: underflow in dt or max_num_steps exceeded", mname);
     else return ODEHIP_OK;
   } else if (status == ODEHIP_ENAN) {
-    set_error("odeint_adjoint_dopri5_backward: non-finite error ratio");
+    set_error("odeint_adjoint_%s_backward: non-finite error ratio", mname);
   } else if (status == ODEHIP_ENOTCONV) {
-    set_error("odeint_adjoint_dopri5_backward: underflow in dt");
+    set_error("odeint_adjoint_%s_backward: underflow in dt", mname);
   } else if (status != 0) {
-    set_error("odeint_adjoint_dopri5_backward: more than max_accept = %d accepted steps", max_accept);
+    set_error("odeint_adjoint_%s_backward: more than max_accept = %d accepted steps", mname, max_accept);
   }
   return status;
 }

@@ -1,9 +1,11 @@
-// Stand-alone front end of the tableau-generic part of ode-rl_amd/csrc/dopri5_control.h (compiled and run by
-// tests/test_adaptive_control_cpu.py, host compiler only).  The first number of every case is the C ABI's adaptive method code
+// Stand-alone front end of ode-rl_amd/csrc/dopri5_control.h (compiled and run by tests/test_adaptive_control_cpu.py and
+// tests/test_dopri5_control_cpu.py, host compiler only).  The first number of every case is the C ABI's adaptive method code
 // (3 dopri5, 4 bosh3).  One case per line of stdin, numbers as hexadecimal floating point; one result per line of stdout (%a):
 //   next   m dt ratio     -> next_step_size(dt, (float)ratio, order of m)
+//   h0     m d0 d1        -> initial_step_h0(d0, d1)   (the same for every method)
 //   dt     m h0 d1 d2     -> initial_step_dt(h0, d1, d2, order of m)
 //   dense  m s x          -> dense_weight(tableau of m, s, x)
+//   dense4 m s x b mid    -> dense_weight(s, x, b, mid, last stage of m): the form device code calls with its own copy of the rows
 //   beta   m i j | csol m s | cerr m s | cmid m s | stages m | order m   -> the tableau itself
 #include <cstdio>
 #include <cstdlib>
@@ -17,10 +19,10 @@ int main() {
   char line[512];
   while (std::fgets(line, sizeof(line), stdin)) {
     char op[16];
-    char num[4][64];
-    const int n = std::sscanf(line, "%15s %63s %63s %63s %63s", op, num[0], num[1], num[2], num[3]) - 1;
+    char num[5][64];
+    const int n = std::sscanf(line, "%15s %63s %63s %63s %63s %63s", op, num[0], num[1], num[2], num[3], num[4]) - 1;
     if (n < 1) continue;
-    double v[4] = {0, 0, 0, 0};
+    double v[5] = {0, 0, 0, 0, 0};
     for (int i = 0; i < n; ++i) v[i] = std::strtod(num[i], nullptr);
     const Tableau* tb = adaptive_tableau((int)v[0]);
     if (!tb) {
@@ -31,8 +33,10 @@ int main() {
     const bool stage_ok = v[1] >= 0 && i1 < tb->stages;
     double r;
     if (!std::strcmp(op, "next") && n == 3) r = next_step_size(v[1], (float)v[2], tb->order);
+    else if (!std::strcmp(op, "h0") && n == 3) r = initial_step_h0((float)v[1], (float)v[2]);
     else if (!std::strcmp(op, "dt") && n == 4) r = initial_step_dt((float)v[1], (float)v[2], (float)v[3], tb->order);
     else if (!std::strcmp(op, "dense") && n == 3 && stage_ok) r = dense_weight(*tb, i1, v[2]);
+    else if (!std::strcmp(op, "dense4") && n == 5 && stage_ok) r = dense_weight(i1, v[2], v[3], v[4], tb->stages - 1);
     else if (!std::strcmp(op, "beta") && n == 3 && stage_ok && i1 < tb->stages - 1 && i2 >= 0 && i2 < kMaxStages - 1) r = tb->beta[i1][i2];
     else if (!std::strcmp(op, "csol") && n == 2 && stage_ok) r = tb->c_sol[i1];
     else if (!std::strcmp(op, "cerr") && n == 2 && stage_ok) r = tb->c_err[i1];

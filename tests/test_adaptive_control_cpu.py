@@ -1,5 +1,5 @@
-"""The tableau-generic step controller proves itself without a device (the pattern of test_dopri5_control_cpu.py, which keeps pinning
-the dopri5 names of the same header).
+"""The tableau-generic step controller proves itself without a device (the pattern of test_dopri5_control_cpu.py, which drives the
+same program with dopri5's method code).
 
 tests/adaptive_control_check.cpp includes ode-rl_amd/csrc/dopri5_control.h and evaluates, for the bosh3 tableau (method code 4):
   the tableau        beta, c_sol, c_error, c_mid, stages, order against tests/_adaptive_ref.BOSH3: exactly (both sides write the same

@@ -1,6 +1,7 @@
 """The adaptive step controller proves itself without a device.
 
-tests/dopri5_control_check.cpp includes ode-rl_amd/csrc/dopri5_control.h -- the one place the Dormand-Prince tableau, the scalar part
+tests/adaptive_control_check.cpp (one program for every tableau; driven here with dopri5's method code) includes
+ode-rl_amd/csrc/dopri5_control.h -- the one place the Dormand-Prince tableau, the scalar part
 of _select_initial_step, _optimal_step_size and the dense-output weights live; the forward solve's controller kernels, the host-driven
 adjoint and the device-controlled adjoint all call it -- and evaluates it under the host compiler.  The results are compared with
 oracle/torchdiffeq_ref.py:
@@ -20,6 +21,7 @@ import torch
 from oracle import torchdiffeq_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DOPRI5 = 3   # ODEHIP_DOPRI5
 
 
 @pytest.fixture(scope="module")
@@ -27,12 +29,12 @@ def check(tmp_path_factory):
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     if cxx is None:
         pytest.fail("no host C++ compiler found")
-    exe = str(tmp_path_factory.mktemp("dopri5_control") / "dopri5_control_check")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", os.path.join(ROOT, "tests", "dopri5_control_check.cpp"), "-o", exe], check=True)
+    exe = str(tmp_path_factory.mktemp("dopri5_control") / "adaptive_control_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", os.path.join(ROOT, "tests", "adaptive_control_check.cpp"), "-o", exe], check=True)
 
     def run(cases):
-        """cases: (op, number, ...) tuples -> one float per case"""
-        text = "".join(op + " " + " ".join(float(v).hex() for v in args) + "\n" for op, *args in cases)
+        """cases: (op, number, ...) tuples -> one float per case; every case goes out with dopri5's method code in front"""
+        text = "".join(op + " " + " ".join(float(v).hex() for v in (DOPRI5, *args)) + "\n" for op, *args in cases)
         res = subprocess.run([exe], input=text, capture_output=True, text=True)
         assert res.returncode == 0, res.stdout + res.stderr
         out = [float.fromhex(x) for x in res.stdout.split()]

@@ -97,6 +97,9 @@ SED[bosh3_keeps_dopri5_exponent]='s|fmax(0.9 / pow((double)ratio, 1.0 / (double)
 SED[bosh3_cmid_on_stage_1]='s|^    {0, 1.0 / 2, 0, 0},$|    {1.0 / 2, 0, 0, 0},|'   # c_mid applied to k1 instead of k2
 SED[bosh3_fsal_hands_over_k3]='s|      const f32x4 k7 = ((const f32x4\*)a.k\[LAST\])\[i\];|      const f32x4 k7 = ((const f32x4*)a.k[LAST == 3 ? 2 : LAST])[i];|'   # f1 of a bosh3 step = k3 instead of k4
 SED[bosh3_initial_step_fifth_root]='s|  else h1 = powf(0.01f / fmaxf(d1, d2), 1.0f / (float)order);|  else h1 = powf(0.01f / fmaxf(d1, d2), 1.0f / 5.0f);|'   # _select_initial_step with dopri5 exponent
+# ---- the adjoint's slot geometry (adjoint_layout.h), shared by the host loop and the device-steered path: both go wrong alike, so
+# their agreement does not show it; the oracle comparison of tests/test_hip_adjoint_paths.py does -- MUT_TESTS="tests/test_hip_adjoint_paths.py"
+SED[adjoint_gp_stride]='s|cap \* NH \* hid + ((size_t)s \* NG + l) \* hid|cap * NH * hid + ((size_t)s * NH + l) * hid|'   # gradient slots of a stage strided by NH, not NG: the seed of stage s is overwritten by stage s + 1 (lower offsets: inside the slot)
 # mutants of the Python binding, "file|sed script": applied to the tree's own file for the run and restored afterwards (run only)
 declare -A PYSED
 PYSED[z0_offset_stuck]='ode-rl_amd/autograd.py|s/gen.set_offset(at + 4)/gen.set_offset(at)/;s/_explicit_seed\[1\] = offset + 1/_explicit_seed[1] = offset/'   # consecutive sample_z0 calls draw the same noise
