@@ -19,12 +19,9 @@
 // store exact zeros, not products with what the forward kept for that (frame, sample) -- the contract of
 // odehip_odeconvgru_encode_train_masked.  No reduction happens here: the bias gradients are column sums of g_gates_raw / g_cand_raw,
 // summed in a fixed order by the weight-gradient launches (wgrad.hip).  No float atomics.
-#include "convgru_gn.h"
+#include "convgru_cell.h"
 
 namespace odehip {
-
-__device__ __forceinline__ f32x4 sigmoid4(const f32x4 v) { return f32x4{sigmoidf_(v.x), sigmoidf_(v.y), sigmoidf_(v.z), sigmoidf_(v.w)}; }
-__device__ __forceinline__ f32x4 tanh4(const f32x4 v) { return f32x4{tanhf(v.x), tanhf(v.y), tanhf(v.z), tanhf(v.w)}; }
 
 // gates_raw: (B, 2H) Q4, grid (2 * hq, B) with hq = H / 4.  Quads [0, hq) are the reset gate, the rest the update gate.  Writes
 // u (B, H) and rh = r * h (B, H).

@@ -26,71 +26,10 @@
 
 #include <vector>
 
-#include "convgru_gn.h"
+#include "convgru_cell.h"
 #include "persist.h"
 
 namespace odehip {
-
-// convgru_backward.hip
-void launch_gn_update_bwd(const float* cand_raw, const float* gamma, const float* beta, const float* gh, const float* z, const float* h_prev,
-                          float* g_cand_raw, float* gz_pre, float* gh_prev, float* dgamma_part, float* dbeta_part, int hidden, int batch,
-                          hipStream_t stream);
-void launch_gn_gates_bwd(const float* gates_raw, const float* gamma, const float* beta, const float* gz_pre, const float* g_rh,
-                         const float* h_prev, float* gh_prev, float* g_gates_raw, float* dgamma_part, float* dbeta_part, int hidden,
-                         int batch, hipStream_t stream);
-void launch_reduce_rows(const float* part, int n_rows, int n_cols, float* out, hipStream_t stream);
-
-// gates_raw (B, 2*hid) Q4 -> z (B,hid) and, with a state, rh = r * h.  HAS_H = false is launched over the z groups alone.
-template <bool HAS_H>
-__global__ __launch_bounds__(256) void seq_gates_kernel(const float* __restrict__ gates_raw, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, const float* __restrict__ h,
-                                                        float* __restrict__ z_out, float* __restrict__ rh_out, int hid_groups) {
-  __shared__ float sh[4];
-  const int g = blockIdx.x, b = blockIdx.y;
-  f32x4 v[8];
-  load_group(gates_raw, b, 2 * hid_groups, g, v);
-  group_norm(v, gamma, beta, g, 1e-5f, sh);
-  const bool is_z = !HAS_H || g < hid_groups;
-  const int gh = is_z ? g : g - hid_groups;
-  const size_t base = ((size_t)(b * hid_groups + gh) * 8) * kPix;
-  f32x4* out = (f32x4*)(is_z ? z_out : rh_out) + base + threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    f32x4 s = {sigmoidf_(v[q].x), sigmoidf_(v[q].y), sigmoidf_(v[q].z), sigmoidf_(v[q].w)};
-    if (HAS_H) {
-      if (!is_z) s *= ((const f32x4*)h + base + threadIdx.x)[q * kPix];
-    }
-    out[q * kPix] = s;
-  }
-}
-
-// cand_raw (B,hid) Q4 -> h' = (1 - z) h + z tanh(GN(cand_raw)) (HAS_H = false: h = 0, h' = z tanh(.)), written as Q4 (h_out) and into
-// the step's NCHW slot of h_seq (sample b at h_seq_slot + b * hid * 256)
-template <bool HAS_H>
-__global__ __launch_bounds__(256) void seq_update_kernel(const float* __restrict__ cand_raw, const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta, const float* __restrict__ h,
-                                                         const float* __restrict__ z, float* __restrict__ h_out,
-                                                         float* __restrict__ h_seq_slot, int hid_groups) {
-  __shared__ float sh[4];
-  const int g = blockIdx.x, b = blockIdx.y;
-  f32x4 v[8];
-  load_group(cand_raw, b, hid_groups, g, v);
-  group_norm(v, gamma, beta, g, 1e-5f, sh);
-  const size_t base = ((size_t)(b * hid_groups + g) * 8) * kPix;
-  const f32x4* zp = (const f32x4*)z + base + threadIdx.x;
-  f32x4* op = (f32x4*)h_out + base + threadIdx.x;
-  float* n = h_seq_slot + ((size_t)b * hid_groups + g) * 32 * kPix + threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const f32x4 c = {tanhf(v[q].x), tanhf(v[q].y), tanhf(v[q].z), tanhf(v[q].w)};
-    const f32x4 zz = zp[q * kPix];
-    f32x4 o = zz * c;
-    if (HAS_H) o = (1.0f - zz) * ((const f32x4*)h + base + threadIdx.x)[q * kPix] + o;
-    op[q * kPix] = o;
-    float* nq = n + (size_t)q * 4 * kPix;
-    nq[0] = o.x; nq[kPix] = o.y; nq[2 * kPix] = o.z; nq[3 * kPix] = o.w;
-  }
-}
 
 namespace {
 
@@ -163,32 +102,6 @@ int check_sequence(const odehip_convgru_cell* c, const odehip_convgru_cell_halve
   return ODEHIP_OK;
 }
 
-// one 5x5 convolution of a step over one or two Q4 sources; `j` picks the images: -1 = the full weights, else half j of hv
-int seq_conv(const odehip_convgru_cell* c, const odehip_convgru_cell_halves* hv, bool gates, int j, const float* s1, int c1, const float* s2, int c2, float* dst, int batch,
-             hipStream_t stream) {
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.src1 = s1;
-  a.src2 = s2;
-  a.q1 = c1 / 4;
-  a.qin = (c1 + c2) / 4;
-  a.qout = (gates ? 2 : 1) * c->hidden / 4;
-  a.bias = gates ? c->b_gates : c->b_can;
-  a.dst = dst;
-  a.batch = batch;
-  a.act = kActNone;
-  int rc;
-  if (c->w_gates_bf16) {
-    a.w_bf16 = j < 0 ? (gates ? c->w_gates_bf16 : c->w_can_bf16) : hv->bf16[j];
-    rc = launch_bf16_5x5(a, stream);
-  } else {
-    a.w_wino = j < 0 ? (gates ? c->w_gates_wino : c->w_can_wino) : hv->wino[j];
-    rc = launch_wino5(a, stream);
-  }
-  ODEHIP_REQUIRE(rc != 1, "convgru_sequence: no 5x5 kernel serves %d -> %d channels", c1 + c2, a.qout * 4);
-  return rc;
-}
-
 int run_forward(const odehip_convgru_cell* c, const odehip_convgru_cell_halves* hv, const float* x_seq, const float* h0, int T, int batch, float* h_seq, void* ws, size_t ws_bytes,
                 bool train, hipStream_t stream, const char* who) {
   int rc = check_sequence(c, hv, T, batch, x_seq != nullptr, h0 != nullptr, train, who);
@@ -196,7 +109,7 @@ int run_forward(const odehip_convgru_cell* c, const odehip_convgru_cell_halves* 
   ODEHIP_REQUIRE(h_seq && ws, "%s: null output or workspace", who);
   const SeqLayout L(c, T, batch, x_seq != nullptr, train);
   ODEHIP_REQUIRE(ws_bytes >= L.total, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, L.total);
-  const int H = c->hidden, I = c->input, HG = H / 32;
+  const int H = c->hidden, I = c->input;
   if (x_seq && (rc = odehip_nchw_to_q4(x_seq, L.x(ws, 0), T * batch, I, stream)) != ODEHIP_OK) return rc;
   // the state before step t lives in slot t (train) / t & 1 (forward); without h0 slot 0 is read by nobody in the forward pass, the
   // reverse sweep reads it as the zero state it stands for
@@ -210,30 +123,10 @@ int run_forward(const odehip_convgru_cell* c, const odehip_convgru_cell_halves* 
     const bool has_h = h0 || t > 0;
     const float* x = x_seq ? L.x(ws, t) : nullptr;
     const float* h = has_h ? hslot(t) : nullptr;
-    float* gates = L.step(ws, L.off_gates, t, 2 * L.hs);
-    float* z = L.step(ws, L.off_z, t, L.hs);
-    float* rh = L.step(ws, L.off_rh, t, L.hs);
-    float* cand = L.step(ws, L.off_cand, t, L.hs);
     float* slot = h_seq + (size_t)t * batch * H * kPix;
-    if (x && has_h) rc = seq_conv(c, hv, true, -1, x, I, h, H, gates, batch, stream);
-    else if (x) rc = seq_conv(c, hv, true, 0, x, I, nullptr, 0, gates, batch, stream);
-    else rc = seq_conv(c, hv, true, 1, h, H, nullptr, 0, gates, batch, stream);
+    rc = cell_forward_step(c, hv, x, h, hslot(t + 1), slot, (long long)H * kPix, batch, L.step(ws, L.off_gates, t, 2 * L.hs),
+                           L.step(ws, L.off_z, t, L.hs), L.step(ws, L.off_rh, t, L.hs), L.step(ws, L.off_cand, t, L.hs), nullptr, stream);
     if (rc != ODEHIP_OK) return rc;
-    if (has_h)
-      hipLaunchKernelGGL(seq_gates_kernel<true>, dim3(2 * HG, batch), dim3(256), 0, stream, gates, c->gn_gates_w, c->gn_gates_b, h, z, rh, HG);
-    else
-      hipLaunchKernelGGL(seq_gates_kernel<false>, dim3(HG, batch), dim3(256), 0, stream, gates, c->gn_gates_w, c->gn_gates_b, nullptr, z,
-                         nullptr, HG);
-    if (x && has_h) rc = seq_conv(c, hv, false, -1, x, I, rh, H, cand, batch, stream);
-    else if (x) rc = seq_conv(c, hv, false, 2, x, I, nullptr, 0, cand, batch, stream);
-    else rc = seq_conv(c, hv, false, 3, rh, H, nullptr, 0, cand, batch, stream);
-    if (rc != ODEHIP_OK) return rc;
-    if (has_h)
-      hipLaunchKernelGGL(seq_update_kernel<true>, dim3(HG, batch), dim3(256), 0, stream, cand, c->gn_can_w, c->gn_can_b, h, z, hslot(t + 1),
-                         slot, HG);
-    else
-      hipLaunchKernelGGL(seq_update_kernel<false>, dim3(HG, batch), dim3(256), 0, stream, cand, c->gn_can_w, c->gn_can_b, nullptr, z,
-                         hslot(t + 1), slot, HG);
   }
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
@@ -280,72 +173,43 @@ extern "C" int odehip_convgru_sequence_backward(const odehip_convgru_cell* c, co
   ODEHIP_REQUIRE(workspace_bytes >= L.total, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, L.total);
   hipStream_t stream = (hipStream_t)stream_;
   void* ws = workspace;
-  float* gz_pre = L.p(ws, L.off_gzpre);
-  float* gh_prev = L.p(ws, L.off_ghprev);
-  float* gx_c = L.p(ws, L.off_gxc);
-  float* g_rh = L.p(ws, L.off_grh);
   float* gh0 = L.p(ws, L.off_gh0);
   float* pgg = L.p(ws, L.off_pgg);
   float* pgc = L.p(ws, L.off_pgc);
   const size_t pgg_half = (size_t)T * batch * 2 * H, pgc_half = (size_t)T * batch * H;
   const bool bf = c->w_gates_bf16 != nullptr;
-
-  // input-gradient convolution of one weight half j (0 gates/x, 1 gates/h, 2 can/x, 3 can/h): plain store or a reverse-sweep target
-  auto conv_bwd = [&](const float* src, int cin, int cout, int j, const BwdArgs* bw, float* dst) {
-    const float* wt = j == 0 ? cb->w_gates_dx : (j == 1 ? cb->w_gates_dh : (j == 2 ? cb->w_can_dx : cb->w_can_dh));
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src1 = src;
-    a.q1 = a.qin = cin / 4;
-    a.qout = cout / 4;
-    a.w_packed = wt;
-    a.w_bf16 = bf ? cb->bf16[j] : nullptr;
-    a.w_wino = a.w_bf16 ? nullptr : cb->wino[j];
-    a.batch = batch;
-    a.combine = bw ? 3 : 0;
-    if (bw) a.bwd = *bw;
-    a.dst = dst;
-    return launch_conv(a, 5, stream);
-  };
+  const CellDgradW dw = dgrad_images(cb, bf);   // the bf16 images only in bf16 mode
 
   if ((rc = odehip_nchw_to_q4(grad_h_seq_nchw, L.p(ws, L.off_gseq), T * batch, H, stream)) != ODEHIP_OK) return rc;
   const float* gh = L.p(ws, L.off_gseq + (size_t)(T - 1) * L.hs);
+  std::vector<CatStep> cat((size_t)T);
   for (int t = T - 1; t >= 0; --t) {
-    const bool has_h = has_h0 || t > 0;
-    const float* h_prev = L.h(ws, t);   // zeros at t == 0 without h0 (written by the train call)
-    float* g_cand = L.p(ws, L.off_gcand + (size_t)t * L.hs);
-    float* g_gates = L.p(ws, L.off_ggates + (size_t)t * 2 * L.hs);
-    launch_gn_update_bwd(L.p(ws, L.off_cand + (size_t)t * L.hs), c->gn_can_w, c->gn_can_b, gh, L.p(ws, L.off_z + (size_t)t * L.hs), h_prev,
-                         g_cand, gz_pre, gh_prev, pgc + (size_t)t * batch * H, pgc + pgc_half + (size_t)t * batch * H, H, batch, stream);
-    if (has_x && (rc = conv_bwd(g_cand, H, I, 2, nullptr, gx_c)) != ODEHIP_OK) return rc;
-    if (has_h) {
-      if ((rc = conv_bwd(g_cand, H, H, 3, nullptr, g_rh)) != ODEHIP_OK) return rc;
-    } else {
-      ODEHIP_CHECK_HIP(hipMemsetAsync(g_rh, 0, L.hs, stream));   // r * 0: nothing arrives at r, and no state lies further back
-    }
-    launch_gn_gates_bwd(L.p(ws, L.off_gates + (size_t)t * 2 * L.hs), c->gn_gates_w, c->gn_gates_b, gz_pre, g_rh, h_prev, gh_prev, g_gates,
-                        pgg + (size_t)t * batch * 2 * H, pgg + pgg_half + (size_t)t * batch * 2 * H, H, batch, stream);
-    BwdArgs w;
-    memset(&w, 0, sizeof(w));
-    w.n_targets = 1;
-    w.tgt[0].a_c = 1.0f;
-    w.tgt[0].g_c = 1.0f;
-    if (has_x) {
-      w.tgt[0].out = L.p(ws, L.off_gx + (size_t)t * L.xs);
-      w.tgt[0].srcA = gx_c;
-      if ((rc = conv_bwd(g_gates, 2 * H, I, 0, &w, nullptr)) != ODEHIP_OK) return rc;
-    }
-    if (has_h) {
-      float* out = t > 0 ? L.p(ws, L.off_gh + (size_t)(t & 1) * L.hs) : gh0;
-      w.tgt[0].out = out;
-      w.tgt[0].srcA = gh_prev;
-      if (t > 0) {   // what arrives at slot t - 1 from outside joins in the same epilogue
-        w.tgt[0].srcB = L.p(ws, L.off_gseq + (size_t)(t - 1) * L.hs);
-        w.tgt[0].b_c = 1.0f;
-      }
-      if ((rc = conv_bwd(g_gates, 2 * H, H, 1, &w, nullptr)) != ODEHIP_OK) return rc;
-      gh = out;
-    }
+    CellBwdStep s;
+    s.cand_raw = L.p(ws, L.off_cand + (size_t)t * L.hs);
+    s.z = L.p(ws, L.off_z + (size_t)t * L.hs);
+    s.gates_raw = L.p(ws, L.off_gates + (size_t)t * 2 * L.hs);
+    s.h_prev = L.h(ws, t);   // zeros at t == 0 without h0 (written by the train call)
+    s.gh = gh;
+    s.g_cand = L.p(ws, L.off_gcand + (size_t)t * L.hs);
+    s.g_gates = L.p(ws, L.off_ggates + (size_t)t * 2 * L.hs);
+    s.gz_pre = L.p(ws, L.off_gzpre);
+    s.gh_prev = L.p(ws, L.off_ghprev);
+    s.gx_c = L.p(ws, L.off_gxc);
+    s.g_rh = L.p(ws, L.off_grh);
+    s.pgc_w = pgc + (size_t)t * batch * H;
+    s.pgc_b = s.pgc_w + pgc_half;
+    s.pgg_w = pgg + (size_t)t * batch * 2 * H;
+    s.pgg_b = s.pgg_w + pgg_half;
+    s.mask_b = nullptr;
+    s.has_x = has_x;
+    s.has_h = has_h0 || t > 0;   // a first step from a zero state: nothing flows further back
+    cat[t] = CatStep{s.g_gates, s.g_cand, has_x ? L.x(ws, t) : nullptr, s.h_prev, L.p(ws, L.off_rh + (size_t)t * L.hs)};
+    // dL/dh_{t-1} = gh_prev + . + grad_h_seq[t-1]: what arrives at slot t - 1 from outside joins in the same epilogue
+    float* out = t > 0 ? L.p(ws, L.off_gh + (size_t)(t & 1) * L.hs) : gh0;
+    rc = cell_backward_step(c, dw, s, bwd_target(L.p(ws, L.off_gx + (size_t)t * L.xs), s.gx_c),
+                            bwd_target(out, s.gh_prev, t > 0 ? L.p(ws, L.off_gseq + (size_t)(t - 1) * L.hs) : nullptr), batch, stream);
+    if (rc != ODEHIP_OK) return rc;
+    if (s.has_h) gh = out;
   }
   if (has_x && (rc = odehip_q4_to_nchw(L.p(ws, L.off_gx), grad_x_seq_nchw, T * batch, I, stream)) != ODEHIP_OK) return rc;
   if (has_h0 && (rc = odehip_q4_to_nchw(gh0, grad_h0_nchw, batch, H, stream)) != ODEHIP_OK) return rc;
@@ -356,13 +220,7 @@ extern "C" int odehip_convgru_sequence_backward(const odehip_convgru_cell* c, co
   float* slabs = L.p(ws, L.off_slab);
   std::vector<WgradPair> host((size_t)4 * T);
   memset(host.data(), 0, host.size() * sizeof(WgradPair));
-  for (int j = 0; j < 4; ++j)
-    for (int t = 0; t < T; ++t) {
-      WgradPair& e = host[(size_t)j * T + t];
-      e.g = j < 2 ? L.p(ws, L.off_ggates + (size_t)t * 2 * L.hs) : L.p(ws, L.off_gcand + (size_t)t * L.hs);
-      e.a = (j & 1) == 0 ? (has_x ? L.x(ws, t) : nullptr) : (j == 1 ? L.h(ws, t) : L.p(ws, L.off_rh + (size_t)t * L.hs));
-      e.scale = 1.0f;
-    }
+  cat_wgrad_entries(host.data(), T, cat.data(), T);
   if ((rc = staged_upload(table0, host.data(), host.size() * sizeof(WgradPair), stream)) != ODEHIP_OK) return rc;
   const int t_first = has_h0 ? 0 : 1, n_state = T - t_first;
   for (int j = 0; j < 2; ++j) {   // gates, can
@@ -381,10 +239,7 @@ extern "C" int odehip_convgru_sequence_backward(const odehip_convgru_cell* c, co
       if (rc != ODEHIP_OK) return rc;
     }
   }
-  launch_reduce_rows(pgg, T * batch, 2 * H, gr->gn_gates_w, stream);
-  launch_reduce_rows(pgg + pgg_half, T * batch, 2 * H, gr->gn_gates_b, stream);
-  launch_reduce_rows(pgc, T * batch, H, gr->gn_can_w, stream);
-  launch_reduce_rows(pgc + pgc_half, T * batch, H, gr->gn_can_b, stream);
+  reduce_gn_partials(pgg, pgc, T * batch, H, gr->gn_gates_w, gr->gn_gates_b, gr->gn_can_w, gr->gn_can_b, stream);
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
 }

@@ -1,5 +1,5 @@
 """ODEConvGRUCell.forward alone (BASELINE shape: B=64, T_in=10, 64 channels) -- timing and, under rocprofv3, the kernel breakdown.
-  python tools/encoder_bench.py [--batch 64] [--frames 10] [--steps 20] [--dtype f32|bf16]"""
+  python tools/encoder_bench.py [--batch 64] [--frames 10] [--steps 20] [--dtype f32|bf16] [--backward]"""
 import argparse
 import json
 import os
@@ -18,6 +18,7 @@ def main():
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--channels", type=int, default=64)
     p.add_argument("--dtype", default="f32", choices=["f32", "bf16"])
+    p.add_argument("--backward", action="store_true", help="time forward + backward (gradient through mean and std)")
     a = p.parse_args()
     import ode_rl_amd
     if a.dtype == "bf16":
@@ -29,16 +30,25 @@ def main():
     enc = ode_rl_amd.ODEConvGRUCell(f, None, (16, 16), C).to(dev)
     x = torch.randn(a.frames, a.batch, C, 16, 16, device=dev) * 0.5
     t = torch.arange(a.frames, dtype=torch.float64, device=dev) / (2 * a.frames)
-    with torch.no_grad():
-        for _ in range(3):
-            enc(x, t)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(a.steps):
-            enc(x, t)
-        torch.cuda.synchronize()
+    gm, gs = torch.randn(a.batch, C, 16, 16, device=dev), torch.randn(a.batch, C, 16, 16, device=dev)
+
+    def step():
+        if not a.backward:
+            with torch.no_grad():
+                return enc(x, t)
+        enc.zero_grad(set_to_none=True)
+        mean, std = enc(x, t)
+        torch.autograd.backward([mean, std], [gm, gs])
+
+    for _ in range(3):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        step()
+    torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / a.steps * 1e3
-    print(json.dumps({"what": "ODEConvGRUCell.forward", "batch": a.batch, "frames": a.frames, "channels": C, "dtype": a.dtype, "ms": ms}))
+    print(json.dumps({"what": "ODEConvGRUCell.forward" + (" + backward" if a.backward else ""), "batch": a.batch, "frames": a.frames, "channels": C, "dtype": a.dtype, "ms": ms}))
 
 
 if __name__ == "__main__":

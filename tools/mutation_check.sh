@@ -55,8 +55,8 @@ SED[ssim_sigma]='s/  const double sigma = 1.5;/  const double sigma = 1.4;/'    
 SED[ssim_interior_shift]='s/^constexpr int kFirstRow = kWinRadius; /constexpr int kFirstRow = kWinRadius + 1; /'   # S averaged over rows 6..59 (row 64 = the words behind each plane in LDS: still inside the allocation)
 SED[ssim_c2]='s/  const double k1 = 0.01, k2 = 0.03, range = (double)data_range;/  const double k1 = 0.01, k2 = 0.02, range = (double)data_range;/'   # C2 = (0.02 R)^2
 SED[ssim_covariance]='s/        const float vxy = uxy - ux \* uy;/        const float vxy = uxy - ux * ux;/'       # vxy = uxy - ux ux
-# ---- ConvGRU sequences (convgru_sequence.hip): the weight halves, the zero state, the batched weight gradient, the h_seq slots
-SED[seq_state_half_from_frame_half]='s/    else rc = seq_conv(c, hv, true, 1, h, H, nullptr, 0, gates, batch, stream);/    else rc = seq_conv(c, hv, true, 0, h, H, nullptr, 0, gates, batch, stream);/'   # zero input: the gates conv runs over the FRAME half of its weights
+# ---- ConvGRU sequences (convgru_sequence.hip; the step itself is cell_forward_step in convgru.hip): the weight halves, the zero state, the batched weight gradient, the h_seq slots
+SED[seq_state_half_from_frame_half]='s/  const int j_gates = x \&\& h ? -1 : (x ? 0 : 1);/  const int j_gates = x \&\& h ? -1 : (x ? 0 : 0);/'   # zero input: the gates conv runs over the FRAME half of its weights
 SED[seq_first_step_reads_h0]='s/    const bool has_h = h0 || t > 0;/    const bool has_h = true;/'   # zero state: the first step reads the (unwritten) state slot
 SED[seq_wgrad_drops_step]='s/      const int n_eval = half == 0 ? T : n_state, a_ch = half == 0 ? I : H;/      const int n_eval = (half == 0 ? T : n_state) - 1, a_ch = half == 0 ? I : H;/'   # batched weight gradient: the last step is left out
 SED[seq_slot_off_by_one]='s/    float\* slot = h_seq + (size_t)t \* batch \* H \* kPix;/    float* slot = h_seq + (size_t)(t > 0 ? t - 1 : 0) * batch * H * kPix;/'   # h_seq[t] written to slot t - 1
@@ -75,7 +75,7 @@ SED[grid_scatter_weights_swapped]='s/      const float w1 = tb.exact\[j\] ? 1.0f
 SED[resident3_as_resident2]='s/        case 3: return launch_resident<3>(a, stream);/        case 3: return launch_resident<2>(a, stream);/'   # 48-channel 3x3: the last 16 input channels dropped
 SED[wino3_as_wino2]='s/    case 3: return launch_wino_n<3>(a, stream);/    case 3: return launch_wino_n<2>(a, stream);/'   # ... and on the Winograd kernel
 SED[bf16_2_as_bf16_1]='s/    case 2: return launch_bf16_n<2>(a, stream);/    case 2: return launch_bf16_n<1>(a, stream);/'   # 32-channel bf16 3x3: the last 16 input channels dropped
-SED[gn_gates_odd_boundary]='s/    if (!is_z) s \*= hp\[q \* kPix\];/    if (!is_z \&\& !((hid_groups \& 1) \&\& hid_groups > 1 \&\& g == hid_groups)) s *= hp[q * kPix];/'   # 3 or 5 groups per gate (hidden 96, 160): the first r group is handled as a z group (no r * h)
+SED[gn_gates_odd_boundary]='s/    if (HAS_H \&\& !is_z) s \*= hp\[q \* kPix\];/    if (HAS_H \&\& !is_z \&\& !((hid_groups \& 1) \&\& hid_groups > 1 \&\& g == hid_groups)) s *= hp[q * kPix];/'   # 3 or 5 groups per gate (hidden 96, 160): the first r group is handled as a z group (no r * h)
 # ---- the norm-free ConvGRU cell of upstream Vid-ODE (convgru_plain.hip; tests/test_hip_vidode_upstream.py)
 SED[plain_gates_swapped]='s/  const bool is_reset = q < hq;/  const bool is_reset = q >= hq;/;s/  const size_t o = ((size_t)b \* hq + (is_reset ? q : q - hq)) \* kPix + threadIdx.x;/  const size_t o = ((size_t)b * hq + (q < hq ? q : q - hq)) * kPix + threadIdx.x;/'   # the first half of conv_gates taken as the update gate (same addresses)
 SED[plain_bwd_drops_bypass]='s/  if (blend) d += (1.0f - m) \* g;  \/\/ the part of the blend that bypasses the cell/  (void)blend;/'   # fractional mask: the (1-m) g term of the state gradient dropped
