@@ -321,6 +321,63 @@ struct PreEpilogue {
   }
 };
 
+// One chunk (16 input channels, all 16 positions xi) of a consumer wave's (16 co x 16 tiles) block, shared by wino_layer and
+// wino_strip_layer: v = this lane's fragment of position 0 in the chunk's V buffer (positions VSTRIDE bytes apart).  Two xi at a time:
+// consecutive MFMAs hit different accumulators (a dependent 16x16x4 issues 8 cycles late); the V fragments of the next pair are read,
+// and the U fragments kUAhead positions on requested, while this pair's 8 MFMAs run.  U ring: slot g % kUAhead holds position g of the
+// layer (g = 16 c + xi); the caller requests the first kUAhead on entry.  no_u: the ablations without memory traffic keep their constants.
+template <int VSTRIDE, int NCHUNK>
+__device__ __forceinline__ void chunk_mma(const char* v, int c, __amdgpu_buffer_rsrc_t ru, int u_off, f32x4 (&uw)[kUAhead],
+                                          f32x4 (&acc)[16], bool no_u) {
+  static_assert(kUAhead % 2 == 0 && kUAhead <= 16, "the U ring is refilled a pair of positions at a time");
+  constexpr int kG = 16 * NCHUNK;
+  f32x4 x0 = *(const f32x4*)(v), x1 = *(const f32x4*)(v + VSTRIDE);
+  f32x4 x0n, x1n;
+#pragma unroll
+  for (int x = 0; x < 16; x += 2) {
+    const int g = c * 16 + x, s0 = g % kUAhead, s1 = (g + 1) % kUAhead;
+    const f32x4 w0 = uw[s0], w1 = uw[s1];
+    if (x + 2 < 16) {
+      x0n = *(const f32x4*)(v + (x + 2) * VSTRIDE);
+      x1n = *(const f32x4*)(v + (x + 3) * VSTRIDE);
+    }
+    if (g + kUAhead < kG && !no_u) {
+      uw[s0] = load_u(ru, u_off, (g + kUAhead) * 2048);
+      uw[s1] = load_u(ru, u_off, (g + kUAhead + 1) * 2048);
+    }
+    acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, x0.x, acc[x], 0, 0, 0);
+    acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, x1.x, acc[x + 1], 0, 0, 0);
+    acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, x0.y, acc[x], 0, 0, 0);
+    acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, x1.y, acc[x + 1], 0, 0, 0);
+    acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, x0.z, acc[x], 0, 0, 0);
+    acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, x1.z, acc[x + 1], 0, 0, 0);
+    acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, x0.w, acc[x], 0, 0, 0);
+    acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, x1.w, acc[x + 1], 0, 0, 0);
+    x0 = x0n; x1 = x1n;
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+    __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, 7, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// The output transform A^T M A in registers: the lane holds M_xi[its co quad][its tile] for all 16 xi (acc[4 row + col]); y[q] is the
+// conv output (bias included) of quad q of its 2x2 tile, pixel (q >> 1, q & 1).
+__device__ __forceinline__ void out_transform(const f32x4 (&acc)[16], f32x4 bias4, f32x4 (&y)[4]) {
+  f32x4 S[2][4];
+#pragma unroll
+  for (int cI = 0; cI < 4; ++cI) {
+    S[0][cI] = acc[0 * 4 + cI] + acc[1 * 4 + cI] + acc[2 * 4 + cI];
+    S[1][cI] = pk_sub(pk_sub(acc[1 * 4 + cI], acc[2 * 4 + cI]), acc[3 * 4 + cI]);
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    y[2 * i] = S[i][0] + S[i][1] + S[i][2] + bias4;
+    y[2 * i + 1] = pk_sub(pk_sub(S[i][1] + bias4, S[i][2]), S[i][3]);
+  }
+}
+
 // One 3x3 layer for workgroup (sample b, 32-channel tile ct, image half rh).  PERSIST: called in a loop by
 // wino_persist_kernel -- the input tile is loaded past the per-CU cache (sc0 sc1: it was written by other CUs of this launch),
 // the first weight chunk is requested BEFORE waiting for the partners, and finished output is announced through hk.done.
@@ -333,7 +390,6 @@ template <int NCHUNK, bool DBG, bool PERSIST, int QOUT = 16, bool ADAPT = false>
 __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, const float* __restrict__ p_u, int p_qin, const ConvArgs& a,
                                            int b, int ct, int rh, char* smem, const PersistHook& hk) {
   static_assert(!PERSIST || (NCHUNK % 2 == 0), "the layer-to-layer LDS hand-over assumes an even chunk count");
-  static_assert(kUAhead % 2 == 0 && kUAhead <= 16, "the U ring is refilled a pair of positions at a time");
   constexpr int kRawAux = PERSIST ? 16 : 0;  // sc1 (agent scope): never served from this CU's vector cache
   char* const Rb = smem;
   char* const Vb = smem + 2 * kWRaw;
@@ -479,9 +535,7 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
   for (int x = 0; x < 16; ++x) acc[x] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int u_off = kq * 512 + (ch * 16 + i16) * 16;  // this lane's 16 bytes of a position's 2 KiB block [quad 4][co 32][4 ci]
   const int v_off = kq * 512 + (thh * 16 + i16) * 16;
-  // U ring: slot g % kUAhead holds position g of the layer (g = 16 c + xi); the request for g + kUAhead goes out with the MFMAs of g.
-  // Buffer loads: the range check keeps every address inside this tile.
-  constexpr int kG = 16 * NCHUNK;
+  // the U ring's first positions (chunk_mma): buffer loads, the range check keeps every address inside this tile
   const bool dbg_nou = dbg_noprod || dbg_nodma;     // the ablations without memory traffic: U fragments are constants
   const __amdgpu_buffer_rsrc_t ru = make_rsrc((const char*)p_u + (size_t)ct * (NCHUNK * kWU), (unsigned)NCHUNK * kWU);
   f32x4 uw[kUAhead];
@@ -607,40 +661,7 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
   for (int c = 0; c < nchunk; ++c) {
     __builtin_amdgcn_s_barrier();  // [c]
     if (PERSIST && c == 0 && wave == 0) pstamp(hk, 4, lane);
-    if (!skip && !dbg_nomfma) {
-      const char* v = Vb + (c & 1) * kWV + v_off;
-      // two xi at a time: consecutive MFMAs hit different accumulators (a dependent 16x16x4 issues 8 cycles late);
-      // the V fragments of the next pair are read, and the U fragments kUAhead positions on requested, while this pair's 8 MFMAs run
-      f32x4 x0 = *(const f32x4*)(v), x1 = *(const f32x4*)(v + 2048);
-      f32x4 x0n, x1n;
-#pragma unroll
-      for (int x = 0; x < 16; x += 2) {
-        const int g = c * 16 + x, s0 = g % kUAhead, s1 = (g + 1) % kUAhead;
-        const f32x4 w0 = uw[s0], w1 = uw[s1];
-        if (x + 2 < 16) {
-          x0n = *(const f32x4*)(v + (x + 2) * 2048);
-          x1n = *(const f32x4*)(v + (x + 3) * 2048);
-        }
-        if (g + kUAhead < kG && !dbg_nou) {
-          uw[s0] = load_u(ru, u_off, (g + kUAhead) * 2048);
-          uw[s1] = load_u(ru, u_off, (g + kUAhead + 1) * 2048);
-        }
-        acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, x0.x, acc[x], 0, 0, 0);
-        acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, x1.x, acc[x + 1], 0, 0, 0);
-        acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, x0.y, acc[x], 0, 0, 0);
-        acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, x1.y, acc[x + 1], 0, 0, 0);
-        acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, x0.z, acc[x], 0, 0, 0);
-        acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, x1.z, acc[x + 1], 0, 0, 0);
-        acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, x0.w, acc[x], 0, 0, 0);
-        acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, x1.w, acc[x + 1], 0, 0, 0);
-        x0 = x0n; x1 = x1n;
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 7, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
+    if (!skip && !dbg_nomfma) chunk_mma<2048, NCHUNK>(Vb + (c & 1) * kWV + v_off, c, ru, u_off, uw, acc, dbg_nou);
     if (st.on && c < 4) {
       asm volatile("" ::"v"(acc[15][0]));
       st.take(3 + c);
@@ -649,13 +670,6 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
   if (skip) return;
   if (PERSIST && wave == 0) pstamp(hk, 5, lane);
 
-  // ---- output transform in registers: lane (tile i16 of half thh, row group kq) holds M_xi[co quad][tile] for all xi
-  f32x4 S[2][4];
-#pragma unroll
-  for (int cI = 0; cI < 4; ++cI) {
-    S[0][cI] = acc[0 * 4 + cI] + acc[1 * 4 + cI] + acc[2 * 4 + cI];
-    S[1][cI] = pk_sub(pk_sub(acc[1 * 4 + cI], acc[2 * 4 + cI]), acc[3 * 4 + cI]);
-  }
   float esum = 0.0f;
   // ADAPT: the same arithmetic as emit_quad's (order 1 for stage combines), on the operands reduced at the start of the layer
   auto emit_adapt = [&](int q, int P, f32x4 v) {
@@ -699,21 +713,14 @@ __device__ __forceinline__ void wino_layer(const float* __restrict__ p_src, cons
       emit_quad(a, b, Q, P, v, esum, a.dbg ? hk.nchw_base + ((size_t)a.dbg - 1) : nullptr);
     }
   };
+  f32x4 y[4];   // lane (tile i16 of half thh, row group kq): its 2x2 tile
+  out_transform(acc, bias4, y);
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const f32x4 y0 = S[i][0] + S[i][1] + S[i][2] + bias4;
-    const f32x4 y1 = pk_sub(pk_sub(S[i][1] + bias4, S[i][2]), S[i][3]);
-    const int P = (r0 + 2 * oty + i) * 16 + 2 * otx;
-    if constexpr (ADAPT) {
-      emit_adapt(2 * i, P, y0);
-      emit_adapt(2 * i + 1, P + 1, y1);
-    } else if (PERSIST) {
-      ep.emit(a, b, Q, 2 * i, P, y0, esum);
-      ep.emit(a, b, Q, 2 * i + 1, P + 1, y1, esum);
-    } else {
-      emit_quad(a, b, Q, P, y0, esum);
-      emit_quad(a, b, Q, P + 1, y1, esum);
-    }
+  for (int q = 0; q < 4; ++q) {
+    const int P = (r0 + 2 * oty + (q >> 1)) * 16 + 2 * otx + (q & 1);
+    if constexpr (ADAPT) emit_adapt(q, P, y[q]);
+    else if (PERSIST) ep.emit(a, b, Q, q, P, y[q], esum);
+    else emit_quad(a, b, Q, P, y[q], esum);
   }
   if (PERSIST) {
     if (a.combine == 1 && a.cmb.err_partials) {
@@ -1056,6 +1063,60 @@ __device__ __forceinline__ void wait_done16(const PersistHook& hk, int lo_word, 
   if (hk.fence) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 }
 
+// The producer of the two row-quarter kernels (wino_layer16, wino_strip_layer): the raw tile is image rows r0 - 1 .. r0 + 4 in
+// wino_layer's 20-slot rows (conflict-free stride-2 reads), zero-padded by the DMA's range check; every producer wave DMAs one
+// channel quad of a chunk and transforms the quad it loaded itself (tq = pw: its own vmcnt suffices), one V row per lane
+// (lane = (tile tt, V row vi): 8 ds_read_b128 + 4 ds_write_b128).  The issue order and the counted waits stay with each kernel.
+struct SixRowProducer {
+  __amdgpu_buffer_rsrc_t rx;
+  char *Rb, *Vb;
+  int pw, vr[2], off_a, off_b, v_off;
+  float sg;
+  __device__ __forceinline__ SixRowProducer(const float* p_src, int b, int r0, int pw_, int lane, char* raw, char* v)
+      : rx(make_rsrc((const char*)p_src + (size_t)b * 16 * kQuadBytes, 16u * kQuadBytes)), Rb(raw), Vb(v), pw(pw_) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int s = 64 * p + lane;
+      const int row = s / 20, w = s - row * 20;
+      const int pc = w < 9 ? 2 * w : 2 * (w - 9) + 1;
+      const int irow = r0 - 1 + row, col = pc - 1;
+      vr[p] = (s < 120 && w < 18 && irow >= 0 && irow < kHW && col >= 0 && col < kHW) ? irow * 256 + col * 16 : kOobOffset;
+    }
+    const int tt = lane & 15, vi = lane >> 4, tq = pw;
+    const int tty = tt >> 3, ttx = tt & 7;
+    // V row vi of B^T d:  0: p0 - p2   1: p1 + p2   2: p2 - p1   3: p3 - p1  (sign of row 3 folded into U): T = a + sg * b
+    const int ra = vi;
+    const int rb = vi < 2 ? 2 : 1;
+    sg = vi == 1 ? 1.0f : -1.0f;
+    const int raw_base = tq * 2048 + (2 * tty * 20 + ttx) * 16;
+    off_a = raw_base + ra * 320;
+    off_b = raw_base + rb * 320;
+    v_off = tq * 256 + tt * 16 + vi * 4 * 1024;
+  }
+  __device__ __forceinline__ void issue_raw(int c, int buf) const {
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, ODEHIP_LDS_PTR(Rb + buf * k16Raw + pw * 2048 + p * 1024), 16, vr[p],
+                                               (c * 4 + pw) * kQuadBytes, 0, 16);
+  }
+  __device__ __forceinline__ void transform(int rbuf, int vbuf) const {
+    const char* r = Rb + rbuf * k16Raw;
+    f32x4 T[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int cj = ((j & 1) * 9 + (j >> 1)) * 16;
+      const f32x4 da = *(const f32x4*)(r + off_a + cj);
+      const f32x4 db = *(const f32x4*)(r + off_b + cj);
+      T[j] = da + db * sg;
+    }
+    char* v = Vb + vbuf * k16V + v_off;
+    *(f32x4*)(v + 0 * 1024) = pk_sub(T[0], T[2]);
+    *(f32x4*)(v + 1 * 1024) = T[1] + T[2];
+    *(f32x4*)(v + 2 * 1024) = pk_sub(T[2], T[1]);
+    *(f32x4*)(v + 3 * 1024) = pk_sub(T[1], T[3]);
+  }
+};
+
 __device__ __forceinline__ void wino_layer16(const float* __restrict__ p_src, const float* __restrict__ p_u, const ConvArgs& a, int b,
                                              int cq, int rq, char* smem, const PersistHook& hk) {
   char* const Ub = smem;
@@ -1074,16 +1135,7 @@ __device__ __forceinline__ void wino_layer16(const float* __restrict__ p_src, co
     const int ct = cq >> 1, half = cq & 1;
     const unsigned u_tile_bytes = (unsigned)nchunk * kWU;   // the 32-channel tile this 16-channel tile is half of
     const __amdgpu_buffer_rsrc_t ru = make_rsrc((const char*)p_u + (size_t)ct * u_tile_bytes, u_tile_bytes);
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc((const char*)p_src + (size_t)b * 16 * kQuadBytes, 16u * kQuadBytes);
-    int vr[2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int s = 64 * p + lane;
-      const int row = s / 20, w = s - row * 20;
-      const int pc = w < 9 ? 2 * w : 2 * (w - 9) + 1;
-      const int irow = r0 - 1 + row, col = pc - 1;
-      vr[p] = (s < 120 && w < 18 && irow >= 0 && irow < kHW && col >= 0 && col < kHW) ? irow * 256 + col * 16 : kOobOffset;
-    }
+    const SixRowProducer pr(p_src, b, r0, pw, lane, Rb, Vb);
     // U: the chunk's 64 (xi, quad) pieces of this channel half are 256 B each, 512 B apart: one instruction moves four of them
     const int vu = (lane >> 4) * 512 + half * 256 + (lane & 15) * 16;
     auto issue_u = [&](int c, int buf) {
@@ -1093,38 +1145,6 @@ __device__ __forceinline__ void wino_layer16(const float* __restrict__ p_src, co
         dma16(ru, Ub + buf * k16U + p * 1024, vu, c * kWU + p * 2048);
       }
     };
-    auto issue_raw = [&](int c, int buf) {
-#pragma unroll
-      for (int p = 0; p < 2; ++p)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, ODEHIP_LDS_PTR(Rb + buf * k16Raw + pw * 2048 + p * 1024), 16, vr[p],
-                                                 (c * 4 + pw) * kQuadBytes, 0, 16);
-    };
-    // transform: lane = (tile tt, V row vi); this wave's quad tq = pw
-    const int tt = lane & 15, vi = lane >> 4, tq = pw;
-    const int tty = tt >> 3, ttx = tt & 7;
-    // V row vi of B^T d:  0: p0 - p2   1: p1 + p2   2: p2 - p1   3: p3 - p1  (sign of row 3 folded into U): T = a + sg * b
-    const int ra = vi == 0 ? 0 : (vi == 1 ? 1 : (vi == 2 ? 2 : 3));
-    const int rb = vi == 0 ? 2 : (vi == 1 ? 2 : 1);
-    const float sg = vi == 1 ? 1.0f : -1.0f;
-    const int raw_base = tq * 2048 + (2 * tty * 20 + ttx) * 16;
-    const int off_a = raw_base + ra * 320, off_b = raw_base + rb * 320;
-    const int v_off = tq * 256 + tt * 16;
-    auto transform = [&](int rbuf, int vbuf) {
-      const char* r = Rb + rbuf * k16Raw;
-      f32x4 T[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int cj = ((j & 1) * 9 + (j >> 1)) * 16;
-        const f32x4 da = *(const f32x4*)(r + off_a + cj);
-        const f32x4 db = *(const f32x4*)(r + off_b + cj);
-        T[j] = da + db * sg;
-      }
-      char* v = Vb + vbuf * k16V + v_off + vi * 4 * 1024;
-      *(f32x4*)(v + 0 * 1024) = pk_sub(T[0], T[2]);
-      *(f32x4*)(v + 1 * 1024) = T[1] + T[2];
-      *(f32x4*)(v + 2 * 1024) = pk_sub(T[2], T[1]);
-      *(f32x4*)(v + 3 * 1024) = pk_sub(T[1], T[3]);
-    };
     // DMA order per wave: U_0 (4) | raw_0 (2) | raw_1 (2) | then per iteration c: U_{c+1} (4) | raw_{c+2} (2)
     issue_u(0, 0);
     if (!hk.first) {
@@ -1133,22 +1153,22 @@ __device__ __forceinline__ void wino_layer16(const float* __restrict__ p_src, co
       const int lo = rq > 0 ? (rq - 1) * 16 : 0, hi = rq < 3 ? (rq + 2) * 16 : 64;
       wait_done16(hk, lo, hi);
     }
-    issue_raw(0, 0);
-    issue_raw(1, 1);
+    pr.issue_raw(0, 0);
+    pr.issue_raw(1, 1);
     wait_vmcnt<2>();   // U_0 and raw_0 landed
-    transform(0, 0);
+    pr.transform(0, 0);
 #pragma unroll
     for (int c = 0; c < nchunk; ++c) {
       __builtin_amdgcn_s_barrier();  // [c]
       if (c + 1 < nchunk) {
         issue_u(c + 1, (c + 1) & 1);
         if (c + 2 < nchunk) {
-          issue_raw(c + 2, c & 1);
+          pr.issue_raw(c + 2, c & 1);
           wait_vmcnt<6>();           // raw_{c+1} landed
         } else {
           wait_vmcnt<4>();
         }
-        transform((c + 1) & 1, (c + 1) & 1);
+        pr.transform((c + 1) & 1, (c + 1) & 1);
         if (c + 2 < nchunk) wait_vmcnt<2>(); else wait_vmcnt<0>();  // U_{c+1} landed
       }
     }
@@ -1565,50 +1585,7 @@ __device__ __forceinline__ void wino_strip_layer(const float* __restrict__ p_src
   if (wave >= 4) {
     // =========================================== PRODUCERS ===========================================
     const int pw = wave - 4;
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc((const char*)p_src + (size_t)b * 16 * kQuadBytes, 16u * kQuadBytes);
-    // raw tile: image rows r0 - 1 .. r0 + 4 in wino_layer's 20-slot rows (conflict-free stride-2 reads), zero-padded by the DMA's
-    // range check
-    int vr[2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int s = 64 * p + lane;
-      const int row = s / 20, w = s - row * 20;
-      const int pc = w < 9 ? 2 * w : 2 * (w - 9) + 1;
-      const int irow = r0 - 1 + row, col = pc - 1;
-      vr[p] = (s < 120 && w < 18 && irow >= 0 && irow < kHW && col >= 0 && col < kHW) ? irow * 256 + col * 16 : kOobOffset;
-    }
-    auto issue_raw = [&](int c, int buf) {
-#pragma unroll
-      for (int p = 0; p < 2; ++p)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, ODEHIP_LDS_PTR(Rb + buf * k16Raw + pw * 2048 + p * 1024), 16, vr[p],
-                                                 (c * 4 + pw) * kQuadBytes, 0, 16);
-    };
-    // transform: lane = (tile tt, V row vi) of the quad this wave DMA'd itself (tq = pw: its own vmcnt suffices)
-    const int tt = lane & 15, vi = lane >> 4, tq = pw;
-    const int tty = tt >> 3, ttx = tt & 7;
-    // V row vi of B^T d:  0: p0 - p2   1: p1 + p2   2: p2 - p1   3: p3 - p1  (sign of row 3 folded into U): T = a + sg * b
-    const int ra = vi;
-    const int rb = vi < 2 ? 2 : 1;
-    const float sg = vi == 1 ? 1.0f : -1.0f;
-    const int raw_base = tq * 2048 + (2 * tty * 20 + ttx) * 16;
-    const int off_a = raw_base + ra * 320, off_b = raw_base + rb * 320;
-    const int v_off = tq * 256 + tt * 16;
-    auto transform = [&](int rbuf, int vbuf) {
-      const char* r = Rb + rbuf * k16Raw;
-      f32x4 T[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int cj = ((j & 1) * 9 + (j >> 1)) * 16;
-        const f32x4 da = *(const f32x4*)(r + off_a + cj);
-        const f32x4 db = *(const f32x4*)(r + off_b + cj);
-        T[j] = da + db * sg;
-      }
-      char* v = Vb + vbuf * k16V + v_off + vi * 4 * 1024;
-      *(f32x4*)(v + 0 * 1024) = pk_sub(T[0], T[2]);
-      *(f32x4*)(v + 1 * 1024) = T[1] + T[2];
-      *(f32x4*)(v + 2 * 1024) = pk_sub(T[2], T[1]);
-      *(f32x4*)(v + 3 * 1024) = pk_sub(T[1], T[3]);
-    };
+    const SixRowProducer pr(p_src, b, r0, pw, lane, Rb, Vb);
     // DMA order per wave: raw_0 (2) | raw_1 (2) | then per iteration c: raw_{c+2} (2); counted waits leave the younger ones in flight
     if (pw == 0) pstamp(hk, 0, lane);
     if (!hk.first) {
@@ -1618,23 +1595,23 @@ __device__ __forceinline__ void wino_strip_layer(const float* __restrict__ p_src
       wait_done16(hk, rq > 0 ? (rq - 1) * 4 : 0, rq < 3 ? (rq + 2) * 4 : 16);
     }
     if (pw == 0) pstamp(hk, 1, lane);
-    issue_raw(0, 0);
-    issue_raw(1, 1);
+    pr.issue_raw(0, 0);
+    pr.issue_raw(1, 1);
     wait_vmcnt<2>();                   // raw_0 landed (raw_1 still in flight)
     if (pw == 0) pstamp(hk, 2, lane);
-    transform(0, 0);
+    pr.transform(0, 0);
     if (pw == 0) pstamp(hk, 3, lane);
 #pragma unroll
     for (int c = 0; c < nchunk; ++c) {
       __builtin_amdgcn_s_barrier();  // [c] V_c ready for the consumers; they are done with chunk c-1
       if (c + 1 < nchunk) {
         if (c + 2 < nchunk) {
-          issue_raw(c + 2, c & 1);   // raw buffer consumed by this wave's transform of chunk c
+          pr.issue_raw(c + 2, c & 1);   // raw buffer consumed by this wave's transform of chunk c
           wait_vmcnt<2>();           // raw_{c+1} landed (raw_{c+2} still in flight)
         } else {
           wait_vmcnt<0>();           // raw_{c+1}, the last one
         }
-        transform((c + 1) & 1, (c + 1) & 1);  // V buffer last read by the MFMAs of chunk c-1
+        pr.transform((c + 1) & 1, (c + 1) & 1);  // V buffer last read by the MFMAs of chunk c-1
       }
     }
     return;
@@ -1648,8 +1625,6 @@ __device__ __forceinline__ void wino_strip_layer(const float* __restrict__ p_src
   // this lane's 16 bytes of a position's 2 KiB block [quad 4][co 32][4 ci] of co tile wave >> 1
   const int u_off = (wave >> 1) * (nchunk * kWU) + kq * 512 + ((wave & 1) * 16 + i16) * 16;
   const int v_off = kq * 256 + i16 * 16;
-  // U ring as in wino_layer: slot g % kUAhead holds position g of the layer (g = 16 c + xi)
-  constexpr int kG = 16 * nchunk;
   const __amdgpu_buffer_rsrc_t ru = make_rsrc(p_u, 2u * nchunk * kWU);
   f32x4 uw[kUAhead];
 #pragma unroll
@@ -1664,56 +1639,15 @@ __device__ __forceinline__ void wino_strip_layer(const float* __restrict__ p_src
   for (int c = 0; c < nchunk; ++c) {
     __builtin_amdgcn_s_barrier();  // [c]
     if (c == 0 && wave == 0) pstamp(hk, 4, lane);
-    const char* v = Vb + (c & 1) * k16V + v_off;
-    // wino_layer's loop: two xi at a time, the next pair's V fragments and the U fragments kUAhead positions on under this pair's MFMAs
-    f32x4 x0 = *(const f32x4*)(v), x1 = *(const f32x4*)(v + 1024);
-    f32x4 x0n, x1n;
-#pragma unroll
-    for (int x = 0; x < 16; x += 2) {
-      const int g = c * 16 + x, s0 = g % kUAhead, s1 = (g + 1) % kUAhead;
-      const f32x4 w0 = uw[s0], w1 = uw[s1];
-      if (x + 2 < 16) {
-        x0n = *(const f32x4*)(v + (x + 2) * 1024);
-        x1n = *(const f32x4*)(v + (x + 3) * 1024);
-      }
-      if (g + kUAhead < kG) {
-        uw[s0] = load_u(ru, u_off, (g + kUAhead) * 2048);
-        uw[s1] = load_u(ru, u_off, (g + kUAhead + 1) * 2048);
-      }
-      acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, x0.x, acc[x], 0, 0, 0);
-      acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, x1.x, acc[x + 1], 0, 0, 0);
-      acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, x0.y, acc[x], 0, 0, 0);
-      acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, x1.y, acc[x + 1], 0, 0, 0);
-      acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, x0.z, acc[x], 0, 0, 0);
-      acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, x1.z, acc[x + 1], 0, 0, 0);
-      acc[x] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, x0.w, acc[x], 0, 0, 0);
-      acc[x + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, x1.w, acc[x + 1], 0, 0, 0);
-      x0 = x0n; x1 = x1n;
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 7, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    chunk_mma<1024, nchunk>(Vb + (c & 1) * k16V + v_off, c, ru, u_off, uw, acc, false);
   }
   if (wave == 0) pstamp(hk, 5, lane);
 
-  // ---- output transform in registers (wino_layer's expressions): lane (tile i16, row group kq) holds M_xi[co quad][tile] for all xi
-  f32x4 S[2][4];
-#pragma unroll
-  for (int cI = 0; cI < 4; ++cI) {
-    S[0][cI] = acc[0 * 4 + cI] + acc[1 * 4 + cI] + acc[2 * 4 + cI];
-    S[1][cI] = pk_sub(pk_sub(acc[1 * 4 + cI], acc[2 * 4 + cI]), acc[3 * 4 + cI]);
-  }
   float esum = 0.0f;
+  f32x4 y[4];   // lane (tile i16, row group kq): its 2x2 tile
+  out_transform(acc, bias4, y);
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const f32x4 y0 = S[i][0] + S[i][1] + S[i][2] + bias4;
-    const f32x4 y1 = pk_sub(pk_sub(S[i][1] + bias4, S[i][2]), S[i][3]);
-    const int P = (r0 + 2 * oty + i) * 16 + 2 * otx;
-    ep.emit(a, b, Q, 2 * i, P, y0, esum);
-    ep.emit(a, b, Q, 2 * i + 1, P + 1, y1, esum);
-  }
+  for (int q = 0; q < 4; ++q) ep.emit(a, b, Q, q, (r0 + 2 * oty + (q >> 1)) * 16 + 2 * otx + (q & 1), y[q], esum);
   // this wave's share of the layer is in L2 once its stores are acknowledged; then it counts itself in
   if (wave == 0) pstamp(hk, 6, lane);
   announce(hk, hk.done + hk.word0 + wave, wave == 0);

@@ -6,7 +6,9 @@ fixed_tableau.h, fstack_bf16.hip, btraj_bf16.hip).
 
 Cases: a 64-channel, 3-layer ODEFunc; euler / midpoint / rk4; forward, forward on a decreasing grid (negated dynamics), saving
 forward + backward, odeint_adjoint; the persistent walk on and off; B = 3 (sixteen-workgroup walk) and 20 (four-workgroup walk);
-T = 2 and 4, T = 1 once per path; one forward + backward on an internal grid; bf16: forward of the three methods, rk4 training
+T = 2 and 4, T = 1 once per path; B = 20 at T = 2 with the strip walk switched off (the four-workgroup co-tile walk at one sample
+per group); rk4 forward + backward at T = 2 with a batch two above the number of groups (two groups carry two samples); one
+forward + backward on an internal grid; bf16: forward of the three methods, rk4 training
 through the whole-trajectory launches at T = 4 and at T = 17 (the sweep cut into two segments).  The arithmetic is deterministic,
 so there is no tolerance."""
 import os
@@ -59,6 +61,21 @@ def run(out_path):
     for path in paths:
         seed += 2
         res[f"{path}.rk4.B3.T1"] = _case(dev, path, "rk4", 3, 1, seed)
+    # the four-group co-tile walk at one sample per group (the strip walk takes these batches unless it is switched off) ...
+    was = lib.odehip_set_strip_walk(0)
+    try:
+        n0 = lib.odehip_strip_walk_launches()
+        for method in ("euler", "rk4"):
+            for path in paths:
+                seed += 2
+                res[f"{path}.{method}.B20.T2.strip_off"] = _case(dev, path, method, 20, 2, seed)
+        assert lib.odehip_strip_walk_launches() == n0, "the strip walk ran although it was switched off"
+    finally:
+        lib.odehip_set_strip_walk(was)
+    # ... and with two samples in a group: a batch just above the number of groups (a group is four workgroups, the grid a
+    # multiple of 32 workgroups), so two groups carry two samples
+    n_groups = torch.cuda.get_device_properties(dev).multi_processor_count // 32 * 8
+    res[f"train.rk4.B{n_groups + 2}.T2.two_samples_per_group"] = _case(dev, "train", "rk4", n_groups + 2, 2, 890)
     res["train.rk4.B3.T3.internal_grid"] = _case(dev, "train", "rk4", 3, 3, 900,
                                                  options={"grid_constructor": ode_rl_amd.step_size_grid(0.07)})
     ode_rl_amd.set_compute_dtype("bf16")

@@ -30,6 +30,9 @@ SED[adapt_ew_coef]='s/    const float c1 = (m.c_dev ? ((ConstF\*)m.c_dev)\[j\] :
 SED[walk16_ew_coef]='s/      s1 = fma4(kv, (m.c_dev ? ((ConstF\*)m.c_dev)\[j\] : m.c1\[j\]) \* hs, s1);/      s1 = fma4(kv, (m.c_dev ? ((ConstF*)m.c_dev)[j] : m.c1[j]) * hs * 1.01f, s1);/'   # ... and their sixteen-workgroup copy (ew_row16)
 SED[dopri5_dense_weight]='s/^ODEHIP_HD inline double dense_weight(int s, double x, double b, double m, int last) {$/ODEHIP_HD inline double dense_weight(int s, double x, double b, double m, int last) { x *= 0.97;/'   # dopri5_control.h: dense-output weights evaluated at the wrong point (one function behind the device controller, the host-driven adjoint and the backward sweep)
 SED[walk16_out_transform]='s/      val = pk_sub(pk_sub(\*(const f32x4\*)(x + 1024) + bias4, \*(const f32x4\*)(x + 2048)), \*(const f32x4\*)(x + 3072));/      val = pk_sub(pk_sub(*(const f32x4*)(x + 1024) + bias4, *(const f32x4*)(x + 3072)), *(const f32x4*)(x + 2048)) * 1.001f;/'   # 16-workgroup walk: second half of the output transform
+# ---- the pieces the walks of conv_wino.hip share: each must turn red a test of EVERY walk that uses it (profiles/mutation_walk_epilogue.txt)
+SED[shared_out_transform]='s/    y\[2 \* i + 1\] = pk_sub(pk_sub(S\[i\]\[1\] + bias4, S\[i\]\[2\]), S\[i\]\[3\]);/    y[2 * i + 1] = pk_sub(pk_sub(S[i][1] + bias4, S[i][3]), S[i][2]) * 1.001f;/'   # out_transform (per-launch kernel, co-tile walks, strip walk): odd output columns; blind to the bit-identity tests (all go wrong alike), caught against the oracle: test_hip_odeint.py::test_full_size_against_oracle[rk4] (strip walk, B = 64) and [dopri5] (adaptive co-tile walk)
+SED[six_row_transform]='s/    \*(f32x4\*)(v + 1 \* 1024) = T\[1\] + T\[2\];/    *(f32x4*)(v + 1 * 1024) = T[1] - T[2];/'   # SixRowProducer (sixteen-workgroup walk, strip walk): V column 1; tests/test_hip_strip_walk.py and a B <= 16 case of test_persistent_trajectory_is_bit_identical_to_per_layer_launches
 SED[saving_slot_offset]='s/  fa.off_y1 = (long long)((tb->stages - 1) \* BL.st);/  fa.off_y1 = (long long)((tb->stages - 2) * BL.st);/'                # saving forward: y1 read from the wrong stage input of the slot
 SED[wgrad_wino5_bt]='s/  out\[0\] = w5_fma2(4.0f, in\[0\], w5_fma2(-5.0f, in\[2\], in\[4\]));/  out[0] = w5_fma2(4.0f, in[0], w5_fma2(-4.0f, in[2], in[4]));/'   # Winograd F(2x2,5x5) weight gradient: B^T row 0
 SED[codec_bwd_dec_tap]='s/          const int pa = (ky \& 1) ^ 1, ta = ky >> 1, pb = (kx \& 1) ^ 1, tb = kx >> 1;/          const int pa = (ky \& 1) ^ 1, ta = ky >> 1, pb = (kx \& 1), tb = kx >> 1;/'   # decoder backward: column parity of the second layer'"'"'s weights
@@ -52,9 +55,9 @@ SED[bf16_mask_launders_nan]='s/          v.x = m.x <= 0.f ? 0.f : v.x; v.y = m.y
 SED[btraj_mask_drops_negative_nan]='s/__device__ __forceinline__ bool bf16_relu_pass(unsigned f32_bits) { return !(__uint_as_float(f32_bits) <= 0.0f); }/__device__ __forceinline__ bool bf16_relu_pass(unsigned f32_bits) { return (int)f32_bits > 0; }/'   # bf16 reverse sweep: the old sign-bit test, a NaN with its sign bit set -> 0
 # ---- evaluation metrics (frame_metrics.hip): the window, the interior, the constants, the covariance
 SED[ssim_sigma]='s/  const double sigma = 1.5;/  const double sigma = 1.4;/'                                   # Gaussian taps of sigma 1.4
-SED[ssim_interior_shift]='s/^constexpr int kFirstRow = kWinRadius; /constexpr int kFirstRow = kWinRadius + 1; /'   # S averaged over rows 6..59 (row 64 = the words behind each plane in LDS: still inside the allocation)
-SED[ssim_c2]='s/  const double k1 = 0.01, k2 = 0.03, range = (double)data_range;/  const double k1 = 0.01, k2 = 0.02, range = (double)data_range;/'   # C2 = (0.02 R)^2
-SED[ssim_covariance]='s/        const float vxy = uxy - ux \* uy;/        const float vxy = uxy - ux * ux;/'       # vxy = uxy - ux ux
+SED[ssim_interior_shift]='s/^constexpr int kSsimCrop = kSsimRadius; /constexpr int kSsimCrop = kSsimRadius + 1; /'   # ssim_window.h (frame_metrics.hip and png_metrics.hip share it): S averaged from row and column 6 on
+SED[ssim_c2]='s/ssim_constant<float>(0.01, range), ssim_constant<float>(0.03, range), sse, ssim);/ssim_constant<float>(0.01, range), ssim_constant<float>(0.02, range), sse, ssim);/'   # C2 = (0.02 R)^2
+SED[ssim_covariance]='s/  const T vxy = uxy - ux \* uy;/  const T vxy = uxy - ux * ux;/'       # vxy = uxy - ux ux
 # ---- ConvGRU sequences (convgru_sequence.hip; the step itself is cell_forward_step in convgru.hip): the weight halves, the zero state, the batched weight gradient, the h_seq slots
 SED[seq_state_half_from_frame_half]='s/  const int j_gates = x \&\& h ? -1 : (x ? 0 : 1);/  const int j_gates = x \&\& h ? -1 : (x ? 0 : 0);/'   # zero input: the gates conv runs over the FRAME half of its weights
 SED[seq_first_step_reads_h0]='s/    const bool has_h = h0 || t > 0;/    const bool has_h = true;/'   # zero state: the first step reads the (unwritten) state slot
@@ -81,7 +84,6 @@ SED[plain_gates_swapped]='s/  const bool is_reset = q < hq;/  const bool is_rese
 SED[plain_bwd_drops_bypass]='s/  if (blend) d += (1.0f - m) \* g;  \/\/ the part of the blend that bypasses the cell/  (void)blend;/'   # fractional mask: the (1-m) g term of the state gradient dropped
 # ---- upstream Vid-ODE's evaluation protocol (png_metrics.hip; tests/test_hip_png_metrics.py)
 SED[png_luma_no_rounding]='s/  return (19595u \* r + 38470u \* g + 7471u \* b + 0x8000u) >> 16;/  return (19595u * r + 38470u * g + 7471u * b) >> 16;/'   # PIL'"'"'s luma truncated instead of rounded
-SED[png_crop_from_row_4]='s/^constexpr int kPngCropRow = kPngRadius; /constexpr int kPngCropRow = kPngRadius - 1; /'   # S averaged over rows 4 .. S-7 (row -1 of the first plane = the reduction scratch in front of it: still inside the allocation)
 # ---- the solver arithmetic in epilogue() (conv_common.h; tests/test_hip_solver_stacks.py): every pattern matches the copy behind the
 # 32x32-accumulator kernels only, not emit_quad()'s; each stays inside the buffers of the layer it is given
 SED[epilogue_drops_k_scale]='s/    kc = act_fwd(kc, a.act) \* m.k_scale;   \/\/ (a Tanh head before the sign)/    kc = act_fwd(kc, a.act);/'   # stage combine: the sign of a decreasing t is lost
