@@ -426,9 +426,15 @@ int odehip_odeconvgru_encode_backward_steps(const odehip_encoder* e, const odehi
  * over the ranks on `stream` (RCCL) and return 0; element counts are multiplied by world_size.  All ranks then take the same
  * accept/reject decisions as one device holding the whole batch (up to summation order).  One collective per attempted step
  * (plus two for the initial step): latency-bound, and the host no longer runs one attempt ahead.  cb = NULL restores
- * per-shard control. */
+ * per-shard control.
+ * odehip_set_norm_allreduce_counted installs the same hook under a wider contract (a pure addition; the call above keeps its own):
+ * every adaptive method code runs under it (ODEHIP_BOSH3 too: what is summed -- d0 and d1, d2, one error norm per attempt -- does not
+ * depend on the stage count), and the element count the norms divide by is summed through the callback as well, ONE more call with
+ * n = 1 at the start of every solve, so the shards need not be equal (world_size is not multiplied in).  Under either hook nothing is
+ * saved by a saving forward (the backward pass re-integrates the logged steps) and the asynchronous start is refused. */
 typedef int (*odehip_allreduce_fn)(float* scratch_dev, int n, void* stream, void* user);
 int odehip_set_norm_allreduce(odehip_allreduce_fn cb, void* user, int world_size, float* scratch_dev);
+int odehip_set_norm_allreduce_counted(odehip_allreduce_fn cb, void* user, int world_size, float* scratch_dev);
 
 size_t odehip_dopri5_workspace_bytes(const odehip_convstack* f, int batch, int n_times);
 
@@ -500,9 +506,12 @@ int odehip_odeint_dopri5_collect(int token, int* stats_host, double* accepted_ho
  * with ODEHIP_DOPRI5.  Both methods run the same drivers from their tableau (csrc/dopri5_control.h): the persistent adaptive walk,
  * the device-side controller and the pinned mailbox, the saving slots (method's stage count per slot) and the reverse sweep.  A
  * workspace is laid out for its method: size it, fill it and read it with one and the same code.  Any other method code:
- * ODEHIP_EINVAL (the size functions return 0).  ODEHIP_BOSH3 under exact-global step control (odehip_set_norm_allreduce) is
- * refused with ODEHIP_EINVAL.  The adjoint pair below takes the method code too: ODEHIP_BOSH3 runs the host-driven backward solve
- * under both norms (the device-steered seminorm path reads the call's tableau as well, but is enabled for dopri5 only).  Arguments are checked before any HIP call.  Pure additions: ODEHIP_ABI_VERSION stays. */
+ * ODEHIP_EINVAL (the size functions return 0).  ODEHIP_BOSH3 under exact-global step control is refused with ODEHIP_EINVAL when the
+ * hook was installed with odehip_set_norm_allreduce, and runs when it was installed with odehip_set_norm_allreduce_counted.  The adjoint pair below takes the method code too: under the seminorm both methods take the device-steered backward solve where it
+ * is available (64-channel fp32 stack, 2 <= n_times <= 256, the adaptive persistent walk, ODEHIP_ADJOINT_DEVICE not 0), else the
+ * host-driven one, which also serves the mixed norm.  odehip_last_adjoint_controller(): which of the two steered the last
+ * odehip_odeint_adjoint_adaptive_backward call of this process (1 device, 0 host, -1 none yet).  Arguments are checked before any HIP
+ * call.  Pure additions: ODEHIP_ABI_VERSION stays. */
 size_t odehip_adaptive_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int method);
 size_t odehip_adaptive_saving_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int max_accept, int method);
 size_t odehip_adaptive_backward_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int n_steps, int method);
@@ -522,6 +531,7 @@ int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_convstack* 
                                             const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w, float* const* grad_b,
                                             int max_accept, int mixed_norm, int* stats_host, void* workspace, size_t workspace_bytes,
                                             void* stream);
+int odehip_last_adjoint_controller(void);
 int odehip_odeint_adaptive_collect(int token, int* stats_host, double* accepted_host, int accepted_cap, int* saved_out);
 int odehip_odeint_adaptive_backward(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host,
                                     int n_times, int batch, const double* accepted_host, int n_steps, const float* z0_nchw,

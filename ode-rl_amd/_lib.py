@@ -230,6 +230,7 @@ SIGNATURES = {
                                              ctypes.c_int, ctypes.c_void_p]),
     "odehip_set_debug_flags": (None, [ctypes.c_int]),
     "odehip_set_norm_allreduce": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "odehip_set_norm_allreduce_counted": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "odehip_set_debug_buffer": (None, [ctypes.c_void_p]),
     "odehip_packed_weight_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "odehip_pack_conv_weight": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
@@ -376,6 +377,7 @@ def _with_method():
     S["odehip_odeint_adaptive_collect"] = S["odehip_odeint_dopri5_collect"]
     res, args = S["odehip_odeint_adjoint_dopri5_backward"]
     S["odehip_odeint_adjoint_adaptive_backward"] = (res, [ctypes.c_int] + list(args))
+    S["odehip_last_adjoint_controller"] = (ctypes.c_int, [])
     res, args = S["odehip_adjoint_dopri5_workspace_bytes"]
     S["odehip_adjoint_adaptive_workspace_bytes"] = (res, list(args) + [ctypes.c_int])
     for head in ("", "_saving", "_backward"):

@@ -1,12 +1,14 @@
 // adjoint_device.hip -- the adaptive adjoint of adjoint_dopri5.hip with the step control ON THE DEVICE and every evaluation on the
-// adaptive persistent walk (BASELINE.json configs[2]; torchdiffeq `odeint_adjoint(..., method="dopri5",
-// adjoint_options={"norm": "seminorm"})`, _impl/adjoint.py).  It reads the Tableau of the call (S stages; dopri5_control.h); the
-// caller's gate admits dopri5 only so far.  Same arithmetic and the same decisions as the host loop there:
+// adaptive persistent walk (BASELINE.json configs[2]; torchdiffeq `odeint_adjoint(..., method="dopri5" | "bosh3",
+// adjoint_options={"norm": "seminorm"})`, _impl/adjoint.py).  It reads the Tableau of the call (S stages, order, c_sol, c_mid, beta;
+// dopri5_control.h) and serves both adaptive methods; the comments count in dopri5's numbers.  Same arithmetic and the same decisions
+// as the host loop there:
 // per interval t[n+1] -> t[n] a fresh solve of the augmented state (y, a) on the flipped time axis -- k1, the initial-step search
 // (_select_initial_step: d0, d1 -> h0; Euler point; d2 -> dt), attempted steps with the error ratio max(rms_y, rms_a), accept /
 // reject and step-size update of _adaptive_step / _optimal_step_size, dense output at t[n] -- but the host never reads a verdict:
 //
-//   * ONE table (cached by content: it is the same for every call on a workspace) holds four row programs -- P3: dense output of an
+//   * ONE table (cached by CONTENT, persist.hip: the same for every call of a method on a workspace; two methods' tables differ in
+//     their rows, so they never share an entry) holds four row programs -- P3: dense output of an
 //     interval's last step (+ grad_out[n]); P0: k1 of a fresh interval; P1: the Euler point of the initial-step search; P2: an attempted
 //     step (two elementwise rows for the stage-2 inputs + S - 1 augmented evaluations; dopri5: six, 62 rows) -- written with
 //     RELOCATABLE pointers (class << 56 | offset, conv_wino.hip rel()) wherever a buffer depends on a decision: the slot an accepted step keeps for the
@@ -17,7 +19,7 @@
 //     (the scaled sums of squares of the initial-step search are NORM ROWS at the end of P0 / P1: per-wave partials, no launch);
 //   * the host only bounds its run-ahead by polling a pinned mailbox (one tick ahead) and, after `done`, launches the weight
 //     gradients (one launch per layer over every recorded stage evaluation, as before) with the entry count it reads there.
-// A training step at B=64, T=10 is 27 ticks instead of ~720 per-layer launches and 27 stream synchronisations.
+// A dopri5 training step at B=64, T=10 is 27 ticks instead of ~720 per-layer launches and 27 stream synchronisations.
 #include <math.h>
 #include <string.h>
 

@@ -15,9 +15,10 @@
 // every accepted step contributes  sum_s w_s * wgrad(GP_s, A_s)  with w_s = dt*b_s (or dt*W_s(x) for the interpolated
 // last step of an interval), and ONE wgrad launch per layer sums all of them at the end (wgrad.hip).
 //
-// Step control is host-driven (one stream synchronisation per attempted step, as torchdiffeq itself does): an attempt
+// Step control in this file is host-driven (one stream synchronisation per attempted step, as torchdiffeq itself does): an attempt
 // is ~1 ms of GPU work, the sync costs ~30 us.  Accepted steps keep their slot (0.28 GB each at B=64); `max_accept`
-// bounds the workspace.
+// bounds the workspace.  The seminorm on a 64-channel fp32 stack is handed to the device-steered path (adjoint_device.hip) first, for
+// either adaptive method; odehip_last_adjoint_controller() says which of the two took the last call.
 #include <math.h>
 #include <string.h>
 
@@ -79,6 +80,7 @@ __global__ __launch_bounds__(256) void theta_add_kernel(float* __restrict__ a, c
 }
 
 static float* g_adj_host = nullptr;  // 256 B of pinned host memory for the per-attempt scalars
+static int g_adj_controller = -1;    // who steered the last adaptive adjoint that got as far as its backward solves: 1 device, 0 host
 
 }  // namespace odehip
 
@@ -103,8 +105,10 @@ extern "C" int odehip_odeint_adjoint_dopri5_backward(const odehip_convstack* f, 
                                                  workspace_bytes, stream_);
 }
 
+extern "C" int odehip_last_adjoint_controller(void) { return g_adj_controller; }
+
 // The host-driven loop below reads the tableau of the call's method (S stages; the comments count in dopri5's 7), and so does the
-// device-steered seminorm path (adjoint_device.hip), which is enabled for dopri5 only: other methods run this loop under both norms.
+// device-steered seminorm path (adjoint_device.hip), which takes the seminorm calls of both methods where it is available.
 extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad,
                                                        const double* t_host, int n_times, int batch, float rtol, float atol,
                                                        const float* y_traj_nchw, const float* grad_out_nchw, float* grad_z0_nchw,
@@ -149,15 +153,19 @@ extern "C" int odehip_odeint_adjoint_adaptive_backward(int method, const odehip_
   auto yq = [&](int n) { return L.p(ws, L.off_y + (size_t)n * L.g.st); };
   auto goq = [&](int n) { return L.p(ws, L.off_go + (size_t)n * L.g.st); };
 
-  if (!mixed_norm && n_times > 1 && method == ODEHIP_DOPRI5) {
+  if (!mixed_norm && n_times > 1) {
     // seminorm on a 64-channel fp32 stack: step control on the device, evaluations on the adaptive persistent walk
     // (adjoint_device.hip); `ran` = 0 when that path is not available here -- the host loop below then takes the call.  The path reads
-    // the tableau; the gate is dopri5 because no other method has been run or measured on it yet (parity tests first).
+    // the call's tableau, so dopri5 and bosh3 take it under the same conditions.
     int ran = 0;
     rc = adjoint_adaptive_device(tb, f, f_dgrad, t_host, n_times, batch, rtol, atol, y_traj_nchw, grad_out_nchw, grad_z0_nchw, grad_w, grad_b,
                                max_accept, stats_host, workspace, workspace_bytes, stream, &ran);
-    if (rc != ODEHIP_OK || ran) return rc;
+    if (rc != ODEHIP_OK || ran) {   // (an error in there is the device path's too: it only returns ran = 0 with ODEHIP_OK)
+      g_adj_controller = 1;
+      return rc;
+    }
   }
+  g_adj_controller = 0;
   rc = odehip_nchw_to_q4(y_traj_nchw, yq(0), n_times * batch, L.C, stream);
   if (rc != ODEHIP_OK) return rc;
   rc = odehip_nchw_to_q4(grad_out_nchw, goq(0), n_times * batch, L.C, stream);

@@ -341,9 +341,12 @@ __global__ void arm_first_step_kernel(DopriState* st, const double* t_out, doubl
   st->j_next = 1;
   st->done = st->n_times <= 1;
 }
+// n_elems_global: null, or (exact-global step control) the all-reduced element count of the whole batch as a float -- a multiple of
+// 256 * channels, so exact far beyond any batch
+__global__ void set_float_kernel(float* p, float v) { *p = v; }
 __global__ void init_state_kernel(DopriState* st, float rtol, float atol, int n_times, int n_partials, long long n_elems,
-                                  int max_steps, int save_max, unsigned long long slot_base, unsigned long long slot_bytes,
-                                  unsigned long long* reloc, int order, int n_stages) {
+                                  const float* n_elems_global, int max_steps, int save_max, unsigned long long slot_base,
+                                  unsigned long long slot_bytes, unsigned long long* reloc, int order, int n_stages) {
   DopriState z;
   memset(&z, 0, sizeof(z));
   z.save_max = save_max;
@@ -356,7 +359,7 @@ __global__ void init_state_kernel(DopriState* st, float rtol, float atol, int n_
   z.atol = atol;
   z.n_times = n_times;
   z.n_partials = n_partials;
-  z.n_elems = n_elems;
+  z.n_elems = n_elems_global ? (long long)*n_elems_global : n_elems;
   z.max_steps = max_steps;
   z.order = order;
   z.n_stages = n_stages;
@@ -411,12 +414,17 @@ static int d5_mailbox(int slot, Mailbox** out) {
   return ODEHIP_OK;
 }
 
-// exact-global step control under batch sharding: every sum of squares is summed over the ranks before it is used
+// exact-global step control under batch sharding: every sum of squares is summed over the ranks before it is used.  What is summed
+// does not depend on the tableau: d0, d1 and d2 of the initial-step search and ONE error norm per attempt, whatever the stage count
 static odehip_allreduce_fn g_reduce_cb = nullptr;
 static void* g_reduce_user = nullptr;
 static int g_reduce_world = 1;
+// Two contracts, one per installing call.  odehip_set_norm_allreduce (0): dopri5 only, the element count is this rank's times the world
+// size (equal shards) -- what its callers have always been handed.  odehip_set_norm_allreduce_counted (1): every adaptive method, and
+// the element count is summed through the callback once per solve, in front of the norms (shards may be uneven).
+static int g_reduce_counted = 0;
 static float* g_reduce_buf = nullptr;
-static int d5_reduce_sums(hipStream_t stream, int count, const float* const* arrays, const int* lens, const int* skip_flag) {
+static int d5_reduce_sums(const char* mname, hipStream_t stream, int count, const float* const* arrays, const int* lens, const int* skip_flag) {
   SumSet ss;
   memset(&ss, 0, sizeof(ss));
   ss.count = count;
@@ -427,7 +435,7 @@ static int d5_reduce_sums(hipStream_t stream, int count, const float* const* arr
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, stream, ss, g_reduce_buf, skip_flag);
   ODEHIP_CHECK_HIP(hipGetLastError());
   const int rcb = g_reduce_cb(g_reduce_buf, count, (void*)stream, g_reduce_user);
-  ODEHIP_REQUIRE(rcb == 0, "odeint_dopri5: the all-reduce callback failed (%d)", rcb);   // (bosh3 is refused under exact-global step control)
+  ODEHIP_REQUIRE(rcb == 0, "odeint_%s: the all-reduce callback failed (%d)", mname, rcb);
   return ODEHIP_OK;
 }
 
@@ -471,7 +479,7 @@ static int d5_attempt(D5Ctx& x) {
   if (x.global_norm) {
     const float* arr[1] = {x.part0};
     const int lens[1] = {x.n_conv_partials};
-    if ((rc = d5_reduce_sums(x.stream, 1, arr, lens, nullptr)) != ODEHIP_OK) return rc;
+    if ((rc = d5_reduce_sums(mname, x.stream, 1, arr, lens, nullptr)) != ODEHIP_OK) return rc;
   }
   hipLaunchKernelGGL(controller_kernel, dim3(1), dim3(256), 0, x.stream, x.state, x.global_norm ? g_reduce_buf : x.part0, x.t_dev, x.mb, x.psync,
                      (int)(persist_sync_bytes(x.batch) / 4));
@@ -549,6 +557,7 @@ extern "C" int odehip_set_norm_allreduce(odehip_allreduce_fn cb, void* user, int
     g_reduce_user = nullptr;
     g_reduce_world = 1;
     g_reduce_buf = nullptr;
+    g_reduce_counted = 0;
     return ODEHIP_OK;
   }
   ODEHIP_REQUIRE(world_size >= 1 && scratch_dev, "set_norm_allreduce: world_size must be >= 1 and scratch_dev non-null");
@@ -556,7 +565,14 @@ extern "C" int odehip_set_norm_allreduce(odehip_allreduce_fn cb, void* user, int
   g_reduce_user = user;
   g_reduce_world = world_size;
   g_reduce_buf = scratch_dev;
+  g_reduce_counted = 0;
   return ODEHIP_OK;
+}
+
+extern "C" int odehip_set_norm_allreduce_counted(odehip_allreduce_fn cb, void* user, int world_size, float* scratch_dev) {
+  const int rc = odehip_set_norm_allreduce(cb, user, world_size, scratch_dev);
+  g_reduce_counted = rc == ODEHIP_OK && cb != nullptr;
+  return rc;
 }
 
 // Workspace: [state | t_out[T] | partials x3 | ping | pong | xs | y | y1 | k1..k7]
@@ -632,7 +648,7 @@ static int dopri5_forward(int method, const odehip_convstack* f, const float* z0
   const Tableau* tb = adaptive_tableau(method);
   ODEHIP_REQUIRE(tb, "odeint_adaptive: unknown adaptive method code %d (ODEHIP_DOPRI5 or ODEHIP_BOSH3)", method);
   const char* const mname = tb->name;
-  ODEHIP_REQUIRE(method == ODEHIP_DOPRI5 || !g_reduce_cb, "odeint_adaptive: exact-global step control (odehip_set_norm_allreduce) is not implemented for bosh3");
+  ODEHIP_REQUIRE(method == ODEHIP_DOPRI5 || !g_reduce_cb || g_reduce_counted, "odeint_adaptive: exact-global step control (odehip_set_norm_allreduce) is not implemented for bosh3");
   int rc = check_stack(f);
   if (rc != ODEHIP_OK) return rc;
   ODEHIP_REQUIRE(z0_nchw && t_host && out_nchw && workspace, "odeint_%s: null pointer", mname);
@@ -704,10 +720,20 @@ static int dopri5_forward(int method, const odehip_convstack* f, const float* z0
   // exact-global mode: the kernels below read ONE already all-reduced scalar instead of the local partial arrays
   const bool global_norm = g_reduce_cb != nullptr;
   auto reduce_sums = [&](int count, const float* const* arrays, const int* lens, const int* skip_flag) -> int {
-    return d5_reduce_sums(stream, count, arrays, lens, skip_flag);
+    return d5_reduce_sums(mname, stream, count, arrays, lens, skip_flag);
   };
+  const bool count_global = global_norm && g_reduce_counted;
+  if (count_global) {
+    // the RMS norms divide by the element count of the WHOLE batch: summed over the ranks like every sum of squares (the shards
+    // need not be equal, so world_size x this rank's count would not do)
+    hipLaunchKernelGGL(set_float_kernel, dim3(1), dim3(1), 0, stream, g_reduce_buf, (float)st_f);
+    ODEHIP_CHECK_HIP(hipGetLastError());
+    const int rcb = g_reduce_cb(g_reduce_buf, 1, (void*)stream, g_reduce_user);
+    ODEHIP_REQUIRE(rcb == 0, "odeint_%s: the all-reduce callback failed (%d)", mname, rcb);
+  }
   hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(1), 0, stream, state, rtol, atol, n_times,
-                     global_norm ? 1 : n_conv_partials, (long long)st_f * (global_norm ? g_reduce_world : 1), max_steps,
+                     global_norm ? 1 : n_conv_partials, (long long)st_f * (global_norm ? g_reduce_world : 1),
+                     count_global ? g_reduce_buf : (const float*)nullptr, max_steps,
                      saving ? save_max_accept : 0, (unsigned long long)(uintptr_t)(bws + BL.off_slots), (unsigned long long)BL.slot_bytes,
                      saving ? reloc : (unsigned long long*)nullptr, tb->order, tb->stages);
   for (int o = 0; o < n_times; o += 32) {

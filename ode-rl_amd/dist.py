@@ -102,14 +102,16 @@ _global_ctl = None   # (callback object, scratch tensor, group): kept alive whil
 
 
 def enable_global_step_control(device, group=None):
-    """dopri5 under batch sharding with torchdiffeq's semantics: ONE error norm over the whole (global) batch.
+    """The adaptive solvers (dopri5, bosh3) under batch sharding with torchdiffeq's semantics: ONE error norm over the whole (global) batch.
 
-    Installs an all-reduce hook in the HIP library (include/odecgru_hip.h: odehip_set_norm_allreduce): every sum of squares
+    Installs an all-reduce hook in the HIP library (include/odecgru_hip.h: odehip_set_norm_allreduce_counted): every sum of squares
     the step controller uses is summed over the ranks of `group` first (a 4..8-byte RCCL all-reduce per attempted step), so
     all ranks take the accept/reject decisions a single device holding the full batch would take.  Every rank must call
-    odeint the same number of times with the same t.  Without it each rank adapts on its own shard (agrees to O(rtol)).
-    dopri5 only: while the hook is installed, odeint(method="bosh3") raises ValueError ("exact-global step control ... is not
-    implemented for bosh3") -- it is refused, not run per shard."""
+    odeint the same number of times with the same t; the shards may be uneven (the element count the norms divide by is summed
+    over the ranks too, once per solve).  Without the hook each rank adapts on its own shard (agrees to O(rtol)).
+    The sums are the same for both methods -- d0, d1, d2 of the initial-step search and one error norm per attempted step -- so
+    odeint(method="bosh3") and its backward pass run under the hook as dopri5's do: nothing is saved by the forward (the backward
+    re-integrates the logged steps), and the asynchronous solve is not available while the hook is installed."""
     global _global_ctl
     import ctypes
     from . import _lib
@@ -125,7 +127,7 @@ def enable_global_step_control(device, group=None):
             traceback.print_exc()
             return 1
     cb = _lib.ALLREDUCE_FN(_cb)
-    _lib.check(_lib.load().odehip_set_norm_allreduce(ctypes.cast(cb, ctypes.c_void_p), None, world, scratch.data_ptr()))
+    _lib.check(_lib.load().odehip_set_norm_allreduce_counted(ctypes.cast(cb, ctypes.c_void_p), None, world, scratch.data_ptr()))
     _global_ctl = (cb, scratch, group)
 
 

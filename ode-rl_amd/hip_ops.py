@@ -866,7 +866,8 @@ def odeint_adjoint_backward(stack, method, t, y_traj, grad_out):
 
 def odeint_adjoint_dopri5_backward(stack, t, y_traj, grad_out, rtol, atol, max_accept=None, stats=None, mixed_norm=False, method="dopri5"):
     """torchdiffeq odeint_adjoint backward with method="dopri5" or "bosh3" (seminorm, or the default mixed norm): (grad_z0, [grad_w...], [grad_b...]).
-    `stats`, if a dict, receives nfe / n_accept / n_reject of the backward solve."""
+    `stats`, if a dict, receives nfe / n_accept / n_reject of the backward solve and `controller`: "device" when the device-steered
+    seminorm path (csrc/adjoint_device.hip) took the call, "host" when the host-driven loop did."""
     m = _adaptive_code(method)
     collect_pending_solves()   # in particular the forward solve whose trajectory this integrates from (its error surfaces here)
     require_device_tensor(grad_out, "grad_out")
@@ -889,7 +890,8 @@ def odeint_adjoint_dopri5_backward(stack, t, y_traj, grad_out, rtol, atol, max_a
                                                          float(atol), _ptr(y_traj), _ptr(grad_out), _ptr(grads[0]), gw_arr, gb_arr,
                                                          int(max_accept), int(bool(mixed_norm)), st, _ptr(ws), ws.numel(), _stream()))
     if stats is not None:
-        stats.update(nfe=int(st[0]), n_accept=int(st[1]), n_reject=int(st[2]))
+        stats.update(nfe=int(st[0]), n_accept=int(st[1]), n_reject=int(st[2]),
+                     controller="device" if lib.odehip_last_adjoint_controller() == 1 else "host")
     return grads
 
 
