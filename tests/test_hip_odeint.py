@@ -332,7 +332,8 @@ def test_host_time_cache_never_serves_a_recycled_address(cuda):
 def test_persistent_trajectory_is_bit_identical_to_per_layer_launches(cuda, method, batch, n_times):
     """One persistent launch per trajectory (workgroups of a sample hand layers over through L2) against one launch per layer:
     same arithmetic in the same order, so the results must be equal bit for bit -- also for batches that are not a multiple
-    of the 64 resident groups and for several passes per group."""
+    of the 64 resident groups and for two samples per group (70: groups 0 .. 5, 128: every group; a group's second pass needs
+    B > 128: tests/test_hip_interleaved_walks.py)."""
     import ode_rl_amd
     lib = ode_rl_amd._lib.load()
     torch.manual_seed(5)

@@ -102,6 +102,12 @@ SED[bosh3_initial_step_fifth_root]='s|  else h1 = powf(0.01f / fmaxf(d1, d2), 1.
 # ---- the adjoint's slot geometry (adjoint_layout.h), shared by the host loop and the device-steered path: both go wrong alike, so
 # their agreement does not show it; the oracle comparison of tests/test_hip_adjoint_paths.py does -- MUT_TESTS="tests/test_hip_adjoint_paths.py"
 SED[adjoint_gp_stride]='s|cap \* NH \* hid + ((size_t)s \* NG + l) \* hid|cap * NH * hid + ((size_t)s * NH + l) * hid|'   # gradient slots of a stage strided by NH, not NG: the seed of stage s is overwritten by stage s + 1 (lower offsets: inside the slot)
+# ---- two samples per group and the second pass of the fp32 walks (conv_wino.hip: persist_walk<ADAPT> and persist_walk_v, one file):
+# each stays inside the buffers it is given and makes no wait longer (all partners of a group take the same wrong sample)
+# -- MUT_TESTS="tests/test_hip_interleaved_walks.py" (profiles/mutation_interleaved_walks.txt)
+SED[interleave_second_sample_dropped]='s/    const int n_interleaved = b + n_groups < pa.batch ? 2 : 1;/    const int n_interleaved = 1;/'   # samples 64 .. 127 are never written
+SED[interleave_wrong_sample]='s/readfirstlane(b + s \* n_groups)/readfirstlane(b)/'   # sample b is walked twice, b + 64 never
+SED[second_pass_skipped]='s/b < pa.batch; b += 2 \* n_groups)/b < pa.batch; b += 4 * n_groups)/'   # samples >= 128 are never written
 # mutants of the Python binding, "file|sed script": applied to the tree's own file for the run and restored afterwards (run only)
 declare -A PYSED
 PYSED[z0_offset_stuck]='ode-rl_amd/autograd.py|s/gen.set_offset(at + 4)/gen.set_offset(at)/;s/_explicit_seed\[1\] = offset + 1/_explicit_seed[1] = offset/'   # consecutive sample_z0 calls draw the same noise
