@@ -194,6 +194,20 @@ int odehip_odeint_adjoint_backward(const odehip_convstack* f, const odehip_convs
                                    float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, void* workspace,
                                    size_t workspace_bytes, void* stream);
 
+/* The adjoint backward on an internal grid (torchdiffeq hands `options` on to every backward interval, so each interval t[i] ->
+ * t[i-1] is stepped through a grid of its own).  grid_host: the points of all those grids, joined, in INCREASING time, n_grid of
+ * them, grid[0] == t[0], grid[n_grid-1] == t[T-1], every output time among them; out_index[p]: the j with grid[p] == t[j], or -1
+ * for a point inside an interval.  Step p+1 -> p integrates the augmented state with one step of `method`; at an output point y is
+ * reset to the stored y[j] and a_y += grad_out[j], at an interior point the solver's own y and a_y go on.  A grid without interior
+ * points gives odehip_odeint_adjoint_backward's result.  fp32 stacks; n_grid <= 4096 and (n_grid - 1) * stages <= 2048
+ * (ODEHIP_EINVAL before any launch otherwise).  Workspace: odehip_odeint_adjoint_grid_workspace_bytes (it grows with n_grid). */
+size_t odehip_odeint_adjoint_grid_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int n_grid, int method);
+int odehip_odeint_adjoint_backward_on_grid(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method,
+                                           const double* t_host, int n_times, const double* grid_host, int n_grid,
+                                           const int* out_index, int batch, const float* y_traj_nchw, const float* grad_out_nchw,
+                                           float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, void* workspace,
+                                           size_t workspace_bytes, void* stream);
+
 /* Adaptive adjoint backward: torchdiffeq `odeint_adjoint(..., method="dopri5", adjoint_options={"norm": "seminorm"})`
  * (BASELINE.json configs[2]; new capability, the reference never calls the adjoint -- modules/DiffEqSolver.py:9).  Each
  * interval t[i] -> t[i-1] is a fresh dopri5 solve of the augmented system with the error norm max(rms_y, rms_a_y); the

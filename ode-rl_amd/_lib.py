@@ -263,6 +263,15 @@ SIGNATURES = {
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                       ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "odehip_odeint_adjoint_grid_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ConvStack), ctypes.c_int, ctypes.c_int,
+                                                                     ctypes.c_int, ctypes.c_int]),
+    "odehip_odeint_adjoint_backward_on_grid": (ctypes.c_int, [ctypes.POINTER(ConvStack), ctypes.POINTER(ConvStack), ctypes.c_int,
+                                                              ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+                                                              ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+                                                              ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                              ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "odehip_adjoint_dopri5_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ConvStack), ctypes.c_int, ctypes.c_int,
                                                                 ctypes.c_int]),
     "odehip_odeint_adjoint_dopri5_backward": (ctypes.c_int, [ctypes.POINTER(ConvStack), ctypes.POINTER(ConvStack),

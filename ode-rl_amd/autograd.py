@@ -304,6 +304,30 @@ class _AdjointOdeint(torch.autograd.Function):
         return _solver_backward_result(*hip_ops.odeint_adjoint_backward(ctx.stack, ctx.method, ctx.t_host, y_traj, grad_out))
 
 
+class _GriddedAdjointOdeint(torch.autograd.Function):
+    """_AdjointOdeint under options={"grid_constructor": fn}: the forward is odeint's own gridded solve and keeps the trajectory alone;
+    the backward hands the options on to every backward interval (hip_ops.adjoint_backward_grid)."""
+
+    @staticmethod
+    def forward(ctx, y0, t_host, method, stack, func, options, *params):
+        from .odeint import internal_grid
+        ctx.mode = hip_ops.current_compute_dtype()
+        out = hip_ops.odeint_fixed_on_grid(stack, method, y0.detach(), t_host, internal_grid(func, y0, t_host, options))
+        ctx.stack, ctx.method, ctx.t_host, ctx.func, ctx.options = stack, method, t_host, func, options
+        hip_ops.record_versions(ctx, params)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    @_pinned
+    def backward(ctx, grad_out):
+        hip_ops.check_versions(ctx, "a parameter of the ODE dynamics")
+        (y_traj,) = ctx.saved_tensors
+        grads = hip_ops.odeint_adjoint_on_grid_backward(ctx.stack, ctx.method, ctx.t_host, y_traj, grad_out, ctx.func, ctx.options)
+        res = _solver_backward_result(*grads)
+        return res[:4] + (None, None) + res[4:]
+
+
 class _AdjointDopri5(torch.autograd.Function):
     """odeint_adjoint with method="dopri5" / "bosh3": adaptive forward (csrc/dopri5.hip), adaptive augmented backward
     (csrc/adjoint_dopri5.hip) under either norm."""
@@ -343,8 +367,15 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
                    adjoint_method=None, adjoint_options=None, adjoint_params=None):
     """`torchdiffeq.odeint_adjoint(func, y0, t, rtol=, atol=, method=, adjoint_options=)`.
 
-    Fixed-grid methods: one backward step of the same method per interval; the internal grids of `odeint` (grid_constructor) are
-    refused here -- torchdiffeq's adjoint builds a new grid for every backward interval, which this path does not do.  dopri5: adaptive backward solve with
+    Fixed-grid methods: one backward step of the same method per interval, or -- after ode_rl_amd.set_adjoint_grids(True); the options
+    are refused as before without it -- with options={"grid_constructor": fn} (`interp: "linear"` next to it;
+    ode_rl_amd.step_size_grid(h) for a step size), on internal grids as torchdiffeq builds them: the forward is
+    `odeint`'s gridded solve, and every backward interval (t[i], t[i-1]) is an `odeint` call of its own on the flipped pair (-t[i],
+    -t[i-1]), so fn is called once per interval, i = T-1 .. 1, and the sub-steps of a step size are anchored at t[i], not at t[i-1]
+    -- they differ from the forward grid's wherever h does not divide the interval.  Inside an interval the solver carries y itself;
+    at an output time y is reset to the stored trajectory and a_y takes grad_out.  Between forward and backward only the (T,B,C,16,16)
+    trajectory is kept, where autograd through `odeint` keeps every activation of the whole grid; the backward's scratch holds the
+    activations of the backward grid.  Not in bf16 mode (TypeError); `adjoint_options` stay refused.  dopri5: adaptive backward solve with
     torchdiffeq's default mixed norm (every parameter tensor's error ratio steers the steps too) or, with
     `adjoint_options={"norm": "seminorm"}`, with the cheaper seminorm; `max_accept` in adjoint_options bounds the accepted
     backward steps whose activations are kept."""
@@ -356,6 +387,10 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
     if adjoint_method is not None and adjoint_method != method:
         raise NotImplementedError("odeint_adjoint(HIP): adjoint_method must equal method")
     check_options(method, options, "odeint_adjoint")
+    gridded = method in FIXED_GRID and (options or {}).get("grid_constructor") is not None
+    if gridded and hip_ops.current_compute_dtype() == "bf16":
+        raise TypeError("odeint_adjoint(HIP): internal grids (grid_constructor) are not implemented in bf16 compute mode (fp32 only); "
+                        'use set_compute_dtype("f32") or drop the grid')
     if adjoint_params is not None and ({id(p) for p in adjoint_params} != {id(p) for p in func.parameters()}):
         # torchdiffeq integrates a_theta for exactly these tensors; this path always does so for every parameter of `func`
         raise NotImplementedError("odeint_adjoint(HIP): adjoint_params must be omitted or be all of func.parameters()")
@@ -370,6 +405,8 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
         raise NotImplementedError("odeint_adjoint(HIP): decreasing time grids are not supported")
     stack = conv_stack_of(func)
     params = _stack_params(stack)
+    if gridded:
+        return _GriddedAdjointOdeint.apply(y0, th, method, stack, func, options, *params)
     if method in FIXED_GRID:
         return _AdjointOdeint.apply(y0, th, method, stack, *params)
     adjoint_options = dict(adjoint_options or {})

@@ -121,8 +121,10 @@ static int check_common(const odehip_convstack* f, int method, const double* t_h
 }
 
 // dW_l, db_l = sum over evaluations e = (n, s) of scale_e * wgrad(GP[n][s][l], A[n][s][l]); one launch per layer.
-// A[n][s][0] is the stage input: y[n] (forward sweep) or y[n+1] (adjoint, integrating backwards) for s = 0.
-static int wgrad_all_layers(const odehip_convstack* f, const FixedLayout& L, void* ws, int n_times, int batch, bool adjoint,
+// A[n][s][0] is the stage input; for s = 0 that is y[n] (forward sweep), or stage0[n] where the caller says so (adjoint, integrating
+// backwards: the state at the step's right end).
+static int wgrad_all_layers(const odehip_convstack* f, const FixedLayout& L, void* ws, int n_times, int batch,
+                            const float* const* stage0 /* host, T-1 entries or null */,
                             const float* eval_scale /* host, (T-1)*S entries or null = 1 */, float* const* grad_w,
                             float* const* grad_b, hipStream_t stream) {
   const int S = L.S, NL = f->n_convs;
@@ -137,7 +139,7 @@ static int wgrad_all_layers(const odehip_convstack* f, const FixedLayout& L, voi
       const int n = e / S, s = e % S;
       WgradPair& p = host[(size_t)l * n_eval + e];
       p.g = L.gp(ws, n, s, wgrad_slot(f, l));
-      p.a = l > 0 ? L.hidden(ws, n, s, l - 1) : (s > 0 ? L.xin(ws, n, s) : L.y(ws, adjoint ? n + 1 : n));
+      p.a = l > 0 ? L.hidden(ws, n, s, l - 1) : (s > 0 ? L.xin(ws, n, s) : stage0 ? stage0[n] : L.y(ws, n));
       p.scale = eval_scale ? eval_scale[e] : 1.0f;
       p.pad_[0] = p.pad_[1] = p.pad_[2] = 0.0f;
     }
@@ -174,7 +176,7 @@ static CombineArgs stage_combine(const FixedCombine& p, int s, const CombineArgs
 }
 
 // The BwdArgs of a chain from its plan: slot(i) resolves a plan's slot to its tensor; the interval's result (kSlotOut) also takes
-// grad_out[n] = `go`, weighted like its source
+// grad_out[n] = `go`, weighted like its source (null: a step that ends inside an output interval, where no gradient arrives)
 template <class Slot>
 static BwdArgs resolve_targets(const FixedTargets& p, const float* h_ptr, const float* go, Slot slot) {
   BwdArgs w;
@@ -186,7 +188,7 @@ static BwdArgs resolve_targets(const FixedTargets& p, const float* h_ptr, const 
     BwdTarget& b = w.tgt[i];
     b.out = slot(t.out); b.srcA = slot(t.src);
     b.a_c = t.a_c; b.a_h = t.a_h; b.g_c = t.g_c; b.g_h = t.g_h;
-    if (t.out == kSlotOut) { b.srcB = go; b.b_c = t.a_c; b.b_h = t.a_h; }
+    if (t.out == kSlotOut && go) { b.srcB = go; b.b_c = t.a_c; b.b_h = t.a_h; }
   }
   return w;
 }
@@ -350,12 +352,12 @@ struct BackwardPass {
   // behind the sweep (rc: what recording it returned): the recorded launch, grad_z0 from the Q4 tensor `g`, the weight / bias
   // gradients -- one launch per layer over all (T-1)*S evaluations -- and the guard: every gradient is NaN-filled if the sweep ran
   // as a persistent launch that gave up
-  int finish(PersistScope& persist, int rc, const float* g, bool adjoint, const float* eval_scale) const {
+  int finish(PersistScope& persist, int rc, const float* g, const float* const* stage0, const float* eval_scale) const {
     const int rc2 = persist.finish(hbuf, L.p(ws, L.off_h), nullptr, batch, (unsigned*)L.p(ws, L.off_psync), f->ks, stream);
     if (rc != ODEHIP_OK || rc2 != ODEHIP_OK) return rc != ODEHIP_OK ? rc : rc2;
     rc = odehip_q4_to_nchw(g, grad_z0_nchw, batch, L.C, stream);
     if (rc != ODEHIP_OK) return rc;
-    rc = wgrad_all_layers(f, L, ws, n_times, batch, adjoint, eval_scale, grad_w, grad_b, stream);
+    rc = wgrad_all_layers(f, L, ws, n_times, batch, stage0, eval_scale, grad_w, grad_b, stream);
     if (rc != ODEHIP_OK) return rc;
     float* regions[1 + 2 * ODEHIP_MAX_LAYERS] = {grad_z0_nchw};
     size_t floats[1 + 2 * ODEHIP_MAX_LAYERS] = {(size_t)batch * L.C * kPix};
@@ -517,68 +519,77 @@ extern "C" int odehip_odeint_fixed_backward(const odehip_convstack* f, const ode
     return ODEHIP_OK;
   };
   rc = sweep();   // moves g: read it only afterwards
-  return bp.finish(persist, rc, g, /*adjoint=*/false, nullptr);
+  return bp.finish(persist, rc, g, nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Adjoint backward (torchdiffeq `odeint_adjoint` semantics, _impl/adjoint.py; NEW capability -- the reference itself
 // never uses it: modules/DiffEqSolver.py:9).  For i = T-1 .. 1 the augmented state (y, a_y, a_theta) is integrated
-// from t[i] back to t[i-1] with ONE step of the same fixed-grid method on the negated dynamics (torchdiffeq flips a
-// decreasing time grid), y is then reset to the stored forward value y[i-1] and a_y += grad_out[i-1].
+// from t[i] back to t[i-1] with the same fixed-grid method on the negated dynamics (torchdiffeq flips a decreasing
+// time grid), y is then reset to the stored forward value y[i-1] and a_y += grad_out[i-1].
 //   d a_y / dt     = -J_f(y)^T a_y          -> the dgrad chain (same MFMA conv kernel, transposed+flipped weights)
-//   d a_theta / dt = -(df/dtheta)^T a_y     -> wgrad over every stage of every interval, weighted dt*b_s, one launch
+//   d a_theta / dt = -(df/dtheta)^T a_y     -> wgrad over every stage of every step, weighted dt*b_s, one launch
 // The stages of y are recomputed from y[i] (nothing saved by the forward pass except the trajectory itself).
-// Workspace: odehip_odeint_workspace_bytes(..., save_for_backward = 1).
+//
+// The sweep runs over the steps of a BACKWARD GRID, given in increasing time: the output times and, with an internal grid
+// (torchdiffeq hands `options` on to every backward interval), the points the caller placed between them.  Step n integrates from
+// point n+1 back to point n.  Where point n is an output, y restarts there from the stored trajectory and a_y takes grad_out: the
+// last stage's forward epilogue stores nothing.  Where it lies inside an interval, the solver's own y goes on: the last stage's
+// epilogue writes y + dt sum_s b_s k'_s (the forward solve's result row) and a_y takes no grad_out term.  Either way a step is
+// S * (NL forward + NL input-gradient) convolutions and nothing else.
 // ---------------------------------------------------------------------------------------------------------------
-extern "C" int odehip_odeint_adjoint_backward(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method,
-                                              const double* t_host, int n_times, int batch, const float* y_traj_nchw,
-                                              const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w,
-                                              float* const* grad_b, void* workspace, size_t workspace_bytes, void* stream_) {
-  int rc = check_backward_args(f, f_dgrad, method, t_host, n_times, batch, y_traj_nchw && grad_out_nchw && grad_z0_nchw && workspace,
-                               grad_w, grad_b, "odeint_adjoint_backward");
-  if (rc != ODEHIP_OK) return rc;
-  const FixedLayout L(f, batch, n_times, method, 1);
-  ODEHIP_REQUIRE(workspace_bytes >= L.total, "odeint_adjoint_backward: workspace too small");
-  ODEHIP_REQUIRE((n_times - 1) * L.S <= kMaxWgradEvals, "odeint_adjoint_backward: too many evaluations (%d)", (n_times - 1) * L.S);
-  hipStream_t stream = (hipStream_t)stream_;
-  void* ws = workspace;
+namespace odehip {
+
+// out_index[p]: the output time grid point p coincides with, or -1 inside an interval; null: the grid is t itself
+static int adjoint_sweep(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method, const double* grid_host, int n_grid,
+                         const int* out_index, int n_times, int batch, const float* y_traj_nchw, const float* grad_out_nchw,
+                         float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, void* ws, const FixedLayout& L,
+                         size_t off_traj, hipStream_t stream) {
   const int NH = L.NH, S = L.S, NL = f->n_convs;
   float* hdev = L.p(ws, L.off_h);
   float *ping = L.p(ws, L.off_ping), *pong = L.p(ws, L.off_pong);
   float* k[3] = {L.p(ws, L.off_k), L.p(ws, L.off_k + L.st), L.p(ws, L.off_k + 2 * L.st)};
   float* sums[3] = {L.p(ws, L.off_gy), L.p(ws, L.off_g2), L.p(ws, L.off_g2 + L.st)};   // Q_2, Q_3 and R: partial sums of the a_y stages
 
-  rc = odehip_nchw_to_q4(y_traj_nchw, L.y(ws, 0), n_times * batch, L.C, stream);
+  int rc = odehip_nchw_to_q4(y_traj_nchw, L.p(ws, off_traj), n_times * batch, L.C, stream);
   if (rc != ODEHIP_OK) return rc;
   rc = odehip_nchw_to_q4(grad_out_nchw, L.go(ws, 0), n_times * batch, L.C, stream);
   if (rc != ODEHIP_OK) return rc;
-  BackwardPass bp = {f, f_dgrad, L, ws, n_times, batch, grad_z0_nchw, grad_w, grad_b, stream, {}};
-  if (n_times == 1) return bp.trivial(grad_out_nchw);
-  fill_step_sizes(bp.hbuf, t_host, n_times);   // dt of the flipped grid, > 0
-  rc = upload_floats(hdev, bp.hbuf, n_times - 1, stream);
+  BackwardPass bp = {f, f_dgrad, L, ws, n_grid, batch, grad_z0_nchw, grad_w, grad_b, stream, {}};
+  if (n_grid == 1) return bp.trivial(grad_out_nchw);
+  fill_step_sizes(bp.hbuf, grid_host, n_grid);   // dt of the flipped grid, > 0
+  rc = upload_floats(hdev, bp.hbuf, n_grid - 1, stream);
   if (rc != ODEHIP_OK) return rc;
 
+  auto output_of = [&](int p) { return out_index ? out_index[p] : p; };
+  // y at grid point p: the stored trajectory at an output, else what the step that ended there left in the layout's y slot
+  auto y_at = [&](int p) -> float* { return output_of(p) >= 0 ? L.p(ws, off_traj + (size_t)output_of(p) * L.st) : L.y(ws, p); };
+
   const FixedTableau& tab = fixed_tableau(method);
-  FixedCombine fwd[kFixedMaxStages];
+  FixedCombine fwd[kFixedMaxStages], carry[kFixedMaxStages];
   FixedTargets plan[kFixedMaxStages];
   for (int s = 0; s < S; ++s) {
     fwd[s] = fixed_combine(tab, s, /*with_result=*/false);
+    carry[s] = fixed_combine(tab, s);
     plan[s] = adjoint_targets(tab, s);
   }
-  // seed: a_y = grad_out[T-1] is the stage-1 adjoint of the last interval
-  ODEHIP_CHECK_HIP(hipMemcpyAsync(L.gp(ws, n_times - 2, 0, NH), L.go(ws, n_times - 1), (size_t)batch * L.C * kPix * 4,
+  // seed: a_y = grad_out[T-1] is the stage-1 adjoint of the last step
+  ODEHIP_CHECK_HIP(hipMemcpyAsync(L.gp(ws, n_grid - 2, 0, NH), L.go(ws, n_times - 1), (size_t)batch * L.C * kPix * 4,
                                   hipMemcpyDeviceToDevice, stream));
   float scales[kMaxWgradEvals];
+  std::vector<const float*> stage0((size_t)n_grid - 1);
   float* a_final = L.p(ws, L.off_xs);
   float* hidv[ODEHIP_MAX_LAYERS];
-  // every interval is conv launches only (recomputed stages + input-gradient chains, all bookkeeping in their epilogues)
+  // every step is conv launches only (recomputed stages + input-gradient chains, all bookkeeping in their epilogues)
   PersistScope persist;
-  if ((rc = persist.begin(f, f_dgrad, (n_times - 1) * S * NL * 2)) != ODEHIP_OK) return rc;
+  if ((rc = persist.begin(f, f_dgrad, (n_grid - 1) * S * NL * 2)) != ODEHIP_OK) return rc;
   auto sweep = [&]() -> int {
-    for (int n = n_times - 2; n >= 0; --n) {
-      const float* y = L.y(ws, n + 1);                       // integrate from t[n+1] back to t[n]
-      float* a_next = n > 0 ? L.gp(ws, n - 1, 0, NH) : a_final;  // a_y at t[n] (+ grad_out[n]) seeds the next interval
-      auto slot = [&](int sl) -> float* {                    // stage 0's tensor is a_y at t[n+1]
+    for (int n = n_grid - 2; n >= 0; --n) {
+      const float* y = stage0[n] = y_at(n + 1);              // integrate from point n+1 back to point n
+      const bool interior = output_of(n) < 0;                // the step ends inside an output interval
+      const float* go = interior ? nullptr : L.go(ws, output_of(n));
+      float* a_next = n > 0 ? L.gp(ws, n - 1, 0, NH) : a_final;  // a_y at point n (+ grad_out there) seeds the next step
+      auto slot = [&](int sl) -> float* {                    // stage 0's tensor is a_y at point n+1
         return sl >= kSlotQ ? sums[sl - kSlotQ - 2] : sl >= 0 ? L.gp(ws, n, sl, NH) : sl == kSlotState ? L.gp(ws, n, 0, NH)
                                                                : sl == kSlotR ? sums[2] : sl == kSlotOut ? a_next : nullptr;
       };
@@ -590,19 +601,84 @@ extern "C" int odehip_odeint_adjoint_backward(const odehip_convstack* f, const o
       base.h_ptr = hdev + n;
       for (int s = 0; s < S; ++s) {
         scales[n * S + s] = bp.hbuf[n] * tab.b[s];
-        // Y_{s+1} = y + dt sum_j a[s+1][j] k_j'.  The last stage only leaves its activations (y is reset to the stored y[n]): its
-        // epilogue stores nothing, and with neither y nor a destination set it reads nothing either
+        // Y_{s+1} = y + dt sum_j a[s+1][j] k_j'.  Before an output the last stage only leaves its activations (y is reset to the
+        // stored trajectory): its epilogue stores nothing, and with neither y nor a destination set it reads nothing either.  Inside
+        // an interval the stages keep the k' the result row reads and the last one writes y at point n.
         CombineArgs c = last;
-        if (s + 1 < S) c = stage_combine(fwd[s], s, base, k, L.xin(ws, n, s + 1), nullptr, nullptr);
+        if (interior) c = stage_combine(carry[s], s, base, k, s + 1 < S ? L.xin(ws, n, s + 1) : nullptr, L.y(ws, n), nullptr);
+        else if (s + 1 < S) c = stage_combine(fwd[s], s, base, k, L.xin(ws, n, s + 1), nullptr, nullptr);
         for (int l = 0; l < NH; ++l) hidv[l] = L.hidden(ws, n, s, l);
         if ((rc = enqueue_f_saving(f, s == 0 ? y : L.xin(ws, n, s), batch, hidv, ping, pong, &c, nullptr, nullptr, stream)) != ODEHIP_OK)
           return rc;
         // K_s = J_f(Y_s)^T A_s, A_s = GP[n][s][NH]
-        if ((rc = bp.dgrad_chain(n, s, resolve_targets(plan[s], hdev + n, L.go(ws, n), slot))) != ODEHIP_OK) return rc;
+        if ((rc = bp.dgrad_chain(n, s, resolve_targets(plan[s], hdev + n, go, slot))) != ODEHIP_OK) return rc;
       }
     }
     return ODEHIP_OK;
   };
   rc = sweep();
-  return bp.finish(persist, rc, a_final, /*adjoint=*/true, scales);
+  return bp.finish(persist, rc, a_final, stage0.data(), scales);
+}
+
+// workspace of the sweep over n_grid points: the solver's layout for that many points; with interior points the Q4 trajectory sits
+// behind it (without, it fills the layout's y slots)
+static size_t adjoint_grid_bytes(const FixedLayout& L, int n_times) { return L.total + al256((size_t)n_times * L.st); }
+
+}  // namespace odehip
+
+// Workspace: odehip_odeint_workspace_bytes(..., save_for_backward = 1).
+extern "C" int odehip_odeint_adjoint_backward(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method,
+                                              const double* t_host, int n_times, int batch, const float* y_traj_nchw,
+                                              const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w,
+                                              float* const* grad_b, void* workspace, size_t workspace_bytes, void* stream_) {
+  int rc = check_backward_args(f, f_dgrad, method, t_host, n_times, batch, y_traj_nchw && grad_out_nchw && grad_z0_nchw && workspace,
+                               grad_w, grad_b, "odeint_adjoint_backward");
+  if (rc != ODEHIP_OK) return rc;
+  const FixedLayout L(f, batch, n_times, method, 1);
+  ODEHIP_REQUIRE(workspace_bytes >= L.total, "odeint_adjoint_backward: workspace too small");
+  ODEHIP_REQUIRE((n_times - 1) * L.S <= kMaxWgradEvals, "odeint_adjoint_backward: too many evaluations (%d)", (n_times - 1) * L.S);
+  return adjoint_sweep(f, f_dgrad, method, t_host, n_times, nullptr, n_times, batch, y_traj_nchw, grad_out_nchw, grad_z0_nchw, grad_w,
+                       grad_b, workspace, L, L.off_y, (hipStream_t)stream_);
+}
+
+extern "C" size_t odehip_odeint_adjoint_grid_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int n_grid, int method) {
+  if (!f || batch <= 0 || n_times <= 0 || n_grid < n_times || f->n_convs < 1) return 0;
+  return adjoint_grid_bytes(FixedLayout(f, batch, n_grid, method, 1), n_times);
+}
+
+// The adjoint backward on an internal grid.  grid_host: the n_grid points of every backward interval's grid, joined and in increasing
+// time, from t[0] to t[T-1]; out_index[p]: the j with grid[p] == t[j], or -1 for a point inside an interval.  fp32 stacks only.
+// Workspace: odehip_odeint_adjoint_grid_workspace_bytes.
+extern "C" int odehip_odeint_adjoint_backward_on_grid(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method,
+                                                      const double* t_host, int n_times, const double* grid_host, int n_grid,
+                                                      const int* out_index, int batch, const float* y_traj_nchw,
+                                                      const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w,
+                                                      float* const* grad_b, void* workspace, size_t workspace_bytes, void* stream_) {
+  const char* who = "odeint_adjoint_backward_on_grid";
+  int rc = check_backward_args(f, f_dgrad, method, t_host, n_times, batch, y_traj_nchw && grad_out_nchw && grad_z0_nchw && workspace,
+                               grad_w, grad_b, who);
+  if (rc != ODEHIP_OK) return rc;
+  ODEHIP_REQUIRE(grid_host && out_index, "%s: null grid", who);
+  ODEHIP_REQUIRE(n_grid >= n_times && n_grid <= kMaxTimes, "%s: a grid of %d points cannot serve %d output times (at most %d points)", who,
+                 n_grid, n_times, kMaxTimes);
+  ODEHIP_REQUIRE(!f->w_fused && !f_dgrad->w_fused && !f->w_bf16[0], "%s: fp32 stacks only", who);
+  const int S = n_stages(method);
+  ODEHIP_REQUIRE((n_grid - 1) * S <= kMaxWgradEvals, "%s: too many evaluations (%d grid steps x %d stages = %d, at most %d)", who,
+                 n_grid - 1, S, (n_grid - 1) * S, kMaxWgradEvals);
+  int j = 0;   // the outputs appear in order, each on a grid point of its own time; the grid starts and ends on one
+  for (int p = 0; p < n_grid; ++p) {
+    ODEHIP_REQUIRE(p == 0 || grid_host[p] > grid_host[p - 1], "%s: the grid must be strictly increasing (grid[%d]=%g, grid[%d]=%g)", who,
+                   p - 1, grid_host[p - 1], p, grid_host[p]);
+    if (out_index[p] < 0) continue;
+    ODEHIP_REQUIRE(j < n_times && out_index[p] == j && grid_host[p] == t_host[j], "%s: grid point %d (%g, output %d) is not output time %d",
+                   who, p, grid_host[p], out_index[p], j);
+    ++j;
+  }
+  ODEHIP_REQUIRE(j == n_times && out_index[0] == 0 && out_index[n_grid - 1] == n_times - 1,
+                 "%s: the grid must start at t[0], end at t[%d] and hold every output time (%d of %d found)", who, n_times - 1, j, n_times);
+  const FixedLayout L(f, batch, n_grid, method, 1);
+  ODEHIP_REQUIRE(workspace_bytes >= adjoint_grid_bytes(L, n_times), "%s: workspace too small (%zu < %zu)", who, workspace_bytes,
+                 adjoint_grid_bytes(L, n_times));
+  return adjoint_sweep(f, f_dgrad, method, grid_host, n_grid, out_index, n_times, batch, y_traj_nchw, grad_out_nchw, grad_z0_nchw, grad_w,
+                       grad_b, workspace, L, L.total, (hipStream_t)stream_);
 }

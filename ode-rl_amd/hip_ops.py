@@ -864,6 +864,81 @@ def odeint_adjoint_backward(stack, method, t, y_traj, grad_out):
     return grads
 
 
+def adjoint_backward_grid(func, y_traj, method, t, options):
+    """The grid of odeint_adjoint's backward pass under options["grid_constructor"], on the host: (grid, out_index).  torchdiffeq solves
+    every backward interval (t[i], t[i-1]), i = T-1 .. 1, as an `odeint` call of its own with the caller's options: the decreasing pair
+    is flipped to (-t[i], -t[i-1]) and the interval's grid is what odeint.internal_grid builds for that pair -- the constructor is called
+    once per interval, in that order, with the state the interval starts from (y_traj[i], or None without a trajectory).  A grid of
+    step_size_grid(h) is therefore anchored at t[i]: sub-steps of h back from t[i], the last one cut short at t[i-1].  `grid` joins the
+    intervals' points in increasing time (float64, T <= G points), out_index[p] is the j with grid[p] == t[j] or -1 inside an interval.
+    ValueError before any launch if the G points or their (G - 1) * stages evaluations of f exceed what the sweep holds."""
+    from .odeint import internal_grid
+    th = host_times(t)
+    points, index = [th[-1:]], [len(th) - 1]   # walked backwards, in flipped time
+    for i in range(len(th) - 1, 0, -1):
+        pair = torch.stack([-th[i], -th[i - 1]])
+        sub = internal_grid(func, None if y_traj is None else y_traj[i], pair, options)
+        points.append(-sub[1:])
+        index += [-1] * (len(sub) - 2) + [i - 1]
+    grid = torch.cat(points).flip(0)
+    g = len(grid)
+    if g > GRID_MAX_POINTS:
+        raise ValueError(f"odeint_adjoint(HIP): the backward grids hold G = {g} points, more than the limit of {GRID_MAX_POINTS} points")
+    if (g - 1) * _STAGES[method] > GRID_MAX_EVALS:
+        raise ValueError(f"odeint_adjoint(HIP): the backward grids hold G = {g} points, which needs {(g - 1) * _STAGES[method]} evaluations "
+                         f"of f; the backward pass keeps at most {GRID_MAX_EVALS} ((G - 1) * {_STAGES[method]} stages of {method})")
+    return grid, index[::-1]
+
+
+def odeint_adjoint_on_grid_backward(stack, method, t, y_traj, grad_out, func, options):
+    """odeint_adjoint_backward with torchdiffeq's `options` handed on to every backward interval (adjoint_backward_grid builds their
+    grids): (grad_z0, [grad_w...], [grad_b...]).  Inside an interval the solver carries y itself; only at an output time is it reset
+    to y_traj and does a_y take grad_out.  Intervals whose grids are their two end points make this odeint_adjoint_backward itself."""
+    grid, index = adjoint_backward_grid(func, y_traj, method, t, options)
+    th = host_times(t)
+    if len(grid) == len(th):
+        return odeint_adjoint_backward(stack, method, th, y_traj, grad_out)
+    if current_compute_dtype() == "bf16":
+        raise TypeError("odeint_adjoint(HIP): internal grids are not implemented in bf16 compute mode (fp32 only)")
+    require_device_tensor(grad_out, "grad_out")
+    require_device_tensor(y_traj, "y_traj")
+    desc = stack.refresh()
+    dg = stack.dgrad_desc()
+    grad_out, y_traj = grad_out.contiguous(), y_traj.contiguous()
+    tarr, garr = _c_times(th), _c_times(grid)
+    n, g, b = len(tarr), len(garr), y_traj.shape[1]
+    lib = _lib.load()
+    m = _lib.METHODS[method]
+    nbytes = lib.odehip_odeint_adjoint_grid_workspace_bytes(ctypes.byref(desc), b, n, g, m)
+    ws = workspace(("adjoint_grid", b, n, m, tuple(desc.channels)), nbytes, grad_out.device)   # grows to the largest G met
+    last_adjoint_grid.update(points=g, workspace_bytes=int(nbytes))
+    grads, gw_arr, gb_arr = _stack_grads(stack, b, grad_out.device)
+    _lib.check(lib.odehip_odeint_adjoint_backward_on_grid(ctypes.byref(desc), ctypes.byref(dg), m, tarr, n, garr, g,
+                                                          (ctypes.c_int * g)(*index), b, _ptr(y_traj), _ptr(grad_out), _ptr(grads[0]),
+                                                          gw_arr, gb_arr, _ptr(ws), ws.numel(), _stream()))
+    return grads
+
+
+_adjoint_grids = False   # odeint_adjoint takes odeint's internal grids (set_adjoint_grids)
+
+
+def set_adjoint_grids(on=True):
+    """Let odeint_adjoint take options={"grid_constructor": fn} for euler / midpoint / rk4 (off by default: the options are refused, as
+    they always were).  On, the adjoint does what torchdiffeq's does -- a grid per BACKWARD interval, built from its flipped end points,
+    so not the forward solve's grid (autograd.odeint_adjoint).  Returns the previous setting."""
+    global _adjoint_grids
+    was = _adjoint_grids
+    _adjoint_grids = bool(on)
+    return was
+
+
+def adjoint_grids_enabled():
+    return _adjoint_grids
+
+
+last_adjoint_grid = {}   # points / workspace_bytes of the most recent gridded adjoint backward (instrumentation)
+
+
 def odeint_adjoint_dopri5_backward(stack, t, y_traj, grad_out, rtol, atol, max_accept=None, stats=None, mixed_norm=False, method="dopri5"):
     """torchdiffeq odeint_adjoint backward with method="dopri5" or "bosh3" (seminorm, or the default mixed norm): (grad_z0, [grad_w...], [grad_b...]).
     `stats`, if a dict, receives nfe / n_accept / n_reject of the backward solve and `controller`: "device" when the device-steered

@@ -67,23 +67,24 @@ def conv_stack_of(func):
 
 
 def check_options(method, options, where="odeint"):
-    """torchdiffeq's `options` that this path implements.  Fixed-grid methods, in `odeint` only: `grid_constructor` (an internal grid
-    of the caller's; the requested times are filled by linear interpolation) and `interp: "linear"` next to it; `step_size` stays
-    refused -- `step_size_grid(step_size)` builds torchdiffeq's grid for it --, as do `perturb` and any other `interp`: they would
-    change the result and are refused rather than ignored.  dopri5 and bosh3: `first_step` and `max_num_steps`.  Looks at no tensor."""
+    """torchdiffeq's `options` that this path implements.  Fixed-grid methods, in `odeint` and -- once
+    set_adjoint_grids(True) has switched them on; refused as before otherwise -- in `odeint_adjoint`: `grid_constructor` (an internal grid of the caller's; the requested times are filled by linear interpolation) and `interp:
+    "linear"` next to it; `step_size` stays refused -- `step_size_grid(step_size)` builds torchdiffeq's grid for it --, as do `perturb`
+    and any other `interp`: they would change the result and are refused rather than ignored.  dopri5 and bosh3: `first_step` and
+    `max_num_steps`.  Looks at no tensor."""
     options = options or {}
     if method in FIXED_GRID:
-        known = {"grid_constructor", "interp"} if where == "odeint" else set()
+        known = {"grid_constructor", "interp"} if where == "odeint" or hip_ops.adjoint_grids_enabled() else set()
     else:
         known = {"first_step", "max_num_steps"}
     unknown = set(options) - known
     if unknown:
         hint = ""
-        if "step_size" in unknown and where == "odeint":
+        if method in FIXED_GRID and not known and unknown & {"step_size", "grid_constructor", "interp"}:
+            hint = (": internal grids under odeint_adjoint are opt-in -- torchdiffeq's adjoint builds a new grid for every backward "
+                    "interval, anchored at its later time, and so does this path after ode_rl_amd.set_adjoint_grids(True)")
+        elif "step_size" in unknown and method in FIXED_GRID:
             hint = ': for a step size pass options={"grid_constructor": ode_rl_amd.step_size_grid(step_size)}'
-        elif method in FIXED_GRID and where != "odeint" and unknown & {"step_size", "grid_constructor", "interp"}:
-            hint = (": internal grids are implemented for odeint only (torchdiffeq's adjoint builds a new grid for every backward "
-                    "interval, which this path does not do)")
         raise ValueError(f"{where}(HIP): unsupported {method} options {sorted(unknown)}{hint}")
     if method in FIXED_GRID:
         if "grid_constructor" in options and not callable(options["grid_constructor"]):

@@ -108,8 +108,14 @@ SED[adjoint_gp_stride]='s|cap \* NH \* hid + ((size_t)s \* NG + l) \* hid|cap * 
 SED[interleave_second_sample_dropped]='s/    const int n_interleaved = b + n_groups < pa.batch ? 2 : 1;/    const int n_interleaved = 1;/'   # samples 64 .. 127 are never written
 SED[interleave_wrong_sample]='s/readfirstlane(b + s \* n_groups)/readfirstlane(b)/'   # sample b is walked twice, b + 64 never
 SED[second_pass_skipped]='s/b < pa.batch; b += 2 \* n_groups)/b < pa.batch; b += 4 * n_groups)/'   # samples >= 128 are never written
+# ---- odeint_adjoint on internal grids (fixed_grid.hip: adjoint_sweep): both stay inside the workspace.  Rejected by the Tanh cases of
+# the new file -- MUT_TESTS="tests/test_hip_grid_adjoint.py" (profiles/mutation_grid_adjoint.txt); the third mutant, the anchoring of the
+# backward grids, lives in the binding (PYSED below)
+SED[grid_adjoint_resets_interior_y]='s/output_of(p) >= 0 ? L.p(ws, off_traj + (size_t)output_of(p) \* L.st) : L.y(ws, p); };/output_of(p) >= 0 ? L.p(ws, off_traj + (size_t)output_of(p) * L.st) : L.p(ws, off_traj + (size_t)(n_times - 1) * L.st); };/'   # inside an interval y comes from the stored trajectory (its last frame), not from the solver
+SED[grid_adjoint_interior_grad_out]='s/      const float\* go = interior ? nullptr : L.go(ws, output_of(n));/      const float* go = L.go(ws, interior ? 0 : output_of(n));/'   # a_y takes a grad_out frame at interior points too
 # mutants of the Python binding, "file|sed script": applied to the tree's own file for the run and restored afterwards (run only)
 declare -A PYSED
+PYSED[grid_adjoint_anchored_low]='ode-rl_amd/hip_ops.py|s/^        pair = torch.stack(\[-th\[i\], -th\[i - 1\]\])$/        pair = torch.stack([th[i - 1], th[i]])/;s/^        points.append(-sub\[1:\])$/        points.append(sub[:-1].flip(0))/'   # the sub-steps of a backward interval anchored at t[i-1]: the constructor sees the unflipped pair
 PYSED[z0_offset_stuck]='ode-rl_amd/autograd.py|s/gen.set_offset(at + 4)/gen.set_offset(at)/;s/_explicit_seed\[1\] = offset + 1/_explicit_seed[1] = offset/'   # consecutive sample_z0 calls draw the same noise
 # ---- VidODE's whole-model backward (tests/test_hip_vidode_grads.py): each leaves every forward value bitwise as it is
 PYSED[vidode_prev_detached]='ode-rl_amd/models/VidODE.py|s/^            prev = sol_out\[:, t, \.\.\.\]$/            prev = sol_out[:, t, ...].detach()/'   # a latent frame reaches the NEXT frame'"'"'s decoder call without a gradient
