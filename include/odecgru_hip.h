@@ -150,7 +150,7 @@ typedef struct odehip_convstack {
   const float* bias[ODEHIP_MAX_LAYERS];
   int final_tanh;                        /* final_act=True appends Tanh (helpers/utils.py:179-181)  */
   int act;                               /* hidden activation: 0 = ReLU, 1 = Tanh (create_convnet's nonlinear); a
-                                            non-ReLU activation or a Tanh head excludes w_fused (the fused kernels are ReLU-only) */
+                                            Tanh head excludes w_fused (the fused kernels take either hidden activation, no head) */
 } odehip_convstack;
 
 size_t odehip_convstack_workspace_bytes(const odehip_convstack* f, int batch);

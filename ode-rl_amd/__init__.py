@@ -6,7 +6,7 @@ from . import _lib  # noqa: F401
 from .odeint import odeint, last_stats, step_size_grid  # noqa: F401
 from .autograd import odeint_adjoint, last_adjoint_stats, sample_z0, last_z0_noise, mse_kl_loss, vidode_l1_loss  # noqa: F401
 from .autograd import instnorm_lrelu, gan_sequences, lsgan_loss  # noqa: F401
-from .hip_ops import set_compute_dtype, current_compute_dtype, set_async_dopri5, collect_pending_solves, set_adjoint_grids  # noqa: F401
+from .hip_ops import set_compute_dtype, set_bf16_tanh, current_compute_dtype, set_async_dopri5, collect_pending_solves, set_adjoint_grids  # noqa: F401
 from .helpers.utils import create_convnet  # noqa: F401
 from .modules.DiffEqSolver import DiffEqSolver, ODEFunc  # noqa: F401
 from .modules.ConvGRUCell import ConvGRUCell  # noqa: F401

@@ -54,7 +54,7 @@ int check_stack(const odehip_convstack* f) {
   for (int i = 0; i < f->n_convs; ++i)
     ODEHIP_REQUIRE(f->w_packed[i] && f->bias[i], "convstack: layer %d has null weights/bias", i);
   if (f->w_fused) {
-    ODEHIP_REQUIRE(f->act == 0 && !f->final_tanh, "convstack: the fused bf16 image supports ReLU stacks without a Tanh head only");
+    ODEHIP_REQUIRE(!f->final_tanh, "convstack: the fused bf16 image supports stacks without a Tanh head only");
     ODEHIP_REQUIRE(f->ks == 3, "convstack: the fused bf16 image needs 3x3 layers");
     for (int i = 0; i <= f->n_convs; ++i)
       ODEHIP_REQUIRE(f->channels[i] == 64, "convstack: the fused bf16 image needs 64-channel layers (channels[%d] = %d)", i, f->channels[i]);
@@ -104,6 +104,7 @@ int enqueue_f_saving(const odehip_convstack* f, const float* x_q4, int batch, fl
     fa.x = x_q4;
     fa.w_fused = f->w_fused;
     fa.n_layers = f->n_convs;
+    fa.act = hidden_act(f);
     for (int l = 0; l < f->n_convs; ++l) {
       fa.bias[l] = f->bias[l];
       if (l < f->n_convs - 1) fa.store[l] = hidden ? hidden[l] : nullptr;
@@ -166,6 +167,7 @@ int enqueue_dgrad_chain(const odehip_convstack* f, const odehip_convstack* fd, i
     fa.x = gp[NL - 1];
     fa.w_fused = fd->w_fused;
     fa.n_layers = NL;
+    fa.act = hidden_act(f);
     for (int e = 0; e < NL - 1; ++e) {
       const int l = NL - 1 - e;
       fa.store[e] = gp[l - 1];
@@ -210,6 +212,9 @@ int enqueue_dgrad_chain(const odehip_convstack* f, const odehip_convstack* fd, i
       a.combine = 2;
       a.bwd.mask_src = hidden[l - 1];  // activation output that fed conv l
       a.act = f->act == 1 ? kActTanh : kActNone;   // its derivative (kActNone: the ReLU mask, as before)
+      // bf16 mode: conv l consumed bf16(y), and the Tanh derivative is formed from that value (kActTanhBf16 lives in epilogue(),
+      // which the bf16 and the direct kernels end in: a layer whose input-gradient conv has no bf16 form runs the direct one)
+      if (f->act == 1 && f->w_bf16[l]) a.act = kActTanhBf16;
       a.bwd.sc_c = 1.0f;
       a.dst = gp[l - 1];
     } else {
@@ -220,7 +225,7 @@ int enqueue_dgrad_chain(const odehip_convstack* f, const odehip_convstack* fd, i
     a.q1 = a.qin = f->channels[l + 1] / 4;
     a.qout = f->channels[l] / 4;
     a.w_packed = fd->w_packed[l];
-    a.w_wino = fd->w_wino[l];
+    a.w_wino = a.act == kActTanhBf16 ? nullptr : fd->w_wino[l];
     a.w_bf16 = fd->w_bf16[l];
     a.bias = nullptr;
     a.batch = batch;

@@ -10,6 +10,8 @@
 // the next conv of the chain multiplies), asynchronously; what comes from HBM: the saved masks (bf16, prefetched a layer ahead,
 // counted in the weight ring's vmcnt waits) and grad_out of the interval's left end.  The bias gradients are summed on the way
 // from the UNROUNDED fp32 gradients, in a fixed order (row sums by DPP, then LDS): deterministic.
+// Tanh hidden layers (template parameter ACT): the saved activation is the Tanh output as bf16, and the "mask" becomes the factor
+// 1 - y^2 of that value -- the derivative of bf16 mode on every path (the per-evaluation chain rounds its fp32 save to match).
 #include <string.h>
 
 #include "fixed_tableau.h"
@@ -46,6 +48,14 @@ __device__ __forceinline__ u32x2b gload8_untracked(const char* p) {
 // threshold_backward passes the gradient where !(v <= 0) -- v positive, or NaN whatever its sign bit
 __device__ __forceinline__ bool bf16_relu_pass(unsigned f32_bits) { return !(__uint_as_float(f32_bits) <= 0.0f); }
 
+// the Tanh derivative from a saved bf16 output y, given as the fp32 bits it widens to: g * (1 - y^2), act_bwd's explicit fma
+__device__ __forceinline__ float bf16_tanh_bwd(float g, unsigned f32_bits) {
+  const float y = __uint_as_float(f32_bits);
+  return g * __builtin_fmaf(-y, y, 1.0f);
+}
+
+// ACT: the hidden activation of the forward (kActRelu / kActTanh), compile-time as in ftraj_bf16_kernel
+template <int ACT>
 __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs ba) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const act = smem;
@@ -252,7 +262,8 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
           }
         }
         if (!has_mask) break;
-        // hidden layer of the chain: gradient w.r.t. conv l-1's output = acc masked by (saved activation > 0); store + tile
+        // hidden layer of the chain: gradient w.r.t. conv l-1's output = acc times the activation's derivative, from the saved
+        // output (ReLU: its sign; Tanh: 1 - y^2); store + tile
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
 #pragma unroll
@@ -262,13 +273,20 @@ __global__ __launch_bounds__(512, 1) void btraj_bf16_rk4_kernel(const BtrajArgs 
           f32x16& acc = nb ? acc1 : acc0;
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            const u32x2b m = mreg[nb * 4 + g];   // 4 bf16, passed where !(v <= 0) as in torch: positive or NaN, either sign bit
-            const bool p0 = bf16_relu_pass(m[0] << 16), p1 = bf16_relu_pass(m[0] & 0xffff0000u), p2 = bf16_relu_pass(m[1] << 16),
-                       p3 = bf16_relu_pass(m[1] & 0xffff0000u);
-            acc[4 * g] = p0 ? acc[4 * g] : 0.f;
-            acc[4 * g + 1] = p1 ? acc[4 * g + 1] : 0.f;
-            acc[4 * g + 2] = p2 ? acc[4 * g + 2] : 0.f;
-            acc[4 * g + 3] = p3 ? acc[4 * g + 3] : 0.f;
+            const u32x2b m = mreg[nb * 4 + g];   // 4 bf16: the activation's output as conv l consumed it
+            if constexpr (ACT == kActTanh) {
+              acc[4 * g] = bf16_tanh_bwd(acc[4 * g], m[0] << 16);
+              acc[4 * g + 1] = bf16_tanh_bwd(acc[4 * g + 1], m[0] & 0xffff0000u);
+              acc[4 * g + 2] = bf16_tanh_bwd(acc[4 * g + 2], m[1] << 16);
+              acc[4 * g + 3] = bf16_tanh_bwd(acc[4 * g + 3], m[1] & 0xffff0000u);
+            } else {   // ReLU: passed where !(v <= 0) as in torch: positive or NaN, either sign bit
+              const bool p0 = bf16_relu_pass(m[0] << 16), p1 = bf16_relu_pass(m[0] & 0xffff0000u), p2 = bf16_relu_pass(m[1] << 16),
+                         p3 = bf16_relu_pass(m[1] & 0xffff0000u);
+              acc[4 * g] = p0 ? acc[4 * g] : 0.f;
+              acc[4 * g + 1] = p1 ? acc[4 * g + 1] : 0.f;
+              acc[4 * g + 2] = p2 ? acc[4 * g + 2] : 0.f;
+              acc[4 * g + 3] = p3 ? acc[4 * g + 3] : 0.f;
+            }
           }
           emit(acc, nb, wave_uniform(gs + (size_t)(l - 1) * ba.stride_g_layer));
         }
@@ -381,13 +399,15 @@ int launch_btraj_bf16_rk4(const odehip_convstack* f_dgrad, const float* grad_out
   ba.n_layers = f_dgrad->n_convs; ba.n_steps = n_times - 1; ba.batch = batch;
   ba.n_lo = n_lo; ba.n_hi = n_hi; ba.state_g = state_g; ba.state_seed = state_seed;
   ODEHIP_REQUIRE(0 <= n_lo && n_lo < n_hi && n_hi <= n_times - 1, "btraj_bf16: bad interval range [%d, %d)", n_lo, n_hi);
+  typedef void (*Kernel)(const BtrajArgs);
+  const Kernel kernels[2] = {btraj_bf16_rk4_kernel<kActRelu>, btraj_bf16_rk4_kernel<kActTanh>};
   static bool attr_set = false;
   if (!attr_set) {
-    ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)btraj_bf16_rk4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    for (const Kernel k : kernels) ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set = true;
   }
   // LDS: tile + ring + [NL][64] sums (the bias slot) + 2 KiB of running row sums per layer
-  hipLaunchKernelGGL(btraj_bf16_rk4_kernel, dim3(batch), dim3(512), kFusedLds + ODEHIP_MAX_LAYERS * 8 * 4 * 16 * 4, stream, ba);
+  hipLaunchKernelGGL(kernels[f_dgrad->act == 1 ? 1 : 0], dim3(batch), dim3(512), kFusedLds + ODEHIP_MAX_LAYERS * 8 * 4 * 16 * 4, stream, ba);
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
 }

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_bf16_kernel(const ConvArgs a) 
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv, xv, acc, 0, 0, 0);
     }
   }
-  epilogue(a, acc, b, ct, (r0 + wave * 2) * 16 + i32, kq, wave);
+  epilogue<true>(a, acc, b, ct, (r0 + wave * 2) * 16 + i32, kq, wave);
 }
 
 // ---- KS x KS convs with a large K extent (the ConvGRU cell's 5x5 convs on cat(x, h), modules/ConvGRUCell.py:40-50): the whole
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256, 1) void conv_bf16_ring_kernel(const ConvArgs a
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv, xv, acc, 0, 0, 0);
     }
   }
-  epilogue(a, acc, b, ct, (r0 + wave * 2) * 16 + i32, kq, wave);
+  epilogue<true>(a, acc, b, ct, (r0 + wave * 2) * 16 + i32, kq, wave);
 }
 
 // out[ct][cb][tap][h][co32][j]: the block-major image of conv_bf16_ring_kernel

@@ -35,6 +35,11 @@ __device__ __forceinline__ f32x4 act_bwd(f32x4 g, f32x4 y, int act) {
   }
   return g;
 }
+// The saved output y of a hidden activation as the next conv consumed it in bf16 mode: rounded to bf16 (NaN stays NaN).  There the
+// Tanh derivative is 1 - bf16(y)^2 on every path: the whole-trajectory reverse sweep (btraj_bf16.hip) has nothing but the bf16 value.
+__device__ __forceinline__ f32x4 bf16_round4(f32x4 y) {
+  return f32x4{(float)(__bf16)y.x, (float)(__bf16)y.y, (float)(__bf16)y.z, (float)(__bf16)y.w};
+}
 // combine-0 store of the per-layer kernels: the activation, or (kActTanhSeed) the Tanh head's backward seed
 __device__ __forceinline__ f32x4 act_store(const ConvArgs& a, size_t off, f32x4 v) {
   if (a.act == kActTanhSeed) return act_bwd(*(const f32x4*)(a.bwd.mask_src + off), act_fwd(v, kActTanh), kActTanh);
@@ -264,6 +269,9 @@ __device__ __forceinline__ f32x16 bias_init(const float* bias, int ct, int kq) {
 
 // ---- epilogue: lane (pixel i32, half kq) holds channel quads 2g+kq of this 32-channel tile
 // part_idx >= 0 overrides the slot of this wave's error-norm partial (kernels whose grid is not (tile, sample))
+// TANH_BF16: the per-layer kernels (conv_q4.hip, conv_bf16.hip), which can meet kActTanhBf16 in a combine-2 row; the fused bf16
+// kernels end in the instantiation without it
+template <bool TANH_BF16 = false>
 __device__ __forceinline__ void epilogue(const ConvArgs& a, const f32x16& acc, int b, int ct, int P, int kq, int wave, int part_idx = -1) {
   if (!a.combine) {
 #pragma unroll
@@ -284,6 +292,12 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, const f32x16& acc, i
         const size_t off = (((size_t)b * a.qout + ct * 8 + 2 * g + kq) * kPix + P) * 4;
         f32x4 v = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
         v *= sc;
+        if constexpr (TANH_BF16) {
+          if (a.act == kActTanhBf16) {   // bf16 mode: the Tanh derivative from y as the forward's conv consumed it
+            *(f32x4*)(a.dst + off) = act_bwd(v, bf16_round4(*(const f32x4*)(w.mask_src + off)), kActTanh);
+            continue;
+          }
+        }
         if (w.mask_src) v = act_bwd(v, *(const f32x4*)(w.mask_src + off), a.act);
         *(f32x4*)(a.dst + off) = v;
       }

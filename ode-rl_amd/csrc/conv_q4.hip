@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_resident_kernel(const float* _
     if (acc[0] == 12345.678f) a.dst[0] = acc[1];  // keep the accumulators live
     return;
   }
-  epilogue(a, acc, b, ct, (r0 + wave * 2) * 16 + i32, kq, wave);
+  epilogue<true>(a, acc, b, ct, (r0 + wave * 2) * 16 + i32, kq, wave);
   if (DBG) st.flush(a);
 }
 
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256, MINB) void conv_ring_kernel(const ConvArgs a) 
     if (acc[0] == 12345.678f) a.dst[0] = acc[1];
     return;
   }
-  epilogue(a, acc, b, ct, (r0 + wave * 2) * 16 + i32, kq, wave);
+  epilogue<true>(a, acc, b, ct, (r0 + wave * 2) * 16 + i32, kq, wave);
   st.flush(a);
 }
 

@@ -15,6 +15,9 @@
 // The same kernel runs the input-gradient chain of the backward passes (transposed+flipped weights in execution order, the
 // ReLU replaced by the saved mask, every layer's fp32 gradient stored for the weight-gradient kernels) and can store the
 // hidden activations (fp32, for a later backward).  The last layer ends in the shared fused epilogue (conv_common.h).
+// The hidden activation is a compile-time parameter of all kernels here (ACT: kActRelu or kActTanh, odehip_convstack.act): Tanh
+// is act_fwd's tanhf forward and, in a gradient chain, g * (1 - bf16(y)^2) from the saved output y -- rounded to bf16 because
+// that is what the next conv consumed and all the whole-trajectory reverse sweep keeps.
 // Used when every layer is 64 -> 64 (the ODEConvGRU dynamics) and a fused weight image is present; batches below 256 leave
 // CUs idle -- at B = 64 one f evaluation still takes ~1/3 of five bf16 launches.
 #include <string.h>
@@ -34,7 +37,8 @@ __device__ __forceinline__ void wait_younger(int n) {
 
 // DBG: diagnostic instantiation that honours the ablation flags in fa.last.debug (1 no weight DMA, 2 no MFMA and no operand
 // reads, 64 MFMA on constant operands); the production instantiation has no such branches in its inner loop.
-template <bool DBG>
+// ACT: the hidden activation (kActRelu / kActTanh), compile-time: the ReLU instantiation is the kernel it was before Tanh existed.
+template <bool DBG, int ACT>
 __global__ __launch_bounds__(512, 1) void fstack_bf16_kernel(const FusedArgs fa) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const act = smem;
@@ -156,7 +160,7 @@ __global__ __launch_bounds__(512, 1) void fstack_bf16_kernel(const FusedArgs fa)
       }
     }
     if (e == NL - 1) break;
-    // ---- hidden layer: ReLU (or the saved mask), optional fp32 store, bf16 back into the SAME tile once every wave has read it
+    // ---- hidden layer: the activation (or, in a gradient chain, its derivative from the saved output), optional fp32 store, bf16 back into the SAME tile once every wave has read it
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     float* st = fa.store[e];
@@ -174,7 +178,13 @@ __global__ __launch_bounds__(512, 1) void fstack_bf16_kernel(const FusedArgs fa)
         const size_t off = (((size_t)b * 16 + Q) * kPix + (nb ? P1 : P0)) * 4;
         if (has_mask) {
           const f32x4 m = mreg[nb * 4 + g];
-          v.x = m.x <= 0.f ? 0.f : v.x; v.y = m.y <= 0.f ? 0.f : v.y; v.z = m.z <= 0.f ? 0.f : v.z; v.w = m.w <= 0.f ? 0.f : v.w;   // NaN passes, as torch
+          if constexpr (ACT == kActTanh) {
+            v = act_bwd(v, bf16_round4(m), kActTanh);   // g * (1 - bf16(y)^2)
+          } else {
+            v.x = m.x <= 0.f ? 0.f : v.x; v.y = m.y <= 0.f ? 0.f : v.y; v.z = m.z <= 0.f ? 0.f : v.z; v.w = m.w <= 0.f ? 0.f : v.w;   // NaN passes, as torch
+          }
+        } else if constexpr (ACT == kActTanh) {
+          v = act_fwd(v, kActTanh);
         } else {
           v.x = relu_f(v.x); v.y = relu_f(v.y); v.z = relu_f(v.z); v.w = relu_f(v.w);
         }
@@ -209,7 +219,7 @@ struct TrajArgs {
   float k_scale;                         // -1: negated dynamics (decreasing time grid)
   // SAVE: base of the stage inputs / hidden activations, slot strides in bytes (evaluation e = n*S + s; layer l)
   char* save_x;                          // [e] : Q4h of x_s (s = 0: y_n)
-  char* save_h;                          // [e][l] : Q4h of the ReLU output of conv l < NL-1
+  char* save_h;                          // [e][l] : Q4h of the activation's output behind conv l < NL-1
   unsigned long long stride_x, stride_h_eval, stride_h_layer;
 };
 
@@ -223,7 +233,7 @@ template <int METHOD> struct StageProgram {
   static constexpr bool in_order(int s) { return st[s].n_prev == 0 || (st[s].prev[st[s].n_prev - 1] == st[s].n_prev - 1 && st[s].n_prev <= 3); }
 };
 
-template <int METHOD, bool SAVE>
+template <int METHOD, bool SAVE, int ACT>
 __global__ __launch_bounds__(512, 1) void ftraj_bf16_kernel(const TrajArgs ta) {
   typedef StageProgram<METHOD> Prog;
   constexpr int S = Prog::S;
@@ -359,7 +369,7 @@ __global__ __launch_bounds__(512, 1) void ftraj_bf16_kernel(const TrajArgs ta) {
           }
         }
         if (e == 0) frame_pending = 0;
-        // the output goes to the OTHER tile: no wave has to be waited for (hidden layer: ReLU; last layer: the next stage input /
+        // the output goes to the OTHER tile: no wave has to be waited for (hidden layer: the activation; last layer: the next stage input /
         // new state, below); the first barrier of the next layer makes it visible
         if (e < NL - 1) {
           char* const dst = SAVE ? wave_uniform(save_h + ev * ta.stride_h_eval + (size_t)e * ta.stride_h_layer) : nullptr;
@@ -367,7 +377,10 @@ __global__ __launch_bounds__(512, 1) void ftraj_bf16_kernel(const TrajArgs ta) {
           for (int nb = 0; nb < 2; ++nb) {
             f32x16 v = nb ? acc1 : acc0;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) v[i] = relu_f(v[i]);
+            for (int i = 0; i < 16; ++i) {
+              if constexpr (ACT == kActTanh) v[i] = tanhf(v[i]);   // act_fwd's function, element by element
+              else v[i] = relu_f(v[i]);
+            }
             emit(v, nb, dst);
           }
           cur ^= 1;
@@ -427,25 +440,30 @@ static void traj_args(TrajArgs& ta, const odehip_convstack* f, const float* z0_n
   ta.k_scale = negate ? -1.0f : 1.0f;
 }
 
-template <int METHOD, bool SAVE>
-static int launch_ftraj(const TrajArgs& ta, int batch, hipStream_t stream) {
+template <int METHOD, bool SAVE, int ACT>
+static int launch_ftraj_act(const TrajArgs& ta, int batch, hipStream_t stream) {
   static bool attr_set = false;
   if (!attr_set) {
-    ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)ftraj_bf16_kernel<METHOD, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)ftraj_bf16_kernel<METHOD, SAVE, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set = true;
   }
-  hipLaunchKernelGGL((ftraj_bf16_kernel<METHOD, SAVE>), dim3(batch), dim3(512), kTrajLds, stream, ta);
+  hipLaunchKernelGGL((ftraj_bf16_kernel<METHOD, SAVE, ACT>), dim3(batch), dim3(512), kTrajLds, stream, ta);
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
+}
+// act: odehip_convstack.act (0 = ReLU, 1 = Tanh)
+template <int METHOD, bool SAVE>
+static int launch_ftraj(const TrajArgs& ta, int act, int batch, hipStream_t stream) {
+  return act == 1 ? launch_ftraj_act<METHOD, SAVE, kActTanh>(ta, batch, stream) : launch_ftraj_act<METHOD, SAVE, kActRelu>(ta, batch, stream);
 }
 
 int launch_ftraj_bf16(const odehip_convstack* f, int method, const float* z0_nchw, float* out_nchw, const float* hdev, int n_times,
                       int batch, int negate, hipStream_t stream) {
   TrajArgs ta;
   traj_args(ta, f, z0_nchw, out_nchw, hdev, n_times, batch, negate);
-  if (method == ODEHIP_EULER) return launch_ftraj<ODEHIP_EULER, false>(ta, batch, stream);
-  if (method == ODEHIP_MIDPOINT) return launch_ftraj<ODEHIP_MIDPOINT, false>(ta, batch, stream);
-  if (method == ODEHIP_RK4) return launch_ftraj<ODEHIP_RK4, false>(ta, batch, stream);
+  if (method == ODEHIP_EULER) return launch_ftraj<ODEHIP_EULER, false>(ta, f->act, batch, stream);
+  if (method == ODEHIP_MIDPOINT) return launch_ftraj<ODEHIP_MIDPOINT, false>(ta, f->act, batch, stream);
+  if (method == ODEHIP_RK4) return launch_ftraj<ODEHIP_RK4, false>(ta, f->act, batch, stream);
   set_error("ftraj_bf16: unknown method %d", method);
   return ODEHIP_EINVAL;
 }
@@ -458,7 +476,7 @@ int launch_ftraj_bf16_saving(const odehip_convstack* f, const float* z0_nchw, fl
   traj_args(ta, f, z0_nchw, out_nchw, hdev, n_times, batch, 0);
   ta.save_x = (char*)save_x; ta.save_h = (char*)save_h;
   ta.stride_x = stride_x; ta.stride_h_eval = stride_h_eval; ta.stride_h_layer = stride_h_layer;
-  return launch_ftraj<ODEHIP_RK4, true>(ta, batch, stream);
+  return launch_ftraj<ODEHIP_RK4, true>(ta, f->act, batch, stream);
 }
 
 // fused image of executed layer `e`: [tap][cb][mb][h][co32][8]
@@ -480,14 +498,16 @@ __global__ __launch_bounds__(256) void pack_fused_bf16_kernel(const float* __res
 int launch_fstack_bf16(const FusedArgs& fa_in, int batch, hipStream_t stream) {
   FusedArgs fa = fa_in;
   fa.last.debug = g_debug_flags;
+  typedef void (*Kernel)(const FusedArgs);
+  const Kernel kernels[4] = {fstack_bf16_kernel<false, kActRelu>, fstack_bf16_kernel<true, kActRelu>, fstack_bf16_kernel<false, kActTanh>,
+                             fstack_bf16_kernel<true, kActTanh>};
   static bool attr_set = false;
   if (!attr_set) {
-    ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)fstack_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)fstack_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    for (const Kernel k : kernels) ODEHIP_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set = true;
   }
-  if (fa.last.debug) hipLaunchKernelGGL(fstack_bf16_kernel<true>, dim3(batch), dim3(512), kFusedLds, stream, fa);
-  else hipLaunchKernelGGL(fstack_bf16_kernel<false>, dim3(batch), dim3(512), kFusedLds, stream, fa);
+  ODEHIP_REQUIRE(fa.act == kActRelu || fa.act == kActTanh, "fstack_bf16: activation code %d", fa.act);
+  hipLaunchKernelGGL(kernels[(fa.act == kActTanh ? 2 : 0) + (fa.last.debug ? 1 : 0)], dim3(batch), dim3(512), kFusedLds, stream, fa);
   ODEHIP_CHECK_HIP(hipGetLastError());
   return ODEHIP_OK;
 }

@@ -39,6 +39,9 @@ constexpr int kActTanh = 2;
 // reverse sweep of a Tanh head (combine 0 only, per-layer kernels only): the head's conv is evaluated again and
 // dst = bwd.mask_src * (1 - tanh(conv)^2), in place (dst == mask_src: the adjoint of f's output becomes that of the head's input)
 constexpr int kActTanhSeed = 3;
+// combine 2 of a layer whose forward conv ran in bf16 (epilogue() of the 32x32-accumulator kernels only): the Tanh derivative from
+// the saved output as that conv consumed it, dst = scale * acc * (1 - bf16(mask_src)^2)
+constexpr int kActTanhBf16 = 4;
 
 // ---- stage-combine epilogue of the LAST conv of f (Runge-Kutta bookkeeping fused in) -------
 // k_cur = conv output.  Optional outputs, all Q4 unless stated:
@@ -162,8 +165,10 @@ struct FusedArgs {
   const void* w_fused;                     // [layer][tap][cb 4][mb 2][lane 64][8] bf16, execution order
   const float* bias[ODEHIP_MAX_LAYERS];    // per executed layer (null: none)
   float* store[ODEHIP_MAX_LAYERS];         // fp32 Q4 output of executed layer e < n-1 (null: not stored)
-  const float* mask[ODEHIP_MAX_LAYERS];    // e < n-1: null -> ReLU, else output *= (mask > 0)
+  const float* mask[ODEHIP_MAX_LAYERS];    // e < n-1: null -> the activation, else its derivative from the saved output `mask`:
+                                           // output *= (mask > 0), or with act == kActTanh output *= 1 - bf16(mask)^2
   int n_layers;
+  int act;                                 // hidden activation: kActRelu or kActTanh
   ConvArgs last;                           // epilogue of the last executed layer (qout = 16)
 };
 int launch_fstack_bf16(const FusedArgs& fa, int batch, hipStream_t stream);

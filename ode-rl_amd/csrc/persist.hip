@@ -67,7 +67,7 @@ static bool persist_available() {
 //    written in order 1 (the adaptive solver's drivers)
 static int persist_layer_kind(const ConvArgs& a) {
   if (a.combine == 4 || a.combine == 5) return a.qout == 16 && !a.src2 ? 3 : 0;   // elementwise / norm rows
-  if (a.act == kActTanhSeed) return 0;   // per-layer kernels only
+  if (a.act == kActTanhSeed || a.act == kActTanhBf16) return 0;   // per-layer kernels only
   if (!a.w_wino || a.w_bf16 || a.src2 || a.q1 != a.qin || a.combine < 0 || a.combine > 3) return 0;
   if (a.qin == 16 && a.qout == 16) return (a.combine == 1 && a.cmb.order == 1) ? 3 : 1;
   if ((a.qin == 32 && a.qout == 16) || (a.qin == 16 && a.qout == 32)) return 2;

@@ -218,6 +218,19 @@ def set_compute_dtype(mode):
     _global_mode = mode
 
 
+# Tanh hidden layers in bf16 mode are opt-in: what a Tanh stack did there before -- TypeError at dispatch -- stays the default, and
+# the derivative they get is a rule of this mode (1 - bf16(y)^2 with y the Tanh output as the next conv consumed it), not what
+# autograd forms from the fp32 y.
+_bf16_tanh = False
+
+
+def set_bf16_tanh(enabled):
+    """Let stacks with Tanh hidden layers (no Tanh head) run in bf16 compute mode; returns the previous setting."""
+    global _bf16_tanh
+    was, _bf16_tanh = _bf16_tanh, bool(enabled)
+    return was
+
+
 def current_compute_dtype():
     forced = getattr(_forced, "mode", None)
     if forced is not None:
@@ -318,15 +331,23 @@ class PackedConvStack:
 
     @property
     def relu_only(self):
-        """ReLU between the convs and no Tanh head: the only stacks the bf16 kernels implement."""
+        """ReLU between the convs and no Tanh head."""
         return self.act == _lib.ACT_RELU and not self.final_tanh
+
+    @property
+    def headless(self):
+        """No Tanh head, ReLU or Tanh between the convs: the stacks the bf16 kernels implement."""
+        return self.act in (_lib.ACT_RELU, _lib.ACT_TANH) and not self.final_tanh
 
     def refresh(self, mode=None):
         mode = mode or current_compute_dtype()
-        if mode == "bf16" and not self.relu_only:   # checked per call: the compute dtype can change between calls on a cached stack
-            raise TypeError("bf16 compute (set_compute_dtype('bf16') or autocast) supports ReLU dynamics without a Tanh head only; "
-                            "this stack has " + ("Tanh hidden layers" if self.act != _lib.ACT_RELU else "a Tanh head") +
-                            ": run it in fp32")
+        if mode == "bf16" and not self.headless:   # checked per call: the compute dtype can change between calls on a cached stack
+            raise TypeError("bf16 compute (set_compute_dtype('bf16') or autocast) supports dynamics without a Tanh head only "
+                            "(final_act=False); this stack has a Tanh head: run it in fp32")
+        if mode == "bf16" and self.act == _lib.ACT_TANH and not _bf16_tanh:   # (per call as well: the switch can change)
+            raise TypeError("bf16 compute (set_compute_dtype('bf16') or autocast) runs Tanh dynamics only once they are switched on with "
+                            "set_bf16_tanh(True): their derivative is then 1 - bf16(y)^2, not autograd's "
+                            "1 - y^2.  Switch them on, or run this stack in fp32")
         stamp = self._current_stamp()
         ent = self._cache.get(mode)
         if ent is not None and ent["stamp"] == stamp:
@@ -364,7 +385,7 @@ class PackedConvStack:
         bf16 = [pack_conv_weight_bf16(c.weight, transpose_flip) if mode == "bf16" and _bf16_ok(ci, co, ks) else None
                 for c, ci, co in zip(convs, cin, cout)]
         fused = (pack_fused_bf16(convs, reverse_transposed=transpose_flip)
-                 if mode == "bf16" and self.relu_only and _fusable(convs, ks) else None)
+                 if mode == "bf16" and self.headless and _fusable(convs, ks) else None)
         d = _lib.ConvStack()
         d.w_fused = fused.data_ptr() if fused is not None else None
         d.n_convs = len(convs)

@@ -326,6 +326,7 @@ class VidODE(nn.Module):
         if out_sel is not None and out_sel.size(1) == sol_y.size(1):
             sol_y = sol_y[out_sel.to(dev).squeeze(-1).bool()].view(b, n_pred, *sol_y.shape[2:])
         pred_outputs = torch.cat(self.get_flowmaps(sol_out=sol_y[:, :n_pred], first_prev_embed=skip_conn_embed, mask=None), dim=1)
+        pred_outputs = pred_outputs.float()   # under autocast the decoder's library convs hand over bf16; the warp and the loss take fp32
         pred_x, warped, masks = self._warp(pred_outputs, start)
         nc = self.opt.input_dim
         extra_info = {"optical_flow": pred_outputs[:, :, :2, ...], "warped_pred_x": warped,
