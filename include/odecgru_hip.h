@@ -996,6 +996,44 @@ int odehip_grid_emit(const float* grid_states, float* out, const int* first, con
 int odehip_grid_scatter(const float* grad_out, float* grad_grid, const int* first, const float* slope, const int* exact, int n_grid,
                         int n_times, long long state_floats, void* table_dev, size_t table_bytes, void* stream);
 
+/* Gradients through NEGATED solves: what torchdiffeq differentiates when t is strictly DEcreasing (it solves dz/ds = -f(z) on
+ * s = -t; the host passes -t, increasing, as for negate != 0 above).  A Runge-Kutta step sees the dynamics only as the product
+ * h * f, so the negated solve IS the plain solver run with the step sizes -h, and every backward pass below is the existing one with
+ * that sign on its step sizes: the same launches, tables and kernels, the sign is data (the forward keeps k_scale = -1 on +h, the
+ * reverse sweeps read -h wherever a slope's seed, a weight gradient's weight or a recomputed stage is formed).  fp32 stacks only
+ * (no bf16 image: ODEHIP_EINVAL); every other limit, the workspace sizes and the argument checks -- before any HIP call -- are those
+ * of the entry named.  The entries above are unchanged, their refusals included.  Pure additions: ODEHIP_ABI_VERSION stays.
+ *   odehip_odeint_fixed_negated_saving      odehip_odeint_fixed(save_for_backward = 1, negate = 1); saved format 0
+ *   odehip_odeint_fixed_negated_backward    odehip_odeint_fixed_backward on that workspace (it re-uploads the step sizes, signed)
+ *   odehip_odeint_adjoint_backward_negated  odehip_odeint_adjoint_backward for a trajectory of the negated solve: interval i runs
+ *                                           from -t[i] back to -t[i-1] on the negation of the negated dynamics, plain f
+ *   odehip_odeint_adaptive_saving_negated   odehip_odeint_adaptive_saving of the negated dynamics: the attempts, the controller and
+ *                                           its accept / reject decisions are odehip_odeint_adaptive(negate = 1)'s
+ *   odehip_odeint_adaptive_backward_negated, _backward_saved_negated   the two backward passes of the accepted steps of such a solve
+ *                                           (accepted_host: the log as reported, dt > 0 on s) */
+int odehip_odeint_fixed_negated_saving(const odehip_convstack* f, int method, const float* z0_nchw, const double* t_host, int n_times,
+                                       int batch, float* out_nchw, void* workspace, size_t workspace_bytes, void* stream);
+int odehip_odeint_fixed_negated_backward(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method, const double* t_host,
+                                         int n_times, int batch, const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w,
+                                         float* const* grad_b, void* workspace, size_t workspace_bytes, void* stream);
+int odehip_odeint_adjoint_backward_negated(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method, const double* t_host,
+                                           int n_times, int batch, const float* y_traj_nchw, const float* grad_out_nchw,
+                                           float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, void* workspace,
+                                           size_t workspace_bytes, void* stream);
+int odehip_odeint_adaptive_saving_negated(int method, const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times,
+                                          int batch, float rtol, float atol, double first_step, int max_steps, float* out_nchw,
+                                          int* stats_host, double* accepted_host, int accepted_cap, int max_accept, int* saved_out,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+int odehip_odeint_adaptive_backward_negated(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host,
+                                            int n_times, int batch, const double* accepted_host, int n_steps, const float* z0_nchw,
+                                            const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w, float* const* grad_b,
+                                            void* workspace, size_t workspace_bytes, void* stream);
+int odehip_odeint_adaptive_backward_saved_negated(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad,
+                                                  const double* t_host, int n_times, int batch, const double* accepted_host, int n_steps,
+                                                  const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w,
+                                                  float* const* grad_b, int max_accept, void* saved_workspace,
+                                                  size_t saved_workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -392,6 +392,15 @@ def _with_method():
     for head in ("", "_saving", "_backward"):
         res, args = S["odehip_dopri5%s_workspace_bytes" % head]
         S["odehip_adaptive%s_workspace_bytes" % head] = (res, list(args) + [ctypes.c_int])
+    # gradients through negated solves (decreasing t): the signatures of the entries they mirror, the fixed-grid pair without the
+    # arguments that are constants there (save_for_backward, negate, saved_format)
+    for tail in ("_saving", "_backward", "_backward_saved"):
+        S["odehip_odeint_adaptive%s_negated" % tail] = S["odehip_odeint_adaptive" + tail]
+    S["odehip_odeint_adjoint_backward_negated"] = S["odehip_odeint_adjoint_backward"]
+    res, args = S["odehip_odeint_fixed"]
+    S["odehip_odeint_fixed_negated_saving"] = (res, list(args[:7]) + list(args[9:11]) + [args[12]])
+    res, args = S["odehip_odeint_fixed_backward"]
+    S["odehip_odeint_fixed_negated_backward"] = (res, list(args[:10]) + list(args[11:]))
 
 
 _with_method()

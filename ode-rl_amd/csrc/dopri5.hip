@@ -633,6 +633,26 @@ extern "C" int odehip_odeint_adaptive_saving(int method, const odehip_convstack*
   return dopri5_forward(method, f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, 0, out_nchw, stats_host, accepted_host,
                         accepted_cap, workspace, workspace_bytes, stream_, max_accept, saved_out);
 }
+// The saving forward of the NEGATED dynamics (a strictly decreasing t; t_host is -t): dopri5_forward(negate = 1) writing its stage
+// inputs and hidden activations into the slots.  The attempts, their error norms and the controller are those of
+// odehip_odeint_adaptive(negate = 1) -- only where a row stores differs -- so both make the same accept / reject decisions.  The
+// slots hold nothing that carries the sign; the backward passes take it on their step sizes (dopri5_backward.hip).
+extern "C" int odehip_odeint_adaptive_saving_negated(int method, const odehip_convstack* f, const float* z0_nchw, const double* t_host,
+                                                     int n_times, int batch, float rtol, float atol, double first_step, int max_steps,
+                                                     float* out_nchw, int* stats_host, double* accepted_host, int accepted_cap,
+                                                     int max_accept, int* saved_out, void* workspace, size_t workspace_bytes,
+                                                     void* stream_) {
+  const char* const mname = adaptive_name(method);
+  ODEHIP_REQUIRE(saved_out && max_accept > 0, "odeint_%s_saving_negated: saved_out is required and max_accept must be positive", mname);
+  *saved_out = 0;
+  ODEHIP_REQUIRE(adaptive_tableau(method), "odeint_adaptive_saving_negated: unknown adaptive method code %d", method);
+  const int rc = check_fp32_stacks(f, nullptr, "odeint_adaptive_saving_negated");
+  if (rc != ODEHIP_OK) return rc;
+  ODEHIP_REQUIRE(workspace_bytes >= odehip_adaptive_saving_workspace_bytes(f, batch, n_times, max_accept, method),
+                 "odeint_%s_saving_negated: workspace too small", mname);
+  return dopri5_forward(method, f, z0_nchw, t_host, n_times, batch, rtol, atol, first_step, max_steps, 1, out_nchw, stats_host, accepted_host,
+                        accepted_cap, workspace, workspace_bytes, stream_, max_accept, saved_out);
+}
 extern "C" int odehip_odeint_dopri5_saving(const odehip_convstack* f, const float* z0_nchw, const double* t_host, int n_times,
                                            int batch, float rtol, float atol, double first_step, int max_steps, float* out_nchw,
                                            int* stats_host, double* accepted_host, int accepted_cap, int max_accept, int* saved_out,

@@ -48,7 +48,7 @@ extern "C" size_t odehip_dopri5_backward_workspace_bytes(const odehip_convstack*
 static int dopri5_backward(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host, int n_times, int batch,
                            const double* accepted_host, int n_steps, const float* z0_nchw, const float* grad_out_nchw,
                            float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, void* workspace, size_t workspace_bytes,
-                           void* stream_, int layout_steps, bool saved);
+                           void* stream_, int layout_steps, bool saved, float sign = 1.0f);
 
 extern "C" int odehip_odeint_dopri5_backward(const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host,
                                              int n_times, int batch, const double* accepted_host, int n_steps,
@@ -94,10 +94,46 @@ extern "C" int odehip_odeint_adaptive_backward_saved(int method, const odehip_co
                          bws, saved_workspace_bytes - (size_t)(bws - (char*)saved_workspace), stream_, max_accept, true);
 }
 
+// The two backward passes of a NEGATED solve (odehip_odeint_adaptive(negate = 1) or odehip_odeint_adaptive_saving_negated; t_host is
+// -t, the log as the controller reported it).  Y_s = y0 + h sum_j beta_sj (-f(Y_j)) is f stepped by -h: sign = -1 puts -h where the
+// re-integration steps and where a seed takes its h; the saved slots, the dense-output abscissas and the rows without h are the same.
+extern "C" int odehip_odeint_adaptive_backward_negated(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad,
+                                                       const double* t_host, int n_times, int batch, const double* accepted_host,
+                                                       int n_steps, const float* z0_nchw, const float* grad_out_nchw, float* grad_z0_nchw,
+                                                       float* const* grad_w, float* const* grad_b, void* workspace, size_t workspace_bytes,
+                                                       void* stream_) {
+  const char* const mname = adaptive_name(method);
+  ODEHIP_REQUIRE(z0_nchw, "odeint_%s_backward_negated: null pointer", mname);
+  ODEHIP_REQUIRE(f_dgrad, "odeint_%s_backward_negated: null stack", mname);
+  const int rc = check_fp32_stacks(f, f_dgrad, "odeint_adaptive_backward_negated");
+  if (rc != ODEHIP_OK) return rc;
+  return dopri5_backward(method, f, f_dgrad, t_host, n_times, batch, accepted_host, n_steps, z0_nchw, grad_out_nchw, grad_z0_nchw, grad_w, grad_b,
+                         workspace, workspace_bytes, stream_, n_steps, false, -1.0f);
+}
+
+extern "C" int odehip_odeint_adaptive_backward_saved_negated(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad,
+                                                             const double* t_host, int n_times, int batch, const double* accepted_host,
+                                                             int n_steps, const float* grad_out_nchw, float* grad_z0_nchw,
+                                                             float* const* grad_w, float* const* grad_b, int max_accept,
+                                                             void* saved_workspace, size_t saved_workspace_bytes, void* stream_) {
+  const char* const mname = adaptive_name(method);
+  ODEHIP_REQUIRE(adaptive_tableau(method), "odeint_adaptive_backward_saved_negated: unknown adaptive method code %d", method);
+  ODEHIP_REQUIRE(f_dgrad, "odeint_%s_backward_saved_negated: null stack", mname);
+  const int rc = check_fp32_stacks(f, f_dgrad, "odeint_adaptive_backward_saved_negated");
+  if (rc != ODEHIP_OK) return rc;
+  ODEHIP_REQUIRE(saved_workspace && max_accept > 0 && n_steps >= 1 && n_steps <= max_accept,
+                 "odeint_%s_backward_saved_negated: needs the saving forward's workspace and 1 <= n_steps <= max_accept", mname);
+  ODEHIP_REQUIRE(saved_workspace_bytes >= odehip_adaptive_saving_workspace_bytes(f, batch, n_times, max_accept, method),
+                 "odeint_%s_backward_saved_negated: workspace smaller than the saving forward's", mname);
+  char* bws = (char*)saved_workspace + al256(odehip_adaptive_workspace_bytes(f, batch, n_times, method));
+  return dopri5_backward(method, f, f_dgrad, t_host, n_times, batch, accepted_host, n_steps, nullptr, grad_out_nchw, grad_z0_nchw, grad_w, grad_b,
+                         bws, saved_workspace_bytes - (size_t)(bws - (char*)saved_workspace), stream_, max_accept, true, -1.0f);
+}
+
 static int dopri5_backward(int method, const odehip_convstack* f, const odehip_convstack* f_dgrad, const double* t_host, int n_times, int batch,
                            const double* accepted_host, int n_steps, const float* z0_nchw, const float* grad_out_nchw,
                            float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, void* workspace, size_t workspace_bytes,
-                           void* stream_, int layout_steps, bool saved) {
+                           void* stream_, int layout_steps, bool saved, float sign) {
   const Tableau* tbp = adaptive_tableau(method);
   ODEHIP_REQUIRE(tbp, "odeint_adaptive_backward: unknown adaptive method code %d (ODEHIP_DOPRI5 or ODEHIP_BOSH3)", method);
   const Tableau& tb = *tbp;
@@ -161,7 +197,7 @@ static int dopri5_backward(int method, const odehip_convstack* f, const odehip_c
   }
   {
     std::vector<float> hs(N);
-    for (int n = 0; n < N; ++n) hs[n] = (float)accepted_host[2 * n + 1];
+    for (int n = 0; n < N; ++n) hs[n] = sign * (float)accepted_host[2 * n + 1];   // what the re-integration steps by
     if ((rc = upload_floats(hdev, hs.data(), N, stream)) != ODEHIP_OK) return rc;
   }
 
@@ -270,7 +306,7 @@ static int dopri5_backward(int method, const odehip_convstack* f, const odehip_c
   std::vector<float> cf;
   for (int n = N - 1; n >= 0; --n) {
     const double t0 = accepted_host[2 * n], t1 = t0 + accepted_host[2 * n + 1];
-    const float h = (float)accepted_host[2 * n + 1];
+    const float h = sign * (float)accepted_host[2 * n + 1];   // every seed below is proportional to h; x is a ratio of times and is not
     const int nout = j_hi[n] - j_lo[n];
     std::vector<float> W((size_t)nout * S);
     for (int i = 0; i < nout; ++i) {

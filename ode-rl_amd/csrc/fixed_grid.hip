@@ -154,9 +154,20 @@ static int wgrad_all_layers(const odehip_convstack* f, const FixedLayout& L, voi
   return ODEHIP_OK;
 }
 
-// step sizes: dt = t1 - t0 in float64, rounded to fp32 when it meets the state (torchdiffeq semantics)
-static void fill_step_sizes(float* hbuf, const double* t_host, int n_times) {
-  for (int i = 0; i + 1 < n_times; ++i) hbuf[i] = (float)(t_host[i + 1] - t_host[i]);
+// step sizes: dt = t1 - t0 in float64, rounded to fp32 when it meets the state (torchdiffeq semantics).  sign = -1: the backward
+// passes of a NEGATED solve.  A Runge-Kutta step sees the dynamics only as h * f, so dz/ds = -f(z) stepped by h is f stepped by -h:
+// with -h in the step-size buffers every seed of a slope (all of them proportional to h), every weight of a weight gradient and
+// every recomputed stage carries the sign of the negated dynamics, and the rows without h (gy += gx) carry none -- as they must
+static void fill_step_sizes(float* hbuf, const double* t_host, int n_times, float sign = 1.0f) {
+  for (int i = 0; i + 1 < n_times; ++i) hbuf[i] = sign * (float)(t_host[i + 1] - t_host[i]);
+}
+
+// the stacks the backward passes take (f checked by check_common)
+static int check_backward_stack(const odehip_convstack* f, const char* who) {
+  for (int l = 0; l <= f->n_convs; ++l)
+    ODEHIP_REQUIRE(f->channels[l] % 64 == 0, "%s: channel counts must be multiples of 64 (channels[%d] = %d)", who, l, f->channels[l]);
+  ODEHIP_REQUIRE(f->ks == 3, "%s: 3x3 dynamics only", who);
+  return ODEHIP_OK;
 }
 
 // The CombineArgs of stage s from its plan: `base` carries y, h_ptr and k_scale, k[j] is where k_j is kept, x_next the next stage's
@@ -212,17 +223,20 @@ static bool bf16_trajectory_ok(const odehip_convstack* f, int method) {
   return is_fixed_method(method);
 }
 
-extern "C" int odehip_odeint_fixed(const odehip_convstack* f, int method, const float* z0_nchw, const double* t_host,
-                                   int n_times, int batch, float* out_nchw, int save_for_backward, int negate,
-                                   void* workspace, size_t workspace_bytes, int* saved_format_out, void* stream_) {
+// who: the entry's name in its messages.  negated_saving: the caller is odehip_odeint_fixed_negated_saving, whose backward carries
+// the sign; its stack must be one the backward takes (fp32 images, 3x3, channel counts that are multiples of 64)
+static int fixed_forward(const odehip_convstack* f, int method, const float* z0_nchw, const double* t_host, int n_times, int batch,
+                         float* out_nchw, int save_for_backward, int negate, void* workspace, size_t workspace_bytes,
+                         int* saved_format_out, void* stream_, const char* who, bool negated_saving) {
   if (saved_format_out) *saved_format_out = 0;
-  int rc = check_common(f, method, t_host, n_times, batch, "odeint_fixed");
-  ODEHIP_REQUIRE(!(negate && save_for_backward), "odeint_fixed: backward through negated dynamics is not supported");
+  int rc = check_common(f, method, t_host, n_times, batch, who);
+  ODEHIP_REQUIRE(negated_saving || !(negate && save_for_backward), "%s: backward through negated dynamics is not supported", who);
   if (rc != ODEHIP_OK) return rc;
-  ODEHIP_REQUIRE(z0_nchw && out_nchw && workspace, "odeint_fixed: null pointer");
-  ODEHIP_REQUIRE(saved_format_out || !save_for_backward, "odeint_fixed: saved_format_out is required with save_for_backward");
+  if (negated_saving && ((rc = check_fp32_stacks(f, nullptr, who)) != ODEHIP_OK || (rc = check_backward_stack(f, who)) != ODEHIP_OK)) return rc;
+  ODEHIP_REQUIRE(z0_nchw && out_nchw && workspace, "%s: null pointer", who);
+  ODEHIP_REQUIRE(saved_format_out || !save_for_backward, "%s: saved_format_out is required with save_for_backward", who);
   const FixedLayout L(f, batch, n_times, method, save_for_backward);
-  ODEHIP_REQUIRE(workspace_bytes >= L.total, "odeint_fixed: workspace too small (%zu < %zu)", workspace_bytes, L.total);
+  ODEHIP_REQUIRE(workspace_bytes >= L.total, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, L.total);
   hipStream_t stream = (hipStream_t)stream_;
   void* ws = workspace;
   const size_t st_b = (size_t)batch * L.C * kPix * 4, st_f = st_b / 4;
@@ -297,6 +311,13 @@ extern "C" int odehip_odeint_fixed(const odehip_convstack* f, int method, const 
   return rc != ODEHIP_OK ? rc : rc2;
 }
 
+extern "C" int odehip_odeint_fixed(const odehip_convstack* f, int method, const float* z0_nchw, const double* t_host,
+                                   int n_times, int batch, float* out_nchw, int save_for_backward, int negate,
+                                   void* workspace, size_t workspace_bytes, int* saved_format_out, void* stream_) {
+  return fixed_forward(f, method, z0_nchw, t_host, n_times, batch, out_nchw, save_for_backward, negate, workspace, workspace_bytes,
+                       saved_format_out, stream_, "odeint_fixed", false);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // What the two backward entries (reverse sweep, adjoint) share: the argument checks, the trivial one-time call, the input-gradient
 // chain of one evaluation, and the tail behind the sweep.
@@ -308,9 +329,7 @@ static int check_backward_args(const odehip_convstack* f, const odehip_convstack
   int rc = check_common(f, method, t_host, n_times, batch, who);
   if (rc != ODEHIP_OK) return rc;
   ODEHIP_REQUIRE(f_dgrad && pointers && grad_w && grad_b, "%s: null pointer", who);
-  for (int l = 0; l <= f->n_convs; ++l)
-    ODEHIP_REQUIRE(f->channels[l] % 64 == 0, "%s: channel counts must be multiples of 64 (channels[%d] = %d)", who, l, f->channels[l]);
-  ODEHIP_REQUIRE(f->ks == 3, "%s: 3x3 dynamics only", who);
+  if ((rc = check_backward_stack(f, who)) != ODEHIP_OK) return rc;
   for (int l = 0; l < f->n_convs; ++l)
     ODEHIP_REQUIRE(f_dgrad->w_packed[l] && grad_w[l] && grad_b[l], "%s: layer %d has null pointers", who, l);
   return ODEHIP_OK;
@@ -373,16 +392,16 @@ struct BackwardPass {
 
 // ---------------------------------------------------------------------------------------------------------------
 // Backward of odehip_odeint_fixed(save_for_backward = 1) on the SAME workspace.
-extern "C" int odehip_odeint_fixed_backward(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method,
-                                            const double* t_host, int n_times, int batch, const float* grad_out_nchw,
-                                            float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, int saved_format,
-                                            void* workspace, size_t workspace_bytes, void* stream_) {
-  int rc = check_backward_args(f, f_dgrad, method, t_host, n_times, batch, grad_out_nchw && grad_z0_nchw && workspace, grad_w, grad_b,
-                               "odeint_fixed_backward");
+// sign = -1: the forward was the negated saving solve (fill_step_sizes)
+static int fixed_backward(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method, const double* t_host, int n_times,
+                          int batch, const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w, float* const* grad_b,
+                          int saved_format, void* workspace, size_t workspace_bytes, void* stream_, float sign, const char* who) {
+  int rc = check_backward_args(f, f_dgrad, method, t_host, n_times, batch, grad_out_nchw && grad_z0_nchw && workspace, grad_w, grad_b, who);
   if (rc != ODEHIP_OK) return rc;
-  ODEHIP_REQUIRE(saved_format == 0 || saved_format == 1, "odeint_fixed_backward: unknown saved format %d", saved_format);
+  if (sign < 0.0f && (rc = check_fp32_stacks(f, f_dgrad, who)) != ODEHIP_OK) return rc;
+  ODEHIP_REQUIRE(saved_format == 0 || saved_format == 1, "%s: unknown saved format %d", who, saved_format);
   const FixedLayout L(f, batch, n_times, method, 1);
-  ODEHIP_REQUIRE(workspace_bytes >= L.total, "odeint_fixed_backward: workspace too small");
+  ODEHIP_REQUIRE(workspace_bytes >= L.total, "%s: workspace too small", who);
   hipStream_t stream = (hipStream_t)stream_;
   void* ws = workspace;
   const int NH = L.NH, S = L.S, NL = f->n_convs;
@@ -478,7 +497,9 @@ extern "C" int odehip_odeint_fixed_backward(const odehip_convstack* f, const ode
   if (rc != ODEHIP_OK) return rc;
   BackwardPass bp = {f, f_dgrad, L, ws, n_times, batch, grad_z0_nchw, grad_w, grad_b, stream, {}};
   if (n_times == 1) return bp.trivial(grad_out_nchw);
-  fill_step_sizes(bp.hbuf, t_host, n_times);
+  fill_step_sizes(bp.hbuf, t_host, n_times, sign);
+  // the forward left +h on the device (its combines carry k_scale = -1); the rows of this sweep read h through h_ptr
+  if (sign < 0.0f && (rc = upload_floats(hdev, bp.hbuf, n_times - 1, stream)) != ODEHIP_OK) return rc;
 
   const FixedTableau& tab = fixed_tableau(method);
   FixedTargets plan[kFixedMaxStages];
@@ -522,6 +543,34 @@ extern "C" int odehip_odeint_fixed_backward(const odehip_convstack* f, const ode
   return bp.finish(persist, rc, g, nullptr, nullptr);
 }
 
+extern "C" int odehip_odeint_fixed_backward(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method,
+                                            const double* t_host, int n_times, int batch, const float* grad_out_nchw,
+                                            float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, int saved_format,
+                                            void* workspace, size_t workspace_bytes, void* stream_) {
+  return fixed_backward(f, f_dgrad, method, t_host, n_times, batch, grad_out_nchw, grad_z0_nchw, grad_w, grad_b, saved_format, workspace,
+                        workspace_bytes, stream_, 1.0f, "odeint_fixed_backward");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// A negated solve under autograd (a strictly decreasing t: the caller passes -t).  The forward is odehip_odeint_fixed(negate = 1)
+// with every activation kept; the backward is the reverse sweep above with -h for h.  The channel limits of the backward are
+// checked by the forward already, so that a solve whose gradient cannot be formed stops before it runs.
+extern "C" int odehip_odeint_fixed_negated_saving(const odehip_convstack* f, int method, const float* z0_nchw, const double* t_host,
+                                                  int n_times, int batch, float* out_nchw, void* workspace, size_t workspace_bytes,
+                                                  void* stream_) {
+  int fmt = 0;
+  return fixed_forward(f, method, z0_nchw, t_host, n_times, batch, out_nchw, 1, 1, workspace, workspace_bytes, &fmt, stream_,
+                       "odeint_fixed_negated_saving", true);
+}
+
+extern "C" int odehip_odeint_fixed_negated_backward(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method,
+                                                    const double* t_host, int n_times, int batch, const float* grad_out_nchw,
+                                                    float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, void* workspace,
+                                                    size_t workspace_bytes, void* stream_) {
+  return fixed_backward(f, f_dgrad, method, t_host, n_times, batch, grad_out_nchw, grad_z0_nchw, grad_w, grad_b, 0, workspace,
+                        workspace_bytes, stream_, -1.0f, "odeint_fixed_negated_backward");
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Adjoint backward (torchdiffeq `odeint_adjoint` semantics, _impl/adjoint.py; NEW capability -- the reference itself
 // never uses it: modules/DiffEqSolver.py:9).  For i = T-1 .. 1 the augmented state (y, a_y, a_theta) is integrated
@@ -544,7 +593,7 @@ namespace odehip {
 static int adjoint_sweep(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method, const double* grid_host, int n_grid,
                          const int* out_index, int n_times, int batch, const float* y_traj_nchw, const float* grad_out_nchw,
                          float* grad_z0_nchw, float* const* grad_w, float* const* grad_b, void* ws, const FixedLayout& L,
-                         size_t off_traj, hipStream_t stream) {
+                         size_t off_traj, hipStream_t stream, float sign = 1.0f) {
   const int NH = L.NH, S = L.S, NL = f->n_convs;
   float* hdev = L.p(ws, L.off_h);
   float *ping = L.p(ws, L.off_ping), *pong = L.p(ws, L.off_pong);
@@ -557,7 +606,9 @@ static int adjoint_sweep(const odehip_convstack* f, const odehip_convstack* f_dg
   if (rc != ODEHIP_OK) return rc;
   BackwardPass bp = {f, f_dgrad, L, ws, n_grid, batch, grad_z0_nchw, grad_w, grad_b, stream, {}};
   if (n_grid == 1) return bp.trivial(grad_out_nchw);
-  fill_step_sizes(bp.hbuf, grid_host, n_grid);   // dt of the flipped grid, > 0
+  // dt of the flipped grid, > 0.  sign = -1: the trajectory is a negated solve's; the negation (k_scale below) of the negated
+  // dynamics is plain f, and with -dt in hdev and in the weights of the weight gradients all three parts of the state follow
+  fill_step_sizes(bp.hbuf, grid_host, n_grid, sign);
   rc = upload_floats(hdev, bp.hbuf, n_grid - 1, stream);
   if (rc != ODEHIP_OK) return rc;
 
@@ -639,6 +690,23 @@ extern "C" int odehip_odeint_adjoint_backward(const odehip_convstack* f, const o
   ODEHIP_REQUIRE((n_times - 1) * L.S <= kMaxWgradEvals, "odeint_adjoint_backward: too many evaluations (%d)", (n_times - 1) * L.S);
   return adjoint_sweep(f, f_dgrad, method, t_host, n_times, nullptr, n_times, batch, y_traj_nchw, grad_out_nchw, grad_z0_nchw, grad_w,
                        grad_b, workspace, L, L.off_y, (hipStream_t)stream_);
+}
+
+// The adjoint backward of a NEGATED solve's trajectory (a strictly decreasing t; t_host is -t).  Workspace as above.
+extern "C" int odehip_odeint_adjoint_backward_negated(const odehip_convstack* f, const odehip_convstack* f_dgrad, int method,
+                                                      const double* t_host, int n_times, int batch, const float* y_traj_nchw,
+                                                      const float* grad_out_nchw, float* grad_z0_nchw, float* const* grad_w,
+                                                      float* const* grad_b, void* workspace, size_t workspace_bytes, void* stream_) {
+  const char* who = "odeint_adjoint_backward_negated";
+  int rc = check_backward_args(f, f_dgrad, method, t_host, n_times, batch, y_traj_nchw && grad_out_nchw && grad_z0_nchw && workspace,
+                               grad_w, grad_b, who);
+  if (rc != ODEHIP_OK) return rc;
+  if ((rc = check_fp32_stacks(f, f_dgrad, who)) != ODEHIP_OK) return rc;
+  const FixedLayout L(f, batch, n_times, method, 1);
+  ODEHIP_REQUIRE(workspace_bytes >= L.total, "%s: workspace too small", who);
+  ODEHIP_REQUIRE((n_times - 1) * L.S <= kMaxWgradEvals, "%s: too many evaluations (%d)", who, (n_times - 1) * L.S);
+  return adjoint_sweep(f, f_dgrad, method, t_host, n_times, nullptr, n_times, batch, y_traj_nchw, grad_out_nchw, grad_z0_nchw, grad_w,
+                       grad_b, workspace, L, L.off_y, (hipStream_t)stream_, -1.0f);
 }
 
 extern "C" size_t odehip_odeint_adjoint_grid_workspace_bytes(const odehip_convstack* f, int batch, int n_times, int n_grid, int method) {

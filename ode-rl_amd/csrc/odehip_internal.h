@@ -214,6 +214,15 @@ inline bool step_is_observed(const unsigned char* step_observed_host, int frame)
 // Q4 state (B,hidden) -> the NCHW latent slot of a step whose cell did not run (convgru.hip)
 void launch_state_to_latent(const float* h, float* h_out_nchw, long long nchw_batch_stride, int hidden, int batch, hipStream_t stream);
 int upload_floats(float* dst, const float* src, int n, hipStream_t stream);  // scalars travel as kernel arguments (async)
+// the entries that differentiate NEGATED solves (fixed_grid.hip, dopri5.hip, dopri5_backward.hip) take fp32 images only: no layer of
+// f, or of f_dgrad where there is one, may carry a bf16 image
+inline int check_fp32_stacks(const odehip_convstack* f, const odehip_convstack* f_dgrad, const char* who) {
+  ODEHIP_REQUIRE(f, "%s: null stack", who);
+  ODEHIP_REQUIRE(!f->w_fused && !(f_dgrad && f_dgrad->w_fused), "%s: fp32 stacks only (the stack carries a fused bf16 image)", who);
+  for (int l = 0; l < f->n_convs && l < ODEHIP_MAX_LAYERS; ++l)
+    ODEHIP_REQUIRE(!f->w_bf16[l] && !(f_dgrad && f_dgrad->w_bf16[l]), "%s: fp32 stacks only (layer %d carries a bf16 image)", who, l);
+  return ODEHIP_OK;
+}
 // f(x) with the stage combine fused into the last conv; `hidden` (n_convs-1 buffers) keeps the ReLU outputs for a backward pass
 int enqueue_f(const odehip_convstack* f, const float* x_q4, int batch, float* ping, float* pong, const CombineArgs* cmb,
               float* plain_dst, const int* skip, hipStream_t stream);

@@ -113,6 +113,9 @@ SED[second_pass_skipped]='s/b < pa.batch; b += 2 \* n_groups)/b < pa.batch; b +=
 # backward grids, lives in the binding (PYSED below)
 SED[grid_adjoint_resets_interior_y]='s/output_of(p) >= 0 ? L.p(ws, off_traj + (size_t)output_of(p) \* L.st) : L.y(ws, p); };/output_of(p) >= 0 ? L.p(ws, off_traj + (size_t)output_of(p) * L.st) : L.p(ws, off_traj + (size_t)(n_times - 1) * L.st); };/'   # inside an interval y comes from the stored trajectory (its last frame), not from the solver
 SED[grid_adjoint_interior_grad_out]='s/      const float\* go = interior ? nullptr : L.go(ws, output_of(n));/      const float* go = L.go(ws, interior ? 0 : output_of(n));/'   # a_y takes a grad_out frame at interior points too
+# ---- gradients through negated solves (a decreasing t): the reverse sweep's seeds lose their -1 -- the step sizes of the backward
+# passes go unsigned (fixed_grid.hip: fill_step_sizes), the increasing case is untouched -- MUT_TESTS="tests/test_hip_reverse_time.py" (profiles/mutation_reverse_time.txt)
+SED[reverse_time_seed_sign]='s/hbuf\[i\] = sign \* (float)(t_host\[i + 1\] - t_host\[i\]);/hbuf[i] = (float)(t_host[i + 1] - t_host[i]);/'
 # mutants of the Python binding, "file|sed script": applied to the tree's own file for the run and restored afterwards (run only)
 declare -A PYSED
 PYSED[grid_adjoint_anchored_low]='ode-rl_amd/hip_ops.py|s/^        pair = torch.stack(\[-th\[i\], -th\[i - 1\]\])$/        pair = torch.stack([th[i - 1], th[i]])/;s/^        points.append(-sub\[1:\])$/        points.append(sub[:-1].flip(0))/'   # the sub-steps of a backward interval anchored at t[i-1]: the constructor sees the unflipped pair
